@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: SDXL-base 1024x1024, 50-step, CFG, bf16 -- images/s of the denoising hot path, one replica per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one ``denoising_step`` (scale+CFG dup -> UNet -> CFG combine -> Euler) over one batch of B=4 synthetic
 1024^2 requests (UNet batch 8), i.e. BASELINE.json configs[1].  images/s = N * B / (50 * step time).  Inputs and
 weights are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra legs (outside the timed region):
+A plain run sets up, runs W warm-up steps, times K steps and prints the line.  --dump-outputs DIR also writes what the
+last timed step handed its caller (every request's latents, fp32) to DIR/latents.npy; weights and inputs are seeded,
+so two runs with the same arguments start from the same tensors.
+
+Extra legs (--full only; outside the timed region):
   roofline     one more step with every GEMM/conv/attention launch bracketed by hipEvents on its stream
                (mx_profile_enable): achieved = algorithmic FLOPs / summed launch time of the dominant kernel
   stream       the BASELINE.md section 4 procedure: fixed-prompt Poisson streams at the reference's offered loads
@@ -108,6 +112,12 @@ def parse():
     ap.add_argument("--pp-steps", type=int, default=10, help="timed stale steps of the --pp leg (after the 5 synchronous warm-up steps, which are timed too)")
     ap.add_argument("--no-cached-mix", action="store_true", help="skip the mixed-stream leg with the block-skip cache on")
     ap.add_argument("--no-two-model", action="store_true", help="skip the configs[4] leg with SDXL and SD3.5 requests interleaved in one stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents the last timed step produced (every request of the batch, fp32) to DIR/latents.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (parity and CPU baseline against the oracle, roofline, stream / mixed / two-model / "
+                         "patch-parallel legs, the SD3.5 block, the stages either side of the loop); the options above that select or skip a leg "
+                         "take effect only with --full")
     a = ap.parse_args()
     if a.mix is None:
         a.mix = 28 if (a.model == "sdxl" and a.res == 1024) else 0
@@ -115,6 +125,9 @@ def parse():
         a.pp = a.gpus if (a.gpus > 1 and a.model == "sdxl") else 0
     if a.pp and (a.pp < 2 or a.gpus % a.pp):
         ap.error(f"--pp {a.pp} must be >= 2 and divide --gpus {a.gpus}")
+    if not a.full:          # a plain run: set up, warm up, the timed steps, the line
+        a.stream_requests, a.mix, a.pp = 0, 0, 0
+        a.no_cpu_baseline = a.no_stages = a.no_roofline = a.no_sd3 = a.no_parity = a.no_cached_mix = a.no_two_model = True
     return a
 
 
@@ -579,6 +592,22 @@ def timed_steps(den, reqs, key, args, dist, device, rehearse):
     return elapsed / args.steps, step
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(reqs, out_dir):
+    """--dump-outputs: the latents the last timed step left on every request of the batch ([B, C, res/8, res/8], batch order) as fp32 in
+    out_dir/latents.npy.  Past DUMP_BYTES_MAX a fixed, seeded choice of whole requests is written instead (still in batch order)."""
+    per_req = reqs[0].latents.numel() * 4
+    keep = list(range(len(reqs)))
+    if per_req * len(keep) > DUMP_BYTES_MAX:
+        keep = sorted(np.random.RandomState(10086).choice(len(reqs), max(1, DUMP_BYTES_MAX // per_req), replace=False).tolist())
+    lat = torch.cat([reqs[i].latents for i in keep], dim=0).float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "latents.npy"), lat)
+    progress(f"wrote {os.path.join(out_dir, 'latents.npy')}: {list(lat.shape)} fp32 ({len(keep)} of {len(reqs)} requests)")
+
+
 def roofline_leg(step, model):
     """one more step with every GEMM / conv / attention / norm launch bracketed by hipEvents on its stream; returns (kernels, roofline)"""
     from sduss_amd import lib
@@ -770,6 +799,8 @@ def main():
     kv0 = net.context_stats() if hasattr(net, "context_stats") else None
     step_s, step = timed_steps(den, reqs, key, args, dist, device, rehearse)
     kv1 = net.context_stats() if kv0 is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(reqs, args.dump_outputs)
     images_per_s = world * args.batch / (STEPS_PER_IMAGE * step_s)
     finite = all(torch.isfinite(r.latents.float()).all().item() for r in reqs)
 

@@ -280,7 +280,7 @@ def test_sd3_two_ranks_equal_one_rank_and_stale_steps(cuda_device):
 
 @pytest.mark.timeout(600)
 def test_bench_gpus2_self_spawn_with_pp_leg_on_the_shared_gpu(cuda_device):
-    """`python bench.py --gpus 2` with no launcher: bench.py starts its two ranks itself (a child torch.distributed.run; the pytest process is only the
+    """`python bench.py --gpus 2 --full` with no launcher: bench.py starts its two ranks itself (a child torch.distributed.run; the pytest process is only the
     grandparent), both on cuda:0 over gloo (MX_BENCH_REHEARSE=1), walks the timed region and the configs[3] --pp leg (one 1024 px request row-split
     over the 2 ranks, 5 synchronous + stale steps) and prints ONE line with n_gpus 2 and a patch_parallel block.  The numbers of a rehearsal mean
     nothing; the control flow, the rank accounting and the pp leg's exchange accounting are what is asserted."""
@@ -291,7 +291,7 @@ def test_bench_gpus2_self_spawn_with_pp_leg_on_the_shared_gpu(cuda_device):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MX_BENCH_REHEARSE"] = "1"
     env["OMP_NUM_THREADS"] = "8"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "1", "--steps", "2", "--warmup", "1", "--pp-steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "1", "--steps", "2", "--warmup", "1", "--full", "--pp-steps", "2",
                         "--stream-requests", "0", "--mix", "0", "--no-cpu-baseline", "--no-roofline", "--no-sd3", "--no-stages", "--no-parity"],
                        env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
