@@ -236,6 +236,17 @@ int mx_gemm_gn_partials_supported(const mx_gemm_desc* d, int conv);   /* 1 when 
  *   MX_FORM_CONV_SMALL_CIN round 5: 3 x 3 conv whose descriptor names cin_valid <= 8 input channels (stride 1, bias only, N % 80 == 0) */
 enum { MX_FORM_TILE_GENERIC = 0, MX_FORM_TILE_256 = 1, MX_FORM_TILE_128 = 2, MX_FORM_PERSISTENT_256 = 3, MX_FORM_SMALL_M = 4, MX_FORM_CONV_SMALL_N = 5, MX_FORM_CONV_SMALL_CIN = 6 };
 int mx_gemm_form(const mx_gemm_desc* d, int conv);
+/* Which kernel INSTANTIATION serves launch number `launch` of mx_gemm (conv = 0) / mx_conv3x3 (conv = 1) of d -- host only, the chooser the launch
+ * dispatches on: its name (the kernel and its template arguments, e.g. "gemm_v2_kernel<160, 2, true, EPI_F_ALL, false>") goes to buf (cap bytes,
+ * NUL-terminated).  launch: 0, and 1 for the second launch of mx_gemm's tail split (mx_gemm_launches).  Returns the name's length, 0 past the last
+ * launch, -1 when no instantiation serves d.  mx_gemm_kernel_names: every instantiation the GEMM / conv launchers can start, one per line; returns
+ * the length of the whole list. */
+int mx_gemm_kernel_name(const mx_gemm_desc* d, int conv, int launch, char* buf, int cap);
+int mx_gemm_kernel_names(char* buf, int cap);
+/* The same for one attention launch over a problem of this shape (B, H, Lq, Lk, ldo; prescaled q; causal, bias and key_chunk as the attention entry
+ * points take them; force_cross = mx_attention_cross_prescaled).  Returns the name's length, -1 when no instantiation serves it. */
+int mx_attention_kernel_name(int B, int H, int Lq, int Lk, int ldo, int prescaled, int causal, int bias, int key_chunk, int force_cross, char* buf, int cap);
+int mx_attention_kernel_names(char* buf, int cap);
 #define MX_STATS_PITCH(slabs) (((slabs) + 3) & ~3)     /* slabs per row of a statistics buffer: [M][pitch][2] floats */
 /* stats[m * 4 * 2 + {0, 1}] = (sum_c x[m][c], sum_c x[m][c]^2), x bf16 [M, C] with row stride ldx: the one-slab input of ln_stats
  * (buffer of M * MX_STATS_PITCH(1) * 2 floats) */

@@ -1069,14 +1069,43 @@ static int fill_attention_args(mx::AttnArgs& a, const void* q, int ldq, const vo
   return 0;
 }
 
-// One launch over ga.n problems (ga.g filled).  The kernel is chosen for the launch as a whole -- by its longest query sequence -- and must
-// be able to serve every problem; otherwise the general register-staged kernel takes them all.
-static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, bool force_cross = false) {
+// Every kernel instantiation the attention launcher can start: T(id, kernel, (template arguments)) / P(id, kernel).  attention_kernel_of
+// returns an id, launch_attention_group starts it through one switch over this list, and mx_attention_kernel_name reports it by name.
+#define MX_ATTN_FORMS(T, P)                                  \
+  T(AK_CROSS_PRE77, attn_cross_kernel, (true, 77))           \
+  T(AK_CROSS_PRE, attn_cross_kernel, (true))                 \
+  T(AK_CROSS, attn_cross_kernel, (false))                    \
+  P(AK_W64, attn_fwd64_kernel)                               \
+  T(AK_DMA_PRE, attn_fwd_dma_kernel, (true))                 \
+  T(AK_DMA, attn_fwd_dma_kernel, (false))                    \
+  T(AK_GEN_PRE_EXTRA, attn_fwd_kernel, (true, true))         \
+  T(AK_GEN_EXTRA, attn_fwd_kernel, (false, true))            \
+  T(AK_GEN_PRE, attn_fwd_kernel, (true))                     \
+  T(AK_GEN, attn_fwd_kernel, (false))
+#define MX_ATTN_UNPAREN(...) __VA_ARGS__
+#define MX_ATTN_TARGS(...) "<" #__VA_ARGS__ ">"
+enum AttnKernelId {
+#define MX_ATTN_ID_T(id, k, targs) id,
+#define MX_ATTN_ID_P(id, k) id,
+  MX_ATTN_FORMS(MX_ATTN_ID_T, MX_ATTN_ID_P)
+#undef MX_ATTN_ID_T
+#undef MX_ATTN_ID_P
+  AK_COUNT
+};
+#define MX_ATTN_NAME_T(id, k, targs) #k MX_ATTN_TARGS targs,
+#define MX_ATTN_NAME_P(id, k) #k,
+static const char* const kAttnKernelNames[AK_COUNT] = {MX_ATTN_FORMS(MX_ATTN_NAME_T, MX_ATTN_NAME_P)};
+
+// The instantiation a launch over ga.n problems (ga.g filled) runs.  The kernel is chosen for the launch as a whole -- by its longest query
+// sequence -- and must be able to serve every problem; otherwise the general register-staged kernel takes them all.  -1: force_cross, and the
+// short-key kernel cannot serve the problems.
+static int attention_kernel_of(const mx::AttnGroup& ga, bool pre, bool force_cross) {
   using namespace mx;
   const int n = ga.n;
   int maxLq = 0;
-  bool all_short = true, all_long_k = true, whole_tiles = true, plain = true, o8 = true;
-  double flops = 0, bytes = 0;
+  bool all_short = true, all_long_k = true, whole_tiles = true, plain = true, o8 = true, extra = false;
+  bool all77 = true;                           // the text encoders' 77 keys: the short-key kernel has a compile-time form for them (attn_cross_body.h, LK), which beats the
+                                               // general kernel at every query length (round 5: 15.7 vs 18.8 us at B8 H20 Lq 1024, profiles/r05_l_cross77_ab.txt)
   for (int i = 0; i < n; ++i) {
     const AttnArgs& a = ga.g[i];
     maxLq = std::max(maxLq, a.Lq);
@@ -1085,23 +1114,39 @@ static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, boo
     whole_tiles = whole_tiles && a.Lk % KT == 0 && a.Lk >= 3 * KT;
     plain = plain && a.key_chunk == 0 && !a.causal && !a.bias;
     o8 = o8 && a.ldo % 8 == 0;
+    extra = extra || a.causal || a.bias;
+    all77 = all77 && a.Lk == 77;
+  }
+  // (at Lq 1024 the general kernel is 7 % faster than the short-key one: both are latency-bound)
+  if (force_cross && !(all_short && plain && o8)) return -1;
+  if (all_short && (maxLq >= 2048 || force_cross || (all77 && pre)) && plain && o8)      // short key sequence: every wave keeps K / V^T in registers
+    return pre && all77 ? AK_CROSS_PRE77 : pre ? AK_CROSS_PRE : AK_CROSS;
+  if (extra) return pre ? AK_GEN_PRE_EXTRA : AK_GEN_EXTRA;                // the masked / biased forms live in the register-staged kernel
+  if (pre && all_long_k && maxLq >= 2048 && o8) return AK_W64;            // 64 query rows per wave (a tie with the 32-row kernels at Lq 1024)
+  if (whole_tiles) return pre ? AK_DMA_PRE : AK_DMA;                      // whole tiles: LDS-DMA staging two tiles ahead
+  return pre ? AK_GEN_PRE : AK_GEN;
+}
+
+// One launch over ga.n problems (ga.g filled), on the instantiation attention_kernel_of chooses.
+static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, bool force_cross = false) {
+  using namespace mx;
+  const int n = ga.n;
+  int maxLq = 0;
+  double flops = 0, bytes = 0;
+  bool extra = false;
+  for (int i = 0; i < n; ++i) {
+    const AttnArgs& a = ga.g[i];
+    maxLq = std::max(maxLq, a.Lq);
+    extra = extra || a.causal || a.bias;
     flops += 4.0 * a.B * a.H * (double)a.Lq * a.Lk * 64.0;
     bytes += 2.0 * a.B * a.H * 64.0 * (2.0 * a.Lq + 2.0 * a.Lk);
   }
-  bool extra = false;
-  for (int i = 0; i < n; ++i) extra = extra || ga.g[i].causal || ga.g[i].bias;
   MX_CHECK(!extra || n == 1, "attention: the causal / bias forms are not grouped");
-  // (at Lq 1024 the general kernel is 7 % faster than the short-key one: both are latency-bound)
-  enum { K_GENERAL, K_CROSS, K_W64, K_DMA } kind = K_GENERAL;
-  if (force_cross) MX_CHECK(all_short && plain && o8, "attention: the short-key kernel needs Lk <= 96, no mask / bias / key chunks and ldo % 8 == 0");
-  bool all77 = true;                           // the text encoders' 77 keys: the short-key kernel has a compile-time form for them (attn_cross_body.h, LK), which beats the
-  for (int i = 0; i < n; ++i) all77 = all77 && ga.g[i].Lk == 77;      // general kernel at every query length (round 5: 15.7 vs 18.8 us at B8 H20 Lq 1024, profiles/r05_l_cross77_ab.txt)
-  if (all_short && (maxLq >= 2048 || force_cross || (all77 && pre)) && plain && o8) kind = K_CROSS;          // short key sequence: every wave keeps K / V^T in registers
-  else if (extra) kind = K_GENERAL;                                       // the masked / biased forms live in the register-staged kernel
-  else if (pre && all_long_k && maxLq >= 2048 && o8) kind = K_W64;        // 64 query rows per wave (a tie with the 32-row kernels at Lq 1024)
-  else if (whole_tiles) kind = K_DMA;                                     // whole tiles: LDS-DMA staging two tiles ahead
-  const int rows = kind == K_W64 ? 256 : 128;
-  if (kind == K_CROSS) {
+  const int form = attention_kernel_of(ga, pre, force_cross);
+  MX_CHECK(form >= 0, "attention: the short-key kernel needs Lk <= 96, no mask / bias / key chunks and ldo % 8 == 0");
+  const bool cross = form == AK_CROSS_PRE77 || form == AK_CROSS_PRE || form == AK_CROSS;
+  const int rows = form == AK_W64 ? 256 : 128;
+  if (cross) {
     // The short-key kernel is latency-bound: a wave pays ~3 us to fetch its head's 24 fragments and ~2.5 us per 32-query block, two workgroups per CU.  With a fixed
     // 64 queries per wave the step's shapes were 1.25 rounds (B8 H20 Lq1024: 640 workgroups on 512 slots) or 2.5 (Lq4096).  Deal the blocks instead: every wave of
     // a (batch, head) takes `per` or `per - 1` consecutive blocks, `per` chosen to minimise rounds x (3 + 2.5 per) -- one round whenever the pairs fit the chip.
@@ -1124,7 +1169,7 @@ static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, boo
   for (int i = 0; i < n; ++i) {
     blocks = (blocks + 7) & ~7L;
     ga.blk0[i] = (int)blocks;
-    ga.nblk[i] = (kind == K_CROSS ? cdiv(ga.g[i].xq_wpb, 4) : cdiv(ga.g[i].Lq, rows)) * ga.g[i].H * ga.g[i].B;
+    ga.nblk[i] = (cross ? cdiv(ga.g[i].xq_wpb, 4) : cdiv(ga.g[i].Lq, rows)) * ga.g[i].H * ga.g[i].B;
     blocks += ga.nblk[i];
   }
   for (int i = n; i < MX_MAX_SEGS; ++i) ga.nblk[i] = 0;
@@ -1133,22 +1178,13 @@ static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, boo
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks), block(256);
   const AttnArgs& a0 = ga.g[0];
-  prof_begin(st, kind == K_CROSS ? PROF_ATTN_CROSS : PROF_ATTN, flops, bytes, n == 1 ? a0.B * a0.H : n, maxLq, a0.Lk);
-  switch (kind) {
-    case K_CROSS: {
-      if (pre && all77) hipLaunchKernelGGL((attn_cross_kernel<true, 77>), grid, block, 0, st, ga);
-      else if (pre) hipLaunchKernelGGL(attn_cross_kernel<true>, grid, block, 0, st, ga);
-      else hipLaunchKernelGGL(attn_cross_kernel<false>, grid, block, 0, st, ga);
-      break;
-    }
-    case K_W64: hipLaunchKernelGGL(attn_fwd64_kernel, grid, block, 0, st, ga); break;
-    case K_DMA:
-      if (pre) hipLaunchKernelGGL(attn_fwd_dma_kernel<true>, grid, block, 0, st, ga); else hipLaunchKernelGGL(attn_fwd_dma_kernel<false>, grid, block, 0, st, ga);
-      break;
-    default:
-      if (extra) { if (pre) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, st, ga); else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, st, ga); }
-      else if (pre) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, st, ga);
-      else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, ga);
+  prof_begin(st, cross ? PROF_ATTN_CROSS : PROF_ATTN, flops, bytes, n == 1 ? a0.B * a0.H : n, maxLq, a0.Lk);
+  switch (form) {
+#define MX_ATTN_T(id, k, targs) case id: hipLaunchKernelGGL((k<MX_ATTN_UNPAREN targs>), grid, block, 0, st, ga); break;
+#define MX_ATTN_P(id, k) case id: hipLaunchKernelGGL(k, grid, block, 0, st, ga); break;
+    MX_ATTN_FORMS(MX_ATTN_T, MX_ATTN_P)
+#undef MX_ATTN_T
+#undef MX_ATTN_P
   }
   prof_end(st);
   MX_LAUNCH_CHECK();
@@ -1222,3 +1258,21 @@ extern "C" int mx_attention_prescaled_chunked(void* stream, const void* q, int l
   return launch_attention(stream, q, ldq, k, ldk, vt, ldvt, vt_batch_stride, o, ldo, B, H, Lq, Lk, 1.0f, true, key_chunk,
                           k_batch_stride, k_chunk_stride, vt_chunk_stride);
 }
+
+/* name of the kernel instantiation one attention launch over a problem of this shape would run (host only): prescaled, causal, bias and key_chunk as the
+ * entry points above take them; force_cross: mx_attention_cross_prescaled.  -1: no instantiation serves it */
+extern "C" int mx_attention_kernel_name(int B, int H, int Lq, int Lk, int ldo, int prescaled, int causal, int bias, int key_chunk, int force_cross,
+                                        char* buf, int cap) {
+  if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return -1;
+  mx::AttnGroup ga;
+  ga.n = 1;
+  mx::AttnArgs& a = ga.g[0];
+  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.ldo = ldo;
+  a.causal = causal ? 1 : 0;
+  a.bias = bias ? reinterpret_cast<const float*>(16) : nullptr;      // (shape query: the chooser only looks at whether there is one)
+  a.key_chunk = key_chunk;
+  const int form = attention_kernel_of(ga, prescaled != 0, force_cross != 0);
+  if (form < 0) return -1;
+  return mx::copy_name(kAttnKernelNames[form], buf, cap);
+}
+extern "C" int mx_attention_kernel_names(char* buf, int cap) { return mx::join_names(kAttnKernelNames, AK_COUNT, buf, cap); }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 
 namespace mx {
@@ -117,6 +118,19 @@ int cu_count();   // compute units of the current device, whole XCD groups (mult
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// kernel-name queries (mx_gemm_kernel_name, mx_attention_kernel_name ...): `name` into buf (cap bytes, NUL-terminated, cut short if it does not
+// fit); returns strlen(name).  join: the n names separated by '\n'; returns the length of the whole list.
+static inline int copy_name(const char* name, char* buf, int cap) {
+  const std::string s(name);
+  if (buf && cap > 0) { const size_t k = std::min(s.size(), (size_t)cap - 1); s.copy(buf, k); buf[k] = 0; }
+  return (int)s.size();
+}
+static inline int join_names(const char* const* names, int n, char* buf, int cap) {
+  std::string s;
+  for (int i = 0; i < n; ++i) { if (i) s += '\n'; s += names[i]; }
+  return copy_name(s.c_str(), buf, cap);
+}
 
 }  // namespace mx
 

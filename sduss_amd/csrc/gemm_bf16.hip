@@ -28,6 +28,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 
 namespace mx {
 
@@ -187,11 +188,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs pk) {
   gemm_epilogue<NI, MI, BN>(p, acc, m0 + wm * 64, n0 + wn * (BN / 2), fr, fq);
 }
 
-int launch_v2(hipStream_t s, const GemmArgs& a, bool conv, int bn, int rows);
-int launch_v5(hipStream_t s, const GemmArgs& a, bool conv, int bn, int rows);
-int launch_v4(hipStream_t s, const GemmArgs& a);
+// the family launchers start the instantiation `form` (gemm_forms.h) that gemm_kernel_of below chose
+int launch_v2(hipStream_t s, const GemmArgs& a, int bn, int form);
+int launch_v5(hipStream_t s, const GemmArgs& a, int bn, int rows, int form);
+int launch_v4(hipStream_t s, const GemmArgs& a, int form);
 bool small_m_serves(const mx_gemm_desc* d, bool conv);      // gemm_small_m.hip: M <= 16, the weight-stream form
-int launch_small_m(hipStream_t s, const GemmArgs& a);
+int small_m_form(long N, long K, int flags);
+int launch_small_m(hipStream_t s, const GemmArgs& a, int form);
 bool conv_small_n_serves(const mx_gemm_desc* d);                // conv_small_n.hip: 3x3 conv with N <= 16 output channels (conv_out)
 int launch_conv_small_n(hipStream_t s, const GemmArgs& a);
 bool conv_small_cin_serves(const mx_gemm_desc* d);              // conv_small_n.hip: 3x3 conv over <= 8 non-zero input channels (conv_in)
@@ -362,6 +365,60 @@ static int stats_slabs_of(const mx_gemm_desc* d, bool conv, const TileChoice& tc
   for (int i = 0; i < d->n_segs; ++i) if (d->segs[i].a_batch_rows > 0 || d->segs[i].c_batch_rows > 0) return 0;
   const int panel = tc.bn / 2;                          // 4 x 2 waves of (16 MI) x (BN / 2)
   return d->N / panel;
+}
+
+// is `form` one of the weight-stream kernels of gemm_small_m.hip (membership in its list, not an id range)
+static bool is_small_m_form(int form) {
+  switch (form) {
+#define MX_SM(id, k, targs) case id: return true;
+    MX_GEMM_SMALL_M_FORMS(MX_SM)
+#undef MX_SM
+    default: return false;
+  }
+}
+
+// The kernel instantiation (gemm_forms.h id) a launch of d on tile choice tc runs, or -1 if none serves it: the smallest instantiation that
+// carries the launch's epilogue features (each carries only its own epilogue code: gemm_args.h, EPI_F_*).  launch() dispatches on it and
+// mx_gemm_kernel_name reports it.
+static int gemm_kernel_of(const mx_gemm_desc* d, bool conv, const TileChoice& tc) {
+  if (d->ln_final && tc.bn != 256) return -1;  // (launch() rejects it)
+  if (small_m_serves(d, conv)) return small_m_form(d->N, d->K, d->flags);
+  if (conv && conv_small_n_serves(d)) return GK_CONV_SMALL_N;
+  if (conv && conv_small_cin_serves(d)) return GK_CONV_SMALL_CIN;
+  const int feat = gemm_epi_features(d->flags);
+  const bool geglu = (d->flags & MX_EPI_GEGLU) != 0;
+  const bool vec = d->rowbias || d->gate;       // per-sample vectors: compiled in only where asked for
+  if (tc.bn == 256) {                           // persistent 256 x 256 (gemm_bf16_v4.hip)
+    if (d->ln_final) {                          // the folded LayerNorm's instantiations: GEGLU / QKV / plain, no per-sample vectors (prepare checked)
+      if (geglu) return (feat & EPI_F_ACT) ? -1 : GK_V4_GEGLU_LN;
+      return feat == EPI_F_QKV ? GK_V4_QKV_LN : feat == 0 ? GK_V4_LN : -1;
+    }
+    if (geglu) return (feat & EPI_F_ACT) ? GK_V4_GEGLU_ACT : GK_V4_GEGLU;      // (the gated epilogue takes no per-sample vectors)
+    if (!vec) return feat == 0 ? GK_V4 : feat == EPI_F_QKV ? GK_V4_QKV : feat == EPI_F_TANH ? GK_V4_TANH : GK_V4_VEC_ALL;
+    return feat == 0 ? GK_V4_VEC : GK_V4_VEC_ALL;
+  }
+  if (tc.bn != 0 && tc.rows == 256) {           // 256-row ping-pong tiles (gemm_bf16_v5.hip)
+    const bool b160 = tc.bn == 160;
+    if (geglu) return (feat & EPI_F_ACT) ? GK_V5_128_GEGLU_ACT : GK_V5_128_GEGLU;      // (pick_tile: 128 features only; no per-sample vectors)
+    if (conv) {
+      if (feat == 0 && !vec) return b160 ? GK_V5_160_CONV : GK_V5_128_CONV;
+      if (feat == 0) return b160 ? GK_V5_160_CONV_VEC : GK_V5_128_CONV_VEC;
+      return b160 ? GK_V5_160_CONV_ALL : GK_V5_128_CONV_ALL;
+    }
+    if (feat == 0 && !vec) return b160 ? GK_V5_160 : GK_V5_128;
+    if (feat == EPI_F_QKV && !vec) return b160 ? GK_V5_160_QKV : GK_V5_128_QKV;
+    return b160 ? GK_V5_160_ALL : GK_V5_128_ALL;
+  }
+  if (tc.bn != 0) {                             // 128-row lock-step tiles (gemm_bf16_v2.hip)
+    const bool b160 = tc.bn == 160;
+    if (geglu) return (feat & EPI_F_ACT) ? GK_V2_128_GEGLU_ACT : GK_V2_128_GEGLU;      // (pick_tile: 128 features only)
+    if (conv) return feat == 0 ? (b160 ? GK_V2_160_CONV : GK_V2_128_CONV) : (b160 ? GK_V2_160_CONV_ALL : GK_V2_128_CONV_ALL);
+    if (feat == 0) return b160 ? GK_V2_160 : GK_V2_128;
+    if (feat == EPI_F_QKV) return b160 ? GK_V2_160_QKV : GK_V2_128_QKV;
+    return b160 ? GK_V2_160_ALL : GK_V2_128_ALL;
+  }
+  if (d->N % 128 == 0) return conv ? GK_GEN128_CONV : GK_GEN128;      // the generic register-prefetch tile kernel
+  return conv ? GK_GEN64_CONV : GK_GEN64;
 }
 
 // validation + the kernel argument block + the tile choice of mx_gemm / mx_conv3x3 (d); the dispatch follows in launch()
@@ -566,28 +623,31 @@ static int launch(void* stream, const mx_gemm_desc* d, bool conv) {
   }
   const int mt128 = grouped ? a.mt_total : cdiv(d->M, BM);      // m-tiles of the generic kernel
   if (d->ln_final) MX_CHECK(v2bn == 256, "gemm: ln_final is the 256 x 256 kernel's form of the folded LayerNorm; this shape does not run there (use ln_stats)");
-  if (small_m_serves(d, conv)) {
-    launch_small_m(s, a);                      // M <= 16: a weight stream (gemm_small_m.hip)
-  } else if (conv && conv_small_n_serves(d)) {
+  const int form = gemm_kernel_of(d, conv, tc);
+  MX_CHECK(form >= 0, v2bn == 256 ? "gemm: no 256 x 256 instantiation serves ln_final with this epilogue (GEGLU, QKV or plain bias only)"
+                                   : "gemm: no kernel instantiation serves this descriptor");
+  if (is_small_m_form(form)) {
+    MX_CHECK(launch_small_m(s, a, form) == 0, "gemm: the small-M launcher was handed a form outside its list");   // M <= 16: a weight stream (gemm_small_m.hip)
+  } else if (form == GK_CONV_SMALL_N) {
     launch_conv_small_n(s, a);                 // N <= 16: the input read once (conv_small_n.hip)
-  } else if (conv && conv_small_cin_serves(d)) {
+  } else if (form == GK_CONV_SMALL_CIN) {
     launch_conv_small_cin(s, a);               // <= 8 non-zero input channels: K = 72 (conv_small_n.hip)
   } else if (v2bn == 256) {
-    MX_CHECK(launch_v4(s, a) == 0, "gemm: no 256 x 256 instantiation serves ln_final with this epilogue (GEGLU, QKV or plain bias only)");   // 256 x 256 ping-pong (gemm_bf16_v4.hip)
+    MX_CHECK(launch_v4(s, a, form) == 0, "gemm: no 256 x 256 instantiation serves ln_final with this epilogue (GEGLU, QKV or plain bias only)");   // 256 x 256 ping-pong (gemm_bf16_v4.hip)
   } else if (v2bn) {
     // 256-row tiles: ping-pong schedule (gemm_bf16_v5.hip).  128-row tiles (small M) stay on the lock-step loop of gemm_bf16_v2.hip: the
     // ping-pong form is a tie there (same-box A/B, profiles/r03_d_gemm_bench_small_*: M2048 N1280 K1280 19.3 vs 19.2 us, conv B2 1280@32 98.9 vs
     // 108.5 us) -- with half the MFMAs per K tile its L phase (5 LDS-DMA issues + 14 fragment reads) outlasts the M phase
-    if (tc.rows == 256) launch_v5(s, a, conv, v2bn, tc.rows);
-    else launch_v2(s, a, conv, v2bn, tc.rows);
-  } else if (use128) {
-    dim3 grid(mt128, d->N / 128);
-    if (conv) hipLaunchKernelGGL((gemm_kernel<128, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gemm_kernel<128, false>), grid, block, 0, s, a);
+    if (tc.rows == 256) MX_CHECK(launch_v5(s, a, v2bn, tc.rows, form) == 0, "gemm: the 256-row launcher was handed a form outside its list");
+    else MX_CHECK(launch_v2(s, a, v2bn, form) == 0, "gemm: the 128-row launcher was handed a form outside its list");
   } else {
-    dim3 grid(mt128, cdiv(d->N, 64));
-    if (conv) hipLaunchKernelGGL((gemm_kernel<64, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gemm_kernel<64, false>), grid, block, 0, s, a);
+    const dim3 grid(mt128, use128 ? d->N / 128 : cdiv(d->N, 64));
+    switch (form) {
+#define MX_GEN(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); break;
+      MX_GEMM_GENERIC_FORMS(MX_GEN)
+#undef MX_GEN
+      default: MX_CHECK(false, "gemm: the generic launcher was handed a form outside its list");
+    }
   }
   prof_end(s);
   MX_LAUNCH_CHECK();
@@ -682,3 +742,22 @@ extern "C" int mx_gemm_splitk(const mx_gemm_desc* d, int conv) {
   if (!d || mx::rows_of(d) <= 0 || d->N <= 0 || d->K <= 0) return 0;
   return mx::pick_tile(d, conv != 0).splitk;
 }
+
+namespace mx {
+static const char* const kGemmKernelNames[GK_COUNT] = {
+  MX_GEMM_GENERIC_FORMS(MX_FORM_NAME_T) MX_GEMM_V2_FORMS(MX_FORM_NAME_T) MX_GEMM_V5_FORMS(MX_FORM_NAME_T) MX_GEMM_V4_FORMS(MX_FORM_NAME_T)
+  MX_GEMM_SMALL_M_FORMS(MX_FORM_NAME_T) MX_GEMM_CONV_SMALL_FORMS(MX_FORM_NAME_P)
+};
+}  // namespace mx
+/* name of the kernel instantiation launch number `launch` (0, or 0 / 1 under the tail split) of mx_gemm / mx_conv3x3 would run (host only) */
+extern "C" int mx_gemm_kernel_name(const mx_gemm_desc* d, int conv, int launch, char* buf, int cap) {
+  if (!d || mx::rows_of(d) <= 0 || d->N <= 0 || d->K <= 0 || launch < 0) return -1;
+  mx_gemm_desc d1, d2;
+  const mx_gemm_desc* q = d;
+  if (!conv && mx::tail_split(d, d1, d2)) { if (launch > 1) return 0; q = launch == 0 ? &d1 : &d2; }
+  else if (launch > 0) return 0;
+  const int form = mx::gemm_kernel_of(q, conv != 0, mx::pick_tile(q, conv != 0));
+  if (form < 0) return -1;
+  return mx::copy_name(mx::kGemmKernelNames[form], buf, cap);
+}
+extern "C" int mx_gemm_kernel_names(char* buf, int cap) { return mx::join_names(mx::kGemmKernelNames, mx::GK_COUNT, buf, cap); }

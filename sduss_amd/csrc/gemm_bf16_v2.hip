@@ -23,6 +23,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 
 
 namespace mx {
@@ -304,24 +305,15 @@ __global__ __launch_bounds__(512, 2) void gemm_v2_kernel(const GemmArgs pk) {
 
 // bn: 160 or 128 features per tile.  This file serves the 128-row tiles (small M: one request, mixed batches); the 256-row tiles run the
 // ping-pong schedule of gemm_bf16_v5.hip (the lock-step 256-row instantiation it replaced: git history, A/B in profiles/r03_*gemm_bench*).
-int launch_v2(hipStream_t s, const GemmArgs& a, bool conv, int bn, int rows) {
-  (void)rows;
+int launch_v2(hipStream_t s, const GemmArgs& a, int bn, int form) {
   const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, 128)) * (a.N / bn) * (a.splitk > 1 ? a.splitk : 1);
   dim3 grid(tiles), block(512);
-#define MX_V2(BN_, CONV_, FEAT_, GEGLU_) hipLaunchKernelGGL((gemm_v2_kernel<BN_, 2, CONV_, FEAT_, GEGLU_>), grid, block, 0, s, a)
-  const int feat = gemm_epi_features(a.flags);
-  if (a.flags & MX_EPI_GEGLU) {               // (pick_tile: 128 features only)
-    if (feat & EPI_F_ACT) MX_V2(128, false, EPI_F_ACT, true); else MX_V2(128, false, 0, true);
-  } else if (conv) {
-    if (bn == 160) { if (feat == 0) MX_V2(160, true, 0, false); else MX_V2(160, true, EPI_F_ALL, false); }
-    else { if (feat == 0) MX_V2(128, true, 0, false); else MX_V2(128, true, EPI_F_ALL, false); }
-  } else if (bn == 160) {
-    if (feat == 0) MX_V2(160, false, 0, false); else if (feat == EPI_F_QKV) MX_V2(160, false, EPI_F_QKV, false); else MX_V2(160, false, EPI_F_ALL, false);
-  } else {
-    if (feat == 0) MX_V2(128, false, 0, false); else if (feat == EPI_F_QKV) MX_V2(128, false, EPI_F_QKV, false); else MX_V2(128, false, EPI_F_ALL, false);
-  }
+  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
+#define MX_V2(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
+    MX_GEMM_V2_FORMS(MX_V2)
 #undef MX_V2
-  return 0;
+    default: return 1;
+  }
 }
 
 }  // namespace mx

@@ -38,6 +38,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 
 #ifndef MX_EXP
 #define MX_EXP 0
@@ -330,33 +331,16 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
 extern "C" int mx_debug_v4_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_v4_stamps), sizeof(g_v4_stamps)); }
 #endif
 
-int launch_v4(hipStream_t s, const GemmArgs& a) {
+int launch_v4(hipStream_t s, const GemmArgs& a, int form) {
   const int ncu = cu_count();
   const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, BM4)) * (a.N / BN4);
   const dim3 grid(tiles > ncu && ncu > 0 ? ncu : tiles), block(512);
-  // the smallest instantiation that serves the launch (each carries only its own epilogue code: gemm_args.h, EPI_F_*)
-  const bool vec = a.rowbias || a.gate;
-  const int feat = gemm_epi_features(a.flags);
-#define MX_V4(VEC_, FEAT_, GEGLU_) hipLaunchKernelGGL((gemm_v4_kernel<VEC_, FEAT_, GEGLU_>), grid, block, 0, s, a)
-  if (a.ln_final != nullptr) {                 // the folded LayerNorm's instantiations: GEGLU / QKV / plain, no per-sample vectors (the launcher checked)
-    if ((a.flags & MX_EPI_GEGLU) && !(feat & EPI_F_ACT)) hipLaunchKernelGGL((gemm_v4_kernel<false, 0, true, true>), grid, block, 0, s, a);
-    else if (!(a.flags & MX_EPI_GEGLU) && feat == EPI_F_QKV) hipLaunchKernelGGL((gemm_v4_kernel<false, EPI_F_QKV, false, true>), grid, block, 0, s, a);
-    else if (!(a.flags & MX_EPI_GEGLU) && feat == 0) hipLaunchKernelGGL((gemm_v4_kernel<false, 0, false, true>), grid, block, 0, s, a);
-    else return 1;
-    return 0;
-  }
-  if (a.flags & MX_EPI_GEGLU) {
-    if (feat & EPI_F_ACT) MX_V4(false, EPI_F_ACT, true); else MX_V4(false, 0, true);      // (the gated epilogue takes no per-sample vectors)
-  } else if (!vec) {
-    if (feat == 0) MX_V4(false, 0, false);
-    else if (feat == EPI_F_QKV) MX_V4(false, EPI_F_QKV, false);
-    else if (feat == EPI_F_TANH) MX_V4(false, EPI_F_TANH, false);
-    else MX_V4(true, EPI_F_ALL, false);
-  } else {
-    if (feat == 0) MX_V4(true, 0, false); else MX_V4(true, EPI_F_ALL, false);
-  }
+  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
+#define MX_V4(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
+    MX_GEMM_V4_FORMS(MX_V4)
 #undef MX_V4
-  return 0;
+    default: return 1;
+  }
 }
 
 }  // namespace mx

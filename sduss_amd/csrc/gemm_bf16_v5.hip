@@ -24,6 +24,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 #include "gemm_v5_body.h"
 
 namespace mx {
@@ -40,28 +41,16 @@ __global__ __launch_bounds__(512, 2) void gemm_v5_kernel(const GemmArgs pk) {
   gemm_v5_tile<BN, MI, CONV, FEAT, GEGLU, VEC>(pk, tm, tn, smem);
 }
 
-// bn: 160 or 128 features per tile; rows: 256, or 128 when the 256-row tiling would leave most CUs idle (small M)
-int launch_v5(hipStream_t s, const GemmArgs& a, bool conv, int bn, int rows) {
+// bn: 160 or 128 features per tile; rows: 256 (the 128-row instantiation MI = 2 was measured and is not built: see the dispatcher in gemm_bf16.hip)
+int launch_v5(hipStream_t s, const GemmArgs& a, int bn, int rows, int form) {
   const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, rows)) * (a.N / bn);
   dim3 grid(tiles), block(512);
-#define MX_V5(BN_, CONV_, FEAT_, GEGLU_, VEC_) hipLaunchKernelGGL((gemm_v5_kernel<BN_, 4, CONV_, FEAT_, GEGLU_, VEC_>), grid, block, 0, s, a)
-  (void)rows;                                 // (the 128-row instantiation MI = 2 was measured and is not built: see the dispatcher in gemm_bf16.hip)
-  const int feat = gemm_epi_features(a.flags);
-  const bool vec = a.rowbias || a.gate;       // per-sample vectors: compiled in only where asked for
-  if (a.flags & MX_EPI_GEGLU) {               // (pick_tile: 128 features only; the gated epilogue takes no per-sample vectors)
-    if (feat & EPI_F_ACT) MX_V5(128, false, EPI_F_ACT, true, false); else MX_V5(128, false, 0, true, false);
-  } else if (conv) {
-    if (bn == 160) { if (feat == 0 && !vec) MX_V5(160, true, 0, false, false); else if (feat == 0) MX_V5(160, true, 0, false, true); else MX_V5(160, true, EPI_F_ALL, false, true); }
-    else { if (feat == 0 && !vec) MX_V5(128, true, 0, false, false); else if (feat == 0) MX_V5(128, true, 0, false, true); else MX_V5(128, true, EPI_F_ALL, false, true); }
-  } else if (bn == 160) {
-    if (feat == 0 && !vec) MX_V5(160, false, 0, false, false); else if (feat == EPI_F_QKV && !vec) MX_V5(160, false, EPI_F_QKV, false, false);
-    else MX_V5(160, false, EPI_F_ALL, false, true);
-  } else {
-    if (feat == 0 && !vec) MX_V5(128, false, 0, false, false); else if (feat == EPI_F_QKV && !vec) MX_V5(128, false, EPI_F_QKV, false, false);
-    else MX_V5(128, false, EPI_F_ALL, false, true);
-  }
+  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
+#define MX_V5(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
+    MX_GEMM_V5_FORMS(MX_V5)
 #undef MX_V5
-  return 0;
+    default: return 1;
+  }
 }
 
 }  // namespace mx

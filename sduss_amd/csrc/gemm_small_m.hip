@@ -11,6 +11,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 
 namespace mx {
 
@@ -158,31 +159,37 @@ bool small_m_serves(const mx_gemm_desc* d, bool conv) {
   return true;
 }
 
-int launch_small_m(hipStream_t s, const GemmArgs& a) {
-  const int ngroups = a.N / 16;
-  const int ncu = cu_count();
+// which of the form's kernels serves an (N x K) weight stream (gemm_forms.h id; the launch geometry below follows from it)
+int small_m_form(long N, long K, int flags) {
+  const bool f32 = (flags & MX_EPI_OUT_F32) != 0;
+  if (N * K > kSmallMLong) return f32 ? GK_SM_STREAM_F32 : GK_SM_STREAM;      // the long stream: persistent waves, one 16-feature group at a time over the whole K
   // few groups (N 1280: 80): sixteen waves split K, so that a wave's share is one or two rounds of loads; many (the stacked projections): four waves per
   // workgroup and as many consecutive groups per workgroup as keep ~8 workgroups per CU busy for the launch's life
-  const bool f32 = (a.flags & MX_EPI_OUT_F32) != 0;
-  if ((long)a.N * a.K > kSmallMLong) {          // the long stream: persistent waves, one 16-feature group at a time over the whole K
+  const bool wide = N / 16 < 2 * cu_count() && K >= 1024;
+  return wide ? (f32 ? GK_SM16_F32 : GK_SM16) : (f32 ? GK_SM4_F32 : GK_SM4);
+}
+
+int launch_small_m(hipStream_t s, const GemmArgs& a, int form) {
+  const int ngroups = a.N / 16;
+  const int ncu = cu_count();
+  if (form == GK_SM_STREAM_F32 || form == GK_SM_STREAM) {
     const size_t lds = (size_t)a.M * (a.K + 8) * 2;
     const int per_cu = std::max(1, std::min(6, (int)((160 * 1024) / (lds + 256))));
     const dim3 grid((unsigned)std::min(cdiv(ngroups, 4), per_cu * ncu));
-    if (f32) hipLaunchKernelGGL((gemm_small_m_stream_kernel<true>), grid, dim3(256), lds, s, a);
+    if (form == GK_SM_STREAM_F32) hipLaunchKernelGGL((gemm_small_m_stream_kernel<true>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((gemm_small_m_stream_kernel<false>), grid, dim3(256), lds, s, a);
     return 0;
   }
-  const bool wide = ngroups < 2 * ncu && a.K >= 1024;
+  const bool wide = form == GK_SM16_F32 || form == GK_SM16;
   const int groups = wide ? 1 : std::max(1, std::min(16, ngroups / (8 * ncu)));
   const dim3 grid((unsigned)cdiv(ngroups, groups));
-  if (wide) {
-    if (f32) hipLaunchKernelGGL((gemm_small_m_kernel<true, 16>), grid, dim3(1024), 0, s, a, groups);
-    else hipLaunchKernelGGL((gemm_small_m_kernel<false, 16>), grid, dim3(1024), 0, s, a, groups);
-  } else {
-    if (f32) hipLaunchKernelGGL((gemm_small_m_kernel<true, 4>), grid, dim3(256), 0, s, a, groups);
-    else hipLaunchKernelGGL((gemm_small_m_kernel<false, 4>), grid, dim3(256), 0, s, a, groups);
+  switch (form) {
+    case GK_SM16_F32: hipLaunchKernelGGL((gemm_small_m_kernel<true, 16>), grid, dim3(1024), 0, s, a, groups); return 0;
+    case GK_SM16: hipLaunchKernelGGL((gemm_small_m_kernel<false, 16>), grid, dim3(1024), 0, s, a, groups); return 0;
+    case GK_SM4_F32: hipLaunchKernelGGL((gemm_small_m_kernel<true, 4>), grid, dim3(256), 0, s, a, groups); return 0;
+    case GK_SM4: hipLaunchKernelGGL((gemm_small_m_kernel<false, 4>), grid, dim3(256), 0, s, a, groups); return 0;
+    default: return 1;
   }
-  return 0;
 }
 
 }  // namespace mx

@@ -204,6 +204,10 @@ SYMBOLS = {
     "mx_gemm_launches": (_i, [C.POINTER(GemmDesc)]),
     "mx_gemm_gn_partials_supported": (_i, [C.POINTER(GemmDesc), _i]),
     "mx_gemm_form": (_i, [C.POINTER(GemmDesc), _i]),
+    "mx_gemm_kernel_name": (_i, [C.POINTER(GemmDesc), _i, _i, C.c_char_p, _i]),
+    "mx_gemm_kernel_names": (_i, [C.c_char_p, _i]),
+    "mx_attention_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "mx_attention_kernel_names": (_i, [C.c_char_p, _i]),
     "mx_groupnorm_nhwc_from_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "mx_unet_patch_cache_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "mx_mmdit_patch_cache_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
@@ -297,3 +301,42 @@ def torch_dtype_code(dtype) -> int:
 def current_stream() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def _name_list(fn) -> list:
+    n = fn(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    fn(buf, n + 1)
+    return buf.value.decode().split("\n")
+
+
+def gemm_kernel_names() -> list:
+    """every kernel instantiation the GEMM / conv launchers can start (mx_gemm_kernel_names)"""
+    return _name_list(load().mx_gemm_kernel_names)
+
+
+def attention_kernel_names() -> list:
+    """every kernel instantiation the attention launcher can start (mx_attention_kernel_names)"""
+    return _name_list(load().mx_attention_kernel_names)
+
+
+def gemm_kernels_of(desc: "GemmDesc", conv: bool = False) -> list:
+    """the instantiation each launch of mx_gemm / mx_conv3x3 (desc) runs, in launch order (two under the tail split); host only"""
+    lib, out, buf = load(), [], C.create_string_buffer(256)
+    while True:
+        n = lib.mx_gemm_kernel_name(C.byref(desc), int(conv), len(out), buf, len(buf))
+        if n == 0:
+            return out
+        if n < 0:
+            raise MxError("mx_gemm_kernel_name: no instantiation serves this descriptor")
+        out.append(buf.value.decode())
+
+
+def attention_kernel_of(B: int, H: int, Lq: int, Lk: int, ldo: int, prescaled: bool = True, causal: bool = False, bias: bool = False,
+                        key_chunk: int = 0, force_cross: bool = False) -> str:
+    """the instantiation one attention launch over a problem of this shape runs (mx_attention_kernel_name); host only"""
+    buf = C.create_string_buffer(256)
+    n = load().mx_attention_kernel_name(B, H, Lq, Lk, ldo, int(prescaled), int(causal), int(bias), key_chunk, int(force_cross), buf, len(buf))
+    if n < 0:
+        raise MxError("mx_attention_kernel_name: no instantiation serves this problem")
+    return buf.value.decode()
