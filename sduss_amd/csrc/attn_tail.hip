@@ -135,7 +135,7 @@ extern "C" int mx_debug_tail_stamps(unsigned long long* out) { return (int)hipMe
 #endif
 
 __global__ __launch_bounds__(512, 2) void attn_tail_kernel(const TailArgs t) {
-  constexpr int STAGE_ELEMS = (256 + kTailBN) * BK5;
+  constexpr int STAGE_ELEMS = (256 + kTailBN) * DMA_BK;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSTAGE5 * STAGE_ELEMS];
   __shared__ int s_ctl[4];      // [0] ticket, [1] abandon flag
   const int tid = threadIdx.x;

@@ -1,5 +1,6 @@
 // Shared argument block and fused epilogue of the gfx950 GEMM / implicit-GEMM kernels (gemm_bf16.hip: generic
-// 128-row tile; gemm_bf16_v2.hip: 256-row pipelined tile).  See gemm_bf16.hip for the orientation: the accumulator
+// 128-row tile and the chooser; gemm_bf16_v2.hip: 128-row LDS-DMA tiles with split-K for the small launches; gemm_bf16_v5.hip /
+// gemm_v5_body.h: 256-row ping-pong tiles, also the conv3x3; gemm_bf16_v4.hip: 256 x 256 persistent ping-pong tiles).  See gemm_bf16.hip for the orientation: the accumulator
 // block acc[i][j] of v_mfma_f32_16x16x32_bf16 holds, per lane, features n = n_wave0 + 16 i + 4 (lane>>4) + {0..3}
 // of token m = m_wave0 + 16 j + (lane & 15).
 #pragma once

@@ -1,5 +1,6 @@
-// bf16 MFMA GEMM, 256 x 256 output tile, PING-PONG schedule of the two wave rows (round 2).  Same math, orientation,
-// swizzle and epilogue as gemm_bf16_v3.hip; what changes is how the eight waves share a CU.
+// bf16 MFMA GEMM, 256 x 256 output tile, PING-PONG schedule of the two wave rows (round 2): the large-N launches (N a multiple of 256).
+// Same math, orientation, swizzle and epilogue as the other LDS-DMA kernels (primitives: gemm_dma_loader.h); what changes is how the eight
+// waves share a CU.  (gemm_v3 below is the lock-step 256 x 256 kernel this one replaced; it is kept under tools/exp/gemm_bf16_v3.hip.)
 //
 // Why.  Measured in round 2 (profiles/r02_a_dma_stream_and_store_microbench.txt): the L2 -> LDS operand stream alone delivers a
 // 64-KB K tile in 0.73-0.79 us (83-90 GB/s per CU) and its 64 MFMAs per wave need ~1.0 us of matrix-pipe time, but the
@@ -39,6 +40,7 @@
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
 #include "gemm_forms.h"
+#include "gemm_dma_loader.h"
 
 #ifndef MX_EXP
 #define MX_EXP 0
@@ -48,25 +50,8 @@ namespace mx {
 
 constexpr int BM4 = 256;
 constexpr int BN4 = 256;
-constexpr int BK4 = 64;
-constexpr int HT_BYTES = 128 * BK4 * 2;        // one half-tile: 128 rows x 64 k = 16 KB
+constexpr int HT_BYTES = 128 * DMA_BK * 2;        // one half-tile: 128 rows x 64 k = 16 KB
 constexpr int NSLOT4 = 10;
-
-__device__ __forceinline__ int swz4(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void glds16_4(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-// raw barrier that neither the compiler's memory motion nor its instruction scheduler crosses
-#define MX_BAR()                                  \
-  do {                                            \
-    asm volatile("" ::: "memory");                \
-    __builtin_amdgcn_s_barrier();                 \
-    asm volatile("" ::: "memory");                \
-    __builtin_amdgcn_sched_barrier(0);            \
-  } while (0)
 
 #define MX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
@@ -98,7 +83,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
   const int mt = gemm_m_tiles(pk, BM4);         // grouped launch (gemm_args.h): the m-tiles of all problems
   const int nt = pk.N / BN4;
   const int total_tiles = mt * nt;
-  const int nk = pk.K / BK4;
+  const int nk = pk.K / DMA_BK;
   const char* abase = reinterpret_cast<const char*>(pk.a);   // grouped: the lowest of the problems' bases (launch_v4 checks the 32-bit reach)
   const char* wbase = reinterpret_cast<const char*>(pk.w);
   const int cs = tid & 7;
@@ -129,18 +114,18 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int row = (i * 512 + tid) >> 3;    // row of the half-tile this thread's chunk belongs to; slot cs holds chunk swz4(row, cs)
+      const int row = (i * 512 + tid) >> 3;    // row of the half-tile this thread's chunk belongs to; slot cs holds chunk swz(row, cs)
       if (c == 0 || c == 3) {                  // XH[q]: rows 64 w + r  <->  token 128 w + 64 q + r of the tile
         const int q = c == 3;
         const int m = tm * BM4 + 128 * (row >> 6) + 64 * q + (row & 63);
         const int mc = m < seg_m ? m : seg_m - 1;  // clamped rows are computed and discarded by the epilogue mask
         long in_row = mc;
         if (abr > 0) { const int b = mc / rpb; in_row = (long)b * abr + aro + (mc - b * rpb); }
-        c_off[c][i] = abyte + (unsigned)((in_row * pk.lda + swz4(row, cs) * 8) * 2);
+        c_off[c][i] = abyte + (unsigned)((in_row * pk.lda + swz(row, cs) * 8) * 2);
       } else {                                 // WH[h]: rows 32 w + r  <->  feature 64 w + 32 h + r of the tile
         const int h = c == 2;
         const int n = tn * BN4 + 64 * (row >> 5) + 32 * h + (row & 31);
-        c_off[c][i] = (unsigned)(((long)n * pk.K + swz4(row, cs) * 8) * 2);
+        c_off[c][i] = (unsigned)(((long)n * pk.K + swz(row, cs) * 8) * 2);
       }
     }
   };
@@ -148,14 +133,14 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
     char* st = smem + c_slot[c] * HT_BYTES;
     const char* base = (c == 0 || c == 3) ? abase : wbase;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) glds16_4(base + c_off[c][i], st + (i * 512 + wave * 64) * 16);
+    for (int i = 0; i < 2; ++i) glds16(base + c_off[c][i], st + (i * 512 + wave * 64) * 16);
     c_slot[c] = c_slot[c] >= NSLOT4 - 4 ? c_slot[c] - (NSLOT4 - 4) : c_slot[c] + 4;
   };
   // hot form: the cursor stays inside its tile (the caller guarantees it)
   auto advance_hot = [&](const int c) __attribute__((always_inline)) {
     ++c_kt[c];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) c_off[c][i] += BK4 * 2;
+    for (int i = 0; i < 2; ++i) c_off[c][i] += DMA_BK * 2;
   };
   auto advance = [&](const int c) __attribute__((always_inline)) {
     if (c_tile[c] >= total_tiles) return;      // parked
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
       return;
     }
 #pragma unroll
-    for (int i = 0; i < 2; ++i) c_off[c][i] += BK4 * 2;
+    for (int i = 0; i < 2; ++i) c_off[c][i] += DMA_BK * 2;
   };
 
   // ---- fragment addresses (bytes from the start of a half-tile): lane (fr, fq) reads row base + fr, chunk 4 ks + fq ----
@@ -177,22 +162,22 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
   unsigned xrd[2], wrd[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    xrd[ks] = (unsigned)(((64 * wm + fr) * BK4 + swz4(fr, ks * 4 + fq) * 8) * 2);
-    wrd[ks] = (unsigned)(((32 * wn + fr) * BK4 + swz4(fr, ks * 4 + fq) * 8) * 2);
+    xrd[ks] = (unsigned)(((64 * wm + fr) * DMA_BK + swz(fr, ks * 4 + fq) * 8) * 2);
+    wrd[ks] = (unsigned)(((32 * wn + fr) * DMA_BK + swz(fr, ks * 4 + fq) * 8) * 2);
   }
   auto read_x = [&](bf16x8 (&xf)[4][2], const int slot) __attribute__((always_inline)) {
     const char* s = smem + slot * HT_BYTES;
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) xf[jj][ks] = *reinterpret_cast<const bf16x8*>(s + xrd[ks] + jj * (16 * BK4 * 2));
+      for (int ks = 0; ks < 2; ++ks) xf[jj][ks] = *reinterpret_cast<const bf16x8*>(s + xrd[ks] + jj * (16 * DMA_BK * 2));
   };
   auto read_w = [&](bf16x8 (&wf)[2][2], const int slot) __attribute__((always_inline)) {
     const char* s = smem + slot * HT_BYTES;
 #pragma unroll
     for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) wf[ii][ks] = *reinterpret_cast<const bf16x8*>(s + wrd[ks] + ii * (16 * BK4 * 2));
+      for (int ks = 0; ks < 2; ++ks) wf[ii][ks] = *reinterpret_cast<const bf16x8*>(s + wrd[ks] + ii * (16 * DMA_BK * 2));
   };
   auto wrap = [](int s) __attribute__((always_inline)) { return s >= NSLOT4 ? s - NSLOT4 : s; };
 
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
   issue(3); advance(3);
   issue(0); advance(0);
   issue(1); advance(1);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // position 0 has landed (this thread's part)
+  wait_vmcnt<4>();                                   // position 0 has landed (this thread's part)
   MX_BAR();
 
   // LN: (mean, rstd) of the lane's eight tokens and the column sums of its 16 features for the NEXT tile, requested before the current tile's
@@ -285,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
       read_x(xf, wrap(rs + 3));
       issue(0); if constexpr (HOT) advance_hot(0); else advance(0);
       issue(1); if constexpr (HOT) advance_hot(1); else advance(1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // all but the two youngest half-tiles: the next stream position has landed
+      wait_vmcnt<4>();                                 // all but the two youngest half-tiles: the next stream position has landed
       MX_BAR();
       // ---- MB ----
       __builtin_amdgcn_s_setprio(1);
@@ -324,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v4_kernel(const GemmArgs pk) {
     MX_STAMP(stamp_i + 2);
     stamp_i += 3;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the past-the-end DMAs before the workgroup retires
+  wait_vmcnt<0>();                                 // drain the past-the-end DMAs before the workgroup retires
 }
 
 #if MX_EXP == 8

@@ -34,7 +34,7 @@ namespace mx {
 // VEC: the per-sample vectors (row bias, gate) are compiled in -- 40 registers of the epilogue; without them the QKV form does not spill
 template <int BN, int MI, bool CONV, int FEAT, bool GEGLU, bool VEC>
 __global__ __launch_bounds__(512, 2) void gemm_v5_kernel(const GemmArgs pk) {
-  constexpr int STAGE_ELEMS = (64 * MI + BN) * BK5;
+  constexpr int STAGE_ELEMS = (64 * MI + BN) * DMA_BK;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSTAGE5 * STAGE_ELEMS];
   int tm, tn;
   gemm_tile_of_block(blockIdx.x, gemm_m_tiles(pk, 64 * MI), pk.N / BN, pk.xcd_map, tm, tn);
