@@ -5,14 +5,15 @@
 // epilogue, flash attention (64-wide heads, here with the causal mask), GEMM epilogues (bias, residual, quick-GELU / GELU).
 //   encode(ids):  x = tok[ids] + pos;  per layer: x += out_proj(attn_causal(qkv(LN1 x)));  x += fc2(act(fc1(LN2 x)));
 //                 hidden = hidden_states[hidden_layer] ;  pooled = text_projection(LN_final(x_last)[eos])
+// Arena, weight lookup and the gemm wrapper: mx::PlanBase (plan_base.h).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <string>
-#include <unordered_map>
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
+#include "plan_base.h"
 
 namespace mx {
 int launch_clip_embed(hipStream_t s, const int* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* out, int rows, int L, int H, int vocab);
@@ -23,43 +24,12 @@ using mx::bf16_t;
 
 struct mx_clip {
   mx_clip_config cfg;
-  const char* blob = nullptr;
-  uint64_t blob_bytes = 0;
-  std::unordered_map<std::string, std::pair<uint64_t, uint64_t>> table;
+  mx::WeightTable weights;
 };
 
 namespace {
-struct Arena {
-  char* base; size_t cap; size_t top; size_t peak; bool dry;
-  void* alloc(size_t bytes) {
-    const size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > peak) peak = top;
-    if (dry) return (void*)(uintptr_t)(0x1000 + a);
-    return (top <= cap) ? base + a : nullptr;
-  }
-};
-
-struct Plan {
-  mx_clip* u; hipStream_t stream; Arena ar; int B; bool dry, lookup; std::string err;
-  bool ok() const { return err.empty(); }
-  bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
-  const void* w(const std::string& name, size_t bytes) {
-    if (dry && !lookup) return (const void*)(uintptr_t)0x1000;
-    auto it = u->table.find(name);
-    if (it == u->table.end()) { fail("missing weight '" + name + "'"); return nullptr; }
-    if (it->second.second != bytes) { fail("weight '" + name + "' has " + std::to_string(it->second.second) + " bytes, expected " + std::to_string(bytes)); return nullptr; }
-    return u->blob + it->second.first;
-  }
-  const bf16_t* wb(const std::string& n, size_t e) { return (const bf16_t*)w(n, e * 2); }
-  const float* wf(const std::string& n, size_t e) { return (const float*)w(n, e * 4); }
-  template <typename T> T* alloc(size_t elems) { T* p = (T*)ar.alloc(elems * sizeof(T)); if (!p) fail("workspace too small"); return p; }
-  bool gemm(mx_gemm_desc& d) {
-    if (!ok()) return false;
-    if (dry) return true;
-    if (mx_gemm(stream, &d)) return fail(std::string("gemm: ") + mx_last_error());
-    return true;
-  }
+struct Plan : mx::PlanBase {
+  mx_clip* u; int B;
   bool linear(const bf16_t* a, const std::string& stem, void* c, int M, int N, int K, const void* residual = nullptr, int flags = 0, bool bias = true) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
     d.a = a; d.lda = K; d.w = wb(stem + ".weight", (size_t)N * K); d.bias = bias ? wf(stem + ".bias", N) : nullptr;
@@ -130,14 +100,12 @@ int run_impl(mx_clip* u, void* stream, const int* ids, void* hidden_out, void* p
              size_t* peak, bool want_pooled) {
   MX_CHECK(u != nullptr, "clip: null handle");
   MX_CHECK(batch > 0, "clip: bad batch");
-  if (!dry) MX_CHECK(ids && ws && u->blob && (hidden_out || pooled_out), "clip: null operand or weights not set");
+  if (!dry) MX_CHECK(ids && ws && u->weights.blob && (hidden_out || pooled_out), "clip: null operand or weights not set");
   Plan p;
-  p.u = u; p.stream = (hipStream_t)stream; p.B = batch; p.dry = dry; p.lookup = lookup;
-  p.ar.base = (char*)ws; p.ar.cap = ws_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = dry;
+  p.u = u; p.B = batch; p.lookup = lookup;
+  if (dry) p.begin_dry(u->weights); else p.begin(u->weights, (hipStream_t)stream, ws, ws_bytes);
   const bool okr = p.run(ids, dry ? (void*)16 : hidden_out, dry ? (want_pooled ? (void*)16 : nullptr) : pooled_out);
-  if (peak) *peak = p.ar.peak;
-  if (!okr) { mx::set_error(p.err); return 1; }
-  return 0;
+  return p.finish(okr, peak);
 }
 }  // namespace
 
@@ -155,14 +123,8 @@ extern "C" mx_clip* mx_clip_create(const mx_clip_config* c) {
 }
 extern "C" void mx_clip_destroy(mx_clip* u) { delete u; }
 extern "C" int mx_clip_set_weights(mx_clip* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n) {
-  MX_CHECK(u && blob && table && n > 0, "clip_set_weights: bad arguments");
-  u->table.clear();
-  for (int i = 0; i < n; ++i) {
-    MX_CHECK(table[i].name != nullptr && table[i].offset % 16 == 0 && table[i].offset + table[i].bytes <= blob_bytes, "clip_set_weights: bad entry");
-    u->table[table[i].name] = {table[i].offset, table[i].bytes};
-  }
-  u->blob = (const char*)blob; u->blob_bytes = blob_bytes;
-  return 0;
+  MX_CHECK(u != nullptr, "clip_set_weights: null handle");
+  return u->weights.set("clip_set_weights", blob, blob_bytes, table, n);
 }
 extern "C" size_t mx_clip_workspace_bytes(const mx_clip* u, int batch) {
   size_t peak = 0;
@@ -170,7 +132,7 @@ extern "C" size_t mx_clip_workspace_bytes(const mx_clip* u, int batch) {
   return peak + 4096;
 }
 extern "C" int mx_clip_validate(const mx_clip* u, int batch) {
-  MX_CHECK(u && u->blob, "clip_validate: weights not set");
+  MX_CHECK(u && u->weights.blob, "clip_validate: weights not set");
   return run_impl(const_cast<mx_clip*>(u), nullptr, nullptr, nullptr, nullptr, batch, nullptr, 0, true, true, nullptr, u->cfg.projection_dim > 0);
 }
 extern "C" int mx_clip_encode(mx_clip* u, void* stream, const int32_t* ids, void* hidden_out, void* pooled_out, int batch, void* workspace,

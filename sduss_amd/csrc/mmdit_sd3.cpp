@@ -13,23 +13,23 @@
 //     attention of attention.py:347-350 is a single kernel launch with no torch.cat; to_out / to_add_out read their
 //     token ranges back through the loader's row remap;
 //   * PatchEmbed's 2x2 stride-2 conv is an im2col + GEMM whose epilogue adds bias and the cropped positional table.
+// Host scaffold (arena, weight lookup, groups, block-cache bookkeeping, the forward driver): plan_base.h; this file holds the MMDiT's own plan,
+// its checks and hooks (struct Model) and the extern "C" entry points, each of which describes its forward as an mx::ForwardCall.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
-#include <map>
-
 #include "graph_cache.h"
-#include "pp_exchange.h"
 #include "patch_cache.h"
+#include "plan_base.h"
 
 namespace mx {
 int launch_patchify(hipStream_t s, const void* in, int dtype, void* out, int B, int C, int H, int W, int ps);
@@ -37,38 +37,22 @@ int launch_unpatchify(hipStream_t s, const void* in, void* out, int dtype, int B
 int launch_crop_pos(hipStream_t s, const void* table, void* out, int m, int h, int w, int d);
 int launch_sinus_embed(hipStream_t s, const float* t, void* out, int B, int dim);
 int launch_sq_diff_partial(hipStream_t s, const void* a, const void* b, long elems_per_sample, int B, double* partial, const int* slot = nullptr);
-int launch_copy_rows(hipStream_t s, void* batch, void* slotted, size_t bytes_per_sample, int B, const int* slot, int scatter);
 }  // namespace mx
 
 using mx::bf16_t;
 
 struct mx_mmdit {
   mx_mmdit_config cfg;
-  const char* blob = nullptr;
-  uint64_t blob_bytes = 0;
-  std::unordered_map<std::string, std::pair<uint64_t, uint64_t>> table;
+  mx::WeightTable weights;
   mx::GraphCache graphs;   // hipGraph replay of the forward, keyed by its arguments (graph_cache.h)
   std::map<std::vector<long>, std::vector<size_t>> pp_sizes;   // recorded exchange sizes of the patch-parallel plan per shape (as in unet_sdxl.cpp)
 };
 
 namespace {
 
-struct Arena {
-  char* base; size_t cap; size_t top; size_t peak; bool dry;
-  void* alloc(size_t bytes) {
-    const size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > peak) peak = top;
-    if (dry) return (void*)(uintptr_t)(0x1000 + a);
-    return (top <= cap) ? base + a : nullptr;
-  }
-};
-
-struct Plan {
+struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchange, block-cache bookkeeping: plan_base.h)
   mx_mmdit* u;
-  hipStream_t stream;
-  Arena ar;
-  int B, H, W, Lt;                 // B = samples of ALL groups; H, W = the first group's latent size (the only one unless mixed)
+  int Lt;
   // Mixed-resolution batch (mx_mmdit_forward_mixed): the requests of every resolution present in ONE launch sequence.  A group = the samples of
   // one resolution.  The image stream is the groups' token rows one after the other, the text stream is per sample (same length everywhere);
   // the joint q|k / V^T / O buffers hold each group's [image ; text] sequences at its own length.  Per-token ops are single launches; the ops
@@ -76,10 +60,6 @@ struct Plan {
   // joint sequence back -- are GROUPED launches (mx_gemm_seg, mx_attention_prescaled_grouped, mx_layernorm_mod_grouped).  The reference
   // re-chunks the tokens of all resolutions into one batch (modules/utils.py:86-122) and regroups them per latent before attention
   // (attention.py:300-372).
-  int ng = 1;
-  int gB[MX_MAX_SEGS], gH[MX_MAX_SEGS], gW[MX_MAX_SEGS], gb0[MX_MAX_SEGS];
-  const void* g_lat[MX_MAX_SEGS]; void* g_out[MX_MAX_SEGS];
-  void set_single(int batch, int h, int w, const void* lat, void* out) { ng = 1; gB[0] = batch; gH[0] = h; gW[0] = w; gb0[0] = 0; g_lat[0] = lat; g_out[0] = out; B = batch; H = h; W = w; }
   typedef std::function<void(int, mx_gemm_seg&)> SegFill;      // fills problem g of a grouped GEMM
   mx_gemm_seg seg_buf[MX_MAX_SEGS];
   const bool* act = nullptr;        // cached mixed batch: the grouped launch covers these resolution groups only (nullptr: all)
@@ -90,12 +70,8 @@ struct Plan {
     for (int g = 0; g < ng; ++g) if (!act || act[g]) fill(g, seg_buf[n++]);
     d.segs = seg_buf; d.n_segs = n;
   }
-  bool dry, lookup = false;
-  bool mute = false;               // block-skip cache: the block is reused, nothing of it is launched
-  bool quiet() const { return dry || mute; }
   // patch parallelism (mx_mmdit_forward_pp; distrifuser models/distri_sd3_transformer_pp.py:87-97, modules/pp/attn.py:202-277): this rank owns
   // the image tokens of H (local) latent rows; the text stream is computed by every rank; K / V^T of the image tokens are all-gathered
-  mx::PPExchange px;
   bool is_pp() const { return px.world > 1; }
   bool all_gather(const void* send, void* recv, size_t bytes_per_rank) {
     if (!ok()) return false;
@@ -129,53 +105,11 @@ struct Plan {
     const size_t nc = pcm_ncmax();
     return ((nc * 64 * sizeof(double) + 2 * (size_t)pcm_slots * sizeof(mx::PcSample) + 4 * nc * sizeof(mx::PcRange)) + 255) & ~(size_t)255;
   }
-  mx_block_cache* bc = nullptr;    // mx_mmdit_forward_cached
   size_t bc_bytes = 0;             // state bytes the plan needs (also the dry answer of mx_mmdit_block_cache_bytes)
   unsigned long long blocks_run = 0;
-  std::vector<float> h_timesteps;
-  int bc_rows = 0;                 // samples a state tensor holds: the batch, or bc->n_slots with one slot per request
-  const int* bc_dslot = nullptr;   // device copy of bc->slots
-  std::vector<unsigned char> bc_valid;
-  bool bc_all_valid = false, bc_any_valid = false;
-  static size_t bc_scratch_bytes(int rows) { return ((size_t)rows * 64 * sizeof(double) + (size_t)rows * sizeof(int) + 255) & ~(size_t)255; }
-  bool bc_store(char* region, const void* t, size_t per_sample_bytes) {
-    if (bc_dslot) { if (mx::launch_copy_rows(stream, (void*)t, region, per_sample_bytes, B, bc_dslot, 1)) return fail(mx_last_error()); return true; }
-    if (hipMemcpyAsync(region, t, per_sample_bytes * B, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("block cache: copy into the state failed");
-    return true;
-  }
-  bool bc_load(void* t, char* region, size_t per_sample_bytes) {
-    if (bc_dslot) { if (mx::launch_copy_rows(stream, t, region, per_sample_bytes, B, bc_dslot, 0)) return fail(mx_last_error()); return true; }
-    if (hipMemcpyAsync(t, region, per_sample_bytes * B, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("block cache: copy out of the state failed");
-    return true;
-  }
-  const char* stage = nullptr; void* stage_out = nullptr; size_t stage_bytes = 0; bool stage_hit = false;
-  std::string err;
+  static constexpr int kBcPartRows = 1, kBcTables = 1;     // head of the state: one row of partial sums, the slot table
+  static size_t bc_scratch_bytes(int rows) { return bc_head_bytes(kBcPartRows, kBcTables, rows); }
 
-  bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
-  bool ok() const { return err.empty(); }
-  const void* w(const std::string& name, size_t expect_bytes) {
-    if (dry && !lookup) return (const void*)(uintptr_t)0x1000;
-    auto it = u->table.find(name);
-    if (it == u->table.end()) { fail("missing weight '" + name + "'"); return nullptr; }
-    if (it->second.second != expect_bytes) {
-      fail("weight '" + name + "' has " + std::to_string(it->second.second) + " bytes, expected " + std::to_string(expect_bytes));
-      return nullptr;
-    }
-    return u->blob + it->second.first;
-  }
-  const bf16_t* wb(const std::string& name, size_t elems) { return (const bf16_t*)w(name, elems * 2); }
-  const float* wf(const std::string& name, size_t elems) { return (const float*)w(name, elems * 4); }
-  template <typename T> T* alloc(size_t elems) {
-    T* p = (T*)ar.alloc(elems * sizeof(T));
-    if (!p) fail("workspace too small");
-    return p;
-  }
-  bool gemm(mx_gemm_desc& d) {
-    if (!ok()) return false;
-    if (quiet()) return true;
-    if (mx_gemm(stream, &d)) return fail(std::string("gemm: ") + mx_last_error());
-    return true;
-  }
   // C = A W^T + bias with the optional fused pieces
   bool linear(const void* a, int lda, const std::string& name, void* c, int ldc, int M, int N, int K, int flags = 0,
               const void* residual = nullptr, int ldr = 0, const float* gate = nullptr, int ldg = 0, int rows_per_batch = 0,
@@ -232,14 +166,6 @@ struct Plan {
       return fail(std::string("attention: ") + mx_last_error());
     return true;
   }
-  void dump(const std::string& name, const bf16_t* t, size_t elems) {
-    if (!stage || quiet() || !ok() || stage_hit) return;
-    if (name != stage) return;
-    if (elems * 2 > stage_bytes) { fail("stage buffer too small for '" + name + "'"); return; }
-    if (hipMemcpyAsync(stage_out, t, elems * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess) fail("stage copy failed");
-    stage_hit = true;
-  }
-
   bool run(const void* latents, int io_dtype, const float* timesteps, const void* ehs, const void* pooled, void* outp) {
     const mx_mmdit_config& c = u->cfg;
     const int d = c.num_attention_heads * 64;
@@ -662,83 +588,39 @@ int check_cfg(const mx_mmdit_config* c) {
   return 0;
 }
 
-int forward_impl(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
-                 const void* pooled, void* out, int batch, int H, int W, int ctx_len, void* workspace, size_t workspace_bytes,
-                 const char* stage, void* stage_out, size_t stage_bytes, bool dry, size_t* peak, bool lookup = false,
-                 const mx_pp_comm* comm = nullptr, const mx_pp_stale* stale = nullptr, size_t* state_need = nullptr,
-                 const mx_unet_group* groups = nullptr, int n_groups = 0) {
-  MX_CHECK(u != nullptr, "mmdit: null handle");
-  if (groups) {        // mixed-resolution batch: `batch`, H, W describe the first group; every group is validated here
-    MX_CHECK(n_groups >= 1 && n_groups <= MX_MAX_SEGS && comm == nullptr, "mmdit: a mixed batch has 1..MX_MAX_SEGS resolution groups and does not run patch-parallel");
-    batch = groups[0].batch; H = groups[0].H; W = groups[0].W; latents = groups[0].latents; out = groups[0].out;
-    for (int g = 0; g < n_groups; ++g) {
-      MX_CHECK(groups[g].batch > 0 && groups[g].H > 0 && groups[g].W > 0 && groups[g].H % u->cfg.patch_size == 0 && groups[g].W % u->cfg.patch_size == 0 &&
-               groups[g].H / u->cfg.patch_size <= u->cfg.pos_embed_max_size && groups[g].W / u->cfg.patch_size <= u->cfg.pos_embed_max_size, "mmdit: bad group shape");
-      MX_CHECK(dry || (groups[g].latents && groups[g].out), "mmdit: null group operand");
-    }
+// what run_forward (plan_base.h) needs to know of the MMDiT
+struct Model {
+  const char* name = "mmdit";
+  static int check_shape(const mx_mmdit* u, int H, int W, const char* msg) {
+    const int ps = u->cfg.patch_size;
+    MX_CHECK(H % ps == 0 && W % ps == 0, msg);
+    MX_CHECK(H / ps <= u->cfg.pos_embed_max_size && W / ps <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
+    return 0;
   }
-  MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "mmdit: bad shape");
-  MX_CHECK(H % u->cfg.patch_size == 0 && W % u->cfg.patch_size == 0, "mmdit: H, W must be multiples of patch_size");
-  MX_CHECK(H / u->cfg.patch_size <= u->cfg.pos_embed_max_size && W / u->cfg.patch_size <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
-  const bool pp = comm != nullptr && comm->world > 1;
-  if (pp) MX_CHECK(comm->rank >= 0 && comm->rank < comm->world && (dry || comm->all_gather != nullptr), "mmdit pp: bad communicator");
-  if (!dry) {
-    MX_CHECK(latents && timesteps && ehs && pooled && out && workspace, "mmdit: null operand");
-    MX_CHECK(u->blob != nullptr, "mmdit: weights not set");
-    MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
+  int check(const mx_mmdit* u, const mx::ForwardCall& c) {
+    for (int g = 1; c.groups && g < c.n_groups; ++g) if (check_shape(u, c.groups[g].H, c.groups[g].W, "mmdit: bad group shape")) return 1;
+    if (check_shape(u, c.H, c.W, "mmdit: H, W must be multiples of patch_size")) return 1;
+    MX_CHECK(c.dry || c.pooled, "mmdit: null operand");
+    return 0;
   }
-  std::string err;
-  size_t plan_peak = 0;
-  auto enqueue = [&](hipStream_t s) {
-    Plan p;
-    p.u = u; p.stream = s; p.Lt = ctx_len;
-    p.set_single(batch, H, W, latents, out);
-    if (groups) {
-      p.ng = n_groups; p.B = 0;
-      for (int g = 0; g < n_groups; ++g) {
-        p.gB[g] = groups[g].batch; p.gH[g] = groups[g].H; p.gW[g] = groups[g].W; p.gb0[g] = p.B; p.g_lat[g] = groups[g].latents; p.g_out[g] = groups[g].out;
-        p.B += groups[g].batch;
-      }
-    }
-    p.dry = dry; p.lookup = lookup; p.stage = stage; p.stage_out = stage_out; p.stage_bytes = stage_bytes;
-    p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = dry;
-    if (pp) p.px.set(comm, stale);
-    if (pp && stale) {      // the state layout (exchanges dealt into chunks, pp_exchange.h) from a host-only recording walk of the same plan
-      const std::vector<long> lk = {(long)batch, (long)H, (long)W, (long)ctx_len, (long)comm->world, (long)io_dtype};
-      auto it = u->pp_sizes.find(lk);
-      if (it == u->pp_sizes.end()) {
-        std::vector<size_t> sizes;
-        Plan q = p;
-        q.dry = true; q.ar.dry = true; q.ar.base = nullptr; q.ar.cap = 0; q.stage = nullptr; q.lookup = false;
-        q.px.record = &sizes;
-        if (!q.run(nullptr, io_dtype, nullptr, nullptr, nullptr, nullptr)) { err = q.err; return false; }
-        it = u->pp_sizes.emplace(lk, std::move(sizes)).first;
-      }
-      p.px.build_layout(it->second);
-    }
-    const bool okr = p.run(latents, io_dtype, timesteps, ehs, pooled, out);
-    plan_peak = p.ar.peak;
-    if (state_need) *state_need = p.px.state_top;
-    if (!okr) err = p.err;
-    return okr;
-  };
-  bool okr;
-  if (dry || stage || pp) {     // (the all-gather callbacks of a patch-parallel forward cannot be captured)
-    okr = enqueue((hipStream_t)stream);
-  } else {
-    std::vector<uint64_t> key = {(uint64_t)batch, (uint64_t)H, (uint64_t)W, (uint64_t)ctx_len, (uint64_t)io_dtype,
-                                 (uint64_t)(uintptr_t)latents, (uint64_t)(uintptr_t)timesteps, (uint64_t)(uintptr_t)ehs,
-                                 (uint64_t)(uintptr_t)pooled, (uint64_t)(uintptr_t)out, (uint64_t)(uintptr_t)workspace,
-                                 (uint64_t)workspace_bytes, (uint64_t)(uintptr_t)u->blob};
-    for (int g = 1; g < n_groups; ++g)
-      for (uint64_t v : {(uint64_t)groups[g].batch, (uint64_t)groups[g].H, (uint64_t)groups[g].W, (uint64_t)(uintptr_t)groups[g].latents, (uint64_t)(uintptr_t)groups[g].out})
-        key.push_back(v);
-    okr = u->graphs.run((hipStream_t)stream, key, enqueue, /*capture_on_miss=*/n_groups <= 1);
-  }
-  if (peak) *peak = plan_peak;
-  if (!okr) { mx::set_error(err); return 1; }
-  return 0;
+  void begin(mx_mmdit*, const mx::ForwardCall&) {}
+  void end(mx_mmdit*, const mx::ForwardCall&, bool) {}
+  void setup(Plan& p, mx_mmdit* u, const mx::ForwardCall& c) { p.u = u; p.Lt = c.ctx_len; }
+  bool run(Plan& p, const mx::ForwardCall& c) { return p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.pooled, c.out); }
+  std::vector<uint64_t> key_scalars(const mx::ForwardCall&) { return {}; }
+  std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.pooled}; }
+};
+int forward_impl(const mx_mmdit* u, const mx::ForwardCall& c) {
+  Model m;
+  return mx::run_forward<Plan>(const_cast<mx_mmdit*>(u), c, m);
 }
+// the call of a host-only walk of the plan at one shape
+mx::ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
+  mx::ForwardCall c;
+  c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
+  return c;
+}
+mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
 
 }  // namespace
 
@@ -751,80 +633,72 @@ extern "C" mx_mmdit* mx_mmdit_create(const mx_mmdit_config* cfg) {
 extern "C" void mx_mmdit_destroy(mx_mmdit* u) { delete u; }
 
 extern "C" int mx_mmdit_set_weights(mx_mmdit* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n) {
-  MX_CHECK(u && blob && table && n > 0, "mmdit_set_weights: bad arguments");
+  MX_CHECK(u != nullptr, "mmdit_set_weights: null handle");
   u->graphs.clear();    // captured graphs hold addresses resolved through the old table
-  u->table.clear();
-  for (int i = 0; i < n; ++i) {
-    MX_CHECK(table[i].name != nullptr, "mmdit_set_weights: null name");
-    MX_CHECK(table[i].offset % 16 == 0, "mmdit_set_weights: tensor offsets must be 16-byte aligned");
-    MX_CHECK(table[i].offset + table[i].bytes <= blob_bytes, "mmdit_set_weights: entry exceeds blob");
-    u->table[table[i].name] = {table[i].offset, table[i].bytes};
-  }
-  u->blob = (const char*)blob;
-  u->blob_bytes = blob_bytes;
-  return 0;
+  return u->weights.set("mmdit_set_weights", blob, blob_bytes, table, n);
 }
 
 extern "C" size_t mx_mmdit_workspace_bytes(const mx_mmdit* u, int batch, int H, int W, int ctx_len) {
   if (!u) return 0;
   size_t peak = 0;
-  if (forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, batch, H, W, ctx_len,
-                   nullptr, 0, nullptr, nullptr, 0, true, &peak))
-    return 0;
-  return peak + 4096;
+  mx::ForwardCall c = dry_call(batch, H, W, ctx_len);
+  c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 4096;
 }
 
 extern "C" int mx_mmdit_validate(const mx_mmdit* u, int batch, int H, int W, int ctx_len) {
-  MX_CHECK(u && u->blob, "mmdit_validate: weights not set");
-  return forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, batch, H, W, ctx_len,
-                      nullptr, 0, nullptr, nullptr, 0, true, nullptr, true);
+  MX_CHECK(u && u->weights.blob, "mmdit_validate: weights not set");
+  mx::ForwardCall c = dry_call(batch, H, W, ctx_len);
+  c.lookup = true;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_mmdit_forward(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
                                 const void* ehs, const void* pooled, void* out, int batch, int H, int W, int ctx_len,
                                 void* workspace, size_t workspace_bytes) {
-  return forward_impl(u, stream, latents, io_dtype, timesteps, ehs, pooled, out, batch, H, W, ctx_len, workspace, workspace_bytes,
-                      nullptr, nullptr, 0, false, nullptr);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
+  c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return forward_impl(u, c);
 }
 
 /* ---- mixed-resolution batch: ONE launch sequence over the requests of every resolution present (see mx_unet_forward_mixed) ---- */
 extern "C" size_t mx_mmdit_workspace_bytes_mixed(const mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len) {
   if (!u || !groups || n_groups < 1 || n_groups > MX_MAX_SEGS) return 0;
   size_t peak = 0;
-  if (forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, ctx_len, nullptr, 0, nullptr, nullptr, 0,
-                   true, &peak, false, nullptr, nullptr, nullptr, groups, n_groups))
-    return 0;
-  return peak + 4096;
+  mx::ForwardCall c = dry_call(0, 0, 0, ctx_len);
+  c.groups = groups; c.n_groups = n_groups; c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 4096;
 }
 
 extern "C" int mx_mmdit_forward_mixed(mx_mmdit* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                       const void* encoder_hidden_states, const void* pooled_projections, int ctx_len, void* workspace,
                                       size_t workspace_bytes) {
   MX_CHECK(groups != nullptr, "mmdit_forward_mixed: null groups");
-  return forward_impl(u, stream, nullptr, io_dtype, timesteps, encoder_hidden_states, pooled_projections, nullptr, 0, 0, 0, ctx_len, workspace,
-                      workspace_bytes, nullptr, nullptr, 0, false, nullptr, false, nullptr, nullptr, nullptr, groups, n_groups);
+  mx::ForwardCall c;
+  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = encoder_hidden_states;
+  c.pooled = pooled_projections; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return forward_impl(u, c);
 }
 
 /* ---- patch parallelism (distrifuser models/distri_sd3_transformer_pp.py, modules/pp/attn.py:202-277) ---- */
 extern "C" size_t mx_mmdit_workspace_bytes_pp(const mx_mmdit* u, int batch, int H_local, int W, int ctx_len, int world) {
   if (!u) return 0;
   size_t peak = 0;
-  mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr;
-  if (forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, nullptr, 0,
-                   nullptr, nullptr, 0, true, &peak, false, &c))
-    return 0;
-  return peak + 4096;
+  const mx_pp_comm comm = sizing_comm(world);
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = &comm; c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 4096;
 }
 
 extern "C" size_t mx_mmdit_pp_state_bytes(const mx_mmdit* u, int batch, int H_local, int W, int ctx_len, int world) {
   if (!u) return 0;
   size_t need = 0;
-  mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr;
+  const mx_pp_comm comm = sizing_comm(world);
   mx_pp_stale st{}; st.mode = MX_PP_WARMUP;
-  if (forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, nullptr, 0,
-                   nullptr, nullptr, 0, true, nullptr, false, &c, &st, &need))
-    return 0;
-  return need + 256;
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = &comm; c.stale = &st; c.state_need = &need;
+  return forward_impl(u, c) ? 0 : need + 256;
 }
 
 extern "C" int mx_mmdit_forward_pp(mx_mmdit* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
@@ -836,14 +710,18 @@ extern "C" int mx_mmdit_forward_pp(mx_mmdit* u, void* stream, const void* latent
     MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "mmdit_forward_pp: state must be 256-byte aligned device memory");
     MX_CHECK(stale->mode != MX_PP_STALE || stale->all_gather_async != nullptr, "mmdit_forward_pp: a stale step needs all_gather_async");
   }
-  return forward_impl(u, stream, latents_local, io_dtype, timesteps, ehs, pooled, out_local, batch, H_local, W, ctx_len, workspace, workspace_bytes,
-                      nullptr, nullptr, 0, false, nullptr, false, comm, stale);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
+  c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.comm = comm; c.stale = stale;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_mmdit_pp_comm_plan(const mx_mmdit* u, int batch, int H_local, int W, int ctx_len, const mx_pp_comm* comm) {
   MX_CHECK(u && comm && comm->all_gather, "mmdit_pp_comm_plan: bad arguments");
-  return forward_impl(const_cast<mx_mmdit*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, nullptr, 0,
-                      nullptr, nullptr, 0, true, nullptr, false, comm);
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = comm;
+  return forward_impl(u, c);
 }
 
 /* ---- the cache at the reference's unit (token chunks) over a mixed batch in ONE launch sequence (include/mxdenoise.h) ---- */
@@ -857,8 +735,8 @@ int pcm_setup(Plan& p, mx_mmdit* u, const mx_unet_group* groups, int n_groups, i
   MX_CHECK(cache && cache->n_slots > 0 && cache->max_h > 0 && cache->max_w > 0 && cache->max_h % patch == 0 && cache->max_w % patch == 0,
            "mmdit_forward_cached_mixed: cache->n_slots, max_h, max_w (multiples of the patch) are required");
   MX_CHECK(ctx_len > 0, "mmdit: bad shape");
-  p.u = u; p.Lt = ctx_len; p.dry = dry;
-  p.ng = n_groups; p.B = 0;
+  p.u = u; p.Lt = ctx_len;
+  p.set_groups(groups, n_groups);
   p.pcm = true; p.pcm_patch = patch; p.pcm_slots = cache->n_slots; p.pcm_maxh = cache->max_h; p.pcm_maxw = cache->max_w;
   p.pcm_img.clear(); p.pcm_ctx.clear(); p.pcm_chunks.clear(); p.pcm_chunk_b.clear(); p.pcm_chunk_g.clear();
   long long row0 = 0;
@@ -868,11 +746,10 @@ int pcm_setup(Plan& p, mx_mmdit* u, const mx_unet_group* groups, int n_groups, i
     MX_CHECK(groups[g].H <= cache->max_h && groups[g].W <= cache->max_w, "mmdit_forward_cached_mixed: a group is larger than the state rows (max_h, max_w)");
     MX_CHECK(groups[g].H / ps <= u->cfg.pos_embed_max_size && groups[g].W / ps <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
     MX_CHECK(dry || (groups[g].latents && groups[g].out), "mmdit: null group operand");
-    p.gB[g] = groups[g].batch; p.gH[g] = groups[g].H; p.gW[g] = groups[g].W; p.gb0[g] = p.B; p.g_lat[g] = groups[g].latents; p.g_out[g] = groups[g].out;
     const int L = (groups[g].H / ps) * (groups[g].W / ps), nc = (groups[g].H / patch) * (groups[g].W / patch);
     MX_CHECK(L % nc == 0, "mmdit_forward_cached_mixed: the tokens of a latent must split into equal chunks");
     for (int k = 0; k < groups[g].batch; ++k) {
-      const int b = p.B + k;
+      const int b = p.gb0[g] + k;
       const int slot = (!dry && cache->slots) ? cache->slots[b] : b;
       p.pcm_img.push_back(mx::PcSample{row0, L, 1, slot, 1});
       p.pcm_ctx.push_back(mx::PcSample{(long long)b * ctx_len, ctx_len, 1, slot, 1});
@@ -882,19 +759,23 @@ int pcm_setup(Plan& p, mx_mmdit* u, const mx_unet_group* groups, int n_groups, i
       }
       row0 += L;
     }
-    p.B += groups[g].batch;
   }
-  p.H = groups[0].H; p.W = groups[0].W;
   p.pcm_nc = (int)p.pcm_chunks.size();
   MX_CHECK(p.B <= cache->n_slots, "mmdit_forward_cached_mixed: more samples than state rows (n_slots)");
   return 0;
 }
-size_t pcm_dry(const mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len, int patch, const mx_block_cache* sizing, bool want_state) {
+// a host-only walk of a plan whose cache mode the caller has set up: sizes against `sizing`, no launches
+bool dry_walk(Plan& p, const mx_mmdit* u, mx_block_cache* sizing) {
+  p.u = const_cast<mx_mmdit*>(u);
+  p.begin_dry(u->weights);
+  p.bc = sizing;
+  if (p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr)) return true;
+  mx::set_error(p.err);
+  return false;
+}
+size_t pcm_dry(const mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len, int patch, mx_block_cache* sizing, bool want_state) {
   Plan p;
-  if (pcm_setup(p, const_cast<mx_mmdit*>(u), groups, n_groups, ctx_len, patch, sizing, true)) return 0;
-  p.stream = nullptr; p.ar.base = nullptr; p.ar.cap = 0; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = true;
-  p.bc = const_cast<mx_block_cache*>(sizing);
-  if (!p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr)) { mx::set_error(p.err); return 0; }
+  if (pcm_setup(p, const_cast<mx_mmdit*>(u), groups, n_groups, ctx_len, patch, sizing, true) || !dry_walk(p, u, sizing)) return 0;
   return want_state ? p.bc_bytes + 256 : p.ar.peak + 256;
 }
 }  // namespace
@@ -918,27 +799,18 @@ extern "C" size_t mx_mmdit_workspace_bytes_cached_mixed(const mx_mmdit* u, const
 extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                              const void* ehs, const void* pooled, int ctx_len, int patch, void* workspace, size_t workspace_bytes,
                                              mx_block_cache* cache) {
-  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, "mmdit_forward_cached_mixed: cache with predict, state, slots and slot_valid is required");
-  MX_CHECK(((uintptr_t)cache->state & 255) == 0, "mmdit_forward_cached_mixed: cache->state must be 256-byte aligned");
+  const std::string who = "mmdit_forward_cached_mixed";
+  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, who + ": cache with predict, state, slots and slot_valid is required");
+  MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
   if (pcm_setup(p, u, groups, n_groups, ctx_len, patch, cache, false)) return 1;
   MX_CHECK(timesteps && ehs && pooled && workspace, "mmdit: null operand");
-  MX_CHECK(u->blob != nullptr, "mmdit: weights not set");
+  MX_CHECK(u->weights.blob != nullptr, "mmdit: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
   const int B = p.B;
-  std::vector<char> seen(cache->n_slots, 0);
-  p.bc_valid.assign(B, 0);
-  p.bc_all_valid = true; p.bc_any_valid = false;
-  for (int b = 0; b < B; ++b) {
-    MX_CHECK(cache->slots[b] >= 0 && cache->slots[b] < cache->n_slots && !seen[cache->slots[b]], "mmdit_forward_cached_mixed: slots must be distinct and inside [0, n_slots)");
-    seen[cache->slots[b]] = 1;
-    p.bc_valid[b] = cache->slot_valid[b] ? 1 : 0;
-    p.bc_all_valid = p.bc_all_valid && p.bc_valid[b]; p.bc_any_valid = p.bc_any_valid || p.bc_valid[b];
-  }
-  p.stream = (hipStream_t)stream;
-  p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = false;
-  p.bc = cache;
-  MX_CHECK(p.pcm_head_bytes() <= cache->state_bytes, "mmdit_forward_cached_mixed: state buffer too small");
+  if (p.bc_begin_slots(who, cache, B)) return 1;
+  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
+  MX_CHECK(p.pcm_head_bytes() <= cache->state_bytes, who + ": state buffer too small");
   const size_t ncm = p.pcm_ncmax();
   char* hp = (char*)cache->state;
   p.pcm_dpart = (double*)hp; hp += ncm * 64 * sizeof(double);
@@ -946,20 +818,14 @@ extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx
   p.pcm_dctx = (mx::PcSample*)hp; hp += (size_t)p.pcm_slots * sizeof(mx::PcSample);
   p.pcm_dchunks = (mx::PcRange*)hp; hp += ncm * sizeof(mx::PcRange);
   p.pcm_dtmp = (mx::PcRange*)hp;
-  p.h_timesteps.resize(B);
-  if (hipMemcpyAsync(p.pcm_dimg, p.pcm_img.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) != hipSuccess ||
-      hipMemcpyAsync(p.pcm_dctx, p.pcm_ctx.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) != hipSuccess ||
-      hipMemcpyAsync(p.pcm_dchunks, p.pcm_chunks.data(), (size_t)p.pcm_nc * sizeof(mx::PcRange), hipMemcpyHostToDevice, p.stream) != hipSuccess ||
-      hipMemcpyAsync(p.h_timesteps.data(), timesteps, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, p.stream) != hipSuccess ||
-      hipStreamSynchronize(p.stream) != hipSuccess) {
-    mx::set_error("mmdit_forward_cached_mixed: moving the tables failed");
-    return 1;
-  }
+  MX_CHECK(hipMemcpyAsync(p.pcm_dimg, p.pcm_img.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+           hipMemcpyAsync(p.pcm_dctx, p.pcm_ctx.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+           hipMemcpyAsync(p.pcm_dchunks, p.pcm_chunks.data(), (size_t)p.pcm_nc * sizeof(mx::PcRange), hipMemcpyHostToDevice, p.stream) == hipSuccess,
+           who + ": moving the tables failed");
+  if (p.bc_read_timesteps(who, timesteps, B)) return 1;
   const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, pooled, groups[0].out);
-  cache->blocks_run = (unsigned)(p.blocks_run & 0xffffffffull); cache->blocks_run_hi = (unsigned)(p.blocks_run >> 32);
   cache->patches_asked = p.pcm_asked; cache->patches_total = p.pcm_total;
-  if (!okr) { mx::set_error(p.err); return 1; }
-  return 0;
+  return p.bc_finish(okr, p.blocks_run);
 }
 
 /* ---- block-skip cache (include/mxdenoise.h; SD3Transformer.py:151-228 with cache_manager.py:163-191) ---- */
@@ -967,71 +833,31 @@ extern "C" size_t mx_mmdit_block_cache_bytes(const mx_mmdit* u, int batch, int H
   if (!u || batch <= 0 || H <= 0 || W <= 0 || ctx_len <= 0 || H % u->cfg.patch_size || W % u->cfg.patch_size) return 0;
   Plan p;
   mx_block_cache sizing{};
-  p.u = const_cast<mx_mmdit*>(u); p.stream = nullptr; p.set_single(batch, H, W, nullptr, nullptr); p.Lt = ctx_len;
-  p.dry = true; p.ar.base = nullptr; p.ar.cap = 0; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = true;
-  p.bc = &sizing; p.bc_rows = batch;
-  if (!p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr)) { mx::set_error(p.err); return 0; }
-  return p.bc_bytes;
+  p.set_single(batch, H, W, nullptr, nullptr); p.Lt = ctx_len; p.bc_rows = batch;
+  return dry_walk(p, u, &sizing) ? p.bc_bytes : 0;
 }
 
 extern "C" int mx_mmdit_forward_cached(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                        const void* pooled, void* out, int batch, int H, int W, int ctx_len, void* workspace,
                                        size_t workspace_bytes, mx_block_cache* cache) {
+  const std::string who = "mmdit_forward_cached";
   MX_CHECK(u != nullptr, "mmdit: null handle");
-  MX_CHECK(cache && cache->predict && cache->state, "mmdit_forward_cached: cache, cache->predict and cache->state are required");
-  MX_CHECK(u->cfg.num_layers <= 64, "mmdit_forward_cached: at most 64 blocks");
+  MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
+  MX_CHECK(u->cfg.num_layers <= 64, who + ": at most 64 blocks");
   MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "mmdit: bad shape");
-  MX_CHECK(H % u->cfg.patch_size == 0 && W % u->cfg.patch_size == 0, "mmdit: H, W must be multiples of patch_size");
-  MX_CHECK(H / u->cfg.patch_size <= u->cfg.pos_embed_max_size && W / u->cfg.patch_size <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
+  if (Model::check_shape(u, H, W, "mmdit: H, W must be multiples of patch_size")) return 1;
   MX_CHECK(latents && timesteps && ehs && pooled && out && workspace, "mmdit: null operand");
-  MX_CHECK(u->blob != nullptr, "mmdit: weights not set");
+  MX_CHECK(u->weights.blob != nullptr, "mmdit: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
-  MX_CHECK(((uintptr_t)cache->state & 255) == 0, "mmdit_forward_cached: cache->state must be 256-byte aligned");
+  MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
-  p.bc_valid.assign(batch, 0);
-  if (cache->slots) {                      // one state row per request (see mx_block_cache)
-    MX_CHECK(cache->slot_valid != nullptr && cache->n_slots >= batch, "mmdit_forward_cached: slots need slot_valid and n_slots >= batch");
-    std::vector<char> seen(cache->n_slots, 0);
-    for (int b = 0; b < batch; ++b) {
-      MX_CHECK(cache->slots[b] >= 0 && cache->slots[b] < cache->n_slots && !seen[cache->slots[b]], "mmdit_forward_cached: slots must be distinct and inside [0, n_slots)");
-      seen[cache->slots[b]] = 1;
-      p.bc_valid[b] = cache->slot_valid[b] ? 1 : 0;
-    }
-    p.bc_rows = cache->n_slots;
-  } else {
-    cache->cached_valid = cache->cached_valid && cache->cached_key == cache->batch_key && cache->cached_batch == batch && cache->cached_h == H &&
-                          cache->cached_w == W;
-    p.bc_valid.assign(batch, cache->cached_valid ? 1 : 0);
-    p.bc_rows = batch;
-  }
-  p.bc_all_valid = true; p.bc_any_valid = false;
-  for (int b = 0; b < batch; ++b) { p.bc_all_valid = p.bc_all_valid && p.bc_valid[b]; p.bc_any_valid = p.bc_any_valid || p.bc_valid[b]; }
-  p.u = u; p.stream = (hipStream_t)stream; p.set_single(batch, H, W, latents, out); p.Lt = ctx_len;
-  p.dry = false;
-  p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = false;
-  p.bc = cache;
-  if (cache->slots) {
-    MX_CHECK(Plan::bc_scratch_bytes(p.bc_rows) <= cache->state_bytes, "mmdit_forward_cached: state buffer too small");
-    int* dslot = (int*)((char*)cache->state + (size_t)p.bc_rows * 64 * sizeof(double));
-    if (hipMemcpyAsync(dslot, cache->slots, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, p.stream) != hipSuccess) {
-      mx::set_error("mmdit_forward_cached: sending the slot table failed");
-      return 1;
-    }
-    p.bc_dslot = dslot;
-  }
-  p.h_timesteps.resize(batch);
-  if (hipMemcpyAsync(p.h_timesteps.data(), timesteps, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, p.stream) != hipSuccess ||
-      hipStreamSynchronize(p.stream) != hipSuccess) {
-    cache->cached_valid = 0;
-    mx::set_error("mmdit_forward_cached: reading the timesteps failed");
-    return 1;
-  }
+  if (p.bc_begin(who, cache, batch, H, W)) return 1;
+  p.u = u; p.Lt = ctx_len;
+  p.set_single(batch, H, W, latents, out);
+  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
+  if (p.bc_send_slots(who, Plan::kBcPartRows, Plan::kBcTables, batch) || p.bc_read_timesteps(who, timesteps, batch)) return 1;
   const bool okr = p.run(latents, io_dtype, timesteps, ehs, pooled, out);
-  cache->blocks_run = (unsigned)p.blocks_run;
-  cache->blocks_run_hi = (unsigned)(p.blocks_run >> 32);
-  if (!okr) { cache->cached_valid = 0; mx::set_error(p.err); return 1; }
-  cache->cached_valid = 1; cache->cached_key = cache->batch_key; cache->cached_batch = batch; cache->cached_h = H; cache->cached_w = W;
-  return 0;
+  return p.bc_finish(okr, p.blocks_run);
 }
 
 extern "C" int mx_mmdit_forward_trace(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
@@ -1039,6 +865,9 @@ extern "C" int mx_mmdit_forward_trace(mx_mmdit* u, void* stream, const void* lat
                                       void* workspace, size_t workspace_bytes, const char* stage, void* stage_out,
                                       size_t stage_out_bytes) {
   MX_CHECK(stage && stage_out, "mmdit_forward_trace: stage and stage_out required");
-  return forward_impl(u, stream, latents, io_dtype, timesteps, ehs, pooled, out, batch, H, W, ctx_len, workspace, workspace_bytes,
-                      stage, stage_out, stage_out_bytes, false, nullptr);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
+  c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
+  return forward_impl(u, c);
 }

@@ -5,14 +5,15 @@
 //   bucketed relative position bias of block 0 shared by all blocks;  h += wo (gelu_new(wi_0 n) * (wi_1 n)), n = RMSNorm(h);  out = RMSNorm(h).
 // Same building blocks as the denoisers (64-wide heads): fused q / k / v GEMM with the V^T epilogue, the flash kernel with an additive bias
 // (mx_attention_prescaled_bias; bias and q both carry log2(e)), the GEGLU epilogue in its tanh form, residuals in the GEMM epilogues.
+// Arena, weight lookup and the gemm wrapper: mx::PlanBase (plan_base.h).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <string>
-#include <unordered_map>
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
+#include "plan_base.h"
 
 namespace mx {
 int launch_clip_embed(hipStream_t s, const int* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* out, int rows, int L, int H, int vocab);
@@ -22,43 +23,12 @@ using mx::bf16_t;
 
 struct mx_t5 {
   mx_t5_config cfg;
-  const char* blob = nullptr;
-  uint64_t blob_bytes = 0;
-  std::unordered_map<std::string, std::pair<uint64_t, uint64_t>> table;
+  mx::WeightTable weights;
 };
 
 namespace {
-struct Arena {
-  char* base; size_t cap; size_t top; size_t peak; bool dry;
-  void* alloc(size_t bytes) {
-    const size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > peak) peak = top;
-    if (dry) return (void*)(uintptr_t)(0x1000 + a);
-    return (top <= cap) ? base + a : nullptr;
-  }
-};
-
-struct Plan {
-  mx_t5* u; hipStream_t stream; Arena ar; int B, L; bool dry, lookup; std::string err;
-  bool ok() const { return err.empty(); }
-  bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
-  const void* w(const std::string& name, size_t bytes) {
-    if (dry && !lookup) return (const void*)(uintptr_t)0x1000;
-    auto it = u->table.find(name);
-    if (it == u->table.end()) { fail("missing weight '" + name + "'"); return nullptr; }
-    if (it->second.second != bytes) { fail("weight '" + name + "' has " + std::to_string(it->second.second) + " bytes, expected " + std::to_string(bytes)); return nullptr; }
-    return u->blob + it->second.first;
-  }
-  const bf16_t* wb(const std::string& n, size_t e) { return (const bf16_t*)w(n, e * 2); }
-  const float* wf(const std::string& n, size_t e) { return (const float*)w(n, e * 4); }
-  template <typename T> T* alloc(size_t elems) { T* p = (T*)ar.alloc(elems * sizeof(T)); if (!p) fail("workspace too small"); return p; }
-  bool gemm(mx_gemm_desc& d) {
-    if (!ok()) return false;
-    if (dry) return true;
-    if (mx_gemm(stream, &d)) return fail(std::string("gemm: ") + mx_last_error());
-    return true;
-  }
+struct Plan : mx::PlanBase {
+  mx_t5* u; int B, L;
   bool linear(const bf16_t* a, const std::string& name, void* c, int M, int N, int K, int ldc, const void* residual = nullptr, int flags = 0) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
     d.a = a; d.lda = K; d.w = wb(name, (size_t)N * K); d.c = c; d.ldc = ldc; d.M = M; d.N = N; d.K = K; d.residual = residual; d.ldr = ldc; d.flags = flags;
@@ -113,14 +83,12 @@ struct Plan {
 int run_impl(mx_t5* u, void* stream, const int* ids, void* out, int batch, int L, void* ws, size_t ws_bytes, bool dry, bool lookup, size_t* peak) {
   MX_CHECK(u != nullptr, "t5: null handle");
   MX_CHECK(batch > 0 && L > 0 && L % 8 == 0 && L <= 4096, "t5: bad batch / sequence length (a multiple of 8, <= 4096)");
-  if (!dry) MX_CHECK(ids && out && ws && u->blob, "t5: null operand or weights not set");
+  if (!dry) MX_CHECK(ids && out && ws && u->weights.blob, "t5: null operand or weights not set");
   Plan p;
-  p.u = u; p.stream = (hipStream_t)stream; p.B = batch; p.L = L; p.dry = dry; p.lookup = lookup;
-  p.ar.base = (char*)ws; p.ar.cap = ws_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = dry;
+  p.u = u; p.B = batch; p.L = L; p.lookup = lookup;
+  if (dry) p.begin_dry(u->weights); else p.begin(u->weights, (hipStream_t)stream, ws, ws_bytes);
   const bool okr = p.run(ids, out);
-  if (peak) *peak = p.ar.peak;
-  if (!okr) { mx::set_error(p.err); return 1; }
-  return 0;
+  return p.finish(okr, peak);
 }
 }  // namespace
 
@@ -136,14 +104,8 @@ extern "C" mx_t5* mx_t5_create(const mx_t5_config* c) {
 }
 extern "C" void mx_t5_destroy(mx_t5* u) { delete u; }
 extern "C" int mx_t5_set_weights(mx_t5* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n) {
-  MX_CHECK(u && blob && table && n > 0, "t5_set_weights: bad arguments");
-  u->table.clear();
-  for (int i = 0; i < n; ++i) {
-    MX_CHECK(table[i].name != nullptr && table[i].offset % 16 == 0 && table[i].offset + table[i].bytes <= blob_bytes, "t5_set_weights: bad entry");
-    u->table[table[i].name] = {table[i].offset, table[i].bytes};
-  }
-  u->blob = (const char*)blob; u->blob_bytes = blob_bytes;
-  return 0;
+  MX_CHECK(u != nullptr, "t5_set_weights: null handle");
+  return u->weights.set("t5_set_weights", blob, blob_bytes, table, n);
 }
 extern "C" size_t mx_t5_workspace_bytes(const mx_t5* u, int batch, int L) {
   size_t peak = 0;
@@ -151,7 +113,7 @@ extern "C" size_t mx_t5_workspace_bytes(const mx_t5* u, int batch, int L) {
   return peak + 4096;
 }
 extern "C" int mx_t5_validate(const mx_t5* u, int batch, int L) {
-  MX_CHECK(u && u->blob, "t5_validate: weights not set");
+  MX_CHECK(u && u->weights.blob, "t5_validate: weights not set");
   return run_impl(const_cast<mx_t5*>(u), nullptr, nullptr, nullptr, batch, L, nullptr, 0, true, true, nullptr);
 }
 extern "C" int mx_t5_encode(mx_t5* u, void* stream, const int32_t* ids, void* out, int batch, int L, void* workspace, size_t workspace_bytes) {

@@ -14,22 +14,22 @@
 //   * the 70 cross-attention K/V projections of encoder_hidden_states are hoisted into one GEMM per width;
 //   * the 17 time_emb_proj linears are one GEMM; its fp32 rows are added in conv1's epilogue;
 //   * GEGLU, bias, residual adds and the nearest-2x upsample are fused into GEMM/conv epilogues/loaders.
+// Host scaffold (arena, weight lookup, groups, block-cache bookkeeping, the forward driver): plan_base.h; this file holds the UNet's own plan,
+// its checks and hooks (struct Model) and the extern "C" entry points, each of which describes its forward as an mx::ForwardCall.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
-#include <map>
-
 #include "graph_cache.h"
-#include "pp_exchange.h"
 #include "patch_cache.h"
+#include "plan_base.h"
 
 namespace mx {
 int launch_prep_latent(hipStream_t s, const void* in, int dtype, void* out, int B, int Cin, int HW, int CP);
@@ -39,7 +39,6 @@ int launch_time_embed(hipStream_t s, const float* timesteps, const void* text_em
 int launch_concat(hipStream_t s, const void* a, const void* b, void* out, long M, int C1, int C2);
 size_t gn_workspace_exact(int B, int H, int W, int C, int patch);
 int launch_sq_diff_partial(hipStream_t s, const void* a, const void* b, long elems_per_sample, int B, double* partial, const int* slot = nullptr);
-int launch_copy_rows(hipStream_t s, void* batch, void* slotted, size_t bytes_per_sample, int B, const int* slot, int scatter);
 int launch_gn_pp_partial(hipStream_t s, const void* x, int C1, const void* x2, int B, int H, int W, int C, int groups, void* workspace, double* sums);
 int launch_gn_pp_finish(hipStream_t s, const void* x, int C1, const void* x2, void* y, long y_img_elems, const float* gamma, const float* beta, const double* all_sums,
                         int world, int B, int H, int W, int C, int groups, int H_total, float eps, int silu, void* workspace,
@@ -53,9 +52,7 @@ using mx::bf16_t;
 
 struct mx_unet {
   mx_unet_config cfg;
-  const char* blob = nullptr;
-  uint64_t blob_bytes = 0;
-  std::unordered_map<std::string, std::pair<uint64_t, uint64_t>> table;
+  mx::WeightTable weights;
   mx::GraphCache graphs;   // hipGraph replay of the forward, keyed by its arguments (graph_cache.h)
   // patch-parallel stale forwards: the exchange sizes of the plan, recorded by a host-only walk ONCE per (batch, H, W, ctx_len, gn_patch, world) instead
   // of at every step (advisor, round 3: the walk sat on the path whose purpose is to hide latency)
@@ -91,19 +88,6 @@ namespace {
 
 constexpr int kConvInPad = 64;  // conv_in input channels are zero-padded to one K tile
 
-struct Arena {
-  char* base; size_t cap; size_t top; size_t peak; bool dry;
-  void* alloc(size_t bytes) {
-    const size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > peak) peak = top;
-    if (dry) return (void*)(uintptr_t)(0x1000 + a);  // never dereferenced on the host
-    return (top <= cap) ? base + a : nullptr;
-  }
-  size_t mark() const { return top; }
-  void release(size_t m) { top = m; }
-};
-
 // (attention width, cross-attention layers of that width) in execution order of first use: the layout of the hoisted K / V^T buffers
 static std::vector<std::pair<int, int>> kv_widths(const mx_unet_config& c) {
   const int nlev = c.n_levels;
@@ -115,48 +99,24 @@ static std::vector<std::pair<int, int>> kv_widths(const mx_unet_config& c) {
   return widths;
 }
 
-struct Plan {
+struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchange, block-cache bookkeeping: plan_base.h)
   mx_unet* u;
-  hipStream_t stream;
-  Arena ar;
-  int B, H, W, ctx_len, gn_patch;   // B = samples of ALL groups; H, W = the first group's latent size (the only one unless mixed)
+  int ctx_len, gn_patch;
   // Mixed-resolution batch (mx_unet_forward_mixed): the requests of every resolution present run through ONE launch sequence.  A group = the
   // samples of one resolution; activations of a level are the groups' token-major images one after the other ([sum_g B_g h_g w_g, C]), so every
   // per-token op (linear layers, LayerNorm) is one ordinary launch over all rows, and the ops with per-image structure (3x3 convs, GroupNorm,
   // the QKV epilogue's V^T, attention) are GROUPED launches: one problem per group, no tile straddling two groups (include/mxdenoise.h,
   // mx_gemm_seg).  The reference reaches the same end by cutting every latent into 256-px patches of one batch (modules/unet.py:104-185).
-  int ng = 1;
-  int gB[MX_MAX_SEGS], gH[MX_MAX_SEGS], gW[MX_MAX_SEGS], gb0[MX_MAX_SEGS];   // per group: samples, latent size, first sample
   int ch[MX_MAX_SEGS], cw[MX_MAX_SEGS];                                       // per group: image size at the CURRENT level
-  const void* g_lat[MX_MAX_SEGS]; void* g_out[MX_MAX_SEGS];
   long rows() const { long m = 0; for (int g = 0; g < ng; ++g) m += (long)gB[g] * ch[g] * cw[g]; return m; }
   long row0(int g) const { long m = 0; for (int k = 0; k < g; ++k) m += (long)gB[k] * ch[k] * cw[k]; return m; }
-  void set_single(int batch, int h, int w, const void* lat, void* out) { ng = 1; gB[0] = batch; gH[0] = h; gW[0] = w; gb0[0] = 0; g_lat[0] = lat; g_out[0] = out; B = batch; H = h; W = w; }
-  bool dry;                 // size-only pass: no launches
-  bool mute = false;        // block-skip cache: walk a block's plan (allocations, weight / K-V / time-embedding cursors) without launching it
-  bool quiet() const { return dry || mute; }
-  mx::PPExchange px;              // the exchange itself, synchronous / warm-up / stale (pp_exchange.h)
-  mx_block_cache* bc = nullptr;   // mx_unet_forward_cached
   char* bc_top = nullptr;         // bump pointer into bc->state: same order and sizes every step
-  int bc_rows = 0;                // samples a state tensor holds: the batch, or bc->n_slots when the caller keeps one slot per request
-  const int* bc_dslot = nullptr;  // device copy of bc->slots (null: sample i lives in row i)
-  std::vector<unsigned char> bc_valid;   // per sample: the state holds its tensors of an earlier step
   std::vector<int> bc_sel;               // selection table of a partially reused block (host copy kept for the forward's lifetime)
-  bool bc_all_valid = false, bc_any_valid = false;
   // head of the state: comparison partial sums, the slot table, the selection table of a partially reused block
-  static size_t bc_scratch_bytes(int lpb, int rows) { return (((size_t)(lpb + 2) * rows * 64 * sizeof(double) + 2 * (size_t)rows * sizeof(int)) + 255) & ~(size_t)255; }
-  int* bc_dsel() const { return (int*)((char*)bc->state + (size_t)(u->cfg.layers_per_block + 2) * bc_rows * 64 * sizeof(double) + (size_t)bc_rows * sizeof(int)); }
-  // batch-ordered tensor <-> its rows in the state
-  bool bc_store(char* region, const void* t, size_t per_sample_bytes) {
-    if (bc_dslot) { if (mx::launch_copy_rows(stream, (void*)t, region, per_sample_bytes, B, bc_dslot, 1)) return fail(mx_last_error()); return true; }
-    if (hipMemcpyAsync(region, t, per_sample_bytes * B, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("block cache: copy into the state failed");
-    return true;
-  }
-  bool bc_load(void* t, char* region, size_t per_sample_bytes) {
-    if (bc_dslot) { if (mx::launch_copy_rows(stream, t, region, per_sample_bytes, B, bc_dslot, 0)) return fail(mx_last_error()); return true; }
-    if (hipMemcpyAsync(t, region, per_sample_bytes * B, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("block cache: copy out of the state failed");
-    return true;
-  }
+  static constexpr int kBcTables = 2;
+  static int bc_part_rows(int lpb) { return lpb + 2; }
+  static size_t bc_scratch_bytes(int lpb, int rows) { return bc_head_bytes(bc_part_rows(lpb), kBcTables, rows); }
+  int* bc_dsel() const { return bc_table(bc_part_rows(u->cfg.layers_per_block), 1); }
   // ---- block cache at the reference's own unit, the PATCH (mx_unet_forward_cached_mixed; cache_manager.py with is_sliced=True) ----
   // Every cached op of a block (resnet conv1 / conv2, the down / upsampler conv, attn1.to_out, attn2.to_out: the modules that own a CacheManager,
   // resnet.py:283,339,386-387; attention.py:57,118) keeps its output per patch in a STATE tensor with one row per request; under a partial
@@ -287,10 +247,6 @@ struct Plan {
   }
 
   unsigned blocks_run = 0;
-  std::vector<float> h_timesteps; // host copy of the timesteps for the predictor
-  bool lookup = false;      // dry pass that still resolves every weight (mx_unet_validate)
-  const char* stage = nullptr; void* stage_out = nullptr; size_t stage_bytes = 0; bool stage_hit = false;
-  std::string err;
   // patch-parallel (mx_unet_forward_pp): this rank owns H (local) of Htot latent rows; distrifuser sync mode (utils.py:119-214)
   int pp_rank = 0, pp_world = 1, Htot = 0;
   bool is_pp() const { return pp_world > 1; }
@@ -300,29 +256,6 @@ struct Plan {
   std::vector<KV> kv;       // one per distinct attention width
   mx_unet::CtxEntry* ctx_e = nullptr;   // the composition's stored K / V^T (forward_impl: ctx_prepare); ctx_hit: already computed
   bool ctx_hit = false;
-
-  bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
-
-  const void* w(const std::string& name, size_t expect_bytes) {
-    if (dry && !lookup) return (const void*)(uintptr_t)0x1000;
-    auto it = u->table.find(name);
-    if (it == u->table.end()) { fail("missing weight '" + name + "'"); return nullptr; }
-    if (it->second.second != expect_bytes) {
-      fail("weight '" + name + "' has " + std::to_string(it->second.second) + " bytes, expected " + std::to_string(expect_bytes));
-      return nullptr;
-    }
-    return u->blob + it->second.first;
-  }
-  const bf16_t* wb(const std::string& name, size_t elems) { return (const bf16_t*)w(name, elems * 2); }
-  const float* wf(const std::string& name, size_t elems) { return (const float*)w(name, elems * 4); }
-
-  template <typename T> T* alloc(size_t elems) {
-    T* p = (T*)ar.alloc(elems * sizeof(T));
-    if (!p) fail("workspace too small");
-    return p;
-  }
-
-  bool ok() const { return err.empty(); }
 
   // ---- patch-parallel helpers --------------------------------------------------------------
   bool all_gather(const void* send, void* recv, size_t bytes_per_rank, bool keep_stale_own = false) {
@@ -392,13 +325,6 @@ struct Plan {
   }
 
   // ---- op wrappers -------------------------------------------------------------------------
-  bool gemm(mx_gemm_desc& d, bool conv) {
-    if (!ok()) return false;
-    if (quiet()) return true;
-    const int rc = conv ? mx_conv3x3(stream, &d) : mx_gemm(stream, &d);
-    if (rc) return fail(std::string("gemm/conv: ") + mx_last_error());
-    return true;
-  }
   // row statistics (sum, sum of squares per row and slab) of the hidden states: what the folded LayerNorms read (mx_gemm_desc.ln_stats)
   // fin / cnt: the FINALISED form (mean, rstd per row: mx_gemm_desc.ln_final) for consumers on the 256 x 256 kernel; cnt = the producers' panel tickets
   struct RowStats { float* buf = nullptr; int slabs = 0; float* fin = nullptr; unsigned* cnt = nullptr; };
@@ -528,14 +454,6 @@ struct Plan {
     if (mx_attention_prescaled_grouped(stream, pr, ng, ldq, ldk, ldo, heads)) return fail(std::string("attention: ") + mx_last_error());
     return true;
   }
-  void dump(const std::string& name, const bf16_t* t, size_t elems) {
-    if (!stage || quiet() || !ok() || stage_hit) return;
-    if (name != stage) return;
-    if (elems * 2 > stage_bytes) { fail("stage buffer too small for '" + name + "'"); return; }
-    if (hipMemcpyAsync(stage_out, t, elems * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess) fail("stage copy failed");
-    stage_hit = true;
-  }
-
   int level_patch(int level) const { return gn_patch > 0 ? std::max(gn_patch >> level, 1) : 0; }
 
   // ---- blocks ------------------------------------------------------------------------------
@@ -1358,115 +1276,77 @@ mx_unet::CtxEntry* ctx_prepare(mx_unet* u, hipStream_t stream, int B, int ctx_le
   return e;
 }
 
-int forward_impl(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
-                 const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len, int gn_patch,
-                 void* workspace, size_t workspace_bytes, const char* stage, void* stage_out, size_t stage_bytes, bool dry,
-                 size_t* peak, bool lookup = false, const mx_pp_comm* comm = nullptr, const mx_pp_stale* stale = nullptr,
-                 size_t* state_need = nullptr, const mx_unet_group* groups = nullptr, int n_groups = 0) {
-  MX_CHECK(u != nullptr, "unet: null handle");
-  if (groups) {        // mixed-resolution batch: `batch`, H, W describe the first group; every group is validated below
-    MX_CHECK(n_groups >= 1 && n_groups <= MX_MAX_SEGS && comm == nullptr, "unet: a mixed batch has 1..MX_MAX_SEGS resolution groups and does not run patch-parallel");
-    batch = groups[0].batch; H = groups[0].H; W = groups[0].W; latents = groups[0].latents; out = groups[0].out;
-    const int dv = 1 << (u->cfg.n_levels - 1);
-    for (int g = 0; g < n_groups; ++g) {
-      MX_CHECK(groups[g].batch > 0 && groups[g].H > 0 && groups[g].W > 0 && groups[g].H % dv == 0 && groups[g].W % dv == 0, "unet: bad group shape");
-      MX_CHECK(dry || (groups[g].latents && groups[g].out), "unet: null group operand");
-      if (gn_patch > 0)
-        MX_CHECK((groups[g].H % gn_patch == 0 && groups[g].W % gn_patch == 0) || (gn_patch >= groups[g].H && gn_patch >= groups[g].W),
-                 "unet: every group's H, W must be multiples of gn_patch");
-    }
-  }
-  const bool pp = comm != nullptr && comm->world > 1;
-  if (pp) {
-    MX_CHECK(comm->rank >= 0 && comm->rank < comm->world && (dry || comm->all_gather != nullptr), "unet pp: bad communicator");
-    MX_CHECK(gn_patch == 0, "unet pp: patch-parallel runs the exact (is_sliced=False) arithmetic");
-    MX_CHECK(H % (1 << (u->cfg.n_levels - 1)) == 0, "unet pp: local rows must be divisible by 2^(levels-1)");
-  }
-  MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "unet: bad shape");
-  const int div = 1 << (u->cfg.n_levels - 1);
-  MX_CHECK(H % div == 0 && W % div == 0, "unet: H, W must be divisible by 2^(levels-1)");
-  MX_CHECK(gn_patch >= 0, "unet: gn_patch must be >= 0");
-  if (gn_patch > 0) {
-    MX_CHECK(H % gn_patch == 0 && W % gn_patch == 0, "unet: H, W must be multiples of gn_patch");
-    MX_CHECK((gn_patch >> (u->cfg.n_levels - 1)) >= 2 || gn_patch >= H, "unet: gn_patch too small for the deepest level (needs >= 2 pixels there)");
-  }
-  if (!dry) {
-    MX_CHECK(latents && timesteps && ehs && text_embeds && time_ids && out && workspace, "unet: null operand");
-    MX_CHECK(u->blob != nullptr, "unet: weights not set");
-    MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
-  }
-  std::string err;
-  size_t plan_peak = 0;
-  // the composition's stored cross-attention K / V^T (mx_unet_set_context_key): plain and mixed forwards; not patch-parallel (its ranks hold row bands)
-  bool ctx_hit = false;
+// what run_forward (plan_base.h) needs to know of the UNet; one object per call: it carries the composition's stored cross-attention K / V^T
+struct Model {
+  const char* name = "unet";
   mx_unet::CtxEntry* ctx_e = nullptr;
-  if (!dry && !pp) {
-    int Btot = batch;
-    if (groups) { Btot = 0; for (int g = 0; g < n_groups; ++g) Btot += groups[g].batch; }
-    ctx_e = ctx_prepare(u, (hipStream_t)stream, Btot, ctx_len, ctx_hit);
-  }
-  if (!dry) u->ctx_key = 0;     // the key names ONE forward: a later call that does not announce itself (a trace, another caller of the handle) projects afresh
-  auto enqueue = [&](hipStream_t s) {
-    Plan p;
-    p.u = u; p.stream = s; p.ctx_len = ctx_len;
-    p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
-    p.set_single(batch, H, W, latents, out);
-    bool patch_covers_all = gn_patch >= H && gn_patch >= W;
-    if (groups) {
-      p.ng = n_groups; p.B = 0;
-      for (int g = 0; g < n_groups; ++g) {
-        p.gB[g] = groups[g].batch; p.gH[g] = groups[g].H; p.gW[g] = groups[g].W; p.gb0[g] = p.B; p.g_lat[g] = groups[g].latents; p.g_out[g] = groups[g].out;
-        p.B += groups[g].batch;
-        patch_covers_all = patch_covers_all && gn_patch >= groups[g].H && gn_patch >= groups[g].W;
-      }
+  bool ctx_hit = false;
+  // H, W against the level count and the GroupNorm patch (is_sliced)
+  static int check_shape(const mx_unet* u, int H, int W, int gn_patch) {
+    const int div = 1 << (u->cfg.n_levels - 1);
+    MX_CHECK(H % div == 0 && W % div == 0, "unet: H, W must be divisible by 2^(levels-1)");
+    MX_CHECK(gn_patch >= 0, "unet: gn_patch must be >= 0");
+    if (gn_patch > 0) {
+      MX_CHECK(H % gn_patch == 0 && W % gn_patch == 0, "unet: H, W must be multiples of gn_patch");
+      MX_CHECK((gn_patch >> (u->cfg.n_levels - 1)) >= 2 || gn_patch >= H, "unet: gn_patch too small for the deepest level (needs >= 2 pixels there)");
     }
-    p.gn_patch = patch_covers_all ? 0 : gn_patch;
-    p.dry = dry; p.lookup = lookup; p.stage = stage; p.stage_out = stage_out; p.stage_bytes = stage_bytes;
-    p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = dry;
-    if (pp) { p.pp_rank = comm->rank; p.pp_world = comm->world; p.Htot = H * comm->world; }
-    if (pp) p.px.set(comm, stale);
-    if (pp && stale) {      // the state layout (exchanges dealt into chunks, pp_exchange.h) from a host-only recording walk of the same plan
-      const std::vector<long> lk = {(long)batch, (long)H, (long)W, (long)ctx_len, (long)gn_patch, (long)comm->world, (long)io_dtype};
-      auto it = u->pp_sizes.find(lk);
-      if (it == u->pp_sizes.end()) {
-        std::vector<size_t> sizes;
-        Plan q = p;
-        q.dry = true; q.ar.dry = true; q.ar.base = nullptr; q.ar.cap = 0; q.stage = nullptr; q.lookup = false;
-        q.px.record = &sizes;
-        if (!q.run(nullptr, io_dtype, nullptr, nullptr, nullptr, nullptr, nullptr)) { err = q.err; return false; }
-        it = u->pp_sizes.emplace(lk, std::move(sizes)).first;
-      }
-      p.px.build_layout(it->second);
-    }
-    const bool okr = p.run(latents, io_dtype, timesteps, ehs, text_embeds, time_ids, out);
-    plan_peak = p.ar.peak;
-    if (state_need) *state_need = p.px.state_top;
-    if (!okr) err = p.err;
-    return okr;
-  };
-  bool okr;
-  if (dry || stage || pp) {     // (the all-gather callbacks of a patch-parallel forward cannot be captured)
-    okr = enqueue((hipStream_t)stream);
-  } else {
-    std::vector<uint64_t> key = {(uint64_t)batch, (uint64_t)H, (uint64_t)W, (uint64_t)ctx_len, (uint64_t)gn_patch, (uint64_t)io_dtype,
-                                 (uint64_t)(uintptr_t)latents, (uint64_t)(uintptr_t)timesteps, (uint64_t)(uintptr_t)ehs,
-                                 (uint64_t)(uintptr_t)text_embeds, (uint64_t)(uintptr_t)time_ids, (uint64_t)(uintptr_t)out,
-                                 (uint64_t)(uintptr_t)workspace, (uint64_t)workspace_bytes, (uint64_t)(uintptr_t)u->blob};
-    for (int g = 1; g < n_groups; ++g)
-      for (uint64_t v : {(uint64_t)groups[g].batch, (uint64_t)groups[g].H, (uint64_t)groups[g].W, (uint64_t)(uintptr_t)groups[g].latents, (uint64_t)(uintptr_t)groups[g].out})
-        key.push_back(v);
-    okr = u->graphs.run((hipStream_t)stream, key, enqueue, /*capture_on_miss=*/n_groups <= 1);
+    return 0;
   }
-  if (peak) *peak = plan_peak;
-  if (ctx_e) {                  // the entry belongs to this stream until the event: later forwards on other streams wait for it
+  int check(const mx_unet* u, const mx::ForwardCall& c) {
+    const int div = 1 << (u->cfg.n_levels - 1);
+    for (int g = 0; c.groups && g < c.n_groups; ++g) {
+      const mx_unet_group& q = c.groups[g];
+      MX_CHECK(q.H % div == 0 && q.W % div == 0, "unet: bad group shape");
+      if (c.gn_patch > 0)
+        MX_CHECK((q.H % c.gn_patch == 0 && q.W % c.gn_patch == 0) || (c.gn_patch >= q.H && c.gn_patch >= q.W), "unet: every group's H, W must be multiples of gn_patch");
+    }
+    if (c.pp()) {
+      MX_CHECK(c.gn_patch == 0, "unet pp: patch-parallel runs the exact (is_sliced=False) arithmetic");
+      MX_CHECK(c.H % div == 0, "unet pp: local rows must be divisible by 2^(levels-1)");
+    }
+    if (check_shape(u, c.H, c.W, c.gn_patch)) return 1;
+    MX_CHECK(c.dry || (c.text_embeds && c.time_ids), "unet: null operand");
+    return 0;
+  }
+  // the composition's stored cross-attention K / V^T (mx_unet_set_context_key): plain and mixed forwards; not patch-parallel (its ranks hold row bands)
+  void begin(mx_unet* u, const mx::ForwardCall& c) {
+    if (c.dry) return;
+    if (!c.pp()) {
+      int Btot = c.batch;
+      if (c.groups) { Btot = 0; for (int g = 0; g < c.n_groups; ++g) Btot += c.groups[g].batch; }
+      ctx_e = ctx_prepare(u, (hipStream_t)c.stream, Btot, c.ctx_len, ctx_hit);
+    }
+    u->ctx_key = 0;     // the key names ONE forward: a later call that does not announce itself (a trace, another caller of the handle) projects afresh
+  }
+  void end(mx_unet*, const mx::ForwardCall& c, bool okr) {
+    if (!ctx_e) return;          // the entry belongs to this stream until the event: later forwards on other streams wait for it
     ctx_e->valid = okr;
-    ctx_e->last = (hipStream_t)stream;
-    ctx_e->recorded = hipEventRecord(ctx_e->ev, (hipStream_t)stream) == hipSuccess;
-    if (!ctx_e->recorded) { (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)stream); }
+    ctx_e->last = (hipStream_t)c.stream;
+    ctx_e->recorded = hipEventRecord(ctx_e->ev, (hipStream_t)c.stream) == hipSuccess;
+    if (!ctx_e->recorded) { (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)c.stream); }
   }
-  if (!okr) { mx::set_error(err); return 1; }
-  return 0;
+  void setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
+    p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
+    bool patch_covers_all = true;
+    for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
+    p.gn_patch = patch_covers_all ? 0 : c.gn_patch;
+    if (c.pp()) { p.pp_rank = c.comm->rank; p.pp_world = c.comm->world; p.Htot = c.H * c.comm->world; }
+  }
+  bool run(Plan& p, const mx::ForwardCall& c) { return p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.text_embeds, c.time_ids, c.out); }
+  std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) { return {(uint64_t)c.gn_patch}; }
+  std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
+};
+int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
+  Model m;
+  return mx::run_forward<Plan>(const_cast<mx_unet*>(u), c, m);
 }
+// the call of a host-only walk of the plan at one shape
+mx::ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
+  mx::ForwardCall c;
+  c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
+  return c;
+}
+mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
 
 }  // namespace
 
@@ -1492,50 +1372,43 @@ extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses)
 }
 
 extern "C" int mx_unet_set_weights(mx_unet* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n) {
-  MX_CHECK(u && blob && table && n > 0, "unet_set_weights: bad arguments");
+  MX_CHECK(u != nullptr, "unet_set_weights: null handle");
   u->graphs.clear();    // captured graphs hold addresses resolved through the old table
   u->ctx_clear();       // stored projections were made with the old weights
-  u->table.clear();
-  for (int i = 0; i < n; ++i) {
-    MX_CHECK(table[i].name != nullptr, "unet_set_weights: null name");
-    MX_CHECK(table[i].offset % 16 == 0, "unet_set_weights: tensor offsets must be 16-byte aligned");
-    MX_CHECK(table[i].offset + table[i].bytes <= blob_bytes, "unet_set_weights: entry exceeds blob");
-    u->table[table[i].name] = {table[i].offset, table[i].bytes};
-  }
-  u->blob = (const char*)blob;
-  u->blob_bytes = blob_bytes;
-  return 0;
+  return u->weights.set("unet_set_weights", blob, blob_bytes, table, n);
 }
 
 extern "C" size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len) {
   if (!u) return 0;
-  size_t peak = 0;
   // the sliced variant needs the larger GroupNorm scratch: size for the smallest legal patch
   size_t best = 0;
   const int div = 1 << (u->cfg.n_levels - 1);
-  const int patches[2] = {0, 2 * div};
-  for (int k = 0; k < 2; ++k) {
-    const int gp = patches[k];
+  for (int gp : {0, 2 * div}) {
     if (gp > 0 && (H % gp != 0 || W % gp != 0 || gp >= H)) continue;
-    if (forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, batch, H, W,
-                     ctx_len, gp, nullptr, 0, nullptr, nullptr, 0, true, &peak))
-      return 0;
-    if (peak > best) best = peak;
+    size_t peak = 0;
+    mx::ForwardCall c = dry_call(batch, H, W, ctx_len);
+    c.gn_patch = gp; c.peak = &peak;
+    if (forward_impl(u, c)) return 0;
+    best = std::max(best, peak);
   }
   return best + 4096;
 }
 
 extern "C" int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len) {
-  MX_CHECK(u && u->blob, "unet_validate: weights not set");
-  return forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, batch, H, W,
-                      ctx_len, 0, nullptr, 0, nullptr, nullptr, 0, true, nullptr, true);
+  MX_CHECK(u && u->weights.blob, "unet_validate: weights not set");
+  mx::ForwardCall c = dry_call(batch, H, W, ctx_len);
+  c.lookup = true;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_unet_forward(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
                                const void* ehs, const void* text_embeds, const float* time_ids, void* out, int batch, int H,
                                int W, int ctx_len, int gn_patch, void* workspace, size_t workspace_bytes) {
-  return forward_impl(u, stream, latents, io_dtype, timesteps, ehs, text_embeds, time_ids, out, batch, H, W, ctx_len, gn_patch,
-                      workspace, workspace_bytes, nullptr, nullptr, 0, false, nullptr);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
+  c.time_ids = time_ids; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes;
+  return forward_impl(u, c);
 }
 
 /* ---- mixed-resolution batch: ONE launch sequence over the requests of every resolution present (the reference batches
@@ -1549,9 +1422,9 @@ extern "C" size_t mx_unet_workspace_bytes_mixed(const mx_unet* u, const mx_unet_
     for (int g = 0; g < n_groups; ++g) legal = legal && (gp == 0 || (groups[g].H % gp == 0 && groups[g].W % gp == 0));
     if (!legal) continue;
     size_t peak = 0;
-    if (forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, ctx_len, gp, nullptr, 0,
-                     nullptr, nullptr, 0, true, &peak, false, nullptr, nullptr, nullptr, groups, n_groups))
-      return 0;
+    mx::ForwardCall c = dry_call(0, 0, 0, ctx_len);
+    c.groups = groups; c.n_groups = n_groups; c.gn_patch = gp; c.peak = &peak;
+    if (forward_impl(u, c)) return 0;
     best = std::max(best, peak);
   }
   return best + 4096;
@@ -1561,97 +1434,68 @@ extern "C" int mx_unet_forward_mixed(mx_unet* u, void* stream, const mx_unet_gro
                                      const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                      size_t workspace_bytes) {
   MX_CHECK(groups != nullptr, "unet_forward_mixed: null groups");
-  return forward_impl(u, stream, nullptr, io_dtype, timesteps, ehs, text_embeds, time_ids, nullptr, 0, 0, 0, ctx_len, gn_patch, workspace, workspace_bytes,
-                      nullptr, nullptr, 0, false, nullptr, false, nullptr, nullptr, nullptr, groups, n_groups);
+  mx::ForwardCall c;
+  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
+  c.time_ids = time_ids; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_unet_forward_mixed_trace(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                            const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                            size_t workspace_bytes, const char* stage, void* stage_out, size_t stage_out_bytes) {
   MX_CHECK(groups != nullptr && stage && stage_out, "unet_forward_mixed_trace: groups, stage and stage_out required");
-  return forward_impl(u, stream, nullptr, io_dtype, timesteps, ehs, text_embeds, time_ids, nullptr, 0, 0, 0, ctx_len, gn_patch, workspace, workspace_bytes,
-                      stage, stage_out, stage_out_bytes, false, nullptr, false, nullptr, nullptr, nullptr, groups, n_groups);
+  mx::ForwardCall c;
+  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
+  c.time_ids = time_ids; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
+  return forward_impl(u, c);
 }
 
 /* ---- block-skip cache (include/mxdenoise.h; the reference's CacheManager, modules/cache_manager.py:101-161) ---- */
+namespace {
+// a host-only walk of a plan whose cache mode the caller has set up: sizes against `sizing`, no launches
+bool dry_walk(Plan& p, const mx_unet* u, mx_block_cache* sizing) {
+  p.u = const_cast<mx_unet*>(u);
+  p.begin_dry(u->weights);
+  p.bc = sizing;
+  if (p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr)) return true;
+  mx::set_error(p.err);
+  return false;
+}
+size_t bc_top_bytes(const Plan& p) { return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000) + 256; }     // (dry walk: the bump pointer starts at a placeholder base, as the arena does)
+}  // namespace
+
 extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, int W) {
   if (!u || batch <= 0 || H <= 0 || W <= 0) return 0;
   const int div = 1 << (u->cfg.n_levels - 1);
   if (H % div || W % div) return 0;
   Plan p;
   mx_block_cache sizing{};
-  p.u = const_cast<mx_unet*>(u); p.stream = nullptr; p.set_single(batch, H, W, nullptr, nullptr); p.ctx_len = 64; p.gn_patch = 0;
-  p.dry = true; p.ar.base = nullptr; p.ar.cap = 0; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = true;
-  p.bc = &sizing; p.bc_rows = batch;
-  if (!p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr)) { mx::set_error(p.err); return 0; }
-  return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000) + 256;     // (dry walk: the bump pointer starts at a placeholder base, as the arena does)
+  p.set_single(batch, H, W, nullptr, nullptr); p.ctx_len = 64; p.gn_patch = 0; p.bc_rows = batch;
+  return dry_walk(p, u, &sizing) ? bc_top_bytes(p) : 0;
 }
 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
+  const std::string who = "unet_forward_cached";
   MX_CHECK(u != nullptr, "unet: null handle");
-  MX_CHECK(cache && cache->predict && cache->state, "unet_forward_cached: cache, cache->predict and cache->state are required");
+  MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
   MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "unet: bad shape");
-  const int div = 1 << (u->cfg.n_levels - 1);
-  MX_CHECK(H % div == 0 && W % div == 0, "unet: H, W must be divisible by 2^(levels-1)");
-  MX_CHECK(gn_patch >= 0, "unet: gn_patch must be >= 0");
-  if (gn_patch > 0) {
-    MX_CHECK(H % gn_patch == 0 && W % gn_patch == 0, "unet: H, W must be multiples of gn_patch");
-    MX_CHECK((gn_patch >> (u->cfg.n_levels - 1)) >= 2 || gn_patch >= H, "unet: gn_patch too small for the deepest level (needs >= 2 pixels there)");
-  }
+  if (Model::check_shape(u, H, W, gn_patch)) return 1;
   MX_CHECK(latents && timesteps && ehs && text_embeds && time_ids && out && workspace, "unet: null operand");
-  MX_CHECK(u->blob != nullptr, "unet: weights not set");
+  MX_CHECK(u->weights.blob != nullptr, "unet: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
-  MX_CHECK(((uintptr_t)cache->state & 255) == 0, "unet_forward_cached: cache->state must be 256-byte aligned");
+  MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
-  p.bc_valid.assign(batch, 0);
-  if (cache->slots) {
-    // one state row per request (the reference's dictionaries are keyed by request id, cache_manager.py:105-133): the caller says where each sample
-    // lives and whether that row holds tensors of an earlier step at this latent size
-    MX_CHECK(cache->slot_valid != nullptr && cache->n_slots >= batch, "unet_forward_cached: slots need slot_valid and n_slots >= batch");
-    std::vector<char> seen(cache->n_slots, 0);
-    for (int b = 0; b < batch; ++b) {
-      MX_CHECK(cache->slots[b] >= 0 && cache->slots[b] < cache->n_slots && !seen[cache->slots[b]], "unet_forward_cached: slots must be distinct and inside [0, n_slots)");
-      seen[cache->slots[b]] = 1;
-      p.bc_valid[b] = cache->slot_valid[b] ? 1 : 0;
-    }
-    p.bc_rows = cache->n_slots;
-  } else {
-    cache->cached_valid = cache->cached_valid && cache->cached_key == cache->batch_key && cache->cached_batch == batch && cache->cached_h == H &&
-                          cache->cached_w == W;
-    p.bc_valid.assign(batch, cache->cached_valid ? 1 : 0);
-    p.bc_rows = batch;
-  }
-  p.bc_all_valid = true; p.bc_any_valid = false;
-  for (int b = 0; b < batch; ++b) { p.bc_all_valid = p.bc_all_valid && p.bc_valid[b]; p.bc_any_valid = p.bc_any_valid || p.bc_valid[b]; }
-  p.u = u; p.stream = (hipStream_t)stream; p.set_single(batch, H, W, latents, out); p.ctx_len = ctx_len;
+  if (p.bc_begin(who, cache, batch, H, W)) return 1;
+  p.u = u; p.ctx_len = ctx_len;
+  p.set_single(batch, H, W, latents, out);
   p.gn_patch = (gn_patch >= H && gn_patch >= W) ? 0 : gn_patch;
-  p.dry = false;
-  p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = false;
-  p.bc = cache;
-  if (cache->slots) {
-    MX_CHECK(Plan::bc_scratch_bytes(u->cfg.layers_per_block, p.bc_rows) <= cache->state_bytes, "unet_forward_cached: state buffer too small");
-    int* dslot = (int*)((char*)cache->state + (size_t)(u->cfg.layers_per_block + 2) * p.bc_rows * 64 * sizeof(double));
-    if (hipMemcpyAsync(dslot, cache->slots, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, p.stream) != hipSuccess) {
-      mx::set_error("unet_forward_cached: sending the slot table failed");
-      return 1;
-    }
-    p.bc_dslot = dslot;
-  }
-  p.h_timesteps.resize(batch);
-  // the predictor's timestep feature: the per-sample timesteps live in device memory like the rest of the step's operands
-  if (hipMemcpyAsync(p.h_timesteps.data(), timesteps, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, p.stream) != hipSuccess ||
-      hipStreamSynchronize(p.stream) != hipSuccess) {
-    cache->cached_valid = 0;
-    mx::set_error("unet_forward_cached: reading the timesteps failed");
-    return 1;
-  }
+  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
+  if (p.bc_send_slots(who, Plan::bc_part_rows(u->cfg.layers_per_block), Plan::kBcTables, batch) || p.bc_read_timesteps(who, timesteps, batch)) return 1;
   const bool okr = p.run(latents, io_dtype, timesteps, ehs, text_embeds, time_ids, out);
-  cache->blocks_run = p.blocks_run; cache->blocks_run_hi = 0;
-  if (!okr) { cache->cached_valid = 0; mx::set_error(p.err); return 1; }
-  cache->cached_valid = 1; cache->cached_key = cache->batch_key; cache->cached_batch = batch; cache->cached_h = H; cache->cached_w = W;
-  return 0;
+  return p.bc_finish(okr, p.blocks_run);
 }
 
 
@@ -1664,17 +1508,14 @@ int pc_setup(Plan& p, mx_unet* u, const mx_unet_group* groups, int n_groups, int
   MX_CHECK(cache && cache->n_slots > 0 && cache->max_h > 0 && cache->max_w > 0 && cache->max_h % gn_patch == 0 && cache->max_w % gn_patch == 0,
            "unet_forward_cached_mixed: cache->n_slots, max_h, max_w (multiples of gn_patch) are required");
   MX_CHECK(ctx_len > 0, "unet: bad shape");
-  p.u = u; p.ctx_len = ctx_len; p.gn_patch = gn_patch; p.dry = dry;
-  p.ng = n_groups; p.B = 0;
   for (int g = 0; g < n_groups; ++g) {
     MX_CHECK(groups[g].batch > 0 && groups[g].H > 0 && groups[g].W > 0 && groups[g].H % gn_patch == 0 && groups[g].W % gn_patch == 0,
              "unet_forward_cached_mixed: every group's H, W must be multiples of gn_patch");
     MX_CHECK(groups[g].H <= cache->max_h && groups[g].W <= cache->max_w, "unet_forward_cached_mixed: a group is larger than the state rows (max_h, max_w)");
     MX_CHECK(dry || (groups[g].latents && groups[g].out), "unet: null group operand");
-    p.gB[g] = groups[g].batch; p.gH[g] = groups[g].H; p.gW[g] = groups[g].W; p.gb0[g] = p.B; p.g_lat[g] = groups[g].latents; p.g_out[g] = groups[g].out;
-    p.B += groups[g].batch;
   }
-  p.H = groups[0].H; p.W = groups[0].W;
+  p.u = u; p.ctx_len = ctx_len; p.gn_patch = gn_patch;
+  p.set_groups(groups, n_groups);
   MX_CHECK(p.B <= cache->n_slots, "unet_forward_cached_mixed: more samples than state rows (n_slots)");
   p.pc = true; p.pc_p0 = gn_patch; p.pc_maxh = cache->max_h; p.pc_maxw = cache->max_w; p.pc_slots = cache->n_slots;
   p.pc_samp.clear(); p.pc_all.clear();
@@ -1691,6 +1532,10 @@ int pc_setup(Plan& p, mx_unet* u, const mx_unet_group* groups, int n_groups, int
   p.pc_np = (int)p.pc_all.size();
   return 0;
 }
+// the patch-unit cache's sizing walk: the plan, walked (nullptr-run: pc_setup or the walk refused)
+bool pc_dry(Plan& p, const mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch, mx_block_cache* sizing) {
+  return !pc_setup(p, const_cast<mx_unet*>(u), groups, n_groups, ctx_len, gn_patch, sizing, true) && dry_walk(p, u, sizing);
+}
 }  // namespace
 
 extern "C" size_t mx_unet_patch_cache_bytes(const mx_unet* u, int n_slots, int max_h, int max_w, int gn_patch) {
@@ -1699,71 +1544,47 @@ extern "C" size_t mx_unet_patch_cache_bytes(const mx_unet* u, int n_slots, int m
   mx_block_cache sizing{};
   sizing.n_slots = n_slots; sizing.max_h = max_h; sizing.max_w = max_w;
   mx_unet_group g{nullptr, nullptr, n_slots, max_h, max_w};
-  if (pc_setup(p, const_cast<mx_unet*>(u), &g, 1, 64, gn_patch, &sizing, true)) return 0;
-  p.stream = nullptr; p.ar.base = nullptr; p.ar.cap = 0; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = true;
-  p.bc = &sizing;
-  if (!p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr)) { mx::set_error(p.err); return 0; }
-  return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000) + 256;
+  return pc_dry(p, u, &g, 1, 64, gn_patch, &sizing) ? bc_top_bytes(p) : 0;
 }
 
 extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch) {
   Plan p;
   mx_block_cache sizing{};
-  sizing.n_slots = 0; sizing.max_h = 0; sizing.max_w = 0;
   if (groups) for (int g = 0; g < n_groups && g < MX_MAX_SEGS; ++g) {
     sizing.n_slots += groups[g].batch; sizing.max_h = std::max(sizing.max_h, groups[g].H); sizing.max_w = std::max(sizing.max_w, groups[g].W);
   }
-  if (pc_setup(p, const_cast<mx_unet*>(u), groups, n_groups, ctx_len, gn_patch, &sizing, true)) return 0;
-  p.stream = nullptr; p.ar.base = nullptr; p.ar.cap = 0; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = true;
-  p.bc = &sizing;
-  if (!p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr)) { mx::set_error(p.err); return 0; }
-  return p.ar.peak + 256;
+  return pc_dry(p, u, groups, n_groups, ctx_len, gn_patch, &sizing) ? p.ar.peak + 256 : 0;
 }
 
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, "unet_forward_cached_mixed: cache with predict, state, slots and slot_valid is required");
-  MX_CHECK(((uintptr_t)cache->state & 255) == 0, "unet_forward_cached_mixed: cache->state must be 256-byte aligned");
+  const std::string who = "unet_forward_cached_mixed";
+  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, who + ": cache with predict, state, slots and slot_valid is required");
+  MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
   if (pc_setup(p, u, groups, n_groups, ctx_len, gn_patch, cache, false)) return 1;
   MX_CHECK(timesteps && ehs && text_embeds && time_ids && workspace, "unet: null operand");
-  MX_CHECK(u->blob != nullptr, "unet: weights not set");
+  MX_CHECK(u->weights.blob != nullptr, "unet: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
   const int B = p.B;
-  std::vector<char> seen(cache->n_slots, 0);
-  p.bc_valid.assign(B, 0);
-  p.bc_all_valid = true; p.bc_any_valid = false;
-  for (int b = 0; b < B; ++b) {
-    MX_CHECK(cache->slots[b] >= 0 && cache->slots[b] < cache->n_slots && !seen[cache->slots[b]], "unet_forward_cached_mixed: slots must be distinct and inside [0, n_slots)");
-    seen[cache->slots[b]] = 1;
-    p.bc_valid[b] = cache->slot_valid[b] ? 1 : 0;
-    p.bc_all_valid = p.bc_all_valid && p.bc_valid[b]; p.bc_any_valid = p.bc_any_valid || p.bc_valid[b];
-  }
-  p.stream = (hipStream_t)stream;
-  p.ar.base = (char*)workspace; p.ar.cap = workspace_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = false;
-  p.bc = cache;
+  if (p.bc_begin_slots(who, cache, B)) return 1;
+  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
   const size_t head = p.pc_head_bytes(p.pc_slots, p.pc_maxh, p.pc_maxw, p.pc_p0);
-  MX_CHECK(head <= cache->state_bytes, "unet_forward_cached_mixed: state buffer too small");
+  MX_CHECK(head <= cache->state_bytes, who + ": state buffer too small");
   const size_t npm = Plan::pc_np_max(p.pc_slots, p.pc_maxh, p.pc_maxw, p.pc_p0);
   char* hp = (char*)cache->state;
   p.pc_dpart = (double*)hp; hp += (size_t)(u->cfg.layers_per_block + 2) * npm * p.pc_p0 * sizeof(double);
   p.pc_dsamp = (mx::PcSample*)hp; hp += (size_t)p.pc_slots * sizeof(mx::PcSample);
   p.pc_dall = (mx::PcPatch*)hp; hp += npm * sizeof(mx::PcPatch);
   p.pc_dask = (mx::PcPatch*)hp;
-  p.h_timesteps.resize(B);
-  if (hipMemcpyAsync(p.pc_dsamp, p.pc_samp.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) != hipSuccess ||
-      hipMemcpyAsync(p.pc_dall, p.pc_all.data(), (size_t)p.pc_np * sizeof(mx::PcPatch), hipMemcpyHostToDevice, p.stream) != hipSuccess ||
-      hipMemcpyAsync(p.h_timesteps.data(), timesteps, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, p.stream) != hipSuccess ||
-      hipStreamSynchronize(p.stream) != hipSuccess) {
-    mx::set_error("unet_forward_cached_mixed: moving the tables failed");
-    return 1;
-  }
+  MX_CHECK(hipMemcpyAsync(p.pc_dsamp, p.pc_samp.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+           hipMemcpyAsync(p.pc_dall, p.pc_all.data(), (size_t)p.pc_np * sizeof(mx::PcPatch), hipMemcpyHostToDevice, p.stream) == hipSuccess,
+           who + ": moving the tables failed");
+  if (p.bc_read_timesteps(who, timesteps, B)) return 1;
   const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, text_embeds, time_ids, groups[0].out);
-  cache->blocks_run = p.blocks_run; cache->blocks_run_hi = 0;
   cache->patches_asked = p.pc_asked; cache->patches_total = p.pc_total;
-  if (!okr) { mx::set_error(p.err); return 1; }
-  return 0;
+  return p.bc_finish(okr, p.blocks_run);
 }
 
 extern "C" int mx_unet_forward_trace(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
@@ -1771,27 +1592,32 @@ extern "C" int mx_unet_forward_trace(mx_unet* u, void* stream, const void* laten
                                      int H, int W, int ctx_len, int gn_patch, void* workspace, size_t workspace_bytes,
                                      const char* stage, void* stage_out, size_t stage_out_bytes) {
   MX_CHECK(stage && stage_out, "unet_forward_trace: stage and stage_out required");
-  return forward_impl(u, stream, latents, io_dtype, timesteps, ehs, text_embeds, time_ids, out, batch, H, W, ctx_len, gn_patch,
-                      workspace, workspace_bytes, stage, stage_out, stage_out_bytes, false, nullptr);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
+  c.time_ids = time_ids; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes; c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
+  return forward_impl(u, c);
 }
 
 /* ---- patch-parallel (BASELINE configs[3]; distrifuser DistriUNetPP, models/distri_sdxl_unet_pp.py:15-216, sync mode) ---- */
 extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_local, int W, int ctx_len, int world) {
   if (!u) return 0;
   size_t peak = 0;
-  mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr;
-  if (forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, 0,
-                   nullptr, 0, nullptr, nullptr, 0, true, &peak, false, &c))
-    return 0;
-  return peak + 4096;
+  const mx_pp_comm comm = sizing_comm(world);
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = &comm; c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 4096;
 }
 
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
-  return forward_impl(u, stream, latents_local, io_dtype, timesteps, ehs, text_embeds, time_ids, out_local, batch, H_local, W, ctx_len, 0,
-                      workspace, workspace_bytes, nullptr, nullptr, 0, false, nullptr, false, comm);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs;
+  c.text_embeds = text_embeds; c.time_ids = time_ids; c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes; c.comm = comm;
+  return forward_impl(u, c);
 }
 
 /* stale-asynchronous steps (distrifuser's default after its warm-up: utils.py:180-214 enqueue / handles; modules/pp/conv2d.py:97-117,
@@ -1799,12 +1625,11 @@ extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_
 extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_local, int W, int ctx_len, int world) {
   if (!u) return 0;
   size_t need = 0;
-  mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr;
+  const mx_pp_comm comm = sizing_comm(world);
   mx_pp_stale st{}; st.mode = MX_PP_WARMUP;
-  if (forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, 0,
-                   nullptr, 0, nullptr, nullptr, 0, true, nullptr, false, &c, &st, &need))
-    return 0;
-  return need + 256;
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = &comm; c.stale = &st; c.state_need = &need;
+  return forward_impl(u, c) ? 0 : need + 256;
 }
 
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
@@ -1814,8 +1639,11 @@ extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* la
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");
   MX_CHECK(stale->mode != MX_PP_STALE || stale->all_gather_async != nullptr, "unet_forward_pp_stale: a stale step needs all_gather_async");
-  return forward_impl(u, stream, latents_local, io_dtype, timesteps, ehs, text_embeds, time_ids, out_local, batch, H_local, W, ctx_len, 0,
-                      workspace, workspace_bytes, nullptr, nullptr, 0, false, nullptr, false, comm, stale);
+  mx::ForwardCall c;
+  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs;
+  c.text_embeds = text_embeds; c.time_ids = time_ids; c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes; c.comm = comm; c.stale = stale;
+  return forward_impl(u, c);
 }
 
 /* host-only walk of the patch-parallel plan that calls comm->all_gather for every exchange of one forward, in order, with
@@ -1823,6 +1651,7 @@ extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* la
  * pre-register buffers, and what tests/test_pp_gloo.py replays over gloo to check the bookkeeping */
 extern "C" int mx_unet_pp_comm_plan(const mx_unet* u, int batch, int H_local, int W, int ctx_len, const mx_pp_comm* comm) {
   MX_CHECK(u && comm && comm->all_gather, "unet_pp_comm_plan: bad arguments");
-  return forward_impl(const_cast<mx_unet*>(u), nullptr, nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr, batch, H_local, W, ctx_len, 0,
-                      nullptr, 0, nullptr, nullptr, 0, true, nullptr, false, comm);
+  mx::ForwardCall c = dry_call(batch, H_local, W, ctx_len);
+  c.comm = comm;
+  return forward_impl(u, c);
 }

@@ -7,15 +7,16 @@
 //   decode(z):  post_quant_conv(z / scaling)  ->  conv_in  ->  mid: resnet, attention, resnet  ->  up blocks (3 resnets each,
 //               nearest-2x + conv between them)  ->  GroupNorm + SiLU  ->  conv_out      (the scaling is folded into post_quant_conv)
 // The reference runs this in fp32 (force_upcast, :48-52); here bf16 storage / fp32 accumulate, tolerance stated in tests/test_vae_gpu.py.
+// Arena, weight lookup and the gemm / conv wrapper: mx::PlanBase (plan_base.h).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
-#include <unordered_map>
-#include <vector>
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
+#include "plan_base.h"
 
 namespace mx {
 int launch_prep_latent(hipStream_t s, const void* in, int dtype, void* out, int B, int Cin, int HW, int CP);
@@ -28,48 +29,14 @@ using mx::bf16_t;
 
 struct mx_vae {
   mx_vae_config cfg;
-  const char* blob = nullptr;
-  uint64_t blob_bytes = 0;
-  std::unordered_map<std::string, std::pair<uint64_t, uint64_t>> table;
+  mx::WeightTable weights;
 };
 
 namespace {
 constexpr int kPad = 64;   // the 4 latent channels are zero-padded to one K tile
 
-struct Arena {
-  char* base; size_t cap; size_t top; size_t peak; bool dry;
-  void* alloc(size_t bytes) {
-    const size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > peak) peak = top;
-    if (dry) return (void*)(uintptr_t)(0x1000 + a);
-    return (top <= cap) ? base + a : nullptr;
-  }
-  size_t mark() const { return top; }
-  void release(size_t m) { top = m; }
-};
-
-struct Plan {
-  mx_vae* u; hipStream_t stream; Arena ar; int B, H, W; bool dry, lookup; std::string err;
-  bool ok() const { return err.empty(); }
-  bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
-  const void* w(const std::string& name, size_t bytes) {
-    if (dry && !lookup) return (const void*)(uintptr_t)0x1000;
-    auto it = u->table.find(name);
-    if (it == u->table.end()) { fail("missing weight '" + name + "'"); return nullptr; }
-    if (it->second.second != bytes) { fail("weight '" + name + "' has " + std::to_string(it->second.second) + " bytes, expected " + std::to_string(bytes)); return nullptr; }
-    return u->blob + it->second.first;
-  }
-  const bf16_t* wb(const std::string& n, size_t e) { return (const bf16_t*)w(n, e * 2); }
-  const float* wf(const std::string& n, size_t e) { return (const float*)w(n, e * 4); }
-  template <typename T> T* alloc(size_t elems) { T* p = (T*)ar.alloc(elems * sizeof(T)); if (!p) fail("workspace too small"); return p; }
-
-  bool gemm(mx_gemm_desc& d, bool conv) {
-    if (!ok()) return false;
-    if (dry) return true;
-    if (conv ? mx_conv3x3(stream, &d) : mx_gemm(stream, &d)) return fail(std::string("gemm/conv: ") + mx_last_error());
-    return true;
-  }
+struct Plan : mx::PlanBase {
+  mx_vae* u; int B, H, W;
   bool linear(const bf16_t* a, int lda, const bf16_t* wgt, const float* bias, void* c, int ldc, int M, int N, int K, const void* residual = nullptr,
               int ldr = 0, float out_scale = 0.f) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
@@ -189,16 +156,14 @@ int run_impl(mx_vae* u, void* stream, const void* latents, int io_dtype, void* o
   MX_CHECK(u != nullptr, "vae: null handle");
   MX_CHECK(batch > 0 && H > 0 && W > 0, "vae: bad shape");
   if (!dry) {
-    MX_CHECK(latents && out && ws && u->blob, "vae: null operand or weights not set");
+    MX_CHECK(latents && out && ws && u->weights.blob, "vae: null operand or weights not set");
     MX_CHECK(io_dtype >= 0 && io_dtype <= 2 && out_dtype >= 0 && out_dtype <= 2, "vae: bad dtype");
   }
   Plan p;
-  p.u = u; p.stream = (hipStream_t)stream; p.B = batch; p.H = H; p.W = W; p.dry = dry; p.lookup = lookup;
-  p.ar.base = (char*)ws; p.ar.cap = ws_bytes; p.ar.top = 0; p.ar.peak = 0; p.ar.dry = dry;
+  p.u = u; p.B = batch; p.H = H; p.W = W; p.lookup = lookup;
+  if (dry) p.begin_dry(u->weights); else p.begin(u->weights, (hipStream_t)stream, ws, ws_bytes);
   const bool okr = p.run(latents, io_dtype, out, out_dtype);
-  if (peak) *peak = p.ar.peak;
-  if (!okr) { mx::set_error(p.err); return 1; }
-  return 0;
+  return p.finish(okr, peak);
 }
 }  // namespace
 
@@ -215,14 +180,8 @@ extern "C" mx_vae* mx_vae_create(const mx_vae_config* c) {
 }
 extern "C" void mx_vae_destroy(mx_vae* u) { delete u; }
 extern "C" int mx_vae_set_weights(mx_vae* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n) {
-  MX_CHECK(u && blob && table && n > 0, "vae_set_weights: bad arguments");
-  u->table.clear();
-  for (int i = 0; i < n; ++i) {
-    MX_CHECK(table[i].name != nullptr && table[i].offset % 16 == 0 && table[i].offset + table[i].bytes <= blob_bytes, "vae_set_weights: bad entry");
-    u->table[table[i].name] = {table[i].offset, table[i].bytes};
-  }
-  u->blob = (const char*)blob; u->blob_bytes = blob_bytes;
-  return 0;
+  MX_CHECK(u != nullptr, "vae_set_weights: null handle");
+  return u->weights.set("vae_set_weights", blob, blob_bytes, table, n);
 }
 extern "C" size_t mx_vae_workspace_bytes(const mx_vae* u, int batch, int H, int W) {
   size_t peak = 0;
@@ -230,7 +189,7 @@ extern "C" size_t mx_vae_workspace_bytes(const mx_vae* u, int batch, int H, int 
   return peak + 4096;
 }
 extern "C" int mx_vae_validate(const mx_vae* u, int batch, int H, int W) {
-  MX_CHECK(u && u->blob, "vae_validate: weights not set");
+  MX_CHECK(u && u->weights.blob, "vae_validate: weights not set");
   return run_impl(const_cast<mx_vae*>(u), nullptr, nullptr, MX_BF16, nullptr, MX_F32, batch, H, W, nullptr, 0, true, true, nullptr);
 }
 extern "C" int mx_vae_decode(mx_vae* u, void* stream, const void* latents, int io_dtype, void* out, int out_dtype, int batch, int H, int W,
