@@ -263,31 +263,6 @@ int mx_gemm_splitk(const mx_gemm_desc* d, int conv);
 /* frees the split-K scratch of `stream` (all != 0: of every stream) after waiting for that stream; library unload frees what is left */
 void mx_gemm_release_scratch(void* stream, int all);
 
-/* ---- the ATTENTION TAIL of a BasicTransformerBlock as ONE launch (round 5; attn_tail.hip).  The four dependent launches
- *   y = attn1.to_out(ao) + y (+ row statistics)  ->  q2 = attn2.to_q(norm2(y))  ->  ao2 = softmax(q2 K^T) V over the text keys  ->  y = attn2.to_out(ao2) + y (+ statistics)
- * (transformer.py:204-262, attention.py:59-110) become work items of one persistent launch: a 256-row panel's items of stage s need stage s - 1 of the same
- * panel only, and the workgroups that take them hand the panel's rows over inside the launch (write-through stores, a ticket per panel and stage).  The
- * three descriptors are EXACTLY those of the separate launches (mx_gemm(out1); mx_gemm(to_q); mx_attention_cross_prescaled; mx_gemm(out2)) and the results
- * equal theirs bit for bit: the same tiles of the same kernels in the same order of summation.  mx_attn_tail_supported tells whether a descriptor can be
- * served (plain C x C linears on 256 x 160 tiles over M = B * L rows, L % 256 == 0, C = heads * 64, ctx_len <= 96; to_q reads out1's output and slab
- * statistics; ao / y / q2 / ao2 four different buffers, the two statistics buffers different).  mx_attn_tail_preferred: 1 when the step plans should
- * take it where it is supported -- MX_ATTN_TAIL=1 in the environment; the DEFAULT IS 0: measured on MI355X the chained launch ties with the four launches
- * in isolation and is 2 % slower inside the SDXL step, so it ships as an option, not as the plan's path.
- * sync: mx_attn_tail_sync_bytes(M) bytes of device memory, ZERO before the first launch; every launch leaves them zero (except the error word read by
- * mx_attn_tail_status: != 0 when a wait inside a launch gave up after ~2^22 polls instead of hanging the device -- that launch's output is invalid). ---- */
-typedef struct mx_attn_tail_desc {
-  mx_gemm_desc out1, to_q, out2;
-  const void* k; int ldk;                    /* the layer's cross-attention keys: bf16 [B * ctx_len, ldk] */
-  const void* vt; int ldvt; int64_t vt_batch_stride;   /* V^T in MX_VT_POS order, per sample */
-  int B, heads, L, ctx_len;
-  unsigned* sync;
-} mx_attn_tail_desc;
-size_t mx_attn_tail_sync_bytes(int M);
-int mx_attn_tail_supported(const mx_attn_tail_desc* d);
-int mx_attn_tail_preferred(void);
-int mx_attn_tail(void* stream, const mx_attn_tail_desc* d);
-int mx_attn_tail_status(void* stream, const unsigned* sync, unsigned* word);
-
 /* V^T key order.  The attention kernel feeds its softmax accumulator straight back to the matrix core as the
  * P operand, and that register layout interleaves keys in blocks of four (lane half h owns keys 4h..4h+3 and
  * 8+4h..8+4h+3 of every 16).  V^T is therefore stored with bits 2 and 3 of the key index swapped, so that each
@@ -309,7 +284,7 @@ int mx_attention(void* stream, const void* q, int ldq, const void* k, int ldk, c
 #define MX_ATTN_QSCALE(scale) ((scale) * 1.4426950408889634f)
 int mx_attention_prescaled(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                            int64_t vt_batch_stride, void* o, int ldo, int B, int H, int Lq, int Lk);
-/* the same through the SHORT-KEY kernel whatever Lq (Lk <= 96: every wave keeps the head's K / V^T in registers): what stage 2 of mx_attn_tail runs;
+/* the same through the SHORT-KEY kernel whatever Lq (Lk <= 96: every wave keeps the head's K / V^T in registers);
  * mx_attention_prescaled itself takes this kernel from Lq >= 2048 and the general one below (the two differ in bf16 rounding of P) */
 int mx_attention_cross_prescaled(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                                  int64_t vt_batch_stride, void* o, int ldo, int B, int H, int Lq, int Lk);

@@ -1161,8 +1161,6 @@ static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, boo
       if (best_t == 0 || t < best_t - 1e-9) { best_t = t; best_per = per; }
       if (wgs <= slots) break;                 // one round: a larger share only lengthens it
     }
-    static const bool fixed64 = [] { const char* e = getenv("MX_XQ_FIXED"); return e && e[0] == '1'; }();      // A/B: the former 64 queries per wave
-    if (fixed64) best_per = 2;
     for (int i = 0; i < n; ++i) ga.g[i].xq_wpb = cdiv(cdiv(ga.g[i].Lq, 32), best_per);
   }
   long blocks = 0;
@@ -1226,7 +1224,7 @@ extern "C" int mx_attention_prescaled(void* stream, const void* q, int ldq, cons
   return launch_attention(stream, q, ldq, k, ldk, vt, ldvt, vt_batch_stride, o, ldo, B, H, Lq, Lk, 1.0f, true);
 }
 
-/* mx_attention_prescaled through the short-key kernel whatever Lq: the separate-launch form of stage 2 of mx_attn_tail (attn_tail.hip) */
+/* mx_attention_prescaled through the short-key kernel whatever Lq */
 extern "C" int mx_attention_cross_prescaled(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                                             int64_t vt_batch_stride, void* o, int ldo, int B, int H, int Lq, int Lk) {
   mx::AttnGroup ga;

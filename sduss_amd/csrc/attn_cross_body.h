@@ -1,6 +1,5 @@
-// The short-key cross-attention body (attention.hip holds the description and the stand-alone kernel attn_cross_kernel): ONE wave computes
-// XK_QPW = 64 queries of one (batch, head) against Lk <= 96 keys held in registers.  Shared with the chained launch of attn_tail.hip, which runs the
-// 77-key cross-attention of a transformer layer between two GEMM stages of the same launch on exactly this code (same bits).
+// The short-key cross-attention body (attention.hip holds the description and the kernel, attn_cross_kernel): ONE wave computes
+// XK_QPW = 64 queries of one (batch, head) against Lk <= 96 keys held in registers.
 #pragma once
 #include "common.h"
 #include "../../include/mxdenoise.h"
@@ -41,10 +40,8 @@ __device__ __forceinline__ float max_across_halves(float x) {
 constexpr int XK_MAXBLK = 3;                   // 32-key blocks (Lk <= 96)
 constexpr int XK_QPW = 64;                     // queries per wave (two 32-query blocks)
 
-// WT: O leaves as write-through (sc1) buffer stores (a chained launch hands it to other workgroups; the launcher keeps O below 2 GB)
-// ---- the pieces: one fragment of the head's K / V^T (global -> register, masked), the queries of a 32-query block, one block's arithmetic.  The stand-alone
-//      kernel's wave keeps the 24 fragments in registers (attn_cross_wave); the chained launch stages them in LDS for the eight waves that share a head
-//      (attn_tail.hip) -- the MFMA operands are the same bits either way. ----
+// ---- the pieces: one fragment of the head's K / V^T (global -> register, masked), the queries of a 32-query block, one block's arithmetic.  The kernel's
+//      wave keeps the 24 fragments in registers (attn_cross_wave). ----
 constexpr int XK_KFRAGS = XK_MAXBLK * 4;       // K fragments of a head: [32-key block][16-feature step]
 constexpr int XK_VFRAGS = 2 * XK_MAXBLK * 2;   // V^T fragments: [16-key step][32-feature half]
 
@@ -96,15 +93,13 @@ __device__ __forceinline__ void xk_load_q(const AttnArgs& p, const int b, const 
 }
 
 // One 32-query block: S^T = K Q^T, single-pass softmax, O^T = V^T P^T, O through the wave's 4-KB LDS patch as whole rows.  kf(kb, ks) / vf(st, db) hand out
-// the fragments (registers or LDS).  WT: O leaves as write-through (sc1) buffer stores (a chained launch hands it to other workgroups; the launcher keeps
-// O below 2 GB).
-template <bool PRE, bool WT, int LK = 0, class KF, class VF>
+// the fragments.
+template <bool PRE, int LK = 0, class KF, class VF>
 __device__ __forceinline__ void xk_block(const AttnArgs& p, const int b, const int head, const int q0, const bf16x8 (&qf)[4], KF&& kf, VF&& vf, char* const patch,
                                          const int lane) {
-#pragma clang fp contract(off)      // the stand-alone kernel and the chained launch must round identically (no multiply-add pair below is meant to fuse)
+#pragma clang fp contract(off)      // no multiply-add pair below is meant to fuse: every instantiation (PRE, LK) rounds alike
   const int r = lane & 31;
   const int hh = lane >> 5;
-  const auto o_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.o, 0, WT ? (int)((long)p.B * p.Lq * p.ldo * 2) : 0, 0x00020000);
   const int Lk = LK > 0 ? LK : p.Lk;
   const int nblk = (Lk + 31) >> 5;             // <= XK_MAXBLK (launcher)
   const int nst = (Lk + 15) >> 4;
@@ -178,14 +173,11 @@ __device__ __forceinline__ void xk_block(const AttnArgs& p, const int b, const i
     const int ch = lane & 7;
     const u32x4 o = *reinterpret_cast<const u32x4*>(patch + row * 128 + ((ch ^ (row & 7)) * 16));
     const int qi = q0 + row;
-    if (qi < p.Lq) {
-      if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b128(o, o_rsrc, (int)((((long)b * p.Lq + qi) * p.ldo + head * 64 + ch * 8) * 2), 0, 16);
-      else *reinterpret_cast<u32x4*>(p.o + ((long)b * p.Lq + qi) * p.ldo + head * 64 + ch * 8) = o;
-    }
+    if (qi < p.Lq) *reinterpret_cast<u32x4*>(p.o + ((long)b * p.Lq + qi) * p.ldo + head * 64 + ch * 8) = o;
   }
 }
 
-// the stand-alone kernel's wave: the head's fragments in registers, XK_QPW queries in 32-query blocks, the next block's queries fetched while one computes
+// the kernel's wave: the head's fragments in registers, XK_QPW queries in 32-query blocks, the next block's queries fetched while one computes
 // the wave's share: `nblocks` consecutive 32-query blocks from query q_wave0 (wave-uniform)
 template <bool PRE, int LK = 0>
 __device__ __forceinline__ void attn_cross_wave(const AttnArgs& p, const int b, const int head, const int q_wave0, const int nblocks, char* const patch, const int lane) {
@@ -205,7 +197,7 @@ __device__ __forceinline__ void attn_cross_wave(const AttnArgs& p, const int b, 
     const int q0 = q_wave0 + blk * 32;
     if (q0 >= p.Lq) break;                     // wave-uniform
     if (blk + 1 < nblocks) xk_load_q(p, b, head, q0 + 32, lane, qn);
-    xk_block<PRE, false, LK>(p, b, head, q0, qf, [&](int kb, int ks) __attribute__((always_inline)) { return kf[kb][ks]; },
+    xk_block<PRE, LK>(p, b, head, q0, qf, [&](int kb, int ks) __attribute__((always_inline)) { return kf[kb][ks]; },
                          [&](int st, int db) __attribute__((always_inline)) { return vf[st][db]; }, patch, lane);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];

@@ -206,8 +206,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_cin_kernel(const GemmArgs p
 }
 
 bool conv_small_n_serves(const mx_gemm_desc* d) {
-  static const bool off = [] { const char* e = getenv("MX_CONV_SMALL_N"); return e && e[0] == '0'; }();      // A/B: the generic tile kernel
-  if (off || d->n_segs != 0 || d->N > 16 || d->N % 4 != 0 || d->Cin % 64 != 0) return false;
+  if (d->n_segs != 0 || d->N > 16 || d->N % 4 != 0 || d->Cin % 64 != 0) return false;
   if (d->stride != 1 || d->up != 0 || d->vhalo != 0 || d->flags != 0) return false;
   if (d->rowbias || d->residual || d->gate || d->out_scale != 0.f || d->gn_part_out || d->splitk > 1) return false;
   if ((((long)d->N * d->K * 2 + 255) & ~255L) + (long)kSnPix * kSnStride > 64 * 1024 || d->ldc % 4 != 0) return false;      // weights + one staged chunk within 64 KB of LDS
@@ -216,8 +215,7 @@ bool conv_small_n_serves(const mx_gemm_desc* d) {
 }
 
 bool conv_small_cin_serves(const mx_gemm_desc* d) {
-  static const bool off = [] { const char* e = getenv("MX_CONV_SMALL_CIN"); return e && e[0] == '0'; }();     // A/B: the tile kernels over the padded input
-  if (off || d->n_segs != 0 || d->cin_valid <= 0 || d->cin_valid > 8 || d->Cin % 8 != 0 || d->N % 80 != 0) return false;
+  if (d->n_segs != 0 || d->cin_valid <= 0 || d->cin_valid > 8 || d->Cin % 8 != 0 || d->N % 80 != 0) return false;
   if (d->stride != 1 || d->up != 0 || d->vhalo != 0 || d->flags != 0) return false;
   if (d->rowbias || d->residual || d->gate || d->out_scale != 0.f || d->gn_part_out || d->splitk > 1 || d->ldc % 8 != 0) return false;
   if ((((long)d->N * kScWRow * 2 + 255) & ~255L) + 4L * 16 * kScStage > 64 * 1024) return false;      // repacked weights + output staging within 64 KB of LDS

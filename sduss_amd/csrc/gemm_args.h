@@ -1,6 +1,6 @@
 // Shared argument block and fused epilogue of the gfx950 GEMM / implicit-GEMM kernels (gemm_bf16.hip: generic
-// 128-row tile and the chooser; gemm_bf16_v2.hip: 128-row LDS-DMA tiles with split-K for the small launches; gemm_bf16_v5.hip /
-// gemm_v5_body.h: 256-row ping-pong tiles, also the conv3x3; gemm_bf16_v4.hip: 256 x 256 persistent ping-pong tiles).  See gemm_bf16.hip for the orientation: the accumulator
+// 128-row tile and the chooser; gemm_bf16_v2.hip: 128-row LDS-DMA tiles with split-K for the small launches; gemm_bf16_v5.hip:
+// 256-row ping-pong tiles, also the conv3x3; gemm_bf16_v4.hip: 256 x 256 persistent ping-pong tiles).  See gemm_bf16.hip for the orientation: the accumulator
 // block acc[i][j] of v_mfma_f32_16x16x32_bf16 holds, per lane, features n = n_wave0 + 16 i + 4 (lane>>4) + {0..3}
 // of token m = m_wave0 + 16 j + (lane & 15).
 #pragma once
@@ -110,8 +110,8 @@ __device__ __forceinline__ float sum_over_fq(float x) {
 template <int NI, int MI>
 __device__ __forceinline__ void gemm_ln_init(const GemmArgs& p, f32x4 (&acc)[NI][MI], const int m_wave0, const int wave_n0, const int fr,
                                              const int fq, float (&rstd)[MI]) {
-#pragma clang fp contract(off)      // (round 5) every fused multiply-add below is written out: two compilations of this function -- the stand-alone kernels and the chained
-                                    // launch of attn_tail.hip -- must round identically, and the contraction the compiler picks depends on the code around it
+#pragma clang fp contract(off)      // (round 5) every fused multiply-add below is written out: the 128-row and the 256-row kernels (gemm_bf16_v2.hip, gemm_bf16_v5.hip) both compile
+                                    // this function and must round identically, and the contraction the compiler picks depends on the code around it
   // statistics layout: row m holds its slabs side by side, ln_stats[(m * pitch + slab) * 2 + {0, 1}], pitch = slabs rounded up to 4: lane
   // (token, fq) reads slabs 4 fq .. 4 fq + 3 (of every group of 16) as two 16-byte loads -- one round trip for up to 16 slabs
   const int slabs = p.ln_slabs;
@@ -553,10 +553,7 @@ __host__ __device__ inline int gemm_epi_features(int flags) {
 // instead of MI: the QKV instantiation of the 256 x 256 kernel)
 // (Tried in round 4 and dropped: the WHOLE fold in the epilogue -- acc * rstd + (bias - rstd * mean * colsum) from one 8-byte load per token block, nothing in
 // front of the K loop.  +7.9 us per GEGLU launch against +4 us for the accumulator start: the block-ahead load does not cover an L2 round trip.)
-// WT: the output tile and its row statistics are stored WRITE-THROUGH (sc1: buffer stores with aux 16 over a descriptor of C, 8-byte agent-scope atomic
-// stores for the statistics) -- a chained launch (attn_tail.hip) hands them to other workgroups of the same launch (cdna guide, Guideline 16 R1); the
-// values stored are the same
-template <int NI, int MI, bool GEGLU, bool VEC = true, bool VPF = true, bool STATS = true, int FEAT = EPI_F_ALL, bool EMIT = STATS, bool RSTD_LOAD = false, bool WT = false>
+template <int NI, int MI, bool GEGLU, bool VEC = true, bool VPF = true, bool STATS = true, int FEAT = EPI_F_ALL, bool EMIT = STATS, bool RSTD_LOAD = false>
 __device__ __forceinline__ void gemm_epilogue_regs(const GemmArgs& p, f32x4 (&acc)[NI][MI], const int m_wave0, const int wave_n0,
                                                    const int fr, const int fq, const float (&ln_rstd_a)[MI]) {
 #pragma clang fp contract(off)      // (round 5) fused multiply-adds are written out (fma4 / fmaf): every instantiation and every translation unit rounds alike
@@ -681,16 +678,8 @@ __device__ __forceinline__ void gemm_epilogue_regs(const GemmArgs& p, f32x4 (&ac
   const unsigned ldr_b = (unsigned)p.ldr * 2u, ldc_b = (unsigned)p.ldc * 2u;
   auto res_at = [&](int row, int col) __attribute__((always_inline)) { return res_base + (unsigned long long)(unsigned)row * ldr_b + (unsigned)(col * 2); };
   auto c_at = [&](int row, int col) __attribute__((always_inline)) { return c_base + (unsigned long long)(unsigned)row * ldc_b + (unsigned)(col * 2); };
-  // stores of the output tile: plain, or write-through through a buffer descriptor of C (WT: the launcher keeps C below 2 GB)
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.c, 0, WT ? (int)((unsigned)p.M * ldc_b) : 0, 0x00020000);
-  auto store_c16 = [&](int row, int col, const u32x4 v) __attribute__((always_inline)) {
-    if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b128(v, c_rsrc, (int)((unsigned)row * ldc_b + (unsigned)(col * 2)), 0, 16);
-    else *reinterpret_cast<u32x4*>(c_at(row, col)) = v;
-  };
-  auto store_c8 = [&](int row, int col, const u32x2 v) __attribute__((always_inline)) {
-    if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b64(v, c_rsrc, (int)((unsigned)row * ldc_b + (unsigned)(col * 2)), 0, 16);
-    else *reinterpret_cast<u32x2*>(c_at(row, col)) = v;
-  };
+  auto store_c16 = [&](int row, int col, const u32x4 v) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(c_at(row, col)) = v; };
+  auto store_c8 = [&](int row, int col, const u32x2 v) __attribute__((always_inline)) { *reinterpret_cast<u32x2*>(c_at(row, col)) = v; };
 
   auto load_res = [&](int j, int pr) __attribute__((always_inline)) -> u32x4 {
     if (!has_res) return u32x4{0u, 0u, 0u, 0u};
@@ -897,7 +886,7 @@ __device__ __forceinline__ void gemm_epilogue_regs(const GemmArgs& p, f32x4 (&ac
       if (fq == 0 && m < p.M) {
         const int slab = wave_n0 / (16 * NI), pitch = (p.N / (16 * NI) + 3) & ~3;
         float* dst = p.stats_out + ((long)m * pitch + slab) * 2;
-        if (WT || p.ln_final_out != nullptr) {  // read back inside this launch (gemm_ln_finalize by the panel's last workgroup; a chained launch's next stage): write-through (sc1)
+        if (p.ln_final_out != nullptr) {        // read back inside this launch (gemm_ln_finalize by the panel's last workgroup): write-through (sc1)
           const unsigned long long bits = (unsigned long long)__float_as_uint(st1) | ((unsigned long long)__float_as_uint(st2) << 32);
           __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {

@@ -593,14 +593,6 @@ static int prepare(void* stream, const mx_gemm_desc* d, bool conv, GemmArgs& a, 
   return 0;
 }
 
-// the argument block of mx_gemm(d) for a launch that runs its tiles itself (attn_tail.hip): the same validation and tile choice
-int gemm_prepare_for_chain(void* stream, const mx_gemm_desc* d, GemmArgs& a, int& bn, int& rows, int& splitk) {
-  TileChoice tc;
-  if (int rc = prepare(stream, d, false, a, tc)) return rc;
-  bn = tc.bn; rows = tc.rows; splitk = tc.splitk;
-  return 0;
-}
-
 static int launch(void* stream, const mx_gemm_desc* d, bool conv) {
   GemmArgs a;
   TileChoice tc;

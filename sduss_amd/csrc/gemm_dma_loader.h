@@ -1,13 +1,13 @@
 // What the LDS-DMA GEMM / implicit-GEMM conv3x3 kernels share: the K-tile depth, the XOR chunk swizzle, the 16-byte global -> LDS copy, the raw
 // barrier, the counted wait, the zero page and the shape of a tile's operand stream.  gemm_bf16_v2.hip (128-row lock-step tiles) and
-// gemm_v5_body.h (256-row ping-pong tiles; through it the chained launch of attn_tail.hip) also share ONE operand loader, gemm_dma_loader.inc;
+// gemm_bf16_v5.hip (256-row ping-pong tiles) also share ONE operand loader, gemm_dma_loader.inc;
 // gemm_bf16_v4.hip takes the primitives only: its four half-tile cursors are a different loader.
 //
 // Why the loader is a fragment included into the kernel body and not a struct here: it was tried as one (cursor state + setup / issue / advance
 // members; with the constant context as members or as arguments; with constant-index unrolling).  Every such form compiles to the same work,
 // but the optimiser takes the aggregate apart at a different point of its pipeline than it does separate locals, and the instruction order and
 // register assignment of all the kernels move with it; the SGPR count of the conv forms moved by 1-4.  As locals and always-inline lambdas of
-// the kernel -- the form the schedules were tuned in -- all 37 kernels keep their register and LDS budget and their instruction
+// the kernel -- the form the schedules were tuned in -- every kernel kept their register and LDS budget and their instruction
 // stream to the letter (profiles/loader_refactor_isa.txt: the table, and a timed example of what a 2-instruction difference in the tile set-up
 // cost).  Re-run that comparison when the fragment changes.
 #pragma once

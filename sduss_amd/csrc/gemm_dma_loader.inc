@@ -1,5 +1,5 @@
 // The operand loader of one BM x BN output tile (BM = 64 * MI rows of X, BN rows of W, K tiles of DMA_BK) for a 512-thread workgroup: the single
-// definition behind gemm_v2_kernel (gemm_bf16_v2.hip) and gemm_v5_tile (gemm_v5_body.h).  A FRAGMENT, included inside the kernel body, not a
+// definition behind gemm_v2_kernel (gemm_bf16_v2.hip) and gemm_v5_tile (gemm_bf16_v5.hip).  A FRAGMENT, included inside the kernel body, not a
 // header: see gemm_dma_loader.h for why, and for the primitives it uses.
 //
 // in scope at the point of inclusion:

@@ -147,8 +147,7 @@ static bool small_m_long_fits(long M, long K) { return M * (K + 8) * 2 <= 64 * 1
 
 // does this form serve d?  (plain linear layers only: bias, per-row residual, SiLU, bf16 or fp32 out)
 bool small_m_serves(const mx_gemm_desc* d, bool conv) {
-  static const bool off = [] { const char* e = getenv("MX_SMALL_M"); return e && e[0] == '0'; }();      // A/B: the generic tile kernel
-  if (off || conv || d->n_segs != 0 || d->M <= 0 || d->M > kSmallMRows) return false;
+  if (conv || d->n_segs != 0 || d->M <= 0 || d->M > kSmallMRows) return false;
   if (d->N % 16 != 0 || d->K % 64 != 0) return false;
   // a long stream (> 64 MB of weights) runs the no-split form, which stages the M x K activations in LDS (64 KB); beyond that the tile kernel
   if ((long)d->N * d->K > kSmallMLong && !small_m_long_fits(d->M, d->K)) return false;

@@ -428,11 +428,6 @@ static int gn_launch_apply(hipStream_t s, GnGroup& G, int silu, bool fold = fals
   MX_LAUNCH_CHECK();
   return 0;
 }
-// MX_GN_FOLD=0: the three-launch form everywhere (A/B, tools/exp)
-static bool gn_fold_in_apply() {
-  static const bool on = [] { const char* e = getenv("MX_GN_FOLD"); return !(e && e[0] == '0'); }();
-  return on;
-}
 }  // namespace mx
 
 extern "C" size_t mx_groupnorm_nhwc_grouped_workspace_bytes(const mx_gn_problem* probs, int n, int C) {
@@ -467,7 +462,7 @@ extern "C" int mx_groupnorm_nhwc_grouped(void* stream, const mx_gn_problem* prob
   hipStream_t s = (hipStream_t)stream;
   prof_begin(s, PROF_NORM, 0.0, bytes);
   // exact statistics everywhere (the sliced form averages patch statistics: gn_fold_kernel): statistics per group, folded by the apply pass itself
-  bool fold = gn_fold_in_apply() && groups <= kFoldGroups;
+  bool fold = groups <= kFoldGroups;
   for (int i = 0; i < n; ++i) fold = fold && G.p[i].patch == 0;
   if (fold) {
     for (int i = 0; i < n; ++i) G.p[i].gpart = G.p[i].part;      // (groups <= C: the per-group sums fit where the per-channel ones would go)

@@ -330,8 +330,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   struct RowStats { float* buf = nullptr; int slabs = 0; float* fin = nullptr; unsigned* cnt = nullptr; };
   unsigned* ln_cnt = nullptr;     // panel tickets of the finalising producers: zeroed once per run, every launch leaves them zero
   static constexpr int kLnCnt = 4096;
-  unsigned* tail_sync = nullptr;  // work tickets of the chained attention-tail launches (mx_attn_tail): zeroed once per run, every launch leaves them zero
-  long tail_rows = 0;             // rows tail_sync is sized for
   // launch d; the statistics of its output rows go to st (from the epilogue when the chosen kernel can, else a pass over the output)
   bool gemm_with_stats(mx_gemm_desc& d, RowStats& st, bool finalise = false) {
     if (!ok()) return false;
@@ -628,21 +626,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const bool pc_fin3 = pc && pass3_shape && st.fin != nullptr;      // GEGLU on the 256 x 256 kernel: (mean, rstd) from the merge kernel
     if (fin1) pass1 = false;
     if (fin3) pass3 = false;
-    // Round 5: the ATTENTION TAIL (attn1.to_out + residual -> attn2.to_q with norm2 folded -> the cross-attention -> attn2.to_out + residual) as ONE
-    // chained launch where its three linears take 256 x 160 tiles (mx_attn_tail; attn_tail.hip): the four launches' results bit for bit.  Its hand-offs
-    // need the cross-attention output and the first projection's row statistics in buffers of their own.  OPT-IN (MX_ATTN_TAIL=1): measured 2 % slower
-    // per SDXL step than the four launches (mx_attn_tail_preferred).
-    bool tail = mx_attn_tail_preferred() != 0 && !pc && !is_pp() && ng == 1 && !pass2 && tail_sync != nullptr && M <= tail_rows && L % 256 == 0;
-    if (getenv("MX_ATTN_TAIL_DEBUG") && !quiet())
-      fprintf(stderr, "[mx attn_tail] transformer %s: tail %d (pc %d pp %d ng %d pass2 %d sync %p M %d rows %ld L %d)\n", p.c_str(), (int)tail, (int)pc, (int)is_pp(), ng,
-              (int)pass2, (void*)tail_sync, M, tail_rows, L);
-    bf16_t* ao2 = nullptr;
-    RowStats stA;
-    if (tail) {
-      ao2 = alloc<bf16_t>((size_t)M * C);
-      stA.buf = (float*)ar.alloc((size_t)M * MX_STATS_PITCH(C / 64) * 2 * sizeof(float));
-      if (!stA.buf) fail("workspace too small");
-    }
     bf16_t* pqc = nullptr; bf16_t* paoc = nullptr; bf16_t* ptc = nullptr;     // patch-unit cache: compact queries / attention output / projection output
     if (pc) { pqc = alloc<bf16_t>((size_t)M * C); paoc = alloc<bf16_t>((size_t)M * C); ptc = alloc<bf16_t>((size_t)M * C); }
     auto normalise = [&]() {      // ln = (y - mean) * rstd, no affine (it lives in the folded weights)
@@ -773,61 +756,26 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       } else {
         attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, (long)C * ldvt, ao, C, heads, L, L);
       }
-      bool chained = false;
-      if (tail && ok()) {
-        auto lin_d = [&](const bf16_t* a_, const std::string& stem, void* c_, const void* res) {
-          mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-          d.a = a_; d.lda = C; d.w = wb(stem + ".weight", (size_t)C * C); d.bias = wf(stem + ".bias", C); d.c = c_; d.ldc = C; d.M = M; d.N = C; d.K = C;
-          d.residual = res; d.ldr = res ? C : 0;
-          return d;
-        };
-        mx_attn_tail_desc td; std::memset(&td, 0, sizeof(td));
-        td.out1 = lin_d(ao, b + ".attn1.to_out.0", y, y);
-        td.out1.stats_out = stA.buf;
-        const int slabs = mx_gemm_stats_slabs(&td.out1);
-        td.to_q = lin_d(y, b + ".attn2.to_q", q2, nullptr);
-        td.to_q.out_scale = MX_ATTN_QSCALE(0.125f);
-        td.to_q.ln_stats = stA.buf; td.to_q.ln_slabs = slabs; td.to_q.ln_colsum = wf(b + ".attn2.to_q.colsum", C); td.to_q.ln_eps = u->cfg.layer_norm_eps;
-        td.out2 = lin_d(ao2, b + ".attn2.to_out.0", y, y);
-        if (!pass3) {
-          td.out2.stats_out = st.buf;
-          if (fin3) { td.out2.ln_final_out = st.fin; td.out2.ln_final_cnt = st.cnt; td.out2.ln_eps = u->cfg.layer_norm_eps; }
-        }
-        const int li = kvp->next;
-        td.k = kvp->k + (size_t)li * C; td.ldk = kvp->ldk; td.vt = kvp->vt + (size_t)li * C * kvp->ldvt; td.ldvt = kvp->ldvt; td.vt_batch_stride = kvp->vt_bstride;
-        td.B = B; td.heads = heads; td.L = L; td.ctx_len = ctx_len; td.sync = tail_sync;
-        if (ok() && slabs > 0 && (quiet() || mx_attn_tail_supported(&td) != 0)) {     // (a dry walk has no operands to validate: it sizes for either form)
-          chained = true;
-          ++kvp->next;
-          if (!pass3) st.slabs = slabs;
-          if (!quiet() && mx_attn_tail(stream, &td)) fail(std::string("attn_tail: ") + mx_last_error());
-        } else {
-          if (getenv("MX_ATTN_TAIL_DEBUG")) fprintf(stderr, "[mx attn_tail] layer %s: slabs %d -> separate launches\n", b.c_str(), slabs);
-          tail = false;        // (the same answer for every layer of this transformer: ask once)
-        }
+      linear(ao, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass2 ? nullptr : &st);
+      // cross-attention (K/V of encoder_hidden_states precomputed for all layers of this width; norm2 in to_q)
+      if (pass2) normalise();
+      linear(pass2 ? ln : y, C, b + ".attn2.to_q.weight", b + ".attn2.to_q.bias", q2, C, M, C, C, nullptr, 0, 0, MX_ATTN_QSCALE(0.125f), nullptr, 0,
+             pass2 ? nullptr : &st);
+      if (ok()) {
+        const int li = kvp->next++;
+        if (ng > 1) {                       // the hoisted K / V^T are per sample: group g reads the rows of its samples
+          mx_attn_problem pr[MX_MAX_SEGS];
+          for (int g = 0; g < ng; ++g) {
+            pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
+            pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
+            pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
+          }
+          attention_grouped(pr, C, kvp->ldk, C, heads);
+        } else
+        attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride,
+                  ao, C, heads, L, ctx_len);
       }
-      if (!chained) {
-        linear(ao, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass2 ? nullptr : &st);
-        // cross-attention (K/V of encoder_hidden_states precomputed for all layers of this width; norm2 in to_q)
-        if (pass2) normalise();
-        linear(pass2 ? ln : y, C, b + ".attn2.to_q.weight", b + ".attn2.to_q.bias", q2, C, M, C, C, nullptr, 0, 0, MX_ATTN_QSCALE(0.125f), nullptr, 0,
-               pass2 ? nullptr : &st);
-        if (ok()) {
-          const int li = kvp->next++;
-          if (ng > 1) {                       // the hoisted K / V^T are per sample: group g reads the rows of its samples
-            mx_attn_problem pr[MX_MAX_SEGS];
-            for (int g = 0; g < ng; ++g) {
-              pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
-              pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
-              pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
-            }
-            attention_grouped(pr, C, kvp->ldk, C, heads);
-          } else
-          attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride,
-                    ao, C, heads, L, ctx_len);
-        }
-        linear(ao, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass3 ? nullptr : &st, false, fin3);
-      }
+      linear(ao, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass3 ? nullptr : &st, false, fin3);
       // GEGLU feed-forward (norm3 in the GEGLU projection)
       if (pass3) normalise();
       linear(pass3 ? ln : y, C, b + ".ff.net.0.proj.weight", b + ".ff.net.0.proj.bias", ff, 4 * C, M, 8 * C, C, nullptr, 0, MX_EPI_GEGLU, 0.f, nullptr, 0,
@@ -855,13 +803,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     // panel tickets of the producers that finalise LayerNorm statistics (transformer()): zero once, every launch leaves them zero
     ln_cnt = (unsigned*)ar.alloc((size_t)kLnCnt * sizeof(unsigned));
     if (ok() && !quiet() && ln_cnt && hipMemsetAsync(ln_cnt, 0, (size_t)kLnCnt * sizeof(unsigned), stream) != hipSuccess) fail("ln tickets: memset failed");
-    tail_rows = 0;                   // rows at level 0: no attention level has more
-    for (int g = 0; g < ng; ++g) tail_rows += (long)gB[g] * gH[g] * gW[g];
-    if (tail_rows > 0 && tail_rows < 2147483647L) {
-      const size_t nb = mx_attn_tail_sync_bytes((int)tail_rows);
-      tail_sync = (unsigned*)ar.alloc(nb);
-      if (ok() && !quiet() && tail_sync && hipMemsetAsync(tail_sync, 0, nb, stream) != hipSuccess) fail("attention tail tickets: memset failed");
-    }
     // ---- time / added-condition embeddings (unet.py:314-341) ----
     bf16_t* tsin = alloc<bf16_t>((size_t)B * C0);
     bf16_t* addin = alloc<bf16_t>((size_t)B * addw);

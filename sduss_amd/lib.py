@@ -52,13 +52,6 @@ class GemmDesc(C.Structure):
     ]
 
 
-class AttnTailDesc(C.Structure):
-    """mx_attn_tail_desc"""
-    _fields_ = [("out1", GemmDesc), ("to_q", GemmDesc), ("out2", GemmDesc),
-                ("k", C.c_void_p), ("ldk", C.c_int), ("vt", C.c_void_p), ("ldvt", C.c_int), ("vt_batch_stride", C.c_int64),
-                ("B", C.c_int), ("heads", C.c_int), ("L", C.c_int), ("ctx_len", C.c_int), ("sync", C.c_void_p)]
-
-
 class AttnProblem(C.Structure):
     """mx_attn_problem"""
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("o", C.c_void_p), ("vt_batch_stride", C.c_int64),
@@ -165,11 +158,6 @@ SYMBOLS = {
     "mx_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _f]),
     "mx_attention_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_cross_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
-    "mx_attn_tail_sync_bytes": (_sz, [_i]),
-    "mx_attn_tail_supported": (_i, [C.POINTER(AttnTailDesc)]),
-    "mx_attn_tail_preferred": (_i, []),
-    "mx_attn_tail": (_i, [_vp, C.POINTER(AttnTailDesc)]),
-    "mx_attn_tail_status": (_i, [_vp, _vp, C.POINTER(C.c_uint)]),
     "mx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "mx_groupnorm_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mx_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),

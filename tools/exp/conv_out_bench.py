@@ -1,5 +1,5 @@
-"""conv_out (320 -> 4 channels, 3x3) and conv_in (4 latent channels zero-padded to 64 -> 320) at the headline batch and for one request: us per launch.
-Run twice on one lease:   python tools/exp/conv_out_bench.py ; MX_CONV_SMALL_N=0 MX_CONV_SMALL_CIN=0 python tools/exp/conv_out_bench.py     (0 = the tile kernels)"""
+"""conv_out (320 -> 4 channels, 3x3) and conv_in (4 latent channels zero-padded to 64 -> 320) at the headline batch and for one request: us per launch of the
+small-N and small-Cin kernels (the tile kernels they were measured against: profiles/r05_r_conv_out_conv_in_kernels.txt)."""
 import os
 import sys
 
@@ -24,7 +24,7 @@ def bench(fn, iters=30):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-print("MX_CONV_SMALL_N =", os.environ.get("MX_CONV_SMALL_N", "(default: small-N form)"))
+print("conv_out (small-N kernel)")
 for b, hw, cin, cout in ((8, 128, 320, 4), (2, 128, 320, 4), (8, 64, 320, 4), (8, 128, 320, 16)):
     x = torch.randn(b, hw, hw, cin, device="cuda", generator=g).bfloat16()
     w = (torch.randn(cout, 9 * cin, device="cuda", generator=g) * (9 * cin) ** -0.5).bfloat16()
@@ -32,7 +32,7 @@ for b, hw, cin, cout in ((8, 128, 320, 4), (2, 128, 320, 4), (8, 64, 320, 4), (8
     t = bench(lambda: ops.conv3x3(x, w, bias))
     print(f"B{b} {hw}x{hw} {cin}->{cout}: {t:7.1f} us   input read at {x.numel() * 2 / t / 1e6:5.2f} TB/s", flush=True)
 
-print("MX_CONV_SMALL_CIN =", os.environ.get("MX_CONV_SMALL_CIN", "(default: small-Cin form)"))
+print("conv_in (small-Cin kernel)")
 for b, hw in ((8, 128), (2, 128), (8, 64)):
     x = torch.zeros(b, hw, hw, 64, device="cuda", dtype=torch.bfloat16)
     x[..., :4] = torch.randn(b, hw, hw, 4, device="cuda", generator=g).bfloat16()

@@ -1,5 +1,5 @@
-"""M <= 16 GEMMs of the two plans (embedding MLPs, stacked time_emb_proj / AdaLN modulation): us per launch.  Run twice on one lease:
-   python tools/exp/small_m_bench.py ; MX_SMALL_M=0 python tools/exp/small_m_bench.py      (0 = the generic 128-row tile kernel)"""
+"""M <= 16 GEMMs of the two plans (embedding MLPs, stacked time_emb_proj / AdaLN modulation): us per launch of the
+weight-stream form (the tile kernel it was measured against: profiles/r05_q_small_m.txt)."""
 import os
 import sys
 
@@ -24,7 +24,6 @@ def bench(fn, iters=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-print("MX_SMALL_M =", os.environ.get("MX_SMALL_M", "(default: weight-stream form)"))
 # (M, N, K, f32 out): SDXL time_embedding.linear_1 / linear_2, add_embedding.linear_1, temb_proj_all; SD3.5 timestep / pooled MLPs, a slice of adaln_all
 for m, n, k, f32 in ((8, 1280, 320, False), (8, 1280, 1280, False), (8, 1280, 2816, False), (8, 13760, 1280, True), (2, 1280, 2816, False), (2, 13760, 1280, True),
                      (8, 1536, 256, False), (8, 1536, 2048, False), (8, 1536, 1536, False), (8, 110592, 1536, True), (8, 442368, 1536, True)):
