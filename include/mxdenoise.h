@@ -737,6 +737,21 @@ int mx_cfg_euler_step(void* stream, const void* noise, void* latents, const floa
 int mx_cfg_flow_step(void* stream, const void* noise, void* latents, const float* sigma, const float* sigma_next,
                      float guidance_scale, int n_lat, int64_t elems_per_latent, int dtype);
 
+/* The same two steps on the WORLD GATHER of the split-batch patch parallelism (sduss_amd/patch_parallel.py; distrifuser
+ * models/distri_sdxl_unet_pp.py:135-171, distri_sd3_transformer_pp.py:242-278), read where it lies: no concatenation into a [2 n, C, H, W] tensor.
+ *   gathered [2 * n_slabs][n_lat][C][H / n_slabs][W] of `dtype`: slot k < n_slabs holds the unconditional prediction of latent rows
+ *            [k * H / n_slabs, (k + 1) * H / n_slabs), slot n_slabs + k the conditional prediction of the same rows (rank-major: the ranks of the
+ *            unconditional half of the world first).  With guidance_scale <= 0 only the first n_slabs slots are read (the plain prediction).
+ *   latents  [n_lat][C][H][W] of `dtype`, updated in place.
+ * Per element the operations are those of mx_cfg_euler_step / mx_cfg_flow_step in the same order (one device function serves both), so the
+ * result equals, bit for bit, re-assembling the gather and calling them; n_slabs == 1 is their `noise` layout.  Any positive sizes with
+ * H % n_slabs == 0; everything else is an error and nothing is launched.  16-byte accesses where both buffers are 16-byte aligned and
+ * (H / n_slabs) * W elements are a whole number of them, element accesses otherwise. */
+int mx_cfg_euler_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next,
+                           float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype);
+int mx_cfg_flow_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next,
+                          float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype);
+
 #ifdef __cplusplus
 }
 #endif

@@ -348,3 +348,29 @@ def cfg_flow_step_(noise: torch.Tensor, latents: torch.Tensor, sigma: torch.Tens
                                   float(guidance_scale), latents.shape[0], latents[0].numel(), _lib.torch_dtype_code(latents.dtype)),
                "mx_cfg_flow_step")
     return latents
+
+
+def _cfg_step_rows_(fn_name: str, gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                    guidance_scale: float, n_slabs: int) -> torch.Tensor:
+    l = _lib.load()
+    assert latents.ndim == 4 and latents.is_contiguous() and gathered.is_contiguous() and gathered.dtype == latents.dtype
+    n_lat, c, h, w = latents.shape
+    assert gathered.numel() >= (2 if guidance_scale > 0 else 1) * latents.numel(), "the gather buffer is smaller than its slots"
+    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
+    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+    _lib.check(getattr(l, fn_name)(_lib.current_stream(), gathered.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
+                                   float(guidance_scale), n_lat, c, h, w, int(n_slabs), _lib.torch_dtype_code(latents.dtype)), fn_name)
+    return latents
+
+
+def cfg_euler_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                         guidance_scale: float, n_slabs: int) -> torch.Tensor:
+    """In place: cfg_euler_step_ on the world gather of the split-batch patch parallelism, read where it lies: gathered
+    [2 * n_slabs, n_lat, C, H / n_slabs, W] = [uncond row slabs ; cond row slabs], latents [n_lat, C, H, W] (mx_cfg_euler_step_rows)."""
+    return _cfg_step_rows_("mx_cfg_euler_step_rows", gathered, latents, sigma, sigma_next, guidance_scale, n_slabs)
+
+
+def cfg_flow_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                        guidance_scale: float, n_slabs: int) -> torch.Tensor:
+    """The flow-match step on the same layout (mx_cfg_flow_step_rows)."""
+    return _cfg_step_rows_("mx_cfg_flow_step_rows", gathered, latents, sigma, sigma_next, guidance_scale, n_slabs)

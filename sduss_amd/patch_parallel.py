@@ -11,6 +11,12 @@ host memory.  The final all-gather of the output rows mirrors distri_sdxl_unet_p
 Buffer bookkeeping (what ``PatchParallelismCommManager`` does with its flat registered buffer, utils.py:119-214): the plan
 allocates every send / receive region from the ONE workspace tensor, so a region is a byte range [offset, offset + n) of that
 tensor and the collective needs no registration step; ``CommLog`` records the ranges so the tests can check them.
+
+Two decompositions of the CFG batch of one request (utils.py:72-116).  ``layout=None``: batch 2 on every rank, rows over all ranks.
+``layout=CfgSplitLayout(world)`` -- distrifuser's default, ``do_classifier_free_guidance=True, split_batch=True``: ranks [0, world/2) compute the
+unconditional row and ranks [world/2, world) the conditional one, each half splitting the latent rows over its world/2 ranks and exchanging over
+that half only; one all-gather over the whole world re-assembles [2, C, H, W] (distri_sdxl_unet_pp.py:135-171), and ``PatchParallelDenoiser`` /
+``PatchParallelSD3Denoiser`` run the scheduler step straight on that gather buffer (mx_cfg_euler_step_rows / mx_cfg_flow_step_rows).
 """
 from __future__ import annotations
 
@@ -31,11 +37,77 @@ def split_rows(latents: torch.Tensor, rank: int, world: int) -> torch.Tensor:
     return latents[:, :, rank * hl:(rank + 1) * hl].contiguous()
 
 
+def walk_comm_plan(plan_fn, handle, batch: int, h_local: int, w: int, ctx_len: int, world: int, rank: int = 0) -> List[Tuple[int, int, int]]:
+    """Host only (no process group, no GPU): the exchanges of one forward of ``plan_fn`` (mx_unet_pp_comm_plan / mx_mmdit_pp_comm_plan of
+    ``handle``) at this shape, in order, as CommLog entries (send_off, recv_off, bytes_per_rank)."""
+    calls: List[Tuple[int, int, int]] = []
+
+    def record(_ctx, _stream, send, recv, nbytes):
+        calls.append((send - 0x1000, recv - 0x1000, nbytes))
+        return 0
+    cb = _lib.ALLGATHER_FN(record)
+    comm = _lib.PPComm(rank, world, cb, None)
+    if plan_fn(handle, batch, h_local, w, ctx_len, C.byref(comm)) != 0:
+        raise _lib.MxError(_lib.load().mx_last_error().decode())
+    return calls
+
+
+class CfgSplitLayout:
+    """Who computes what of the CFG batch [uncond ; cond] of one request: the rank arithmetic of distrifuser's DistriConfig (utils.py:72-116).
+    Splitting (CFG and ``split_batch``): ``n_device_per_batch = world // 2`` (1 when that is 0), rank r computes batch row ``batch_idx(r)`` and the
+    latent row slab ``split_idx(r)`` of it; ``batch_ranks(b)`` are the ranks of one branch (distrifuser's batch_group), ``pair_ranks(s)`` the two ranks
+    holding slab s of the two branches (its split_group).  Otherwise ``n_device_per_batch = world``: every rank runs the whole batch and no group exists."""
+
+    def __init__(self, world: int, do_classifier_free_guidance: bool = True, split_batch: bool = True):
+        assert world > 0 and world & (world - 1) == 0, "the world size must be a power of two (utils.py:52)"
+        self.world = world
+        self.do_classifier_free_guidance, self.split_batch = do_classifier_free_guidance, split_batch
+        if do_classifier_free_guidance and split_batch:          # utils.py:72-77
+            self.n_device_per_batch = world // 2 or 1
+        else:
+            self.n_device_per_batch = world
+        self.batch_groups: Optional[list] = None                 # filled by make_groups
+        self.pair_groups: Optional[list] = None
+
+    @property
+    def splits(self) -> bool:
+        """the CFG rows live on two rank groups (utils.py:90: groups exist from world 2 on)"""
+        return self.do_classifier_free_guidance and self.split_batch and self.world >= 2
+
+    def batch_idx(self, rank: int) -> int:                       # utils.py:102-109
+        if self.do_classifier_free_guidance and self.split_batch:
+            return 1 - int(rank < self.world // 2)
+        return 0
+
+    def split_idx(self, rank: int) -> int:                       # utils.py:111-116
+        return rank % self.n_device_per_batch
+
+    def batch_ranks(self, b: int) -> List[int]:                  # utils.py:93
+        return list(range(b * (self.world // 2), (b + 1) * (self.world // 2)))
+
+    def pair_ranks(self, s: int) -> List[int]:                   # utils.py:97
+        return [s, s + self.world // 2]
+
+    def make_groups(self, dist=None, **new_group_kwargs) -> None:
+        """Create the torch.distributed groups in distrifuser's order (utils.py:90-98): both batch groups, then the world / 2 pair groups.  A
+        collective over the default group: EVERY rank calls ``new_group`` for EVERY group, its own or not, as torch requires.  Does nothing when
+        the layout does not split or the groups exist."""
+        if not self.splits or self.batch_groups is not None:
+            return
+        if dist is None:
+            import torch.distributed as dist
+        assert dist.get_world_size() == self.world, "the layout is over the default process group"
+        self.batch_groups = [dist.new_group(self.batch_ranks(b), **new_group_kwargs) for b in range(2)]
+        self.pair_groups = [dist.new_group(self.pair_ranks(s), **new_group_kwargs) for s in range(self.world // 2)]
+
+
 class CommLog:
-    """byte ranges of the workspace that went through the collective, per call: (send_off, recv_off, bytes_per_rank)"""
+    """byte ranges of the workspace that went through the collective, per call: (send_off, recv_off, bytes_per_rank); ``world_calls``: the gathers
+    of the output rows over the whole world under a CfgSplitLayout, per call (bytes_per_rank, ranks) -- they do not touch the workspace"""
 
     def __init__(self):
         self.calls: List[Tuple[int, int, int]] = []
+        self.world_calls: List[Tuple[int, int]] = []
 
     def check(self, ws_bytes: int, world: int) -> None:
         for so, ro, nb in self.calls:
@@ -48,9 +120,14 @@ class CommLog:
 class PatchParallelUNet:
     """``forward_local(latents_local, ...)`` -> this rank's output rows; ``forward(latents, ...)`` -> the whole output on every
     rank (rows all-gathered).  ``group`` is the torch.distributed group of the ranks sharing the request (distrifuser's
-    batch_group, utils.py:93-97)."""
+    batch_group, utils.py:93-97).
+    ``layout``: a CfgSplitLayout over the default process group (``group`` stays None).  When it splits, ``forward`` takes the CFG batch
+    [2n, C, H, W] = [uncond... ; cond...] with 2n rows of every conditioning tensor, runs this rank's branch (n rows) on its row slab over its
+    batch group, and gathers over the world; ``forward_gathered`` returns that gather as it lies.  A layout that does not split (no CFG,
+    ``split_batch=False``, one rank) changes nothing."""
 
-    def __init__(self, unet, group=None, log: Optional[CommLog] = None, mode: str = "sync", warmup_steps: int = 4):
+    def __init__(self, unet, group=None, log: Optional[CommLog] = None, mode: str = "sync", warmup_steps: int = 4,
+                 layout: Optional[CfgSplitLayout] = None):
         """mode: "sync" (every step exchanges fresh tensors; distrifuser "full_sync"), "stale_gn" or "corrected_async_gn" (distrifuser's
         default, utils.py:30-32): `warmup_steps` synchronous steps, then stale-asynchronous ones (mx_unet_forward_pp_stale).  Call
         ``reset()`` when a new request starts (distrifuser resets its counters per generation, models/base_model.py)."""
@@ -64,6 +141,15 @@ class PatchParallelUNet:
         self._cb_async = _lib.ALLGATHER_INPLACE_FN(self._all_gather_async)
         self.unet = unet
         self.dist = dist
+        self.layout = layout if layout is not None and layout.splits else None
+        if self.layout is not None:
+            # the exchanges of the branch forward run over this rank's half of the world: rank / world below are those of the batch group
+            assert group is None, "a CfgSplitLayout is over the default process group"
+            layout.make_groups(dist)
+            self.world_rank = dist.get_rank()
+            self.batch_idx, split = layout.batch_idx(self.world_rank), layout.split_idx(self.world_rank)
+            group = layout.batch_groups[self.batch_idx]
+            assert dist.get_rank(group) == split and dist.get_world_size(group) == layout.n_device_per_batch
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
@@ -191,8 +277,50 @@ class PatchParallelUNet:
         _lib.check(rc, "mx_unet_forward_pp")
         return out
 
+    def _single_rank(self, latents, timestep, *cond) -> torch.Tensor:
+        """one rank per branch (world 2): nothing to exchange, the ordinary forward (mx_unet_forward / mx_mmdit_forward)"""
+        return self.unet.forward_one(latents.contiguous(), timestep, *cond)
+
+    def forward_gathered(self, latents: torch.Tensor, timestep, *cond) -> torch.Tensor:
+        """Under a splitting layout: the CFG batch [2n, C, H, W] and its conditioning in (the arguments of ``forward``), the world gather out as it
+        lies: [world, n, C, H / n_device_per_batch, W], slot r = the output rows of world rank r (distri_sdxl_unet_pp.py:135-168) -- the
+        ``gathered`` of ops.cfg_euler_step_rows_ / cfg_flow_step_rows_ with n_slabs = n_device_per_batch."""
+        lay = self.layout
+        assert lay is not None, "forward_gathered needs a CfgSplitLayout that splits the CFG batch"
+        assert latents.shape[0] % 2 == 0, "the CFG batch is [uncond... ; cond...]"
+        n = latents.shape[0] // 2
+        rows = slice(self.batch_idx * n, (self.batch_idx + 1) * n)                     # :137-147
+        if torch.is_tensor(timestep) and timestep.ndim > 0 and timestep.numel() > 1:
+            assert timestep.numel() == 2 * n
+            timestep = timestep.reshape(-1)[rows]
+        cond = tuple(c[rows] for c in cond)
+        if self.world == 1:
+            local = self._single_rank(latents[rows], timestep, *cond)
+        else:
+            local = self.forward_local(split_rows(latents[rows], self.rank, self.world), timestep, *cond)
+        local = local.contiguous()
+        if self.log is not None:
+            self.log.world_calls.append((local.numel() * local.element_size(), lay.world))
+        if self.backend == "gloo":                   # tests: through host memory
+            host = local.cpu()
+            parts = [torch.empty_like(host) for _ in range(lay.world)]
+            self.dist.all_gather(parts, host)
+            return torch.stack(parts).to(local.device)
+        buf = torch.empty((lay.world, *local.shape), dtype=local.dtype, device=local.device)
+        self.dist.all_gather_into_tensor(buf, local)
+        return buf
+
+    def _forward_split(self, latents: torch.Tensor, timestep, *cond) -> torch.Tensor:
+        """[2n, C, H, W]: slots [0, npb) concatenated along the rows into row block 0, slots [npb, world) into row block 1 (:169-170)"""
+        buf = self.forward_gathered(latents, timestep, *cond)
+        _world, n, c, hs, w = buf.shape
+        npb = self.world
+        return buf.view(2, npb, n, c, hs, w).permute(0, 2, 3, 1, 4, 5).reshape(2 * n, c, npb * hs, w)
+
     def forward(self, latents: torch.Tensor, timestep, encoder_hidden_states, text_embeds, time_ids) -> torch.Tensor:
         """whole latent in, whole noise prediction out on every rank (distri_sdxl_unet_pp.py:167-195)."""
+        if self.layout is not None:
+            return self._forward_split(latents, timestep, encoder_hidden_states, text_embeds, time_ids)
         local = self.forward_local(split_rows(latents, self.rank, self.world), timestep, encoder_hidden_states, text_embeds, time_ids)
         if self.backend == "gloo":
             parts = [torch.empty_like(local.cpu()) for _ in range(self.world)]
@@ -244,9 +372,67 @@ class PatchParallelSD3(PatchParallelUNet):
         return out
 
     def forward(self, latents: torch.Tensor, timestep, encoder_hidden_states, pooled) -> torch.Tensor:
+        if self.layout is not None:
+            return self._forward_split(latents, timestep, encoder_hidden_states, pooled)
         local = self.forward_local(split_rows(latents, self.rank, self.world), timestep, encoder_hidden_states, pooled)
         host = self.backend == "gloo"
         mine = local.cpu() if host else local
         parts = [torch.empty_like(mine) for _ in range(self.world)]
         self.dist.all_gather(parts, mine, group=self.group)
         return torch.cat([p.to(local.device) for p in parts], dim=2)
+
+
+class PatchParallelDenoiser:
+    """One step of ONE request of pipeline.py (``Request``) under a splitting CfgSplitLayout, as SDXLDenoiser._step_resolution runs it on one
+    GPU: mx_euler_scale_input (CFG duplication fused) -> ``PatchParallelUNet.forward_gathered`` -> mx_cfg_euler_step_rows on the gather buffer.
+    Every rank holds the whole latents, as in distrifuser, and applies the same kernel to the same gathered bytes: after a step the latents are
+    bit-identical on all ranks."""
+
+    def __init__(self, pp: PatchParallelUNet, guidance_scale: float = 5.0):
+        from .step_state import StepCache
+        assert pp.layout is not None, "the step on the gather buffer needs a CfgSplitLayout that splits the CFG batch"
+        self.pp = pp
+        self.guidance_scale = guidance_scale
+        self._cache = StepCache(pp.unet.device)
+
+    def _cond(self, req) -> tuple:
+        return (torch.cat([req.negative_prompt_embeds, req.prompt_embeds], dim=0),
+                torch.cat([req.negative_pooled_prompt_embeds, req.pooled_prompt_embeds], dim=0),
+                torch.cat([req.negative_add_time_ids, req.add_time_ids], dim=0))
+
+    def _scale_input(self, lat: torch.Tensor, sig: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        return ops.euler_scale_input(lat, sig, 2)
+
+    def _step_rows(self, buf, lat, sig, sig_next) -> None:
+        from . import ops
+        ops.cfg_euler_step_rows_(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)
+
+    @torch.inference_mode()
+    def step(self, req) -> None:
+        e = self._cache.entry((req.resolution, req.request_id, id(req)), [req], lambda: self._cond(req))
+        lat = self._cache.latents(e, [req])
+        sig, sig_next, ts = self._cache.step_scalars(e, [req])
+        buf = self.pp.forward_gathered(self._scale_input(lat, sig), torch.cat([ts, ts], dim=0), *e.cond)
+        self._step_rows(buf, lat, sig, sig_next)
+        req.step_index += 1
+        req.latents = lat[0:1]
+
+
+class PatchParallelSD3Denoiser(PatchParallelDenoiser):
+    """The same for one ``SD3Request`` of pipeline_sd3.py over a PatchParallelSD3: no input scaling, the flow-match step (mx_cfg_flow_step_rows)."""
+
+    def __init__(self, pp: PatchParallelSD3, guidance_scale: float = 7.0):
+        super().__init__(pp, guidance_scale)
+
+    def _cond(self, req) -> tuple:
+        return (torch.cat([req.negative_prompt_embeds, req.prompt_embeds], dim=0),
+                torch.cat([req.negative_pooled_prompt_embeds, req.pooled_prompt_embeds], dim=0))
+
+    def _scale_input(self, lat: torch.Tensor, sig: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        return ops.euler_scale_input(lat, torch.zeros_like(sig), 2)      # exact x / 1 copy == torch.cat([latents] * 2)
+
+    def _step_rows(self, buf, lat, sig, sig_next) -> None:
+        from . import ops
+        ops.cfg_flow_step_rows_(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)
