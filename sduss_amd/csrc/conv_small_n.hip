@@ -11,6 +11,7 @@
 #include "common.h"
 #include "../../include/mxdenoise.h"
 #include "gemm_args.h"
+#include "gemm_forms.h"
 
 namespace mx {
 
@@ -222,7 +223,8 @@ bool conv_small_cin_serves(const mx_gemm_desc* d) {
   return true;
 }
 
-int launch_conv_small_cin(hipStream_t s, const GemmArgs& a) {
+int launch_conv_small_cin(hipStream_t s, const GemmArgs& a, int form) {
+  if (form != GK_CONV_SMALL_CIN) return 1;
   const int tiles = a.B * ((a.Hin + 3) / 4) * ((a.Win + 15) / 16);
   const size_t lds = (((size_t)a.N * kScWRow * 2 + 255) & ~(size_t)255) + 4 * 16 * kScStage;
   const int per_cu = std::max(1, std::min(4, (int)((160 * 1024) / (lds + 256))));
@@ -230,7 +232,8 @@ int launch_conv_small_cin(hipStream_t s, const GemmArgs& a) {
   return 0;
 }
 
-int launch_conv_small_n(hipStream_t s, const GemmArgs& a) {
+int launch_conv_small_n(hipStream_t s, const GemmArgs& a, int form) {
+  if (form != GK_CONV_SMALL_N) return 1;
   const int tiles = a.B * ((a.Hin + 3) / 4) * ((a.Win + 15) / 16);
   const size_t lds = (((size_t)a.N * a.K * 2 + 255) & ~(size_t)255) + (size_t)kSnPix * kSnStride;
   const int per_cu = std::max(1, std::min(6, (int)((160 * 1024) / (lds + 256))));        // workgroups a CU holds (LDS)

@@ -156,13 +156,12 @@ __global__ __launch_bounds__(512, 2) void gemm_v2_kernel(const GemmArgs pk) {
   }
 }
 
-// bn: 160 or 128 features per tile.  This file serves the 128-row tiles (small M: one request, mixed batches); the 256-row tiles run the
+// This file serves the 128-row tiles (small M: one request, mixed batches); the 256-row tiles run the
 // ping-pong schedule of gemm_bf16_v5.hip (the lock-step 256-row instantiation it replaced: git history, A/B in profiles/r03_*gemm_bench*).
-int launch_v2(hipStream_t s, const GemmArgs& a, int bn, int form) {
-  const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, 128)) * (a.N / bn) * (a.splitk > 1 ? a.splitk : 1);
-  dim3 grid(tiles), block(512);
-  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
-#define MX_V2(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
+int launch_v2(hipStream_t s, const GemmArgs& a, int form) {
+  const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, 128)) * (a.splitk > 1 ? a.splitk : 1);      // x N / BN: 160 or 128 features per tile
+  switch (form) {                             // the instantiation the route names (gemm_dispatch.cpp): gemm_forms.h
+#define MX_V2(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), dim3(tiles * (a.N / (MX_FORM_FIRST targs))), dim3(512), 0, s, a); return 0;
     MX_GEMM_V2_FORMS(MX_V2)
 #undef MX_V2
     default: return 1;

@@ -320,7 +320,7 @@ int launch_v4(hipStream_t s, const GemmArgs& a, int form) {
   const int ncu = cu_count();
   const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, BM4)) * (a.N / BN4);
   const dim3 grid(tiles > ncu && ncu > 0 ? ncu : tiles), block(512);
-  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
+  switch (form) {                             // the instantiation the route names (gemm_dispatch.cpp): gemm_forms.h
 #define MX_V4(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
     MX_GEMM_V4_FORMS(MX_V4)
 #undef MX_V4

@@ -152,12 +152,11 @@ __global__ __launch_bounds__(512, 2) void gemm_v5_kernel(const GemmArgs pk) {
   gemm_v5_tile<BN, MI, CONV, FEAT, GEGLU, VEC>(pk, tm, tn, smem);
 }
 
-// bn: 160 or 128 features per tile; rows: 256 (the 128-row instantiation MI = 2 was measured and is not built: see the dispatcher in gemm_bf16.hip)
-int launch_v5(hipStream_t s, const GemmArgs& a, int bn, int rows, int form) {
-  const int tiles = (a.nseg > 0 ? a.mt_total : cdiv(a.M, rows)) * (a.N / bn);
-  dim3 grid(tiles), block(512);
-  switch (form) {                             // the instantiation gemm_kernel_of (gemm_bf16.hip) chose: gemm_forms.h
-#define MX_V5(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), grid, block, 0, s, a); return 0;
+// 256 rows x 160 or 128 features per tile (the 128-row instantiation MI = 2 was measured and is not built: see launch() in gemm_dispatch.cpp)
+int launch_v5(hipStream_t s, const GemmArgs& a, int form) {
+  const int mt = a.nseg > 0 ? a.mt_total : cdiv(a.M, 256);
+  switch (form) {                             // the instantiation the route names (gemm_dispatch.cpp): gemm_forms.h
+#define MX_V5(id, k, targs) case id: hipLaunchKernelGGL((k<MX_FORM_UNPAREN targs>), dim3(mt * (a.N / (MX_FORM_FIRST targs))), dim3(512), 0, s, a); return 0;
     MX_GEMM_V5_FORMS(MX_V5)
 #undef MX_V5
     default: return 1;

@@ -1,5 +1,5 @@
 // Every kernel instantiation the GEMM / conv launchers can start, as X-macro lists.  An entry is T(id, kernel, (template arguments)) or
-// P(id, kernel) for a kernel without template arguments.  The chooser in gemm_bf16.hip (gemm_kernel_of) returns an id; each family's launcher
+// P(id, kernel) for a kernel without template arguments.  The route in gemm_dispatch.cpp (form_of) names an id; each family's launcher
 // starts it through one switch over its list, and mx_gemm_kernel_name / mx_gemm_kernel_names report the same entries by name
 // ("gemm_v2_kernel<160, 2, true, EPI_F_ALL, false>": the kernel and its template arguments as written here).
 #pragma once
@@ -70,6 +70,7 @@
   P(GK_CONV_SMALL_CIN, conv3x3_small_cin_kernel)
 
 #define MX_FORM_UNPAREN(...) __VA_ARGS__
+#define MX_FORM_FIRST(x, ...) x        /* MX_FORM_FIRST targs: the first template argument (the tile's features BN of the tile kernels) */
 #define MX_FORM_TARGS(...) "<" #__VA_ARGS__ ">"
 #define MX_FORM_NAME_T(id, k, targs) #k MX_FORM_TARGS targs,
 #define MX_FORM_NAME_P(id, k) #k,
