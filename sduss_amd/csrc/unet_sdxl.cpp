@@ -99,6 +99,41 @@ static std::vector<std::pair<int, int>> kv_widths(const mx_unet_config& c) {
   return widths;
 }
 
+// ---- the arguments of Plan::linear() and Plan::conv() by name: a call states the required fields in order and adds what else it means ----
+// row statistics (sum, sum of squares per row and slab) of the hidden states: what the folded LayerNorms read (mx_gemm_desc.ln_stats)
+// fin / cnt: the FINALISED form (mean, rstd per row: mx_gemm_desc.ln_final) for consumers on the 256 x 256 kernel; cnt = the producers' panel tickets
+struct RowStats { float* buf = nullptr; int slabs = 0; float* fin = nullptr; unsigned* cnt = nullptr; };
+struct Linear {
+  const bf16_t* a; int lda; std::string stem; void* c; int ldc; int M, N, K;      // c[M, N] = a[M, K] * "<stem>.weight"^T + "<stem>.bias"
+  const void* residual = nullptr; int ldr = 0; int flags = 0; float out_scale = 0.f;
+  const bf16_t* a2 = nullptr; int lda2 = 0;
+  const RowStats* ln = nullptr; bool ln_final = false;
+  RowStats* stats_out = nullptr; bool finalise = false;
+  Linear& plus(const void* r, int ld) { residual = r; ldr = ld; return *this; }
+  Linear& epilogue(int f) { flags = f; return *this; }
+  Linear& scaled(float s) { out_scale = s; return *this; }
+  Linear& concat(const bf16_t* x2, int ld2) { a2 = x2; lda2 = ld2; return *this; }                  // A = [a | a2] along K (a2 null: a alone)
+  // the A operand is the UN-normalised hidden state and the LayerNorm in front of this linear is folded into it (weights.py fold_layernorm):
+  // statistics st (null: a is already normalised), column sums "<stem>.colsum"; final: the (mean, rstd) form
+  Linear& folded_ln(const RowStats* st, bool final = false) { ln = st; ln_final = final; return *this; }
+  // also produce the statistics of the output rows (null: not wanted); fin: the producer finalises them
+  Linear& leaves_stats(RowStats* st, bool fin = false) { stats_out = st; finalise = fin; return *this; }
+};
+// where a 3x3 conv reads: the tensor and, patch-parallel, the base of the padded image it is the interior of (one halo row above and below)
+struct ConvIn { bf16_t* t = nullptr; bf16_t* padded = nullptr; };
+struct Conv {
+  ConvIn in; int Hin, Win, Cin; std::string prefix; bf16_t* out; int Cout;         // (Hin, Win: the first group's image)
+  int stride = 1, up = 0, corner_patch = 0;
+  const float* rowbias = nullptr; int ldrb = 0; const void* residual = nullptr;
+  float* gn_part = nullptr; bool* gn_done = nullptr;
+  Conv& strided(int s) { stride = s; return *this; }
+  Conv& upsampled() { up = 1; return *this; }                                      // nearest-2x in the loader
+  Conv& row_bias(const float* rb, int ld) { rowbias = rb; ldrb = ld; return *this; }
+  Conv& plus(const void* r) { residual = r; return *this; }
+  // ask the launch to leave the GroupNorm partial sums of its output (mx_gemm_desc.gn_part_out); *done tells whether it could
+  Conv& gn_partials(float* part, bool* done) { gn_part = part; gn_done = done; return *this; }
+};
+
 struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchange, block-cache bookkeeping: plan_base.h)
   mx_unet* u;
   int ctx_len, gn_patch;
@@ -185,12 +220,13 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (mx::launch_pc_scatter(stream, src, p, 0, C, reg, pc_row_elems(level, C), pc_list(), pc_count(), pc_dsamp, level, p)) return fail(mx_last_error());
     return true;
   }
-  // A 3x3 conv whose output every patch caches.  `corner`: the corner_patch argument of the whole-image form (all patches ask: the ordinary
+  // A 3x3 conv whose output every patch caches.  c.corner_patch: that of the whole-image form (all patches ask: the ordinary
   // launch, then a copy into the state).  Partial mask: gather the asking patches with their halos (stride 2: one extra outer ring of zeros, so
   // that the pad-1 stride-2 launch's output o + 1 has the taps of the reference's pad-0 output o), ONE conv over the compact batch, scatter the
-  // interiors into the state.  The op's output = state (+ time-embedding row) (+ residual) for every patch.
-  bool pc_conv(const bf16_t* x, int h, int wd, int Cin, const std::string& prefix, bf16_t* out, int Cout, int stride, int up, int corner, int level,
-               const float* vec, int ldvec, const bf16_t* residual) {
+  // interiors into the state.  The op's output = state (+ time-embedding row c.rowbias) (+ c.residual) for every patch.
+  bool pc_conv(const Conv& c, int level) {
+    const bf16_t* x = c.in.t; const std::string& prefix = c.prefix;
+    const int Cin = c.Cin, Cout = c.Cout, stride = c.stride, up = c.up;
     const int lo = level + (stride == 2 ? 1 : 0) - up;
     const int p_in = (pc_p0 >> level) << up, p_out = pc_p0 >> lo;
     const int halo_lo = stride == 2 ? 2 : 1, halo_hi = stride == 2 ? 0 : 1;
@@ -203,7 +239,9 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     // compute more than 90 % of the whole images' pixels, the whole-image launch runs and only the asking patches are renewed from it
     const bool whole = !pc_partial || (double)pc_nask * Po * Po >= 0.9 * (double)pc_np * p_out * p_out;
     if (whole) {
-      conv(x, h, wd, Cin, prefix, cout, Cout, stride, up, corner);
+      Conv w{c.in, c.Hin, c.Win, Cin, prefix, cout, Cout};
+      w.stride = stride; w.up = up; w.corner_patch = c.corner_patch;
+      conv(w);
       if (!pc_partial) pc_store(cout, reg, lo, Cout);
       else if (ok() && !quiet() && mx::launch_pc_patch_store(stream, cout, reg, pc_row_elems(lo, Cout), Cout, pc_dask, pc_nask, pc_dsamp, lo, p_out)) fail(mx_last_error());
     } else {
@@ -218,7 +256,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       }
     }
     ar.release(mk);
-    return pc_load(out, reg, lo, Cout, vec, ldvec, residual);
+    return pc_load(c.out, reg, lo, Cout, c.rowbias, c.ldrb, (const bf16_t*)c.residual);
   }
   // attention of the compact query rows of every sample with asking patches against that sample's own keys: problems of one sample each
   bool pc_attention(const bf16_t* qc, const bf16_t* kbase, int ldk, long k_sample_stride, const bf16_t* vtbase, const long* vt_sample_off, const int* ldvt_s,
@@ -325,9 +363,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   }
 
   // ---- op wrappers -------------------------------------------------------------------------
-  // row statistics (sum, sum of squares per row and slab) of the hidden states: what the folded LayerNorms read (mx_gemm_desc.ln_stats)
-  // fin / cnt: the FINALISED form (mean, rstd per row: mx_gemm_desc.ln_final) for consumers on the 256 x 256 kernel; cnt = the producers' panel tickets
-  struct RowStats { float* buf = nullptr; int slabs = 0; float* fin = nullptr; unsigned* cnt = nullptr; };
   unsigned* ln_cnt = nullptr;     // panel tickets of the finalising producers: zeroed once per run, every launch leaves them zero
   static constexpr int kLnCnt = 4096;
   // launch d; the statistics of its output rows go to st (from the epilogue when the chosen kernel can, else a pass over the output)
@@ -348,37 +383,32 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (final) d.ln_final = st.fin; else { d.ln_stats = st.buf; d.ln_slabs = st.slabs; }
     d.ln_colsum = wf(csname, d.N); d.ln_eps = u->cfg.layer_norm_eps;
   }
-  // ln: the A operand is the UN-normalised hidden state and the LayerNorm in front of this linear is folded into it (weights.py
-  // fold_layernorm): statistics ln, column sums `wname`-stem + ".colsum".  stats_out: also produce the statistics of the output rows.
-  bool linear(const bf16_t* a, int lda, const std::string& wname, const std::string& bname, void* c, int ldc, int M, int N,
-              int K, const void* residual = nullptr, int ldr = 0, int flags = 0, float out_scale = 0.f, const bf16_t* a2 = nullptr, int lda2 = 0,
-              const RowStats* ln = nullptr, RowStats* stats_out = nullptr, bool ln_final = false, bool finalise = false) {
+  bool linear(const Linear& l) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-    d.out_scale = out_scale;
-    if (a2) { d.a2 = a2; d.lda2 = lda2; d.k_split = lda; }      // A = [a | a2] along K, read in place
-    d.a = a; d.lda = lda; d.w = wb(wname, (size_t)N * K); d.bias = bname.empty() ? nullptr : wf(bname, N);
-    d.c = c; d.ldc = ldc; d.M = M; d.N = N; d.K = K; d.residual = residual; d.ldr = ldr; d.flags = flags;
-    if (ln) use_ln(d, *ln, wname.substr(0, wname.size() - 6) + "colsum", ln_final);      // "<stem>.weight" -> "<stem>.colsum"
-    if (stats_out) return gemm_with_stats(d, *stats_out, finalise);
+    d.out_scale = l.out_scale;
+    if (l.a2) { d.a2 = l.a2; d.lda2 = l.lda2; d.k_split = l.lda; }      // A = [a | a2] along K, read in place
+    d.a = l.a; d.lda = l.lda; d.w = wb(l.stem + ".weight", (size_t)l.N * l.K); d.bias = wf(l.stem + ".bias", l.N);
+    d.c = l.c; d.ldc = l.ldc; d.M = l.M; d.N = l.N; d.K = l.K; d.residual = l.residual; d.ldr = l.ldr; d.flags = l.flags;
+    if (l.ln) use_ln(d, *l.ln, l.stem + ".colsum", l.ln_final);
+    if (l.stats_out) return gemm_with_stats(d, *l.stats_out, l.finalise);
     return gemm(d, false);
   }
   // 3x3 conv over the images of every group at the current level (Hin, Win: the first group's size; the others come from ch / cw).  A mixed
   // batch is ONE grouped launch: problem g = group g's images, its output grid, its samples' rows of the time-embedding row bias.
-  // gn_part / gn_done: ask the launch to leave the GroupNorm partial sums of its output (mx_gemm_desc.gn_part_out); *gn_done tells whether it could
   int conv_cin_valid = 0;   // set around conv_in's launch
-  bool conv(const bf16_t* x, int Hin, int Win, int Cin, const std::string& prefix, bf16_t* out, int Cout, int stride, int up,
-            int corner_patch, const float* rowbias = nullptr, int ldrb = 0, const void* residual = nullptr, int vhalo = 0, float* gn_part = nullptr,
-            bool* gn_done = nullptr) {
+  bool conv(const Conv& c) {
+    const bf16_t* x = c.in.padded ? c.in.padded : c.in.t;
+    const int Cin = c.Cin, Cout = c.Cout, stride = c.stride, up = c.up;
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-    d.vhalo = vhalo;
-    const int Hv = Hin << up, Wv = Win << up;
-    d.a = x; d.w = wb(prefix + ".weight", (size_t)Cout * 9 * Cin); d.bias = wf(prefix + ".bias", Cout);
-    d.c = out; d.ldc = Cout; d.B = gB[0]; d.Hin = Hin; d.Win = Win; d.Cin = Cin;
+    d.vhalo = c.in.padded ? 1 : 0;            // (the rows above and below the image are in memory)
+    const int Hv = c.Hin << up, Wv = c.Win << up;
+    d.a = x; d.w = wb(c.prefix + ".weight", (size_t)Cout * 9 * Cin); d.bias = wf(c.prefix + ".bias", Cout);
+    d.c = c.out; d.ldc = Cout; d.B = gB[0]; d.Hin = c.Hin; d.Win = c.Win; d.Cin = Cin;
     d.Hout = (Hv + stride - 1) / stride; d.Wout = (Wv + stride - 1) / stride; d.stride = stride; d.up = up;
-    d.corner_patch = corner_patch;
+    d.corner_patch = c.corner_patch;
     d.M = gB[0] * d.Hout * d.Wout; d.N = Cout; d.K = 9 * Cin;
-    d.rowbias = rowbias; d.ldrb = ldrb; d.rows_per_batch = d.Hout * d.Wout;
-    d.residual = residual; d.ldr = Cout;
+    d.rowbias = c.rowbias; d.ldrb = c.ldrb; d.rows_per_batch = d.Hout * d.Wout;
+    d.residual = c.residual; d.ldr = Cout;
     mx_gemm_seg sg[MX_MAX_SEGS];
     if (ng > 1) {
       std::memset(sg, 0, sizeof(sg));
@@ -388,14 +418,14 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         q.B = gB[g]; q.Hin = ch[g]; q.Win = cw[g];
         q.Hout = ((ch[g] << up) + stride - 1) / stride; q.Wout = ((cw[g] << up) + stride - 1) / stride;
         q.M = gB[g] * q.Hout * q.Wout; q.rows_per_batch = q.Hout * q.Wout;
-        q.a = x + in0 * Cin; q.c = out + out0 * Cout;
-        q.residual = residual ? (const bf16_t*)residual + out0 * Cout : nullptr;
-        q.rowbias = rowbias ? rowbias + (long)gb0[g] * ldrb : nullptr;
+        q.a = x + in0 * Cin; q.c = c.out + out0 * Cout;
+        q.residual = c.residual ? (const bf16_t*)c.residual + out0 * Cout : nullptr;
+        q.rowbias = c.rowbias ? c.rowbias + (long)gb0[g] * c.ldrb : nullptr;
         in0 += (long)gB[g] * ch[g] * cw[g]; out0 += q.M;
       }
       d.segs = sg; d.n_segs = ng;
     }
-    if (gn_part && gn_done && ng == 1 && mx_gemm_gn_partials_supported(&d, 1)) { d.gn_part_out = gn_part; *gn_done = true; }
+    if (c.gn_part && c.gn_done && ng == 1 && mx_gemm_gn_partials_supported(&d, 1)) { d.gn_part_out = c.gn_part; *c.gn_done = true; }
     d.cin_valid = conv_cin_valid;             // (conv_in only: the latent's channels inside its zero-padded rows)
     return gemm(d, true);
   }
@@ -454,6 +484,41 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   }
   int level_patch(int level) const { return gn_patch > 0 ? std::max(gn_patch >> level, 1) : 0; }
 
+  // ---- a 3x3 conv in the plan's mode: these four hide it from the blocks ------------------------
+  // row-split image (patch-parallel): GroupNorm from gathered sums, convs on halo'd inputs (modules/pp/{groupnorm,conv2d}.py);
+  // patch-unit cache: the conv per patch from the op's state, its GroupNorm on all rows (resnet.py:390-460 with a mask)
+  ConvIn alloc_conv_in(int h, int wd, int C) {
+    if (!is_pp()) return {alloc<bf16_t>((size_t)rows() * C), nullptr};
+    bf16_t* P = alloc_padded(h, wd, C);
+    return {interior(P, wd, C), P};
+  }
+  // n = silu(GroupNorm(x)) at the block's eps, halo rows included
+  bool norm_into(const ConvIn& n, const bf16_t* x, const std::string& prefix, int h, int wd, int C, int level, const bf16_t* x2 = nullptr, int C1 = 0) {
+    if (!is_pp()) return groupnorm(x, n.t, prefix, h, wd, C, u->cfg.norm_eps, true, level_patch(level), x2, C1);
+    groupnorm_pp(x, n.t, (long)(h + 2) * wd * C, prefix, h, wd, C, u->cfg.norm_eps, true, level, x2, C1);
+    return halo_exchange(n.padded, h, wd, C);
+  }
+  // level: that of the conv's input; the corner rule of the sliced form is that of the output grid's patch
+  bool block_conv(Conv c, int level) {
+    if (is_pp()) return conv(c);             // (exact arithmetic: no corner rule)
+    c.corner_patch = level_patch(level - c.up);
+    return pc ? pc_conv(c, level) : conv(c);
+  }
+  // the same for a tensor that no GroupNorm of the plan wrote (down / upsampler): patch-parallel pads a copy first, for the length of the conv
+  bool block_conv_of(bf16_t* x, Conv c, int level) {
+    const size_t mk = ar.mark();
+    c.in = {x, nullptr};
+    if (is_pp()) {
+      if (c.stride == 2 && c.Hin % 2) fail("patch-parallel: local rows must stay even down to the last level");
+      c.in = alloc_conv_in(c.Hin, c.Win, c.Cin);
+      copy_to_padded(x, c.in.padded, c.Hin, c.Win, c.Cin);
+      halo_exchange(c.in.padded, c.Hin, c.Win, c.Cin);
+    }
+    block_conv(c, level);
+    ar.release(mk);
+    return ok();
+  }
+
   // ---- blocks ------------------------------------------------------------------------------
   // modules/resnet.py:390-460
   // x2 != nullptr: the block's input is the channel concatenation [x (Cin - C2 channels) | x2 (C2 channels)] of an up block
@@ -463,71 +528,28 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const int C1 = Cin - C2;
     bf16_t* out = alloc<bf16_t>((size_t)M * Cout);
     const size_t m = ar.mark();
-    const int patch = level_patch(level);
-    if (is_pp()) {     // row-split image: GroupNorm from gathered sums, convs on halo'd inputs (modules/pp/{groupnorm,conv2d}.py)
-      bf16_t* n1p = alloc_padded(h, wd, Cin);
-      groupnorm_pp(x, interior(n1p, wd, Cin), (long)(h + 2) * wd * Cin, p + ".norm1", h, wd, Cin, u->cfg.norm_eps, true, level, x2, C1);
-      halo_exchange(n1p, h, wd, Cin);
-      bf16_t* h1 = alloc<bf16_t>((size_t)M * Cout);
-      conv(n1p, h, wd, Cin, p + ".conv1", h1, Cout, 1, 0, 0, temb_all ? temb_all + temb_off : nullptr, temb_total, nullptr, 1);
-      temb_off += Cout;
-      bf16_t* n2p = alloc_padded(h, wd, Cout);
-      groupnorm_pp(h1, interior(n2p, wd, Cout), (long)(h + 2) * wd * Cout, p + ".norm2", h, wd, Cout, u->cfg.norm_eps, true, level);
-      halo_exchange(n2p, h, wd, Cout);
-      const bf16_t* sc = x;
-      if (Cin != Cout) {
-        bf16_t* s2 = alloc<bf16_t>((size_t)M * Cout);
-        if (x2) linear(x, C1, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin, nullptr, 0, 0, 0.f, x2, C2);
-        else linear(x, Cin, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin);
-        sc = s2;
-      }
-      conv(n2p, h, wd, Cout, p + ".conv2", out, Cout, 1, 0, 0, nullptr, 0, sc, 1);
-      ar.release(m);
-      dump(p, out, (size_t)M * Cout);
-      return out;
-    }
-    if (pc) {          // patch-unit cache: conv1 / conv2 per patch from the op's state, everything else on all rows (resnet.py:390-460 with a mask)
-      bf16_t* n1 = alloc<bf16_t>((size_t)M * Cin);
-      groupnorm(x, n1, p + ".norm1", h, wd, Cin, u->cfg.norm_eps, true, patch, x2, C1);
-      bf16_t* h1 = alloc<bf16_t>((size_t)M * Cout);
-      pc_conv(n1, h, wd, Cin, p + ".conv1", h1, Cout, 1, 0, patch, level, temb_all ? temb_all + temb_off : nullptr, temb_total, nullptr);
-      temb_off += Cout;
-      bf16_t* n2 = alloc<bf16_t>((size_t)M * Cout);
-      groupnorm(h1, n2, p + ".norm2", h, wd, Cout, u->cfg.norm_eps, true, patch);
-      const bf16_t* sc = x;
-      if (Cin != Cout) {
-        bf16_t* s2 = alloc<bf16_t>((size_t)M * Cout);
-        if (x2) linear(x, C1, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin, nullptr, 0, 0, 0.f, x2, C2);
-        else linear(x, Cin, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin);
-        sc = s2;
-      }
-      pc_conv(n2, h, wd, Cout, p + ".conv2", out, Cout, 1, 0, patch, level, nullptr, 0, sc);
-      ar.release(m);
-      dump(p, out, (size_t)M * Cout);
-      return out;
-    }
-    bf16_t* n1 = alloc<bf16_t>((size_t)M * Cin);
-    groupnorm(x, n1, p + ".norm1", h, wd, Cin, u->cfg.norm_eps, true, patch, x2, C1);
+    ConvIn n1 = alloc_conv_in(h, wd, Cin);
+    norm_into(n1, x, p + ".norm1", h, wd, Cin, level, x2, C1);
     bf16_t* h1 = alloc<bf16_t>((size_t)M * Cout);
     // norm2's statistics come from conv1's own launch where it can leave them (round 4: one resolution, exact statistics, a 256-row tile): per 64
-    // output rows and channel the sums of conv + bias + time embedding, so the statistics pass over h1 does not run (resnet.py:414-429)
+    // output rows and channel the sums of conv + bias + time embedding, so the statistics pass over h1 does not run (resnet.py:414-429).  The
+    // plain path only: patch-parallel statistics are gathered over the ranks, the patch-unit cache's h1 comes out of the state merge
     float* gpart = nullptr;
     bool gdone = false;
-    if (ng == 1 && patch == 0 && M % 64 == 0 && (h * wd) % 64 == 0) gpart = (float*)ar.alloc((size_t)(M / 64) * Cout * 2 * sizeof(float));
-    conv(n1, h, wd, Cin, p + ".conv1", h1, Cout, 1, 0, patch, temb_all ? temb_all + temb_off : nullptr, temb_total, nullptr, 0, gpart, &gdone);
+    if (!is_pp() && !pc && ng == 1 && level_patch(level) == 0 && M % 64 == 0 && (h * wd) % 64 == 0) gpart = (float*)ar.alloc((size_t)(M / 64) * Cout * 2 * sizeof(float));
+    const float* temb = temb_all ? temb_all + temb_off : nullptr;       // this block's columns of the one time_emb_proj GEMM
     temb_off += Cout;
-    bf16_t* n2 = alloc<bf16_t>((size_t)M * Cout);
-    if (gdone) groupnorm_from_partials(h1, n2, p + ".norm2", h, wd, Cout, u->cfg.norm_eps, true, gpart, wf(p + ".conv1.bias", Cout),
-                                       temb_all ? temb_all + (temb_off - Cout) : nullptr, temb_total);
-    else groupnorm(h1, n2, p + ".norm2", h, wd, Cout, u->cfg.norm_eps, true, patch);
+    block_conv(Conv{n1, h, wd, Cin, p + ".conv1", h1, Cout}.row_bias(temb, temb_total).gn_partials(gpart, &gdone), level);
+    ConvIn n2 = alloc_conv_in(h, wd, Cout);
+    if (gdone) groupnorm_from_partials(h1, n2.t, p + ".norm2", h, wd, Cout, u->cfg.norm_eps, true, gpart, wf(p + ".conv1.bias", Cout), temb, temb_total);
+    else norm_into(n2, h1, p + ".norm2", h, wd, Cout, level);
     const bf16_t* sc = x;
-    if (Cin != Cout) {
+    if (Cin != Cout) {                    // the 1x1 shortcut, over [x | x2] in place
       bf16_t* s2 = alloc<bf16_t>((size_t)M * Cout);
-      if (x2) linear(x, C1, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin, nullptr, 0, 0, 0.f, x2, C2);
-      else linear(x, Cin, p + ".conv_shortcut.weight", p + ".conv_shortcut.bias", s2, Cout, M, Cout, Cin);
+      linear(Linear{x, C1, p + ".conv_shortcut", s2, Cout, M, Cout, Cin}.concat(x2, C2));
       sc = s2;
     }
-    conv(n2, h, wd, Cout, p + ".conv2", out, Cout, 1, 0, patch, nullptr, 0, sc);
+    block_conv(Conv{n2, h, wd, Cout, p + ".conv2", out, Cout}.plus(sc), level);
     ar.release(m);
     dump(p, out, (size_t)M * Cout);
     return out;
@@ -542,7 +564,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   bf16_t* transformer(const std::string& p, const bf16_t* x, int h, int wd, int C, int heads, int layers, int level) {
     const int L = h * wd;                 // tokens per image of the first group (the only one unless the batch is mixed)
     const int M = (int)rows();
-    const int ctx = u->cfg.cross_attention_dim;
     // per group: tokens per image, first row, its V^T block (rows of MX_VT_LD(tokens) keys)
     int gL[MX_MAX_SEGS], gldvt[MX_MAX_SEGS]; long gr0[MX_MAX_SEGS], gvt0[MX_MAX_SEGS], vt_elems = 0;
     for (int g = 0; g < ng; ++g) {
@@ -604,7 +625,6 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     }
     // Patch-unit cache: the hidden state in front of norm2 / norm3 is produced by the state-merge kernel.  Round 5: that kernel leaves the row statistics
     // (pc_load_stats), so the folded LayerNorms work as on the exact path; only a PARTIAL mask keeps a pass in front of attn2.to_q -- over the asking rows alone.
-    const bool pass3_shape = pass3;
     // Round 4: where the consumer runs on the 256 x 256 kernel (pass1 / pass3) and the launches that write the hidden state in front of it can
     // FINALISE the row statistics (256-row tiles: mx_gemm_ln_final_supported), the pass disappears as well: the producer's last workgroup per
     // panel leaves (mean, rstd) per row and the consumer starts its accumulators from those 8 bytes (mx_gemm_desc.ln_final).  No patch cache, not
@@ -621,17 +641,18 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       fin1 = ng == 1 && pass1 && can_finalise(C, false) && (layers == 1 || can_finalise(4 * C, true));
       fin3 = pass3 && can_finalise(C, true);
       if (pc) fin3 = false;                  // (norm3's statistics come from the merge kernel, not from a finalising GEMM)
-      if (fin1 || fin3 || (pc && pass3_shape)) { st.fin = (float*)ar.alloc((size_t)M * 2 * sizeof(float)); st.cnt = ln_cnt; if (!st.fin) fail("workspace too small"); }
+      if (fin1 || fin3 || (pc && pass3)) { st.fin = (float*)ar.alloc((size_t)M * 2 * sizeof(float)); st.cnt = ln_cnt; if (!st.fin) fail("workspace too small"); }
     }
-    const bool pc_fin3 = pc && pass3_shape && st.fin != nullptr;      // GEGLU on the 256 x 256 kernel: (mean, rstd) from the merge kernel
+    const bool pc_fin3 = pc && pass3 && st.fin != nullptr;      // GEGLU on the 256 x 256 kernel: (mean, rstd) from the merge kernel
     if (fin1) pass1 = false;
     if (fin3) pass3 = false;
+    const bool folded3 = !pass3 || pc_fin3, final3 = fin3 || pc_fin3;         // norm3 in the GEGLU projection: through statistics, and those finalised
     bf16_t* pqc = nullptr; bf16_t* paoc = nullptr; bf16_t* ptc = nullptr;     // patch-unit cache: compact queries / attention output / projection output
     if (pc) { pqc = alloc<bf16_t>((size_t)M * C); paoc = alloc<bf16_t>((size_t)M * C); ptc = alloc<bf16_t>((size_t)M * C); }
     auto normalise = [&]() {      // ln = (y - mean) * rstd, no affine (it lives in the folded weights)
       if (ok() && !quiet() && mx_layernorm(stream, y, ln, nullptr, nullptr, M, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
     };
-    linear(n, C, p + ".proj_in.weight", p + ".proj_in.bias", y, C, M, C, C, nullptr, 0, 0, 0.f, nullptr, 0, nullptr, pass1 ? nullptr : &st, false, fin1);
+    linear(Linear{n, C, p + ".proj_in", y, C, M, C, C}.leaves_stats(pass1 ? nullptr : &st, fin1));
     // patch-parallel: every rank gathers the other ranks' K rows and V^T columns (modules/pp/attn.py:137: all_gather(kv))
     // -- K alone travels: the QKV epilogue writes q|k interleaved, so the K halves are packed into a contiguous send buffer first
     bf16_t* k_send = nullptr; bf16_t* k_all = nullptr; bf16_t* vt_all = nullptr;
@@ -643,100 +664,34 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     }
     KV* kvp = kv_for(C);
     if (!kvp && ok()) fail("no cross-attention K/V buffer for width " + std::to_string(C));
-    for (int k = 0; k < layers && ok(); ++k) {
-      const std::string b = p + ".transformer_blocks." + std::to_string(k);
-      if (pc) {
-        // PatchBasicTransformerBlock under a per-patch mask (transformer.py:167-290): the LayerNorms, the q | k | v projection of attn1 and the
-        // feed-forward run on all rows; the self-attention core + to_out and the whole cross-attention run for the asking patches and the
-        // others take the op's cached output (attention.py:59-110, 121-232); then the residual adds
-        const int pp2 = (pc_p0 >> level) * (pc_p0 >> level);
-        const int Mc = pc_count() * pp2;
-        std::vector<long> vt_off(B); std::vector<int> ldvt_s(B), Lk_s(B);
-        for (int g = 0; g < ng; ++g) for (int i = 0; i < gB[g]; ++i) { const int bb = gb0[g] + i; vt_off[bb] = gvt0[g] + (long)i * C * gldvt[g]; ldvt_s[bb] = gldvt[g]; Lk_s[bb] = gL[g]; }
-        auto self_attention_all = [&]() {
-          if (ng > 1) {
-            mx_attn_problem pr[MX_MAX_SEGS];
-            for (int g = 0; g < ng; ++g) {
-              pr[g].q = qk + gr0[g] * 2 * C; pr[g].k = qk + gr0[g] * 2 * C + C; pr[g].vt = vt + gvt0[g]; pr[g].o = ao + gr0[g] * C;
-              pr[g].vt_batch_stride = (int64_t)C * gldvt[g]; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = gL[g]; pr[g].ldvt = gldvt[g];
-            }
-            attention_grouped(pr, 2 * C, 2 * C, C, heads);
-          } else attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, (long)C * ldvt, ao, C, heads, L, L);
-        };
-        {   // norm1 folded into the fused q | k | v projection exactly as on the exact path (its producers are ordinary GEMMs)
-          if (pass1) normalise();
-          mx_gemm_desc d = qkv_desc(b, pass1 ? ln : y);
-          if (!pass1) { use_ln(d, st, b + ".attn1.to_qkv.colsum", fin1); if (!fin1) use_ln_grouped(d, st); } else wf(b + ".attn1.to_qkv.colsum", 3 * C);
-          gemm(d, false);
-        }
-        char* reg1 = pc_region(level, C);
-        if (!pc_partial) {
-          self_attention_all();
-          linear(ao, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", ptc, C, M, C, C);
-          pc_store(ptc, reg1, level, C);
-        } else {
-          pc_gather_rows(qk, 2 * C, C, pqc, level);
-          pc_attention(pqc, qk + C, 2 * C, -1, vt, vt_off.data(), ldvt_s.data(), 0, paoc, C, heads, level, Lk_s.data());
-          linear(paoc, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", ptc, C, Mc, C, C);
-          pc_scatter_rows(ptc, C, reg1, level);
-        }
-        // y += attn1's (fresh or cached) output; norm2's statistics come with the merge when to_q runs over all rows
-        const bool stats2 = !pc_partial && !pass2;
-        if (stats2) { pc_load_stats(y, reg1, level, C, y, st.buf, nullptr); st.slabs = 1; }
-        else pc_load(y, reg1, level, C, nullptr, 0, y);
-        char* reg2 = pc_region(level, C);
-        const int li = ok() ? kvp->next++ : 0;
-        if (!pc_partial) {
-          if (!stats2) normalise();
-          linear(stats2 ? y : ln, C, b + ".attn2.to_q.weight", b + ".attn2.to_q.bias", q2, C, M, C, C, nullptr, 0, 0, MX_ATTN_QSCALE(0.125f), nullptr, 0, stats2 ? &st : nullptr);
-          if (ok()) {
-            if (ng > 1) {
-              mx_attn_problem pr[MX_MAX_SEGS];
-              for (int g = 0; g < ng; ++g) {
-                pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
-                pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
-                pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
-              }
-              attention_grouped(pr, C, kvp->ldk, C, heads);
-            } else attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride, ao, C, heads, L, ctx_len);
-          }
-          linear(ao, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", ptc, C, M, C, C);
-          pc_store(ptc, reg2, level, C);
-        } else {
-          // the asking rows alone are normalised (the pass over all M rows in front of this gather cost as much as attn2 saved)
-          pc_gather_rows(y, C, C, paoc, level);
-          if (ok() && !quiet() && mx_layernorm(stream, paoc, pqc, nullptr, nullptr, Mc, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
-          linear(pqc, C, b + ".attn2.to_q.weight", b + ".attn2.to_q.bias", q2, C, Mc, C, C, nullptr, 0, 0, MX_ATTN_QSCALE(0.125f));
-          if (ok()) {
-            std::vector<long> cvt_off(B); std::vector<int> cld(B, kvp->ldvt), clk(B, ctx_len);
-            for (int bb = 0; bb < B; ++bb) cvt_off[bb] = (long)bb * kvp->vt_bstride;
-            pc_attention(q2, kvp->k + (size_t)li * C, kvp->ldk, (long)ctx_len * kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, cvt_off.data(), cld.data(),
-                         kvp->vt_bstride, paoc, C, heads, level, clk.data());
-          }
-          linear(paoc, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", ptc, C, Mc, C, C);
-          pc_scatter_rows(ptc, C, reg2, level);
-        }
-        // y += attn2's output; norm3's statistics with the merge: finalised for the 256 x 256 GEGLU kernel, one slab for the others
-        if (pc_fin3) pc_load_stats(y, reg2, level, C, y, nullptr, st.fin);
-        else if (!pass3) { pc_load_stats(y, reg2, level, C, y, st.buf, nullptr); st.slabs = 1; }
-        else pc_load(y, reg2, level, C, nullptr, 0, y);
-        if (pass3 && !pc_fin3) normalise();
-        {
-          const bool folded = pc_fin3 || !pass3;
-          linear(folded ? y : ln, C, b + ".ff.net.0.proj.weight", b + ".ff.net.0.proj.bias", ff, 4 * C, M, 8 * C, C, nullptr, 0, MX_EPI_GEGLU, 0.f, nullptr, 0,
-                 folded ? &st : nullptr, nullptr, pc_fin3);
-        }
-        linear(ff, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", y, C, M, C, 4 * C, y, C, 0, 0.f, nullptr, 0, nullptr,
-               (k + 1 < layers && !pass1) ? &st : nullptr, false, fin1 && k + 1 < layers);
-        continue;
+    // ---- the two attention launches over all rows: one grouped launch over the groups' problems in a mixed batch ----
+    auto self_problems = [&](mx_attn_problem* pr) {
+      for (int g = 0; g < ng; ++g) {
+        pr[g].q = qk + gr0[g] * 2 * C; pr[g].k = qk + gr0[g] * 2 * C + C; pr[g].vt = vt + gvt0[g]; pr[g].o = ao + gr0[g] * C;
+        pr[g].vt_batch_stride = (int64_t)C * gldvt[g]; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = gL[g]; pr[g].ldvt = gldvt[g];
       }
-      // self-attention (norm1 in the fused q / k / v projection)
-      {
-        if (pass1) normalise();
-        mx_gemm_desc d = qkv_desc(b, pass1 ? ln : y);
-        if (!pass1) { use_ln(d, st, b + ".attn1.to_qkv.colsum", fin1); if (!fin1) use_ln_grouped(d, st); } else wf(b + ".attn1.to_qkv.colsum", 3 * C);
-        gemm(d, false);
+    };
+    auto cross_problems = [&](mx_attn_problem* pr, int li) {      // the hoisted K / V^T are per sample: group g reads the rows of its samples
+      for (int g = 0; g < ng; ++g) {
+        pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
+        pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
+        pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
       }
+    };
+    auto self_attention = [&]() {               // ao = attention(q, k, v of qk | vt)
+      mx_attn_problem pr[MX_MAX_SEGS];
+      if (ng > 1) { self_problems(pr); attention_grouped(pr, 2 * C, 2 * C, C, heads); }
+      else attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, (long)C * ldvt, ao, C, heads, L, L);
+    };
+    auto cross_attention = [&](int li) {        // ao = attention(q2, layer li of the hoisted K / V^T)
+      if (!ok()) return;
+      mx_attn_problem pr[MX_MAX_SEGS];
+      if (ng > 1) { cross_problems(pr, li); attention_grouped(pr, C, kvp->ldk, C, heads); }
+      else attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride, ao, C, heads, L, ctx_len);
+    };
+    // ---- between the q | k | v projection and the feed-forward: y += attn1, y += attn2, leaving norm3's input form ----
+    // self-attention -> to_out -> residual, then the cross-attention on layer li of the K / V^T of encoder_hidden_states (norm2 in to_q)
+    auto attend = [&](const std::string& b, int li) {
       if (is_pp()) {
         if (ok() && !dry && hipMemcpy2DAsync(k_send, (size_t)C * 2, qk + C, (size_t)2 * C * 2, (size_t)C * 2, M, hipMemcpyDeviceToDevice, stream) != hipSuccess)
           fail("patch-parallel: K pack failed");
@@ -746,46 +701,80 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
             mx_attention_prescaled_chunked(stream, qk, 2 * C, k_all, C, vt_all, ldvt, (int64_t)C * ldvt, ao, C, B, heads, L, pp_world * L, L,
                                            (int64_t)L * C, (int64_t)M * C, (int64_t)B * C * ldvt))
           fail(std::string("attention: ") + mx_last_error());
-      } else if (ng > 1) {
-        mx_attn_problem pr[MX_MAX_SEGS];
-        for (int g = 0; g < ng; ++g) {
-          pr[g].q = qk + gr0[g] * 2 * C; pr[g].k = qk + gr0[g] * 2 * C + C; pr[g].vt = vt + gvt0[g]; pr[g].o = ao + gr0[g] * C;
-          pr[g].vt_batch_stride = (int64_t)C * gldvt[g]; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = gL[g]; pr[g].ldvt = gldvt[g];
-        }
-        attention_grouped(pr, 2 * C, 2 * C, C, heads);
-      } else {
-        attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, (long)C * ldvt, ao, C, heads, L, L);
-      }
-      linear(ao, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass2 ? nullptr : &st);
-      // cross-attention (K/V of encoder_hidden_states precomputed for all layers of this width; norm2 in to_q)
+      } else self_attention();
+      linear(Linear{ao, C, b + ".attn1.to_out.0", y, C, M, C, C}.plus(y, C).leaves_stats(pass2 ? nullptr : &st));
       if (pass2) normalise();
-      linear(pass2 ? ln : y, C, b + ".attn2.to_q.weight", b + ".attn2.to_q.bias", q2, C, M, C, C, nullptr, 0, 0, MX_ATTN_QSCALE(0.125f), nullptr, 0,
-             pass2 ? nullptr : &st);
-      if (ok()) {
-        const int li = kvp->next++;
-        if (ng > 1) {                       // the hoisted K / V^T are per sample: group g reads the rows of its samples
-          mx_attn_problem pr[MX_MAX_SEGS];
-          for (int g = 0; g < ng; ++g) {
-            pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
-            pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
-            pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
-          }
-          attention_grouped(pr, C, kvp->ldk, C, heads);
-        } else
-        attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride,
-                  ao, C, heads, L, ctx_len);
+      linear(Linear{pass2 ? ln : y, C, b + ".attn2.to_q", q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(pass2 ? nullptr : &st));
+      cross_attention(li);
+      linear(Linear{ao, C, b + ".attn2.to_out.0", y, C, M, C, C}.plus(y, C).leaves_stats(pass3 ? nullptr : &st, fin3));
+    };
+    // PatchBasicTransformerBlock under a per-patch mask (transformer.py:167-290): the LayerNorms, the q | k | v projection of attn1 and the
+    // feed-forward run on all rows; the self-attention core + to_out and the whole cross-attention run for the asking patches and the
+    // others take the op's cached output (attention.py:59-110, 121-232); then the residual adds
+    std::vector<long> vt_off(pc ? B : 0); std::vector<int> ldvt_s(vt_off.size()), Lk_s(vt_off.size());
+    if (pc) for (int g = 0; g < ng; ++g) for (int i = 0; i < gB[g]; ++i) { const int bb = gb0[g] + i; vt_off[bb] = gvt0[g] + (long)i * C * gldvt[g]; ldvt_s[bb] = gldvt[g]; Lk_s[bb] = gL[g]; }
+    auto attend_masked = [&](const std::string& b, int li) {
+      const int pp2 = (pc_p0 >> level) * (pc_p0 >> level);
+      const int Mc = pc_count() * pp2;
+      char* reg1 = pc_region(level, C);
+      if (!pc_partial) {
+        self_attention();
+        linear(Linear{ao, C, b + ".attn1.to_out.0", ptc, C, M, C, C});
+        pc_store(ptc, reg1, level, C);
+      } else {
+        pc_gather_rows(qk, 2 * C, C, pqc, level);
+        pc_attention(pqc, qk + C, 2 * C, -1, vt, vt_off.data(), ldvt_s.data(), 0, paoc, C, heads, level, Lk_s.data());
+        linear(Linear{paoc, C, b + ".attn1.to_out.0", ptc, C, Mc, C, C});
+        pc_scatter_rows(ptc, C, reg1, level);
       }
-      linear(ao, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", y, C, M, C, C, y, C, 0, 0.f, nullptr, 0, nullptr, pass3 ? nullptr : &st, false, fin3);
+      // y += attn1's (fresh or cached) output; norm2's statistics come with the merge when to_q runs over all rows
+      const bool stats2 = !pc_partial && !pass2;
+      if (stats2) { pc_load_stats(y, reg1, level, C, y, st.buf, nullptr); st.slabs = 1; }
+      else pc_load(y, reg1, level, C, nullptr, 0, y);
+      char* reg2 = pc_region(level, C);
+      if (!pc_partial) {
+        if (!stats2) normalise();
+        linear(Linear{stats2 ? y : ln, C, b + ".attn2.to_q", q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(stats2 ? &st : nullptr));
+        cross_attention(li);
+        linear(Linear{ao, C, b + ".attn2.to_out.0", ptc, C, M, C, C});
+        pc_store(ptc, reg2, level, C);
+      } else {
+        // the asking rows alone are normalised (the pass over all M rows in front of this gather cost as much as attn2 saved)
+        pc_gather_rows(y, C, C, paoc, level);
+        if (ok() && !quiet() && mx_layernorm(stream, paoc, pqc, nullptr, nullptr, Mc, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
+        linear(Linear{pqc, C, b + ".attn2.to_q", q2, C, Mc, C, C}.scaled(MX_ATTN_QSCALE(0.125f)));
+        if (ok()) {
+          std::vector<long> cvt_off(B); std::vector<int> cld(B, kvp->ldvt), clk(B, ctx_len);
+          for (int bb = 0; bb < B; ++bb) cvt_off[bb] = (long)bb * kvp->vt_bstride;
+          pc_attention(q2, kvp->k + (size_t)li * C, kvp->ldk, (long)ctx_len * kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, cvt_off.data(), cld.data(),
+                       kvp->vt_bstride, paoc, C, heads, level, clk.data());
+        }
+        linear(Linear{paoc, C, b + ".attn2.to_out.0", ptc, C, Mc, C, C});
+        pc_scatter_rows(ptc, C, reg2, level);
+      }
+      // y += attn2's output; norm3's statistics with the merge: finalised for the 256 x 256 GEGLU kernel, one slab for the others
+      if (pc_fin3) pc_load_stats(y, reg2, level, C, y, nullptr, st.fin);
+      else if (!pass3) { pc_load_stats(y, reg2, level, C, y, st.buf, nullptr); st.slabs = 1; }
+      else pc_load(y, reg2, level, C, nullptr, 0, y);
+    };
+    for (int k = 0; k < layers && ok(); ++k) {
+      const std::string b = p + ".transformer_blocks." + std::to_string(k);
+      {   // self-attention's fused q | k | v projection, norm1 folded into it (the hidden state in front of it comes from ordinary GEMMs in every mode)
+        if (pass1) normalise();
+        mx_gemm_desc d = qkv_desc(b, pass1 ? ln : y);
+        if (!pass1) { use_ln(d, st, b + ".attn1.to_qkv.colsum", fin1); if (!fin1) use_ln_grouped(d, st); } else wf(b + ".attn1.to_qkv.colsum", 3 * C);
+        gemm(d, false);
+      }
+      const int li = ok() ? kvp->next++ : 0;
+      if (pc) attend_masked(b, li); else attend(b, li);
       // GEGLU feed-forward (norm3 in the GEGLU projection)
-      if (pass3) normalise();
-      linear(pass3 ? ln : y, C, b + ".ff.net.0.proj.weight", b + ".ff.net.0.proj.bias", ff, 4 * C, M, 8 * C, C, nullptr, 0, MX_EPI_GEGLU, 0.f, nullptr, 0,
-             pass3 ? nullptr : &st, nullptr, fin3);
-      linear(ff, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", y, C, M, C, 4 * C, y, C, 0, 0.f, nullptr, 0, nullptr,
-             (k + 1 < layers && !pass1) ? &st : nullptr, false, fin1 && k + 1 < layers);
+      if (!folded3) normalise();
+      linear(Linear{folded3 ? y : ln, C, b + ".ff.net.0.proj", ff, 4 * C, M, 8 * C, C}.epilogue(MX_EPI_GEGLU).folded_ln(folded3 ? &st : nullptr, final3));
+      const bool more = k + 1 < layers;        // the next layer's norm1 reads what ff.net.2 leaves
+      linear(Linear{ff, 4 * C, b + ".ff.net.2", y, C, M, C, 4 * C}.plus(y, C).leaves_stats(more && !pass1 ? &st : nullptr, fin1 && more));
     }
-    linear(y, C, p + ".proj_out.weight", p + ".proj_out.bias", out, C, M, C, C, x, C);
+    linear(Linear{y, C, p + ".proj_out", out, C, M, C, C}.plus(x, C));
     ar.release(m0);
-    (void)ctx;
     dump(p, out, (size_t)M * C);
     return out;
   }
@@ -813,23 +802,17 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     bf16_t* t2 = alloc<bf16_t>((size_t)B * T);
     bf16_t* a1 = alloc<bf16_t>((size_t)B * T);
     bf16_t* semb = alloc<bf16_t>((size_t)B * T);
-    linear(tsin, C0, "time_embedding.linear_1.weight", "time_embedding.linear_1.bias", t1, T, B, T, C0, nullptr, 0, MX_EPI_SILU);
-    linear(t1, T, "time_embedding.linear_2.weight", "time_embedding.linear_2.bias", t2, T, B, T, T);
-    linear(addin, addw, "add_embedding.linear_1.weight", "add_embedding.linear_1.bias", a1, T, B, T, addw, nullptr, 0, MX_EPI_SILU);
+    linear(Linear{tsin, C0, "time_embedding.linear_1", t1, T, B, T, C0}.epilogue(MX_EPI_SILU));
+    linear(Linear{t1, T, "time_embedding.linear_2", t2, T, B, T, T});
+    linear(Linear{addin, addw, "add_embedding.linear_1", a1, T, B, T, addw}.epilogue(MX_EPI_SILU));
     // silu(emb + aug_emb): the only consumer of emb is time_emb_proj(silu(emb)) (resnet.py:421)
-    linear(a1, T, "add_embedding.linear_2.weight", "add_embedding.linear_2.bias", semb, T, B, T, T, t2, T, MX_EPI_SILU);
+    linear(Linear{a1, T, "add_embedding.linear_2", semb, T, B, T, T}.plus(t2, T).epilogue(MX_EPI_SILU));
     // all time_emb_proj linears in one GEMM, fp32 out
-    temb_total = 0;
-    {
-      int prev = C0;
-      for (int i = 0; i < nlev; ++i) { for (int j = 0; j < c.layers_per_block; ++j) temb_total += c.block_out_channels[i]; prev = c.block_out_channels[i]; }
-      (void)prev;
-      temb_total += 2 * c.block_out_channels[nlev - 1];
-      for (int i = 0; i < nlev; ++i) temb_total += (c.layers_per_block + 1) * c.block_out_channels[nlev - 1 - i];
-    }
+    temb_total = 2 * c.block_out_channels[nlev - 1];
+    for (int i = 0; i < nlev; ++i) temb_total += (2 * c.layers_per_block + 1) * c.block_out_channels[i];     // down: layers_per_block resnets a level, up: one more
     temb_all = alloc<float>((size_t)B * temb_total);
     temb_off = 0;
-    linear(semb, T, "temb_proj_all.weight", "temb_proj_all.bias", temb_all, temb_total, B, temb_total, T, nullptr, 0, MX_EPI_OUT_F32);
+    linear(Linear{semb, T, "temb_proj_all", temb_all, temb_total, B, temb_total, T}.epilogue(MX_EPI_OUT_F32));
 
     // ---- cross-attention K / V^T of encoder_hidden_states for every layer, one GEMM per width ----
     kv.clear();
@@ -862,13 +845,16 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     for (int g = 0; g < ng && ok() && !dry; ++g)
       if (mx::launch_prep_latent(stream, g_lat[g], io_dtype, x0 + row0(g) * kConvInPad, gB[g], c.in_channels, ch[g] * cw[g], kConvInPad)) fail(mx_last_error());
     bf16_t* x = alloc<bf16_t>((size_t)rows() * C0);
+    // patches are cut from the true latent: no corner rule (unet.py:123-158), and no patch caches conv_in: conv(), not block_conv().  The
+    // patch-parallel padded copy is allocated behind x and stays for the forward (every later offset counts from it)
+    ConvIn in0{x0, nullptr};
     if (is_pp()) {
-      bf16_t* x0p = alloc_padded(h, wd, kConvInPad);
-      copy_to_padded(x0, x0p, h, wd, kConvInPad);
-      halo_exchange(x0p, h, wd, kConvInPad);
-      conv(x0p, h, wd, kConvInPad, "conv_in", x, C0, 1, 0, 0, nullptr, 0, nullptr, 1);
-    } else
-    { conv_cin_valid = c.in_channels <= 8 ? 8 : 0; conv(x0, h, wd, kConvInPad, "conv_in", x, C0, 1, 0, 0); conv_cin_valid = 0; }  // patches are cut from the true latent: no corner rule (unet.py:123-158)
+      in0 = alloc_conv_in(h, wd, kConvInPad);
+      copy_to_padded(x0, in0.padded, h, wd, kConvInPad);
+      halo_exchange(in0.padded, h, wd, kConvInPad);
+    } else conv_cin_valid = c.in_channels <= 8 ? 8 : 0;
+    conv(Conv{in0, h, wd, kConvInPad, "conv_in", x, C0});
+    conv_cin_valid = 0;
     dump("conv_in", x, (size_t)rows() * C0);
 
     struct Skip { bf16_t* t; int C; int h, wd; int level; };
@@ -894,18 +880,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         size_t drows = 0;
         for (int g = 0; g < ng; ++g) drows += (size_t)gB[g] * ((ch[g] + 1) / 2) * ((cw[g] + 1) / 2);
         bf16_t* d = alloc<bf16_t>(drows * Cout);
-        if (is_pp()) {
-          if (h % 2) fail("patch-parallel: local rows must stay even down to the last level");
-          const size_t mk = ar.mark();
-          bf16_t* xp = alloc_padded(h, wd, Cout);
-          copy_to_padded(x, xp, h, wd, Cout);
-          halo_exchange(xp, h, wd, Cout);
-          conv(xp, h, wd, Cout, dp + ".conv", d, Cout, 2, 0, 0, nullptr, 0, nullptr, 1);
-          ar.release(mk);
-        } else if (pc)
-        pc_conv(x, h, wd, Cout, dp + ".conv", d, Cout, 2, 0, level_patch(i), i, nullptr, 0, nullptr);   // PatchDownsample2D with a mask (resnet.py:341-378)
-        else
-        conv(x, h, wd, Cout, dp + ".conv", d, Cout, 2, 0, level_patch(i));   // resnet.py:364-371
+        block_conv_of(x, Conv{{}, h, wd, Cout, dp + ".conv", d, Cout}.strided(2), i);   // resnet.py:364-371; PatchDownsample2D (resnet.py:341-378) under a mask
         h /= 2; wd /= 2;
         for (int g = 0; g < ng; ++g) { ch[g] = (ch[g] + 1) / 2; cw[g] = (cw[g] + 1) / 2; }
         x = d;
@@ -936,17 +911,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       if (i != nlev - 1) {
         const std::string upn = "up_blocks." + std::to_string(i) + ".upsamplers.0";
         bf16_t* d = alloc<bf16_t>((size_t)rows() * 4 * Cout);
-        if (is_pp()) {
-          const size_t mk = ar.mark();
-          bf16_t* xp = alloc_padded(h, wd, Cout);
-          copy_to_padded(x, xp, h, wd, Cout);
-          halo_exchange(xp, h, wd, Cout);
-          conv(xp, h, wd, Cout, upn + ".conv", d, Cout, 1, 1, 0, nullptr, 0, nullptr, 1);
-          ar.release(mk);
-        } else if (pc)
-        pc_conv(x, h, wd, Cout, upn + ".conv", d, Cout, 1, 1, level_patch(level - 1), level, nullptr, 0, nullptr);   // PatchUpsample2D with a mask (resnet.py:280-339)
-        else
-        conv(x, h, wd, Cout, upn + ".conv", d, Cout, 1, 1, level_patch(level - 1));  // resnet.py:316, 327-333
+        block_conv_of(x, Conv{{}, h, wd, Cout, upn + ".conv", d, Cout}.upsampled(), level);   // resnet.py:316, 327-333; PatchUpsample2D (resnet.py:280-339) under a mask
         h *= 2; wd *= 2;
         for (int g = 0; g < ng; ++g) { ch[g] *= 2; cw[g] *= 2; }
         x = d;
@@ -1144,16 +1109,11 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       const int Co = c.out_channels;
       const int ldo = (Co + 3) / 4 * 4;
       bf16_t* o = alloc<bf16_t>(M * ldo);
-      if (is_pp()) {
-        bf16_t* np_ = alloc_padded(h, wd, C0);
-        groupnorm_pp(x, interior(np_, wd, C0), (long)(h + 2) * wd * C0, "conv_norm_out", h, wd, C0, c.norm_eps, true, 0);
-        halo_exchange(np_, h, wd, C0);
-        conv(np_, h, wd, C0, "conv_out", o, ldo, 1, 0, 0, nullptr, 0, nullptr, 1);
-      } else {
-      bf16_t* n = alloc<bf16_t>(M * C0);
-      groupnorm(x, n, "conv_norm_out", h, wd, C0, c.norm_eps, true, level_patch(0));
-      conv(n, h, wd, C0, "conv_out", o, ldo, 1, 0, level_patch(0));
-      }
+      ConvIn n = alloc_conv_in(h, wd, C0);        // (not released: the forward ends here)
+      norm_into(n, x, "conv_norm_out", h, wd, C0, 0);
+      Conv co{n, h, wd, C0, "conv_out", o, ldo};  // no patch caches conv_out: conv(), not block_conv()
+      co.corner_patch = level_patch(0);
+      conv(co);
       dump("conv_out", o, M * ldo);
       for (int g = 0; g < ng && ok() && !dry; ++g)
         if (mx::launch_nhwc_to_nchw(stream, o + row0(g) * ldo, g_out[g], io_dtype, gB[g], Co, ch[g] * cw[g], ldo)) fail(mx_last_error());
@@ -1287,6 +1247,14 @@ mx::ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
   c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
   return c;
 }
+// the fields every forward entry point fills alike; the image (latents, out, batch, H, W) or the groups, gn_patch and the mode's own fields follow
+mx::ForwardCall forward_call(void* stream, int io_dtype, const float* timesteps, const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len,
+                             void* workspace, size_t workspace_bytes) {
+  mx::ForwardCall c;
+  c.stream = stream; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds; c.time_ids = time_ids; c.ctx_len = ctx_len;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return c;
+}
 mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
 
 }  // namespace
@@ -1345,10 +1313,8 @@ extern "C" int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int c
 extern "C" int mx_unet_forward(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
                                const void* ehs, const void* text_embeds, const float* time_ids, void* out, int batch, int H,
                                int W, int ctx_len, int gn_patch, void* workspace, size_t workspace_bytes) {
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
-  c.time_ids = time_ids; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace;
-  c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W; c.gn_patch = gn_patch;
   return forward_impl(u, c);
 }
 
@@ -1375,9 +1341,8 @@ extern "C" int mx_unet_forward_mixed(mx_unet* u, void* stream, const mx_unet_gro
                                      const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                      size_t workspace_bytes) {
   MX_CHECK(groups != nullptr, "unet_forward_mixed: null groups");
-  mx::ForwardCall c;
-  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
-  c.time_ids = time_ids; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.groups = groups; c.n_groups = n_groups; c.gn_patch = gn_patch;
   return forward_impl(u, c);
 }
 
@@ -1385,9 +1350,8 @@ extern "C" int mx_unet_forward_mixed_trace(mx_unet* u, void* stream, const mx_un
                                            const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                            size_t workspace_bytes, const char* stage, void* stage_out, size_t stage_out_bytes) {
   MX_CHECK(groups != nullptr && stage && stage_out, "unet_forward_mixed_trace: groups, stage and stage_out required");
-  mx::ForwardCall c;
-  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
-  c.time_ids = time_ids; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.groups = groups; c.n_groups = n_groups; c.gn_patch = gn_patch;
   c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
   return forward_impl(u, c);
 }
@@ -1533,10 +1497,9 @@ extern "C" int mx_unet_forward_trace(mx_unet* u, void* stream, const void* laten
                                      int H, int W, int ctx_len, int gn_patch, void* workspace, size_t workspace_bytes,
                                      const char* stage, void* stage_out, size_t stage_out_bytes) {
   MX_CHECK(stage && stage_out, "unet_forward_trace: stage and stage_out required");
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.text_embeds = text_embeds;
-  c.time_ids = time_ids; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.gn_patch = gn_patch; c.workspace = workspace;
-  c.workspace_bytes = workspace_bytes; c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W; c.gn_patch = gn_patch;
+  c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
   return forward_impl(u, c);
 }
 
@@ -1554,10 +1517,8 @@ extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs;
-  c.text_embeds = text_embeds; c.time_ids = time_ids; c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace;
-  c.workspace_bytes = workspace_bytes; c.comm = comm;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
   return forward_impl(u, c);
 }
 
@@ -1580,10 +1541,8 @@ extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* la
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");
   MX_CHECK(stale->mode != MX_PP_STALE || stale->all_gather_async != nullptr, "unet_forward_pp_stale: a stale step needs all_gather_async");
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs;
-  c.text_embeds = text_embeds; c.time_ids = time_ids; c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace;
-  c.workspace_bytes = workspace_bytes; c.comm = comm; c.stale = stale;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm; c.stale = stale;
   return forward_impl(u, c);
 }
 

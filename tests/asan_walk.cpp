@@ -122,6 +122,22 @@ int main() {
     REQUIRE(say("mx_unet_workspace_bytes_cached_mixed(1 x 16, 2 x 32; 77, 32)", mx_unet_workspace_bytes_cached_mixed(t, tg, 2, 77, 32)) == 0);   // 16 is not a multiple of 32
     REQUIRE(say("mx_unet_workspace_bytes_cached_mixed(no groups)", mx_unet_workspace_bytes_cached_mixed(t, nullptr, 0, 77, 8)) == 0);
     REQUIRE(say("mx_unet_workspace_bytes_cached_mixed(1 x 16, 2 x 32; 0, 8)", mx_unet_workspace_bytes_cached_mixed(t, tg, 2, 0, 8)) == 0);
+    // three resolutions in one launch sequence, and the patch-parallel plan down to its smallest legal split (16 local rows over three levels)
+    mx_unet_group t3[3]; std::memset(t3, 0, sizeof(t3));
+    const int tres[3] = {16, 24, 32};
+    for (int i = 0; i < 3; ++i) { t3[i].batch = i + 1; t3[i].H = t3[i].W = tres[i]; }
+    REQUIRE(say("mx_unet_workspace_bytes_mixed(1 x 16, 2 x 24, 3 x 32; 77)", mx_unet_workspace_bytes_mixed(t, t3, 3, 77)) > 0);
+    for (int world : {2, 4}) {
+      const int hl = 64 / world;
+      const size_t ws = say(call("tiny mx_unet_workspace_bytes_pp(2, %d, 64, 77, %d)", hl, world), mx_unet_workspace_bytes_pp(t, 2, hl, 64, 77, world));
+      REQUIRE(ws > 0);
+      REQUIRE(say(call("tiny mx_unet_pp_state_bytes(2, %d, 64, 77, %d)", hl, world), mx_unet_pp_state_bytes(t, 2, hl, 64, 77, world)) > 0);
+      mx_pp_comm comm; comm.rank = world - 1; comm.world = world; comm.all_gather = count_gather; comm.ctx = nullptr;
+      begin_exchanges(ws);
+      REQUIRE(say(call("tiny mx_unet_pp_comm_plan(2, %d, 64, 77, rank %d of %d)", hl, world - 1, world), (size_t)mx_unet_pp_comm_plan(t, 2, hl, 64, 77, &comm)) == 0);
+      say_exchanges("tiny mx_unet_pp_comm_plan");
+      REQUIRE(n_exchanges > 0);
+    }
     mx_unet_destroy(t);
   }
 
