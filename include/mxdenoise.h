@@ -644,6 +644,12 @@ typedef int (*mx_skip_predict_fn)(void* ctx, int block, int is_up, int n_samples
 int mx_forest_predict(const int32_t* left, const int32_t* right, const int32_t* feature, const double* threshold, const double* p1,
                       const int32_t* roots, int n_trees, const float* X, int n_rows, int n_feat, unsigned char* out);
 typedef void (*mx_skip_observe_fn)(void* ctx, int block, int n_samples, const float* out_mse);
+/* A flattened forest in DEVICE memory, the layout mx_forest_predict takes (sduss_amd/block_cache.py CompiledForest.to_device).  The struct itself
+ * lives on the host. */
+typedef struct mx_device_forest {
+  const int32_t *left, *right, *feature; const double *threshold, *p1; const int32_t* roots;
+  int n_trees, n_nodes, n_feat;
+} mx_device_forest;
 typedef struct mx_block_cache {
   mx_skip_predict_fn predict;
   void* ctx;
@@ -669,6 +675,21 @@ typedef struct mx_block_cache {
    * gn_patch), and, out, the patches that asked / the patches seen over the blocks of the last forward */
   int max_h, max_w;
   unsigned long long patches_asked, patches_total;
+  /* Opt-in, patch / chunk unit only (mx_unet_forward_cached_mixed, mx_mmdit_forward_cached_mixed): the decision taken ON THE DEVICE.  With
+   * dev_down set, each block's features, forest answer, counter rule and list of asking units come from one kernel launch and the host reads back
+   * only the counts that size the following launches; predict may be NULL and is never called, observe must be NULL.  dev_down decides the down
+   * and mid blocks (and every MMDiT block), dev_up the up blocks (NULL: dev_down); a forest's n_feat must be 2 + the inputs of every block it
+   * serves.  dev_counters (device, zeroed by the caller once): the reuse counters, laid out [block][slot][unit of the slot's max_h x max_w grid],
+   * followed by the kernel's scratch; the layout follows the REQUEST (its state row), so a composition change needs no remapping, and a sample
+   * with slot_valid 0 reads as zero and is overwritten.  decisions_out (optional, host): the run flags of every block of the forward, in call order
+   * (units in row order).  All zero: nothing changes.  Setting dev_down on the sample-unit entries (mx_unet_forward_cached,
+   * mx_mmdit_forward_cached) is an error: they keep the host decision. */
+  const struct mx_device_forest* dev_down;
+  const struct mx_device_forest* dev_up;
+  int32_t* dev_counters;
+  size_t dev_counters_bytes;  /* >= mx_skip_counters_bytes(blocks of the model, n_slots, (max_h / patch) * (max_w / patch)) */
+  int forced_after;
+  unsigned char* decisions_out;
 } mx_block_cache;
 size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, int W);
 int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
@@ -691,7 +712,7 @@ int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io
  * State: one row per request (slots / slot_valid / n_slots as above, required), rows laid out for max_h x max_w latents;
  * mx_unet_patch_cache_bytes(u, n_slots, max_h, max_w, gn_patch) bytes.  Needs gn_patch > 0 with every group's H, W multiples of it.  The
  * workspace is larger than mx_unet_workspace_bytes_mixed (compact patch batches): mx_unet_workspace_bytes_cached_mixed.  Not graph-captured
- * (one host decision per block).  Oracle: oracle/cache_patch_ref.py; tests/test_block_cache_gpu.py. */
+ * (one read-back per block).  Oracle: oracle/cache_patch_ref.py; tests/test_block_cache_gpu.py. */
 size_t mx_unet_patch_cache_bytes(const mx_unet* u, int n_slots, int max_h, int max_w, int gn_patch);
 size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch);
 int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
@@ -719,6 +740,42 @@ size_t mx_mmdit_workspace_bytes_cached_mixed(const mx_mmdit* u, const mx_unet_gr
 int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                   const void* encoder_hidden_states, const void* pooled_projections, int ctx_len, int patch, void* workspace,
                                   size_t workspace_bytes, mx_block_cache* cache);
+
+/* The device-side decision of the patch / chunk unit (mx_block_cache.dev_down).  One statement of the rule serves both sides
+ * (sduss_amd/csrc/skip_decide.h): a unit's feature is the fp64 sum of its partial sums in order / its element count, rounded to fp32
+ * (MX_MSE_UNCACHED for a sample that is not valid); the row [block, timestep of the unit's sample, features] goes through the forest as in
+ * mx_forest_predict; prev = uncached ? 0 : counter, forced = prev == forced_after, run = raw | forced | uncached, new counter =
+ * (uncached | run) ? 0 : prev + 1; the asking units are listed in row order; first[b] = index of sample b's first asking unit, first[B] = n_ask. */
+#define MX_SKIP_MAX_IN 8
+size_t mx_skip_counters_bytes(int n_blocks, int n_slots, int max_units_per_slot);
+/* Host twin of the kernel, for CPU tests and as the documentation of the exact semantics (no GPU needed).  forest: HOST pointers.  n units in row
+ * order (unit_sample non-decreasing), n_in = forest->n_feat - 2 finalised features per unit (mse[n][n_in]; rows of a sample that is not valid are
+ * ignored), counters[n]: one per unit, in / out.  ask_out[n]: the indices of the asking units, first_out[n_samples + 1]. */
+int mx_skip_decide_host(const mx_device_forest* forest, int block, int forced_after, int n, int n_samples, const int32_t* unit_sample,
+                        const unsigned char* sample_valid, const float* timesteps, const float* mse, int32_t* counters, unsigned char* run_out,
+                        int32_t* ask_out, int32_t* first_out, int32_t* n_ask_out);
+/* The kernel itself on caller-made tables (what the step plans launch once per block; tests/test_skip_decide_gpu.py).  Every pointer but `forest`
+ * is device memory.  kind 0: units = patches {int32 b, py, px, pad} over samples {int64 row0; int32 h, w, slot, npx}, the counter of a patch is
+ * [slot][py * grid_w + px], input i has part_len[i] partial sums per unit from partial + part_off[i] over part_elems[i] elements; kind 1: units =
+ * token ranges {int64 row0; int32 rows, slot, srow0} with unit_sample naming their sample, counter [slot][srow0 / rows], 64 partial sums per unit
+ * over rows * part_elems[0] elements.  record (int32 [MX_SKIP_REC_FIRST + n_samples + 1]): status (non-zero: the forest points outside itself),
+ * n_ask, asking and total units per group (sample_group, optional), first[].  ask_units (kind 0, optional): the asking patches, in order. */
+#define MX_SKIP_REC_STATUS 0
+#define MX_SKIP_REC_NASK 1
+#define MX_SKIP_REC_GASK 2
+#define MX_SKIP_REC_GTOT (2 + MX_MAX_SEGS)
+#define MX_SKIP_REC_FIRST (2 + 2 * MX_MAX_SEGS)
+typedef struct mx_skip_decide_args {
+  const mx_device_forest* forest;
+  int block, forced_after, n, n_samples, n_in, kind;
+  const void* units; const void* samples;
+  const int32_t* unit_sample; const int32_t* sample_group;
+  const unsigned char* sample_valid; const float* timesteps;
+  const double* partial; int64_t part_off[MX_SKIP_MAX_IN]; int part_len[MX_SKIP_MAX_IN]; double part_elems[MX_SKIP_MAX_IN];
+  int32_t* counters; int units_per_slot, grid_w, n_counters;     /* this block's row of the counters and its length */
+  unsigned char* run; void* ask_units; int32_t* ask_index; int32_t* record;
+} mx_skip_decide_args;
+int mx_skip_decide_device(void* stream, const mx_skip_decide_args* args);
 
 /* ------------------------------------------------------------------------------------------
  * The element-wise steps either side of the model call.

@@ -85,6 +85,37 @@ class CompiledForest:
         self.n_features = int(forest.n_features_in_)
         self._lib = _lib.load()
 
+    @classmethod
+    def from_threshold(cls, threshold: float, n_features: int) -> "CompiledForest":
+        """The one-tree forest that answers as ``ThresholdPredictor(threshold)`` does on rows of ``n_features`` columns, ties included: a chain over
+        the input differences (features 2 ..): ``x <= threshold`` goes on to the next feature, anything larger ends in a leaf with p1 = 1, and the
+        last "on" branch is a leaf with p1 = 0."""
+        m = int(n_features) - 2
+        assert m >= 1, "a feature row is [block, timestep, at least one input difference]"
+        leaf0, leaf1 = m, m + 1
+        return cls.from_tables([i + 1 if i < m - 1 else leaf0 for i in range(m)] + [-1, -1], [leaf1] * m + [-1, -1],
+                               [2 + i for i in range(m)] + [-2, -2], [float(threshold)] * m + [-2.0, -2.0], [0.0] * m + [0.0, 1.0], [0], n_features)
+
+    @classmethod
+    def from_tables(cls, left, right, feature, threshold, p1, roots, n_features: int) -> "CompiledForest":
+        """a forest given directly in the flattened layout of mx_forest_predict (leaves: left = right = -1)"""
+        self = cls.__new__(cls)
+        self.left, self.right, self.feature = (np.ascontiguousarray(a, dtype=np.int32) for a in (left, right, feature))
+        self.threshold, self.p1 = np.ascontiguousarray(threshold, dtype=np.float64), np.ascontiguousarray(p1, dtype=np.float64)
+        self.roots = np.ascontiguousarray(roots, dtype=np.int32)
+        n = len(self.left)
+        assert len(self.right) == len(self.feature) == len(self.threshold) == len(self.p1) == n and len(self.roots) > 0
+        inner = self.left >= 0
+        assert ((self.left < n) & (self.right < n)).all() and (self.right[inner] >= 0).all() and ((self.roots >= 0) & (self.roots < n)).all()
+        assert ((self.feature[inner] >= 0) & (self.feature[inner] < n_features)).all(), "a split names a feature outside the row"
+        self.n_features = int(n_features)
+        self._lib = _lib.load()
+        return self
+
+    def to_device(self, device) -> "DeviceForest":
+        """the six tables as device tensors plus the mx_device_forest that names them (mx_block_cache.dev_down / dev_up)"""
+        return DeviceForest(self, device)
+
     def predict(self, features: np.ndarray) -> np.ndarray:
         X = np.ascontiguousarray(features, dtype=np.float32)
         assert X.ndim == 2 and X.shape[1] == self.n_features
@@ -93,6 +124,19 @@ class CompiledForest:
                                                self.p1.ctypes.data, self.roots.ctypes.data, len(self.roots), X.ctypes.data, X.shape[0], X.shape[1],
                                                out.ctypes.data), "mx_forest_predict")
         return out.astype(np.int64)
+
+
+class DeviceForest:
+    """A CompiledForest in device memory: ``tensors`` keep the tables alive, ``struct`` is the mx_device_forest (host) pointing at them."""
+
+    def __init__(self, forest: CompiledForest, device):
+        self.n_features = forest.n_features
+        names = ("left", "right", "feature", "threshold", "p1", "roots")
+        self.tensors = {k: torch.from_numpy(np.ascontiguousarray(getattr(forest, k))).to(device) for k in names}
+        self.struct = _lib.DeviceForestC()
+        for k in names:
+            setattr(self.struct, k, self.tensors[k].data_ptr())
+        self.struct.n_trees, self.struct.n_nodes, self.struct.n_feat = len(forest.roots), len(forest.left), forest.n_features
 
 
 def decide(mask: np.ndarray, previous: np.ndarray, forced_after: int = FORCED_RUN_AFTER):
@@ -266,34 +310,85 @@ class PatchSkipCache:
     sample id, i.e. per request and CFG half), the per-patch reuse counters and the predictor callback (one call per block for the patches of
     all samples of all resolutions)."""
 
-    def __init__(self, down, up=None, forced_after: int = FORCED_RUN_AFTER, max_latent: int = 128, mmdit_ctx_len: Optional[int] = None):
+    def __init__(self, down, up=None, forced_after: int = FORCED_RUN_AFTER, max_latent: int = 128, mmdit_ctx_len: Optional[int] = None,
+                 on_device: bool = False):
         """mmdit_ctx_len: set for the SD3 / SD3.5 transformer (mx_mmdit_forward_cached_mixed): the unit is then the token chunk
-        "<request id>-<k>" (modules/utils.py:86-122), one cache point per joint block, forced run after two reuses (pass forced_after=2)."""
+        "<request id>-<k>" (modules/utils.py:86-122), one cache point per joint block, forced run after two reuses (pass forced_after=2).
+        on_device: the decision is taken by the library's kernel (mx_block_cache.dev_down): no callback, the counters live in device memory and
+        ``previous`` reads them back on demand.  Needs predictors the device can evaluate: CompiledForest, a fitted scikit-learn forest or a
+        ThresholdPredictor (turned into CompiledForest.from_threshold at bind(), when the width of the blocks' feature rows is known)."""
         self.mmdit_ctx_len = mmdit_ctx_len
         wrap = lambda p: CompiledForest(p) if hasattr(p, "estimators_") and hasattr(p, "n_features_in_") else p
         self.down, self.up = wrap(down), wrap(up if up is not None else down)
+        self.on_device = bool(on_device)
+        if self.on_device:
+            for p in (self.down, self.up):
+                if not isinstance(p, (CompiledForest, ThresholdPredictor)):
+                    raise TypeError(f"on_device=True needs a CompiledForest, a fitted scikit-learn forest or a ThresholdPredictor, not {type(p).__name__}: "
+                                    "QuantilePredictor and arbitrary objects with .predict are host-only")
+        self._counters: Optional[torch.Tensor] = None       # on_device: [block][slot][unit] int32 + the kernel's scratch
+        self._dev_forests, self._dec_buf, self._n_blocks = {}, None, 0
         self.forced_after = forced_after
         self.max_latent = max_latent
         self.state: Optional[torch.Tensor] = None
         self.desc = _lib.BlockCacheC()
         self._cb = _lib.SKIP_PREDICT_FN(self._predict)
-        self.desc.predict = self._cb
+        if not self.on_device:
+            self.desc.predict = self._cb
         self._slot_of, self._cap, self._patch, self._pending = {}, 0, None, None
         self._keys = []                                      # patch keys of the forward in flight, in the library's row order
         self._prev = {}                                      # block -> int64[len(_keys)]: consecutive reuses per patch, aligned with _keys (remapped by bind())
         self.decisions, self.features, self.history = [], [], []
-        self.record_features = False
+        self._record_features = False
         self.error: Optional[BaseException] = None
         self.patches_asked = self.patches_total = 0
 
     @property
+    def record_features(self):
+        return self._record_features
+
+    @record_features.setter
+    def record_features(self, value):
+        if value and self.on_device:
+            raise ValueError("record_features needs the host decision: with on_device=True the feature rows never leave the device")
+        self._record_features = bool(value)
+
+    def _unit_index(self):
+        """on_device: where the counter of each key of the forward lives inside a block's row of the counters ([slot][unit of the slot's grid])"""
+        grid = self.max_latent // self._patch
+        idx = []
+        for key in self._keys:
+            if self.mmdit_ctx_len is None:
+                rid, py, px = key.rsplit("-", 2)
+                unit = int(py) * grid + int(px)
+            else:
+                rid, k = key.rsplit("-", 1)
+                unit = int(k)
+            idx.append(self._slot_by_name[rid] * grid * grid + unit)
+        return np.asarray(idx, dtype=np.int64)
+
+    @property
     def previous(self):
         """block -> {patch key: consecutive reuses} (the reference's per-key dictionaries, cache_manager.py:128,150); kept as arrays aligned with the forward's
-        patch order, because this callback runs seven times per forward on the critical path (the GPU idles while it decides)"""
+        patch order, because this callback runs seven times per forward on the critical path (the GPU idles while it decides).  on_device: read
+        back from the device counters (a diagnostic: synchronises; not on the step path)."""
+        if self.on_device:
+            if self._counters is None or not self._keys:
+                return {}
+            per_block = self._cap * (self.max_latent // self._patch) ** 2
+            c = self._counters[:self._n_blocks * per_block * 4].view(torch.int32).reshape(self._n_blocks, per_block).cpu().numpy()
+            idx = self._unit_index()
+            return {blk: {k: int(v) for k, v in zip(self._keys, c[blk, idx])} for blk in range(self._n_blocks)}
         return {blk: {k: int(v) for k, v in zip(self._keys, arr)} for blk, arr in self._prev.items()}
 
     @previous.setter
     def previous(self, value):
+        if self.on_device:
+            if value:
+                raise ValueError("on_device=True: the counters live in device memory and can only be cleared")
+            if self._counters is not None:
+                self._counters.zero_()
+            return
         pos = {k: i for i, k in enumerate(self._keys)}
         self._prev = {}
         for blk, counts in value.items():
@@ -352,6 +447,9 @@ class PatchSkipCache:
             self.state = None
             self.state = torch.empty(need, dtype=torch.uint8, device=model.device)
             self._slot_of, self.previous = {}, {}
+            self._counters = None
+        if self.on_device:
+            self._bind_device(model, n, gn_patch)
         keep = {k: v for k, v in self._slot_of.items() if k in set(row_ids)}       # ids that left are forgotten (cache_manager.py:131,153)
         free = sorted(set(range(self._cap)) - set(keep.values()))
         valid = []
@@ -362,6 +460,7 @@ class PatchSkipCache:
                 keep[rid] = free.pop(0)
                 valid.append(0)
         self._pending = keep
+        self._slot_by_name = {str(k): v for k, v in keep.items()}
         keys, i = [], 0
         for b, h, w in shapes:                                # the library's patch order: group, sample, patch row, patch column
             for _ in range(b):
@@ -370,7 +469,11 @@ class PatchSkipCache:
                 else:
                     keys += [f"{row_ids[i]}-{k}" for k in range((h // gn_patch) * (w // gn_patch))]
                 i += 1
-        if keys != self._keys:                                 # a new composition: the counters follow their patches, patches that left are forgotten
+        if self.on_device:                                     # the device counters follow the request's state row: nothing to remap
+            self._keys = keys
+            self._dec_buf = np.zeros(self._n_blocks * len(keys), dtype=np.uint8)
+            self.desc.decisions_out = self._dec_buf.ctypes.data
+        elif keys != self._keys:                               # a new composition: the counters follow their patches, patches that left are forgotten
             old_pos = {k: i for i, k in enumerate(self._keys)}
             idx = np.array([old_pos.get(k, -1) for k in keys], dtype=np.int64)
             for blk, arr in list(self._prev.items()):
@@ -386,9 +489,34 @@ class PatchSkipCache:
         self.decisions, self.error = [], None
         return C.byref(self.desc)
 
+    def _bind_device(self, model, n, gn_patch):
+        """on_device: the forests in device memory (once per model device and row width), the counters (re-allocated with the state, zeroed) and
+        the descriptor's dev_* fields"""
+        cfg = model.cfg
+        mmdit = self.mmdit_ctx_len is not None
+        self._n_blocks = cfg.num_layers if mmdit else 2 * len(cfg.block_out_channels) + 1
+        widths = (3, 3) if mmdit else (3, 2 + cfg.layers_per_block + 2)          # feature-row width of the blocks `down` / `up` decide
+        lib = _lib.load()
+        for name, pred, nf in (("down", self.down, widths[0]), ("up", self.up, widths[1])):
+            if (name, nf) not in self._dev_forests:
+                cf = pred if isinstance(pred, CompiledForest) else CompiledForest.from_threshold(pred.threshold, nf)
+                self._dev_forests[(name, nf)] = cf.to_device(model.device)
+        units = (self.max_latent // gn_patch) ** 2
+        need = lib.mx_skip_counters_bytes(self._n_blocks, self._cap, units)
+        if self._counters is None or self._counters.numel() < need:
+            self._counters = torch.zeros(need, dtype=torch.uint8, device=model.device)
+        d = self.desc
+        d.dev_down = C.pointer(self._dev_forests[("down", widths[0])].struct)
+        d.dev_up = C.pointer(self._dev_forests[("up", widths[1])].struct)
+        d.dev_counters, d.dev_counters_bytes = self._counters.data_ptr(), self._counters.numel()
+        d.forced_after = int(self.forced_after)
+
     def after_forward(self):
         if self._pending is not None:
             self._slot_of, self._pending = self._pending, None
+        if self.on_device:                                     # the run flags of every block, in call order
+            n = len(self._keys)
+            self.decisions = [(blk, self._dec_buf[blk * n:(blk + 1) * n].astype(bool)) for blk in range(self._n_blocks)]
         self.history.append(int(self.desc.blocks_run) | int(self.desc.blocks_run_hi) << 32)
         self.patches_asked += int(self.desc.patches_asked)
         self.patches_total += int(self.desc.patches_total)

@@ -4,6 +4,8 @@
 
 #include "../../include/mxdenoise.h"
 #include "common.h"
+#include "patch_cache.h"
+#include "skip_decide.h"
 
 namespace mx {
 static thread_local std::string g_err;
@@ -105,5 +107,37 @@ extern "C" int mx_forest_predict(const int32_t* left, const int32_t* right, cons
     }
     out[r] = acc / n_trees > 0.5 ? 1 : 0;                  // argmax of the mean class probabilities (ties: class 0)
   }
+  return 0;
+}
+
+/* ---- the device-side decision's sizes and its host twin (include/mxdenoise.h; the rule is skip_decide.h, the kernel patch_cache.hip) ---- */
+extern "C" size_t mx_skip_counters_bytes(int n_blocks, int n_slots, int max_units_per_slot) {
+  if (n_blocks <= 0 || n_slots <= 0 || max_units_per_slot <= 0) { mx::set_error("skip_counters_bytes: bad arguments"); return 0; }
+  return mx::SkipScratch::bytes(n_blocks, n_slots, max_units_per_slot);
+}
+
+extern "C" int mx_skip_decide_host(const mx_device_forest* forest, int block, int forced_after, int n, int n_samples, const int32_t* unit_sample,
+                                   const unsigned char* sample_valid, const float* timesteps, const float* mse, int32_t* counters,
+                                   unsigned char* run_out, int32_t* ask_out, int32_t* first_out, int32_t* n_ask_out) {
+  MX_CHECK(forest && forest->left && forest->right && forest->feature && forest->threshold && forest->p1 && forest->roots && forest->n_trees > 0 &&
+           forest->n_nodes > 0, "skip_decide_host: incomplete forest");
+  const int n_in = forest->n_feat - 2;
+  MX_CHECK(n_in >= 1 && n_in <= MX_SKIP_MAX_IN, "skip_decide_host: the forest's n_feat must be 2 + the inputs of the block (1..MX_SKIP_MAX_IN)");
+  MX_CHECK(n >= 0 && n_samples > 0 && unit_sample && sample_valid && timesteps && mse && counters && run_out && ask_out && first_out && n_ask_out,
+           "skip_decide_host: bad arguments");
+  int n_ask = 0, bad = 0;
+  for (int b = 0; b <= n_samples; ++b) first_out[b] = 0;
+  for (int j = 0; j < n; ++j) {
+    const int b = unit_sample[j];
+    MX_CHECK(b >= 0 && b < n_samples && (j == 0 || unit_sample[j - 1] <= b), "skip_decide_host: unit_sample must be non-decreasing and inside [0, n_samples)");
+    float x[2 + MX_SKIP_MAX_IN];
+    x[0] = (float)block; x[1] = timesteps[b];
+    for (int i = 0; i < n_in; ++i) x[2 + i] = sample_valid[b] ? mse[(size_t)j * n_in + i] : MX_MSE_UNCACHED;
+    run_out[j] = (unsigned char)mx::skip_unit(*forest, x, counters[j], forced_after, &counters[j], &bad);
+    if (run_out[j]) { ask_out[n_ask++] = j; first_out[b + 1]++; }
+  }
+  for (int b = 0; b < n_samples; ++b) first_out[b + 1] += first_out[b];
+  *n_ask_out = n_ask;
+  MX_CHECK(!bad, "skip_decide_host: the forest points outside its tables");
   return 0;
 }

@@ -45,6 +45,7 @@ struct mx_mmdit {
   mx_mmdit_config cfg;
   mx::WeightTable weights;
   mx::GraphCache graphs;   // hipGraph replay of the forward, keyed by its arguments (graph_cache.h)
+  mx::PinnedBuf skip_pin;  // the per-block read-back of the device-side skip decision (mx_block_cache.dev_down)
   std::map<std::vector<long>, std::vector<size_t>> pp_sizes;   // recorded exchange sizes of the patch-parallel plan per shape (as in unet_sdxl.cpp)
 };
 
@@ -369,33 +370,46 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
           if (ok() && mx::launch_pc_image_copy(stream, t, reg, pcm_dctx, B, 0, d, row_c, to_batch, vec, ntot, res, (long)Lt * d, gate)) fail(mx_last_error()); };
         // ---- decision, per chunk ----
         const int NC = pcm_nc;
-        std::vector<float> mse(NC, MX_MSE_UNCACHED);
-        if (bc_any_valid) {
-          std::vector<double> hp((size_t)NC * 64);
-          if (mx::launch_pc_range_sq_diff(stream, x, r_in, row_i, d, pcm_dchunks, NC, pcm_dpart)) { fail(mx_last_error()); break; }
-          if (hipMemcpyAsync(hp.data(), pcm_dpart, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-              hipStreamSynchronize(stream) != hipSuccess) { fail("mmdit patch cache: reading the input differences failed"); break; }
-          for (int j = 0; j < NC; ++j) {
-            if (!bc_valid[pcm_chunk_b[j]]) continue;
-            double t = 0.0;
-            for (int k = 0; k < 64; ++k) t += hp[(size_t)j * 64 + k];
-            mse[j] = (float)(t / ((double)pcm_chunks[j].rows * d));
-          }
-        }
+        if (bc_any_valid && mx::launch_pc_range_sq_diff(stream, x, r_in, row_i, d, pcm_dchunks, NC, pcm_dpart)) { fail(mx_last_error()); break; }
         std::vector<unsigned char> run(NC, 1);
-        std::vector<float> tpp(NC);
-        for (int j = 0; j < NC; ++j) tpp[j] = h_timesteps[pcm_chunk_b[j]];
-        if (bc->predict(bc->ctx, i, 0, NC, 1, tpp.data(), mse.data(), run.data())) { fail("mmdit patch cache: the predictor failed"); break; }
         bool gany[MX_MAX_SEGS] = {false, false, false, false};
         int gask[MX_MAX_SEGS] = {0, 0, 0, 0}, gtot[MX_MAX_SEGS] = {0, 0, 0, 0};
-        bool any = false;
-        for (int j = 0; j < NC; ++j) {
-          if (!bc_valid[pcm_chunk_b[j]]) run[j] = 1;
-          const int g = pcm_chunk_g[j];
-          ++gtot[g];
-          if (run[j]) { gany[g] = true; any = true; ++gask[g]; ++pcm_asked; }
-          ++pcm_total;
+        // THE DECISION -- the one place the two modes differ: it leaves run[], gask[] and gtot[]
+        if (bc_dev) {
+          // on the device (mx_block_cache.dev_down): one launch, one record read back (patch_cache.hip pc_decide_kernel; skip_decide.h)
+          mx_skip_decide_args a{};
+          a.forest = bc->dev_down; a.n_in = 1; a.kind = 1; a.units = pcm_dchunks; a.unit_sample = bc_skip.unit_sample; a.partial = pcm_dpart;
+          a.part_len[0] = 64; a.part_elems[0] = (double)d;
+          const unsigned char* flags = nullptr;
+          const int32_t* rec = bc_dev_decide(a, i, true, &flags);
+          if (!rec) break;
+          run.assign(flags, flags + NC);
+          for (int g = 0; g < MX_MAX_SEGS; ++g) { gask[g] = rec[MX_SKIP_REC_GASK + g]; gtot[g] = rec[MX_SKIP_REC_GTOT + g]; }
+        } else {
+          // on the host: the partial sums come back and the caller's predictor answers
+          std::vector<float> mse(NC, MX_MSE_UNCACHED);
+          if (bc_any_valid) {
+            std::vector<double> hp((size_t)NC * 64);
+            if (hipMemcpyAsync(hp.data(), pcm_dpart, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess) { fail("mmdit patch cache: reading the input differences failed"); break; }
+            for (int j = 0; j < NC; ++j) {
+              if (!bc_valid[pcm_chunk_b[j]]) continue;
+              double t = 0.0;
+              for (int k = 0; k < 64; ++k) t += hp[(size_t)j * 64 + k];
+              mse[j] = (float)(t / ((double)pcm_chunks[j].rows * d));
+            }
+          }
+          std::vector<float> tpp(NC);
+          for (int j = 0; j < NC; ++j) tpp[j] = h_timesteps[pcm_chunk_b[j]];
+          if (bc->predict(bc->ctx, i, 0, NC, 1, tpp.data(), mse.data(), run.data())) { fail("mmdit patch cache: the predictor failed"); break; }
+          for (int j = 0; j < NC; ++j) {
+            if (!bc_valid[pcm_chunk_b[j]]) run[j] = 1;
+            ++gtot[pcm_chunk_g[j]];
+            if (run[j]) ++gask[pcm_chunk_g[j]];
+          }
         }
+        bool any = false;
+        for (int g = 0; g < MX_MAX_SEGS; ++g) { gany[g] = gask[g] > 0; any = any || gany[g]; pcm_asked += gask[g]; pcm_total += gtot[g]; }
         img_copy(x, r_in, 0, nullptr, nullptr, 0);                           // the cached input is always the latest one (cache_manager.py:183)
         if (!any) {                                                           // SD3Transformer.py:219-228: both streams from the block's caches
           img_copy(x, r_out, 1, nullptr, nullptr, 0);
@@ -800,10 +814,14 @@ extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx
                                              const void* ehs, const void* pooled, int ctx_len, int patch, void* workspace, size_t workspace_bytes,
                                              mx_block_cache* cache) {
   const std::string who = "mmdit_forward_cached_mixed";
-  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, who + ": cache with predict, state, slots and slot_valid is required");
+  MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
+           who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
   if (pcm_setup(p, u, groups, n_groups, ctx_len, patch, cache, false)) return 1;
+  // the device decision: every joint block compares its image stream (one input)
+  const int ups = (cache->max_h / patch) * (cache->max_w / patch);
+  if (Plan::bc_dev_check(who, cache, u->cfg.num_layers, ups, 1, 0)) return 1;
   MX_CHECK(timesteps && ehs && pooled && workspace, "mmdit: null operand");
   MX_CHECK(u->weights.blob != nullptr, "mmdit: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
@@ -822,6 +840,9 @@ extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx
            hipMemcpyAsync(p.pcm_dctx, p.pcm_ctx.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
            hipMemcpyAsync(p.pcm_dchunks, p.pcm_chunks.data(), (size_t)p.pcm_nc * sizeof(mx::PcRange), hipMemcpyHostToDevice, p.stream) == hipSuccess,
            who + ": moving the tables failed");
+  std::vector<int> group_of(B);
+  for (int g = 0; g < p.ng; ++g) for (int k = 0; k < p.gB[g]; ++k) group_of[p.gb0[g] + k] = g;
+  if (p.bc_dev_begin(who, u->skip_pin, u->cfg.num_layers, ups, timesteps, p.pcm_chunk_b, std::move(group_of), true)) return 1;
   if (p.bc_read_timesteps(who, timesteps, B)) return 1;
   const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, pooled, groups[0].out);
   cache->patches_asked = p.pcm_asked; cache->patches_total = p.pcm_total;
@@ -842,6 +863,7 @@ extern "C" int mx_mmdit_forward_cached(mx_mmdit* u, void* stream, const void* la
                                        size_t workspace_bytes, mx_block_cache* cache) {
   const std::string who = "mmdit_forward_cached";
   MX_CHECK(u != nullptr, "mmdit: null handle");
+  MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the chunk unit only (mx_mmdit_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
   MX_CHECK(u->cfg.num_layers <= 64, who + ": at most 64 blocks");
   MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "mmdit: bad shape");

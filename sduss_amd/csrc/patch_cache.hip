@@ -10,11 +10,13 @@
 //   pc_scatter       a compact batch of patches (cropped) -> the patches' places in the requests' state rows (update_and_return's
 //                    `output[mask] = new_output`, cache_manager.py:95-97)
 //   pc_patch_sq_diff per patch: sum of (x - cached x)^2 (the predictor's feature, cache_manager.py:112-123, 141-144)
+//   pc_decide        the block's run / reuse decision for every unit from those sums (opt-in, mx_block_cache.dev_down): small and latency-bound
 //
 // Geometry: samples are described at LEVEL 0 (latent resolution) and every kernel takes the level of its tensor: image h >> level, w >> level,
 // first row row0 >> 2 level, patch edge p0 >> level (the patch grid of a sample is the same at every level).
 #include "common.h"
 #include "patch_cache.h"
+#include "skip_decide.h"
 #include "../../include/mxdenoise.h"
 #include <algorithm>
 
@@ -277,4 +279,91 @@ int launch_pc_patch_sq_diff(hipStream_t st, const void* x, const void* state, lo
   return 0;
 }
 
+// The decision of one block for all units (skip_decide.h states the rule; mx_skip_decide_host is the same loop on the host).  One workgroup:
+// thread t takes unit j0 + t of each chunk of 256; the asking units are compacted in row order by a ballot per wave, the waves' totals in LDS
+// and an offset carried from chunk to chunk.  Units arrive grouped by sample, so first[b] is written by the first unit of sample b.
+constexpr int kDecideThreads = 256;
+__global__ __launch_bounds__(kDecideThreads) void pc_decide_kernel(const mx_skip_decide_args a, const mx_device_forest f) {
+  __shared__ float s_x[kDecideThreads][2 + MX_SKIP_MAX_IN];
+  __shared__ int s_wave[kDecideThreads / 64];
+  __shared__ int s_group[2 * MX_MAX_SEGS];
+  __shared__ int s_bad;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PcPatch* patches = (const PcPatch*)a.units;
+  const PcRange* ranges = (const PcRange*)a.units;
+  const PcSample* samp = (const PcSample*)a.samples;
+  if (tid < 2 * MX_MAX_SEGS) s_group[tid] = 0;
+  if (tid == 0) s_bad = 0;
+  __syncthreads();
+  auto sample_of = [&](int j) { return a.kind == 0 ? patches[j].b : a.unit_sample[j]; };
+  int base = 0;                                            // asking units before this chunk (the same in every thread)
+  for (int j0 = 0; j0 < a.n; j0 += kDecideThreads) {
+    const int j = j0 + tid;
+    int run = 0, b = 0, bad = 0;
+    if (j < a.n) {
+      b = sample_of(j);
+      if (b < 0 || b >= a.n_samples) { b = 0; bad = 1; }
+      int slot, u, rows = 1;
+      if (a.kind == 0) { slot = samp[b].slot; u = patches[j].py * a.grid_w + patches[j].px; }
+      else { slot = ranges[j].slot; rows = ranges[j].rows; u = rows > 0 ? ranges[j].srow0 / rows : -1; }
+      float* x = s_x[tid];
+      x[0] = (float)a.block; x[1] = a.timesteps[b];
+      const bool valid = a.sample_valid[b] != 0;
+      for (int i = 0; i < a.n_in; ++i) {
+        if (!valid) x[2 + i] = MX_MSE_UNCACHED;            // nothing cached for this request: the marker
+        else if (a.kind == 0) x[2 + i] = skip_finalise(a.partial + a.part_off[i] + (long)j * a.part_len[i], a.part_len[i], a.part_elems[i]);
+        else x[2 + i] = skip_finalise(a.partial + (long)j * 64, 64, (double)rows * a.part_elems[0]);
+      }
+      const long ci = (long)slot * a.units_per_slot + u;
+      const bool inside = slot >= 0 && u >= 0 && u < a.units_per_slot && ci < a.n_counters;
+      int32_t next = 0;
+      run = skip_unit(f, x, inside ? a.counters[ci] : 0, a.forced_after, &next, &bad);
+      if (inside) a.counters[ci] = next; else bad = 1;
+      a.run[j] = (unsigned char)run;
+      if (a.sample_group) {
+        const int g = a.sample_group[b];
+        if (g >= 0 && g < MX_MAX_SEGS) { atomicAdd(&s_group[MX_MAX_SEGS + g], 1); if (run) atomicAdd(&s_group[g], 1); } else bad = 1;
+      }
+      if (bad) atomicOr(&s_bad, 1);
+    }
+    const unsigned long long asking = __ballot(run);
+    if (lane == 0) s_wave[wave] = __popcll(asking);
+    __syncthreads();
+    int idx = base + __popcll(asking & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) idx += s_wave[w];
+    if (j < a.n) {
+      if (run) {
+        if (a.ask_units) ((PcPatch*)a.ask_units)[idx] = patches[j];
+        if (a.ask_index) a.ask_index[idx] = j;
+      }
+      if (j == 0 || sample_of(j - 1) != b) a.record[MX_SKIP_REC_FIRST + b] = idx;
+    }
+    for (int w = 0; w < kDecideThreads / 64; ++w) base += s_wave[w];
+    __syncthreads();                                       // the next chunk rewrites s_wave
+  }
+  if (tid == 0) { a.record[MX_SKIP_REC_STATUS] = s_bad; a.record[MX_SKIP_REC_NASK] = base; a.record[MX_SKIP_REC_FIRST + a.n_samples] = base; }
+  if (tid < 2 * MX_MAX_SEGS) a.record[MX_SKIP_REC_GASK + tid] = s_group[tid];
+}
+
+int launch_pc_decide(hipStream_t st, const mx_skip_decide_args& a) {
+  MX_CHECK(a.forest && a.n > 0 && a.n_samples > 0 && a.n_in >= 1 && a.n_in <= MX_SKIP_MAX_IN && (a.kind == 0 || a.kind == 1), "pc_decide: bad shape");
+  const mx_device_forest& f = *a.forest;
+  MX_CHECK(f.left && f.right && f.feature && f.threshold && f.p1 && f.roots && f.n_trees > 0 && f.n_nodes > 0, "pc_decide: incomplete device forest");
+  MX_CHECK(f.n_feat == 2 + a.n_in, "pc_decide: the forest's n_feat must be 2 + the inputs of the block");
+  MX_CHECK(a.units && a.sample_valid && a.timesteps && a.partial && a.counters && a.run && a.record, "pc_decide: null operand");
+  MX_CHECK(a.kind == 0 ? (a.samples != nullptr && a.grid_w > 0) : (a.unit_sample != nullptr && a.ask_units == nullptr && a.n_in == 1),
+           "pc_decide: the tables of the unit kind are missing (token ranges: unit_sample, one input, no patch list)");
+  MX_CHECK(a.units_per_slot > 0 && a.n_counters >= a.units_per_slot, "pc_decide: bad counter row");
+  for (int i = 0; i < (a.kind == 0 ? a.n_in : 1); ++i)
+    MX_CHECK(a.part_elems[i] > 0.0 && (a.kind == 1 || (a.part_len[i] > 0 && a.part_off[i] >= 0)), "pc_decide: bad partial-sum layout");
+  hipLaunchKernelGGL(pc_decide_kernel, dim3(1), dim3(kDecideThreads), 0, st, a, f);
+  MX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mx
+
+extern "C" int mx_skip_decide_device(void* stream, const mx_skip_decide_args* args) {
+  MX_CHECK(args != nullptr, "skip_decide_device: null arguments");
+  return mx::launch_pc_decide((hipStream_t)stream, *args);
+}

@@ -21,6 +21,7 @@
 #include "../../include/mxdenoise.h"
 #include "common.h"
 #include "graph_cache.h"
+#include "patch_cache.h"
 #include "pp_exchange.h"
 
 namespace mx {
@@ -198,6 +199,75 @@ struct DenoiserPlan : PlanBase, Groups {
     if (bc_keyed) bc->cached_valid = 0;
     set_error(who + ": reading the timesteps failed");
     return 1;
+  }
+  // ---- the decision on the device (mx_block_cache.dev_down; the patch / chunk unit: mx_*_forward_cached_mixed) ----
+  // The host keeps what sizes the following launches: per block it reads back ONE record (n_ask, first[], the group counts; the flags when
+  // somebody wants them) instead of every partial sum, and calls nobody.
+  bool bc_dev = false;
+  SkipScratch bc_skip;
+  int bc_dev_ups = 0;                        // units of a slot's max_h x max_w grid
+  const float* bc_dev_ts = nullptr;          // the caller's device timesteps
+  std::vector<int> bc_dev_unit_b, bc_dev_group;   // host: sample of each unit, group of each sample
+  int32_t* bc_dev_rec = nullptr;             // pinned, owned by the model handle: the record, then the flags
+  size_t bc_dev_dec = 0;                     // flags written to bc->decisions_out so far
+  // what can be refused before anything is launched: n_in_down / n_in_up = inputs of the blocks dev_down / dev_up decide (0: no such block)
+  static int bc_dev_check(const std::string& who, const mx_block_cache* cache, int n_blocks, int ups, int n_in_down, int n_in_up) {
+    if (!cache->dev_down) return 0;
+    MX_CHECK(cache->observe == nullptr, who + ": observe is a host callback and must be NULL with a device forest (dev_down)");
+    const mx_device_forest* up = cache->dev_up ? cache->dev_up : cache->dev_down;
+    MX_CHECK(n_in_down <= MX_SKIP_MAX_IN && n_in_up <= MX_SKIP_MAX_IN, who + ": a block has more inputs than MX_SKIP_MAX_IN");
+    MX_CHECK(cache->dev_down->n_feat == 2 + n_in_down,
+             who + ": dev_down has n_feat " + std::to_string(cache->dev_down->n_feat) + ", its blocks need " + std::to_string(2 + n_in_down));
+    MX_CHECK(n_in_up == 0 || up->n_feat == 2 + n_in_up, who + ": dev_up has n_feat " + std::to_string(up->n_feat) + ", its blocks need " + std::to_string(2 + n_in_up));
+    MX_CHECK(cache->forced_after >= 0, who + ": forced_after must not be negative");
+    MX_CHECK(cache->dev_counters && ((uintptr_t)cache->dev_counters & 7) == 0 && cache->dev_counters_bytes >= SkipScratch::bytes(n_blocks, cache->n_slots, ups),
+             who + ": dev_counters too small (mx_skip_counters_bytes)");
+    return 0;
+  }
+  // carve the scratch behind the counters and send this forward's tables; `unit_b`: the sample of every unit in row order
+  int bc_dev_begin(const std::string& who, PinnedBuf& pin, int n_blocks, int ups, const float* timesteps, std::vector<int> unit_b, std::vector<int> group_of,
+                   bool send_unit_b) {
+    bc_dev = bc->dev_down != nullptr;
+    if (!bc_dev) return 0;
+    bc_skip = SkipScratch(bc->dev_counters, n_blocks, bc->n_slots, ups);
+    bc_dev_ups = ups; bc_dev_ts = timesteps; bc_dev_unit_b = std::move(unit_b); bc_dev_group = std::move(group_of); bc_dev_dec = 0;
+    MX_CHECK((int)bc_dev_unit_b.size() <= bc->n_slots * ups && (int)bc_dev_group.size() == B, who + ": more units than the counters hold");
+    bc_dev_rec = (int32_t*)pin.get(SkipScratch::record_ints(bc->n_slots) * sizeof(int32_t) + (size_t)bc->n_slots * ups);
+    MX_CHECK(bc_dev_rec != nullptr, who + ": no pinned memory for the decision record");
+    MX_CHECK(hipMemcpyAsync(bc_skip.valid, bc_valid.data(), (size_t)B, hipMemcpyHostToDevice, stream) == hipSuccess &&
+             hipMemcpyAsync(bc_skip.sample_group, bc_dev_group.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess &&
+             (!send_unit_b || hipMemcpyAsync(bc_skip.unit_sample, bc_dev_unit_b.data(), bc_dev_unit_b.size() * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess),
+             who + ": sending the decision's tables failed");
+    return 0;
+  }
+  // One block: the caller has filled the unit tables, the partial sums and the forest of `a`.  Returns the record (MX_SKIP_REC_*), the flags behind
+  // it in *flags -- read back from the device, or, when no sample holds state (every unit runs; the kernel only zeroes their counters), written
+  // here without any synchronisation.
+  const int32_t* bc_dev_decide(mx_skip_decide_args& a, int block, bool want_flags, const unsigned char** flags) {
+    const int n = (int)bc_dev_unit_b.size();
+    a.block = block; a.forced_after = bc->forced_after; a.n = n; a.n_samples = B;
+    a.counters = bc_skip.counters + (size_t)block * bc->n_slots * bc_dev_ups; a.units_per_slot = bc_dev_ups; a.n_counters = bc->n_slots * bc_dev_ups;
+    a.sample_valid = bc_skip.valid; a.sample_group = bc_skip.sample_group; a.timesteps = bc_dev_ts; a.run = bc_skip.flags; a.record = bc_skip.record;
+    if (launch_pc_decide(stream, a)) { fail(mx_last_error()); return nullptr; }
+    int32_t* rec = bc_dev_rec;
+    unsigned char* fl = (unsigned char*)(rec + SkipScratch::record_ints(bc->n_slots));
+    want_flags = want_flags || bc->decisions_out != nullptr;
+    if (bc_any_valid) {
+      const size_t bytes = SkipScratch::record_ints(bc->n_slots) * sizeof(int32_t) + (want_flags ? (size_t)n : 0);
+      if (hipMemcpyAsync(rec, bc_skip.record, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        fail("block cache: reading the decision record failed"); return nullptr;
+      }
+      if (rec[MX_SKIP_REC_STATUS] != 0) { fail("block cache: the device forest or the unit tables point outside themselves"); return nullptr; }
+    } else {
+      std::memset(rec, 0, SkipScratch::record_ints(bc->n_slots) * sizeof(int32_t));
+      std::memset(fl, 1, (size_t)n);
+      rec[MX_SKIP_REC_NASK] = n;
+      for (int j = 0; j < n; ++j) { const int b = bc_dev_unit_b[j]; rec[MX_SKIP_REC_FIRST + b + 1]++; rec[MX_SKIP_REC_GASK + bc_dev_group[b]]++; rec[MX_SKIP_REC_GTOT + bc_dev_group[b]]++; }
+      for (int b = 0; b < B; ++b) rec[MX_SKIP_REC_FIRST + b + 1] += rec[MX_SKIP_REC_FIRST + b];
+    }
+    if (bc->decisions_out) { std::memcpy(bc->decisions_out + bc_dev_dec, fl, (size_t)n); bc_dev_dec += (size_t)n; }
+    if (flags) *flags = fl;
+    return rec;
   }
   // batch-ordered tensor <-> its rows in the state
   bool bc_store(char* region, const void* t, size_t per_sample_bytes) {

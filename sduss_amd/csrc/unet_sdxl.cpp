@@ -54,6 +54,7 @@ struct mx_unet {
   mx_unet_config cfg;
   mx::WeightTable weights;
   mx::GraphCache graphs;   // hipGraph replay of the forward, keyed by its arguments (graph_cache.h)
+  mx::PinnedBuf skip_pin;  // the per-block read-back of the device-side skip decision (mx_block_cache.dev_down)
   // patch-parallel stale forwards: the exchange sizes of the plan, recorded by a host-only walk ONCE per (batch, H, W, ctx_len, gn_patch, world) instead
   // of at every step (advisor, round 3: the walk sat on the path whose purpose is to hide latency)
   std::map<std::vector<long>, std::vector<size_t>> pp_sizes;
@@ -944,48 +945,69 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         return;
       }
       if (!ok()) return;
-      std::vector<float> mse((size_t)pc_np * nf, MX_MSE_UNCACHED);
-      if (bc_any_valid) {
-        size_t off = 0;
-        std::vector<size_t> offs(nf);
-        for (int f = 0; f < nf && ok(); ++f) {
-          const int pl = pc_p0 >> ins[f].level;
-          offs[f] = off;
-          if (mx::launch_pc_patch_sq_diff(stream, ins[f].p, in_cache[f], pc_row_elems(ins[f].level, ins[f].C), ins[f].C, pc_dall, pc_np, pc_dsamp, ins[f].level, pl,
-                                          pc_dpart + off)) fail(mx_last_error());
-          off += (size_t)pc_np * pl;
-        }
-        std::vector<double> hp(off);
-        if (ok() && (hipMemcpyAsync(hp.data(), pc_dpart, off * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                     hipStreamSynchronize(stream) != hipSuccess)) fail("patch cache: reading the input differences failed");
-        for (int f = 0; f < nf; ++f) {
-          const int pl = pc_p0 >> ins[f].level;
-          for (int j = 0; j < pc_np; ++j) {
-            if (!bc_valid[pc_all[j].b]) continue;                  // nothing cached for this request: the marker stays (cache_manager.py:110,139)
-            double t = 0.0;
-            for (int r = 0; r < pl; ++r) t += hp[offs[f] + (size_t)j * pl + r];
-            mse[(size_t)j * nf + f] = (float)(t / ((double)pl * pl * ins[f].C));
-          }
-        }
+      // the features: per patch and pixel row, the sum of (input - cached input)^2, left on the device
+      size_t off = 0;
+      std::vector<size_t> offs(nf);
+      for (int f = 0; f < nf && ok() && bc_any_valid; ++f) {
+        const int pl = pc_p0 >> ins[f].level;
+        offs[f] = off;
+        if (mx::launch_pc_patch_sq_diff(stream, ins[f].p, in_cache[f], pc_row_elems(ins[f].level, ins[f].C), ins[f].C, pc_dall, pc_np, pc_dsamp, ins[f].level, pl,
+                                        pc_dpart + off)) fail(mx_last_error());
+        off += (size_t)pc_np * pl;
       }
       if (!ok()) return;
-      std::vector<unsigned char> run(pc_np, 1);
-      std::vector<float> tpp(pc_np);
-      for (int j = 0; j < pc_np; ++j) tpp[j] = h_timesteps[pc_all[j].b];
-      if (bc->predict(bc->ctx, idx, is_up ? 1 : 0, pc_np, nf, tpp.data(), mse.data(), run.data())) { fail("patch cache: the predictor failed"); return; }
-      pc_ask.clear(); pc_ask_first.assign(B + 1, 0);
-      for (int j = 0; j < pc_np; ++j) {
-        if (!bc_valid[pc_all[j].b]) run[j] = 1;                    // a patch without cached tensors has nothing to reuse (uninitialised rows in the reference)
-        if (run[j]) { pc_ask.push_back(pc_all[j]); pc_ask_first[pc_all[j].b + 1]++; }
+      // THE DECISION -- the one place the two modes differ.  Either way it leaves pc_nask, pc_ask_first and, when some patch does not ask, the
+      // list of the asking patches in pc_dask.
+      if (bc_dev) {
+        // on the device (mx_block_cache.dev_down): one launch finalises the features, walks the forest, applies the counter rule and compacts
+        // the list; the host reads back the counts alone (patch_cache.hip pc_decide_kernel; skip_decide.h)
+        mx_skip_decide_args a{};
+        a.forest = (is_up && bc->dev_up) ? bc->dev_up : bc->dev_down;
+        a.n_in = nf; a.kind = 0; a.units = pc_dall; a.samples = pc_dsamp; a.partial = pc_dpart; a.grid_w = pc_maxw / pc_p0; a.ask_units = pc_dask;
+        for (int f = 0; f < nf; ++f) {
+          const int pl = pc_p0 >> ins[f].level;
+          a.part_off[f] = (int64_t)offs[f]; a.part_len[f] = pl; a.part_elems[f] = (double)pl * pl * ins[f].C;
+        }
+        const int32_t* rec = bc_dev_decide(a, idx, false, nullptr);
+        if (!rec) return;
+        pc_nask = rec[MX_SKIP_REC_NASK];
+        pc_ask_first.assign(rec + MX_SKIP_REC_FIRST, rec + MX_SKIP_REC_FIRST + B + 1);
+      } else {
+        // on the host: every partial sum comes back, the caller's predictor answers, the list goes out again
+        std::vector<float> mse((size_t)pc_np * nf, MX_MSE_UNCACHED);
+        if (bc_any_valid) {
+          std::vector<double> hp(off);
+          if (hipMemcpyAsync(hp.data(), pc_dpart, off * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+              hipStreamSynchronize(stream) != hipSuccess) { fail("patch cache: reading the input differences failed"); return; }
+          for (int f = 0; f < nf; ++f) {
+            const int pl = pc_p0 >> ins[f].level;
+            for (int j = 0; j < pc_np; ++j) {
+              if (!bc_valid[pc_all[j].b]) continue;                  // nothing cached for this request: the marker stays (cache_manager.py:110,139)
+              double t = 0.0;
+              for (int r = 0; r < pl; ++r) t += hp[offs[f] + (size_t)j * pl + r];
+              mse[(size_t)j * nf + f] = (float)(t / ((double)pl * pl * ins[f].C));
+            }
+          }
+        }
+        std::vector<unsigned char> run(pc_np, 1);
+        std::vector<float> tpp(pc_np);
+        for (int j = 0; j < pc_np; ++j) tpp[j] = h_timesteps[pc_all[j].b];
+        if (bc->predict(bc->ctx, idx, is_up ? 1 : 0, pc_np, nf, tpp.data(), mse.data(), run.data())) { fail("patch cache: the predictor failed"); return; }
+        pc_ask.clear(); pc_ask_first.assign(B + 1, 0);
+        for (int j = 0; j < pc_np; ++j) {
+          if (!bc_valid[pc_all[j].b]) run[j] = 1;                    // a patch without cached tensors has nothing to reuse (uninitialised rows in the reference)
+          if (run[j]) { pc_ask.push_back(pc_all[j]); pc_ask_first[pc_all[j].b + 1]++; }
+        }
+        for (int b = 0; b < B; ++b) pc_ask_first[b + 1] += pc_ask_first[b];
+        pc_nask = (int)pc_ask.size();
+        if (pc_nask > 0 && pc_nask < pc_np &&
+            hipMemcpyAsync(pc_dask, pc_ask.data(), pc_ask.size() * sizeof(mx::PcPatch), hipMemcpyHostToDevice, stream) != hipSuccess) {
+          fail("patch cache: sending the list of asking patches failed"); return;
+        }
       }
-      for (int b = 0; b < B; ++b) pc_ask_first[b + 1] += pc_ask_first[b];
-      pc_nask = (int)pc_ask.size();
       pc_partial = pc_nask < pc_np;
       const bool any = pc_nask > 0;
       pc_total += (unsigned long long)pc_np; pc_asked += (unsigned long long)pc_nask;
-      if (any && pc_partial && hipMemcpyAsync(pc_dask, pc_ask.data(), pc_ask.size() * sizeof(mx::PcPatch), hipMemcpyHostToDevice, stream) != hipSuccess) {
-        fail("patch cache: sending the list of asking patches failed"); return;
-      }
       for (int f = 0; f < nf && ok(); ++f) pc_store(ins[f].p, in_cache[f], ins[f].level, ins[f].C);   // the cached input is always the latest one (:133,153)
       const size_t n0 = skips.size();
       mute = !any;
@@ -1385,6 +1407,7 @@ extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* late
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
   const std::string who = "unet_forward_cached";
   MX_CHECK(u != nullptr, "unet: null handle");
+  MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
   MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "unet: bad shape");
   if (Model::check_shape(u, H, W, gn_patch)) return 1;
@@ -1465,10 +1488,14 @@ extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_u
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
   const std::string who = "unet_forward_cached_mixed";
-  MX_CHECK(cache && cache->predict && cache->state && cache->slots && cache->slot_valid, who + ": cache with predict, state, slots and slot_valid is required");
+  MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
+           who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
   Plan p;
   if (pc_setup(p, u, groups, n_groups, ctx_len, gn_patch, cache, false)) return 1;
+  // the device decision: the down and mid blocks compare their input, an up block its input and the skips it consumes
+  const int n_blocks = 2 * u->cfg.n_levels + 1, ups = (cache->max_h / gn_patch) * (cache->max_w / gn_patch);
+  if (Plan::bc_dev_check(who, cache, n_blocks, ups, 1, u->cfg.layers_per_block + 2)) return 1;
   MX_CHECK(timesteps && ehs && text_embeds && time_ids && workspace, "unet: null operand");
   MX_CHECK(u->weights.blob != nullptr, "unet: weights not set");
   MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
@@ -1486,6 +1513,10 @@ extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_u
   MX_CHECK(hipMemcpyAsync(p.pc_dsamp, p.pc_samp.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
            hipMemcpyAsync(p.pc_dall, p.pc_all.data(), (size_t)p.pc_np * sizeof(mx::PcPatch), hipMemcpyHostToDevice, p.stream) == hipSuccess,
            who + ": moving the tables failed");
+  std::vector<int> unit_b(p.pc_np), group_of(B);
+  for (int j = 0; j < p.pc_np; ++j) unit_b[j] = p.pc_all[j].b;
+  for (int g = 0; g < p.ng; ++g) for (int k = 0; k < p.gB[g]; ++k) group_of[p.gb0[g] + k] = g;
+  if (p.bc_dev_begin(who, u->skip_pin, n_blocks, ups, timesteps, std::move(unit_b), std::move(group_of), false)) return 1;
   if (p.bc_read_timesteps(who, timesteps, B)) return 1;
   const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, text_embeds, time_ids, groups[0].out);
   cache->patches_asked = p.pc_asked; cache->patches_total = p.pc_total;

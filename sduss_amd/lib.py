@@ -111,12 +111,35 @@ MSE_UNCACHED = 9.2233720368547758e18
 SKIP_OBSERVE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float))
 
 
+class DeviceForestC(C.Structure):
+    """mx_device_forest: a flattened forest whose tables live in device memory (block_cache.CompiledForest.to_device)"""
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("feature", C.c_void_p), ("threshold", C.c_void_p), ("p1", C.c_void_p),
+                ("roots", C.c_void_p), ("n_trees", C.c_int), ("n_nodes", C.c_int), ("n_feat", C.c_int)]
+
+
+SKIP_MAX_IN = 8
+SKIP_REC_STATUS, SKIP_REC_NASK, SKIP_REC_GASK, SKIP_REC_GTOT, SKIP_REC_FIRST = 0, 1, 2, 2 + MAX_SEGS, 2 + 2 * MAX_SEGS
+
+
+class SkipDecideArgs(C.Structure):
+    """mx_skip_decide_args: one launch of the device-side decision on caller-made tables (mx_skip_decide_device)"""
+    _fields_ = [("forest", C.POINTER(DeviceForestC)), ("block", C.c_int), ("forced_after", C.c_int), ("n", C.c_int), ("n_samples", C.c_int),
+                ("n_in", C.c_int), ("kind", C.c_int), ("units", C.c_void_p), ("samples", C.c_void_p), ("unit_sample", C.c_void_p),
+                ("sample_group", C.c_void_p), ("sample_valid", C.c_void_p), ("timesteps", C.c_void_p), ("partial", C.c_void_p),
+                ("part_off", C.c_int64 * SKIP_MAX_IN), ("part_len", C.c_int * SKIP_MAX_IN), ("part_elems", C.c_double * SKIP_MAX_IN),
+                ("counters", C.c_void_p), ("units_per_slot", C.c_int), ("grid_w", C.c_int), ("n_counters", C.c_int),
+                ("run", C.c_void_p), ("ask_units", C.c_void_p), ("ask_index", C.c_void_p), ("record", C.c_void_p)]
+
+
 class BlockCacheC(C.Structure):
     _fields_ = [("predict", SKIP_PREDICT_FN), ("ctx", C.c_void_p), ("state", C.c_void_p), ("state_bytes", C.c_size_t),
                 ("batch_key", C.c_uint64), ("cached_key", C.c_uint64), ("cached_valid", C.c_int), ("cached_batch", C.c_int),
                 ("cached_h", C.c_int), ("cached_w", C.c_int), ("blocks_run", C.c_uint), ("blocks_run_hi", C.c_uint), ("observe", SKIP_OBSERVE_FN),
                 ("slots", C.POINTER(C.c_int32)), ("slot_valid", C.POINTER(C.c_ubyte)), ("n_slots", C.c_int),
-                ("max_h", C.c_int), ("max_w", C.c_int), ("patches_asked", C.c_ulonglong), ("patches_total", C.c_ulonglong)]
+                ("max_h", C.c_int), ("max_w", C.c_int), ("patches_asked", C.c_ulonglong), ("patches_total", C.c_ulonglong),
+                # opt-in: the decision on the device (patch / chunk unit only)
+                ("dev_down", C.POINTER(DeviceForestC)), ("dev_up", C.POINTER(DeviceForestC)), ("dev_counters", C.c_void_p),
+                ("dev_counters_bytes", C.c_size_t), ("forced_after", C.c_int), ("decisions_out", C.c_void_p)]
 
 
 class CLIPConfigC(C.Structure):
@@ -179,6 +202,9 @@ SYMBOLS = {
     "mx_unet_validate": (_i, [_vp, _i, _i, _i, _i]),
     "mx_unet_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz]),
     "mx_forest_predict": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "mx_skip_counters_bytes": (_sz, [_i, _i, _i]),
+    "mx_skip_decide_host": (_i, [C.POINTER(DeviceForestC), _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mx_skip_decide_device": (_i, [_vp, C.POINTER(SkipDecideArgs)]),
     "mx_mmdit_workspace_bytes_pp": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_pp_state_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_forward_pp": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz]),

@@ -151,8 +151,118 @@ def main_patch_unit():
         print(f"{name:>14s} " + " ".join(f"{v:8.2f}" for v in row[:7]) + f"   {row[7]:8.2f}   {state:8.0f}", flush=True)
 
 
+def block_threshold_forest(thresholds, n_features):
+    """ONE forest for the blocks of `thresholds` (block -> threshold): splits on feature 0, the block index, lead to one threshold chain per
+    block (CompiledForest.from_threshold's: run when any input difference exceeds the block's threshold)"""
+    from sduss_amd.block_cache import CompiledForest
+    left, right, feat, thr, p1 = [], [], [], [], []
+
+    def node(l, r, f, t, p):
+        left.append(l); right.append(r); feat.append(f); thr.append(t); p1.append(p)
+        return len(left) - 1
+    leaf0, leaf1 = node(-1, -1, -2, -2.0, 0.0), node(-1, -1, -2, -2.0, 1.0)
+    nxt = leaf1                                              # a block nobody calibrated: run
+    for blk in sorted(thresholds, reverse=True):
+        on = leaf0
+        for k in range(n_features - 1, 1, -1):              # the chain, last feature first: x <= thr goes on, anything larger runs
+            on = node(on, leaf1, k, float(thresholds[blk]), 0.0)
+        nxt = node(on, nxt, 0, blk + 0.5, 0.0)               # block index <= blk + 0.5: this block's chain (larger indices were split off above)
+    return CompiledForest.from_tables(left, right, feat, thr, p1, [nxt], n_features)
+
+
+def main_decide(where, steps=20):
+    """--decide device|host: the patch / chunk-unit cached forward with the decision taken on the device (mx_block_cache.dev_down) or on the host.
+    The asking fraction is fixed by calibration: a host pass with QuantilePredictor(q) records the feature rows, each block's threshold is the q
+    quantile of its rows' largest input difference, and ONE forest per row width built from those thresholds then serves BOTH paths, so they
+    execute the same patches.  Latents drift from step to step by a different amount per patch, cycling through a fixed set."""
+    from sduss_amd.block_cache import PatchSkipCache, QuantilePredictor
+    dev = torch.device("cuda:0")
+    wheres = where.split(",")                                # "host,device,host,device": alternating legs over ONE model and ONE calibration
+    assert all(w in ("host", "device") for w in wheres), "--decide device|host"
+
+    def drifting(shape, patch, n_sets, g):
+        base = torch.randn(shape, device=dev, generator=g)
+        sets = []
+        for _ in range(n_sets):
+            amp = torch.rand(shape[0], 1, shape[2] // patch, shape[3] // patch, device=dev, generator=g)
+            amp = amp.repeat_interleave(patch, 2).repeat_interleave(patch, 3)
+            sets.append((base + 0.3 * amp * torch.randn(shape, device=dev, generator=g)).to(torch.bfloat16))
+        return sets
+
+    def measure(name, exact, cached, widths, q, n_blocks, mmdit_ctx_len=None):
+        if q is None:                                        # asking fraction 1.0: a threshold below every difference
+            thr = {b: -1.0 for b in range(n_blocks)}
+        else:
+            cal = PatchSkipCache(QuantilePredictor(q), forced_after=1 << 30, mmdit_ctx_len=mmdit_ctx_len)
+            cal.record_features = True
+            for s in range(6):
+                cached(cal, s)
+            thr = {}
+            for f in cal.features[n_blocks:]:                # the first forward is uncached
+                m = f[:, 2:].max(axis=1)
+                thr.setdefault(int(f[0, 0]), []).append(m)
+            thr = {b: float(np.quantile(np.concatenate(v), q)) for b, v in thr.items()}
+            del cal
+            torch.cuda.empty_cache()
+        down = block_threshold_forest(thr, widths[0])
+        up = block_threshold_forest(thr, widths[1]) if widths[1] != widths[0] else down
+        for leg in wheres:
+            pc = PatchSkipCache(down, up, forced_after=1 << 30, mmdit_ctx_len=mmdit_ctx_len, on_device=leg == "device")
+            for s in range(3):
+                cached(pc, s)
+            torch.cuda.synchronize()
+            a0, t0n = pc.patches_asked, pc.patches_total
+            t0 = time.perf_counter()
+            for s in range(steps):
+                cached(pc, 3 + s)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) / steps * 1e3
+            frac = (pc.patches_asked - a0) / max(1, pc.patches_total - t0n)
+            ex = timed(exact, n=steps)
+            print(f"{name:>30s} decide={leg:6s} target f={1.0 if q is None else 1 - q:4.2f} reached f={frac:5.3f} cached {ms:8.2f} ms   exact {ex:8.2f} ms   "
+                  f"cached/exact {ms / ex:5.3f}   ({steps} timed steps)", flush=True)
+            del pc
+            torch.cuda.empty_cache()
+
+    # ---- SDXL, 8 x 1024^2, patch 256 px ----
+    cfg = UNetConfig.sdxl_base()
+    net = MxUNet(cfg, synthetic_params(cfg, device=dev), device=dev)
+    g = torch.Generator(device=dev).manual_seed(3)
+    b, px = 8, 1024
+    sets = drifting((b, 4, px // 8, px // 8), 32, 5, g)
+    t = torch.full((b,), 801.0, device=dev)
+    e = torch.randn(b, 77, cfg.cross_attention_dim, device=dev, generator=g).to(torch.bfloat16)
+    te = torch.randn(b, cfg.text_embed_dim, device=dev, generator=g).to(torch.bfloat16)
+    ti = torch.tensor([[px, px, 0, 0, px, px]], device=dev, dtype=torch.float32).repeat(b, 1)
+    ids = [f"r{i}" for i in range(b)]
+    exact = lambda: net.forward_mixed([sets[0]], t, e, te, ti, gn_patch=32)
+    cached = lambda pc, s: net.forward_mixed_cached(pc, [sets[s % len(sets)]], ids, t, e, te, ti, gn_patch=32)
+    n_blocks = 2 * len(cfg.block_out_channels) + 1
+    for q in (None, 0.5):
+        measure("SDXL 8x1024 patch unit", exact, cached, (3, 2 + cfg.layers_per_block + 2), q, n_blocks)
+    del net
+    torch.cuda.empty_cache()
+
+    # ---- SD3.5-medium, 1024^2, chunk unit ----
+    from sduss_amd.config import MMDiTConfig
+    from sduss_amd.transformer_sd3 import MxSD3Transformer
+    from sduss_amd.weights import synthetic_mmdit_params
+    mcfg = MMDiTConfig.sd35_medium()
+    mnet = MxSD3Transformer(mcfg, synthetic_mmdit_params(mcfg, device=dev), device=dev)
+    b, lt = 8, 333
+    msets = drifting((b, mcfg.in_channels, px // 8, px // 8), 32, 5, g)
+    t = torch.full((b,), 801.0, device=dev)
+    e = torch.randn(b, lt, mcfg.joint_attention_dim, device=dev, generator=g).to(torch.bfloat16)
+    p = torch.randn(b, mcfg.pooled_projection_dim, device=dev, generator=g).to(torch.bfloat16)
+    exact = lambda: mnet.forward_mixed([msets[0]], t, e, p)
+    cached = lambda pc, s: mnet.forward_mixed_cached(pc, [msets[s % len(msets)]], ids, t, e, p, 32)
+    measure("SD3.5-medium 8x1024 chunk unit", exact, cached, (3, 3), 0.5, mcfg.num_layers, mmdit_ctx_len=lt)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "patch":
+    if "--decide" in sys.argv:
+        main_decide(sys.argv[sys.argv.index("--decide") + 1])
+    elif len(sys.argv) > 1 and sys.argv[1] == "patch":
         main_patch_unit()
     else:
         main()
