@@ -15,14 +15,20 @@
 //   * PatchEmbed's 2x2 stride-2 conv is an im2col + GEMM whose epilogue adds bias and the cropped positional table.
 // Host scaffold (arena, weight lookup, groups, block-cache bookkeeping, the forward driver): plan_base.h; this file holds the MMDiT's own plan,
 // its checks and hooks (struct Model) and the extern "C" entry points, each of which describes its forward as an mx::ForwardCall.
+// One plan serves every mode (exact, mixed-resolution, patch-parallel, the per-sample and the chunk-unit block cache) and states each rule once:
+//   * Seq joint, image + Plan::place() -- where a group's rows lie in the streams, the joint sequence and V^T; every grouped operand comes from it;
+//   * linear(Linear{...}) -- required fields in order, the rest by name (.epilogue .plus .gated .rows .from .only); qkv() beside it;
+//   * attend()  -- the attention of a sequence set in the mode's form (one problem, per group, per active group, local queries x gathered keys);
+//   * project() -- how an attention projection's result reaches its stream (gated epilogue; chunk cache: materialise, state, gated copy);
+//   * the layer loop -- one block body between what brackets it (nothing; decide / after around a muted walk; pcm_open and the output stores).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mxdenoise.h"
@@ -51,6 +57,47 @@ struct mx_mmdit {
 
 namespace {
 
+// V^T rows padded to whole 128-byte lines: with the minimal MX_VT_LD(4429) = 4432 every 64-key tile row straddles two lines and the
+// joint attention ran at 850 TFLOP/s against 1000 at an aligned length (tools/exp/attn_shapes_probe.py)
+int vt_ld(int keys) { return (MX_VT_LD(keys) + 63) / 64 * 64; }
+
+// The stream the rows of a launch belong to: the image tokens (L_g rows per sample of group g) or the text tokens (Lt rows per sample everywhere)
+enum Stream { kNoStream, kImage, kText };
+
+// One attention site's q|k, V^T and O buffers and how the sequences lie in them: the samples of group g one after the other from row row0[g]
+// (q|k, O) / element vt0[g] (V^T), each len[g] = image tokens + `tail` rows long.  tail = Lt: the joint sequence [image ; text]; 0: attn2's
+// image tokens alone -- which is also the layout of the image STREAM's tensors (first row and rows per sample of a group).
+struct Seq {
+  int tail = 0;
+  int len[MX_MAX_SEGS], ldvt[MX_MAX_SEGS];
+  long row0[MX_MAX_SEGS], vt0[MX_MAX_SEGS];
+  long rows = 0, vt_elems = 0;
+  bf16_t *qk = nullptr, *vt = nullptr, *o = nullptr;
+  void lay(const mx::Groups& G, int ps, int d, int tail_rows) {
+    tail = tail_rows; rows = 0; vt_elems = 0;
+    for (int g = 0; g < G.ng; ++g) {
+      len[g] = (G.gH[g] / ps) * (G.gW[g] / ps) + tail; ldvt[g] = vt_ld(len[g]);
+      row0[g] = rows; vt0[g] = vt_elems;
+      rows += (long)G.gB[g] * len[g]; vt_elems += (long)G.gB[g] * d * ldvt[g];
+    }
+  }
+};
+
+// ---- the arguments of Plan::linear() by name: a call states the required fields in order and adds what else it means ----
+struct Linear {
+  const void* a; int lda; std::string stem; void* c; int ldc; int M, N, K;        // c[M, N] = a[M, K] * "<stem>.weight"^T + "<stem>.bias"
+  int flags = 0; const void* residual = nullptr; int ldr = 0; const float* gate = nullptr; int ldg = 0;
+  Stream stream = kNoStream; const Seq* a_seq = nullptr; const bool* act = nullptr;
+  Linear& epilogue(int f) { flags = f; return *this; }
+  Linear& plus(const void* r, int ld) { residual = r; ldr = ld; return *this; }
+  Linear& gated(const float* g, int ld) { gate = g; ldg = ld; return *this; }      // c = residual + gate[sample] * (...): one fp32 row per sample
+  // a, c, the residual are per-row tensors of stream s and the gate is per sample: yields rows_per_batch and, in a mixed batch, the groups' problems
+  Linear& rows(Stream s) { stream = s; return *this; }
+  // a is the O buffer of sequence set q: the launch reads the stream's rows out of every sample's sequence (the loader's row remap)
+  Linear& from(const Seq& q) { a_seq = &q; return *this; }
+  Linear& only(const bool* groups) { act = groups; return *this; }                // cached mixed batch: the problems of these groups only
+};
+
 struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchange, block-cache bookkeeping: plan_base.h)
   mx_mmdit* u;
   int Lt;
@@ -61,14 +108,35 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   // joint sequence back -- are GROUPED launches (mx_gemm_seg, mx_attention_prescaled_grouped, mx_layernorm_mod_grouped).  The reference
   // re-chunks the tokens of all resolutions into one batch (modules/utils.py:86-122) and regroups them per latent before attention
   // (attention.py:300-372).
-  typedef std::function<void(int, mx_gemm_seg&)> SegFill;      // fills problem g of a grouped GEMM
+  // WHERE A GROUP'S ROWS LIE is stated here once (laid out at the top of run()): every operand of every grouped launch is derived from it.
+  Seq joint, image;
+  long row0(Stream s, int g) const { return s == kImage ? image.row0[g] : (long)gb0[g] * Lt; }      // first row of group g in the stream's tensors
+  int rpb(Stream s, int g) const { return s == kImage ? image.len[g] : Lt; }                         // rows per sample
+  int rows(Stream s) const { return s == kImage ? (int)image.rows : B * Lt; }
+  // Group g's operands of launch d on the rows of stream s, into q: a problem of the grouped launch, or d itself (g = 0: the descriptor
+  // describes the first group).  from: A is that sequence set's O buffer; into: C is its q|k buffer, with its V^T.
+  template <class Q> void place(Q& q, const mx_gemm_desc& d, Stream s, const Seq* from, const Seq* into, int g) const {
+    const long r = row0(s, g);
+    const int off = s == kImage ? 0 : image.len[g];            // the stream's first row inside a joint sequence
+    q.rows_per_batch = rpb(s, g);
+    q.a = (const bf16_t*)d.a + (from ? from->row0[g] : r) * d.lda;
+    if (from && from->tail) { q.a_batch_rows = from->len[g]; q.a_row_off = off; }
+    q.c = (bf16_t*)d.c + (into ? into->row0[g] : r) * d.ldc;
+    if (into) { q.vt = into->vt + into->vt0[g]; q.ldvt = into->ldvt[g]; }
+    if (into && into->tail) { q.c_batch_rows = into->len[g]; q.c_row_off = off; }
+    if (d.residual) q.residual = (const bf16_t*)d.residual + r * d.ldr;
+    if (d.gate) q.gate = d.gate + (long)gb0[g] * d.ldg;
+  }
   mx_gemm_seg seg_buf[MX_MAX_SEGS];
-  const bool* act = nullptr;        // cached mixed batch: the grouped launch covers these resolution groups only (nullptr: all)
-  void attach(mx_gemm_desc& d, const SegFill& fill) {
-    if (ng <= 1 || !fill) return;
+  // act: the grouped launch covers these resolution groups only (nullptr: all).  The text stream has one length everywhere: its launches are
+  // grouped only where they meet the joint sequence.
+  void attach(mx_gemm_desc& d, Stream s, const Seq* from, const Seq* into, const bool* act) {
+    if (s == kNoStream) return;
+    place(d, d, s, from, into, 0);
+    if (ng <= 1 || (s == kText && !from && !into)) return;
     std::memset(seg_buf, 0, sizeof(seg_buf));
     int n = 0;
-    for (int g = 0; g < ng; ++g) if (!act || act[g]) fill(g, seg_buf[n++]);
+    for (int g = 0; g < ng; ++g) if (!act || act[g]) { mx_gemm_seg& q = seg_buf[n++]; place(q, d, s, from, into, g); q.M = gB[g] * q.rows_per_batch; }
     d.segs = seg_buf; d.n_segs = n;
   }
   // patch parallelism (mx_mmdit_forward_pp; distrifuser models/distri_sd3_transformer_pp.py:87-97, modules/pp/attn.py:202-277): this rank owns
@@ -106,65 +174,41 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const size_t nc = pcm_ncmax();
     return ((nc * 64 * sizeof(double) + 2 * (size_t)pcm_slots * sizeof(mx::PcSample) + 4 * nc * sizeof(mx::PcRange)) + 255) & ~(size_t)255;
   }
+  // the state's base: the caller's buffer, or in a sizing walk a placeholder that is only counted from
+  char* pcm_base() const { return dry ? (char*)(uintptr_t)0x1000 : (char*)bc->state; }
   size_t bc_bytes = 0;             // state bytes the plan needs (also the dry answer of mx_mmdit_block_cache_bytes)
   unsigned long long blocks_run = 0;
   static constexpr int kBcPartRows = 1, kBcTables = 1;     // head of the state: one row of partial sums, the slot table
   static size_t bc_scratch_bytes(int rows) { return bc_head_bytes(kBcPartRows, kBcTables, rows); }
 
   // C = A W^T + bias with the optional fused pieces
-  bool linear(const void* a, int lda, const std::string& name, void* c, int ldc, int M, int N, int K, int flags = 0,
-              const void* residual = nullptr, int ldr = 0, const float* gate = nullptr, int ldg = 0, int rows_per_batch = 0,
-              int a_batch_rows = 0, int a_row_off = 0, const SegFill& fill = nullptr) {
+  bool linear(const Linear& l) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-    d.a = a; d.lda = lda; d.w = wb(name + ".weight", (size_t)N * K); d.bias = wf(name + ".bias", N);
-    d.c = c; d.ldc = ldc; d.M = M; d.N = N; d.K = K; d.flags = flags; d.residual = residual; d.ldr = ldr;
-    d.gate = gate; d.ldg = ldg; d.rows_per_batch = rows_per_batch; d.a_batch_rows = a_batch_rows; d.a_row_off = a_row_off;
-    attach(d, fill);
+    d.a = l.a; d.lda = l.lda; d.w = wb(l.stem + ".weight", (size_t)l.N * l.K); d.bias = wf(l.stem + ".bias", l.N);
+    d.c = l.c; d.ldc = l.ldc; d.M = l.M; d.N = l.N; d.K = l.K; d.flags = l.flags; d.residual = l.residual; d.ldr = l.ldr; d.gate = l.gate; d.ldg = l.ldg;
+    attach(d, l.stream, l.a_seq, nullptr, l.act);
     return gemm(d);
   }
-  // fused q|k|v projection of `rows_per_batch` tokens per sample into the joint buffers at row offset `row_off`; the epilogue
-  // RMS-normalises every q / k head (norm_q / norm_k, attention.py:332-346, 377-388) and scales q for mx_attention_prescaled
-  bool qkv(const void* a, const std::string& name, const std::string& qnorm, const std::string& knorm, bf16_t* qk, bf16_t* vt, int ldvt,
-           int M, int d_model, int rows_per_batch, int joint_rows, int row_off, const SegFill& fill = nullptr) {
+  // fused q|k|v projection "<stem>" of stream s's tokens into their rows of sequence set `into` (q|k interleaved, V transposed); the epilogue
+  // RMS-normalises every q / k head ("<norm>q.weight", "<norm>k.weight"; attention.py:332-346, 377-388) and scales q for mx_attention_prescaled
+  bool qkv(const bf16_t* a, Stream s, const std::string& stem, const std::string& norm, const Seq& into) {
+    const int d_model = u->cfg.num_attention_heads * 64;
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-    d.a = a; d.lda = d_model; d.w = wb(name + ".weight", (size_t)3 * d_model * d_model); d.bias = wf(name + ".bias", 3 * d_model);
-    d.c = qk; d.ldc = 2 * d_model; d.M = M; d.N = 3 * d_model; d.K = d_model; d.flags = MX_EPI_QKV | MX_EPI_RMSNORM; d.seg = d_model; d.period = 3;
-    d.vt = vt; d.ldvt = ldvt; d.rows_per_batch = rows_per_batch; d.c_batch_rows = joint_rows; d.c_row_off = row_off;
-    d.rms_wq = wf(qnorm, 64); d.rms_wk = wf(knorm, 64); d.rms_eps = u->cfg.norm_eps; d.out_scale = MX_ATTN_QSCALE(0.125f);
-    attach(d, fill);
+    d.a = a; d.lda = d_model; d.w = wb(stem + ".weight", (size_t)3 * d_model * d_model); d.bias = wf(stem + ".bias", 3 * d_model);
+    d.c = into.qk; d.ldc = 2 * d_model; d.M = rows(s); d.N = 3 * d_model; d.K = d_model; d.flags = MX_EPI_QKV | MX_EPI_RMSNORM; d.seg = d_model; d.period = 3;
+    d.rms_wq = wf(norm + "q.weight", 64); d.rms_wk = wf(norm + "k.weight", 64); d.rms_eps = u->cfg.norm_eps; d.out_scale = MX_ATTN_QSCALE(0.125f);
+    attach(d, s, nullptr, &into, nullptr);
     return gemm(d);
   }
-  // image: the rows are the image stream (per-group tokens per sample in a mixed batch); otherwise the text stream (Lt rows per sample)
-  bool lnmod(const bf16_t* x, bf16_t* y, bf16_t* y2, const float* scale, const float* shift, const float* scale2,
-             const float* shift2, int ldmod, int M, int C, int rows_per_batch, bool image = false) {
+  // LayerNorm + modulation of stream s by per-sample fp32 rows (row stride ldmod); y2: the second modulation of the same normalised rows
+  bool lnmod(Stream s, const bf16_t* x, bf16_t* y, bf16_t* y2, const float* scale, const float* shift, const float* scale2, const float* shift2, int ldmod) {
     if (!ok()) return false;
     if (quiet()) return true;
-    if (image && ng > 1) {
-      int rpb[MX_MAX_SEGS];
-      const int ps = u->cfg.patch_size;
-      for (int g = 0; g < ng; ++g) rpb[g] = (gH[g] / ps) * (gW[g] / ps);
-      if (mx_layernorm_mod_grouped(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, C, u->cfg.norm_eps, gB, rpb, ng))
-        return fail(std::string("layernorm_mod: ") + mx_last_error());
-      return true;
-    }
-    if (mx_layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, M, C, rows_per_batch, u->cfg.norm_eps))
+    const int C = u->cfg.num_attention_heads * 64;
+    if (s == kImage && ng > 1
+          ? mx_layernorm_mod_grouped(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, C, u->cfg.norm_eps, gB, image.len, ng)
+          : mx_layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, rows(s), C, rpb(s, 0), u->cfg.norm_eps))
       return fail(std::string("layernorm_mod: ") + mx_last_error());
-    return true;
-  }
-  bool attention(const bf16_t* qk, int d_model, const bf16_t* vt, int ldvt, bf16_t* o, int heads, int L) {
-    if (!ok()) return false;
-    if (quiet()) return true;
-    // q carries MX_ATTN_QSCALE(1/8) from the QKV epilogue (RMSNorm + out_scale)
-    if (mx_attention_prescaled(stream, qk, 2 * d_model, qk + d_model, 2 * d_model, vt, ldvt, (int64_t)d_model * ldvt, o, d_model, B, heads, L, L))
-      return fail(std::string("attention: ") + mx_last_error());
-    return true;
-  }
-  // queries from the local q|k rows, keys from a packed K buffer of another length (patch-parallel: local queries, gathered keys)
-  bool attention_qk(const bf16_t* q, const bf16_t* k, int d_model, const bf16_t* vt, int ldvt, bf16_t* o, int heads, int Lq, int Lk) {
-    if (!ok()) return false;
-    if (quiet()) return true;
-    if (mx_attention_prescaled(stream, q, 2 * d_model, k, d_model, vt, ldvt, (int64_t)d_model * ldvt, o, d_model, B, heads, Lq, Lk))
-      return fail(std::string("attention: ") + mx_last_error());
     return true;
   }
   bool run(const void* latents, int io_dtype, const float* timesteps, const void* ehs, const void* pooled, void* outp) {
@@ -174,29 +218,14 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const int ps = c.patch_size;
     const int h = H / ps, wd = W / ps;
     const int L = h * wd;
-    const int Lj = L + Lt;
-    // V^T rows padded to whole 128-byte lines: with the minimal MX_VT_LD(4429) = 4432 every 64-key tile row straddles two lines and the
-    // joint attention ran at 850 TFLOP/s against 1000 at an aligned length (tools/exp/attn_shapes_probe.py)
-    const int ldvt_j = (MX_VT_LD(Lj) + 63) / 64 * 64;
-    const int ldvt_i = (MX_VT_LD(L) + 63) / 64 * 64;
     const int Kp = ps * ps * c.in_channels;
-    // per group (one unless the batch is mixed): image tokens per sample, joint sequence, V^T row lengths, first rows / elements of the group
-    // in the image stream, in the joint q|k / O buffers and in the two V^T buffers
-    int gL[MX_MAX_SEGS], gLj[MX_MAX_SEGS], gldj[MX_MAX_SEGS], gldi[MX_MAX_SEGS];
-    long r0[MX_MAX_SEGS], jr0[MX_MAX_SEGS], vj0[MX_MAX_SEGS], vi0[MX_MAX_SEGS];
-    long rows_i = 0, rows_j = 0, el_vj = 0, el_vi = 0;
-    for (int g = 0; g < ng; ++g) {
-      gL[g] = (gH[g] / ps) * (gW[g] / ps); gLj[g] = gL[g] + Lt;
-      gldj[g] = (MX_VT_LD(gLj[g]) + 63) / 64 * 64; gldi[g] = (MX_VT_LD(gL[g]) + 63) / 64 * 64;
-      r0[g] = rows_i; jr0[g] = rows_j; vj0[g] = el_vj; vi0[g] = el_vi;
-      rows_i += (long)gB[g] * gL[g]; rows_j += (long)gB[g] * gLj[g]; el_vj += (long)gB[g] * d * gldj[g]; el_vi += (long)gB[g] * d * gldi[g];
-    }
+    joint.lay(*this, ps, d, Lt);
+    image.lay(*this, ps, d, 0);
     if (ng > 1 && (is_pp() || (bc && !pcm))) return fail("mmdit: a mixed-resolution batch runs neither patch-parallel nor through the per-sample block cache");
-    const int MI = (int)rows_i, MT = B * Lt;
+    const int MI = rows(kImage), MT = rows(kText);
     // patch-parallel: L counts this rank's image tokens; the keys of the joint attention are all ranks' image tokens, then the text tokens
     const int world = px.world;
-    const int Ltot = L * world, Ljt = Ltot + Lt;
-    const int ldvt_jt = (MX_VT_LD(Ljt) + 63) / 64 * 64, ldvt_it = (MX_VT_LD(Ltot) + 63) / 64 * 64;
+    const int Ltot = L * world;
     if (is_pp() && L % 16 != 0) return fail("mmdit pp: local image tokens must be a multiple of 16 (V^T key order, MX_VT_POS)");
     if (is_pp() && bc) return fail("mmdit pp: not combined with the block-skip cache");
 
@@ -215,37 +244,32 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (ok() && !dry && mx::launch_sinus_embed(stream, timesteps, tsin, B, 256)) fail(mx_last_error());
     bf16_t* t1 = alloc<bf16_t>((size_t)B * d); bf16_t* t2 = alloc<bf16_t>((size_t)B * d);
     bf16_t* p1 = alloc<bf16_t>((size_t)B * d); bf16_t* semb = alloc<bf16_t>((size_t)B * d);
-    linear(tsin, 256, "time_text_embed.timestep_embedder.linear_1", t1, d, B, d, 256, MX_EPI_SILU);
-    linear(t1, d, "time_text_embed.timestep_embedder.linear_2", t2, d, B, d, d);
-    linear(pooled, c.pooled_projection_dim, "time_text_embed.text_embedder.linear_1", p1, d, B, d, c.pooled_projection_dim, MX_EPI_SILU);
+    linear(Linear{tsin, 256, "time_text_embed.timestep_embedder.linear_1", t1, d, B, d, 256}.epilogue(MX_EPI_SILU));
+    linear(Linear{t1, d, "time_text_embed.timestep_embedder.linear_2", t2, d, B, d, d});
+    linear(Linear{pooled, c.pooled_projection_dim, "time_text_embed.text_embedder.linear_1", p1, d, B, d, c.pooled_projection_dim}.epilogue(MX_EPI_SILU));
     // silu(temb): every consumer of temb applies SiLU first (AdaLayerNormZero / ZeroX / Continuous)
-    linear(p1, d, "time_text_embed.text_embedder.linear_2", semb, d, B, d, d, MX_EPI_SILU, t2, d);
+    linear(Linear{p1, d, "time_text_embed.text_embedder.linear_2", semb, d, B, d, d}.epilogue(MX_EPI_SILU).plus(t2, d));
     float* mod = alloc<float>((size_t)B * ntot);
-    linear(semb, d, "adaln_all", mod, ntot, B, ntot, d, MX_EPI_OUT_F32);
+    linear(Linear{semb, d, "adaln_all", mod, ntot, B, ntot, d}.epilogue(MX_EPI_OUT_F32));
 
     // ---- PatchEmbed + positional table (:82-83), context_embedder (:115) ----
     bf16_t* patches = alloc<bf16_t>((size_t)MI * Kp);
     for (int g = 0; g < ng && ok() && !dry; ++g)
-      if (mx::launch_patchify(stream, g_lat[g], io_dtype, patches + r0[g] * Kp, gB[g], c.in_channels, gH[g], gW[g], ps)) fail(mx_last_error());
-    bf16_t* pos = alloc<bf16_t>(ng > 1 ? (size_t)MI * d : (size_t)Ltot * d);      // (mixed: one cropped table per group, [L_g, d] at the group's first row)
-    if (ng > 1) {
-      const bf16_t* table = wb("pos_embed.table", (size_t)c.pos_embed_max_size * c.pos_embed_max_size * d);
-      for (int g = 0; g < ng && ok(); ++g) {
-        if (gH[g] / ps > c.pos_embed_max_size || gW[g] / ps > c.pos_embed_max_size) return fail("mmdit: latent larger than the positional table");
-        if (!dry && mx::launch_crop_pos(stream, table, pos + r0[g] * d, c.pos_embed_max_size, gH[g] / ps, gW[g] / ps, d)) fail(mx_last_error());
-      }
-    } else {
-      // the centre crop is taken for the WHOLE grid (distri_sd3_transformer_pp.py:87 embeds before it slices); this rank reads its rows
-      const bf16_t* table = wb("pos_embed.table", (size_t)c.pos_embed_max_size * c.pos_embed_max_size * d);
-      if (h * world > c.pos_embed_max_size) return fail("mmdit: latent larger than the positional table");
-      if (ok() && !dry && mx::launch_crop_pos(stream, table, pos, c.pos_embed_max_size, h * world, wd, d)) fail(mx_last_error());
-      if (pos) pos += (size_t)px.rank * L * d;
+      if (mx::launch_patchify(stream, g_lat[g], io_dtype, patches + image.row0[g] * Kp, gB[g], c.in_channels, gH[g], gW[g], ps)) fail(mx_last_error());
+    // One centre crop of the table per group, [L_g, d] at the group's first row.  Patch-parallel: the crop is taken for the WHOLE grid
+    // (distri_sd3_transformer_pp.py:87 embeds before it slices) and this rank reads its rows.
+    bf16_t* pos = alloc<bf16_t>(ng > 1 ? (size_t)MI * d : (size_t)Ltot * d);
+    const bf16_t* table = wb("pos_embed.table", (size_t)c.pos_embed_max_size * c.pos_embed_max_size * d);
+    for (int g = 0; g < ng && ok(); ++g) {
+      const int gh = gH[g] / ps * world, gw = gW[g] / ps;
+      if (gh > c.pos_embed_max_size || (ng > 1 && gw > c.pos_embed_max_size)) return fail("mmdit: latent larger than the positional table");   // (one group: its width is the entry point's check)
+      if (!dry && mx::launch_crop_pos(stream, table, pos + image.row0[g] * d, c.pos_embed_max_size, gh, gw, d)) fail(mx_last_error());
     }
+    if (pos) pos += (size_t)px.rank * L * d;
     bf16_t* x = alloc<bf16_t>((size_t)MI * d);
-    linear(patches, Kp, "pos_embed.proj", x, d, MI, d, Kp, MX_EPI_RES_BCAST, pos, d, nullptr, 0, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-      q.a = patches + r0[g] * Kp; q.c = x + r0[g] * d; q.residual = pos + r0[g] * d; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; });
+    linear(Linear{patches, Kp, "pos_embed.proj", x, d, MI, d, Kp}.epilogue(MX_EPI_RES_BCAST).plus(pos, d).rows(kImage));
     bf16_t* ctx = alloc<bf16_t>((size_t)MT * d);
-    linear(ehs, c.joint_attention_dim, "context_embedder", ctx, d, MT, d, c.joint_attention_dim);
+    linear(Linear{ehs, c.joint_attention_dim, "context_embedder", ctx, d, MT, d, c.joint_attention_dim});
     dump("embed", x, (size_t)MI * d);
     dump("context_embed", ctx, (size_t)MT * d);
 
@@ -253,17 +277,17 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     bf16_t* xin = alloc<bf16_t>((size_t)MI * d);
     bf16_t* x2in = alloc<bf16_t>((size_t)MI * d);
     bf16_t* cin = alloc<bf16_t>((size_t)MT * d);
-    bf16_t* qk_j = alloc<bf16_t>((size_t)rows_j * 2 * d);
-    bf16_t* vt_j = alloc<bf16_t>((size_t)el_vj);
-    bf16_t* o_j = alloc<bf16_t>((size_t)rows_j * d);
-    bf16_t* qk_i = alloc<bf16_t>((size_t)MI * 2 * d);
-    bf16_t* vt_i = alloc<bf16_t>((size_t)el_vi);
-    bf16_t* o_i = alloc<bf16_t>((size_t)MI * d);
+    joint.qk = alloc<bf16_t>((size_t)joint.rows * 2 * d);
+    joint.vt = alloc<bf16_t>((size_t)joint.vt_elems);
+    joint.o = alloc<bf16_t>((size_t)joint.rows * d);
+    image.qk = alloc<bf16_t>((size_t)MI * 2 * d);
+    image.vt = alloc<bf16_t>((size_t)image.vt_elems);
+    image.o = alloc<bf16_t>((size_t)MI * d);
     bf16_t* ff = alloc<bf16_t>((size_t)MI * 4 * d);
     bf16_t* ffc = alloc<bf16_t>((size_t)MT * 4 * d);
     bf16_t* pcm_ti = pcm ? alloc<bf16_t>((size_t)MI * d) : nullptr;          // cached mixed batch: to_out / to_add_out results before the gate
     bf16_t* pcm_tc = pcm ? alloc<bf16_t>((size_t)MT * d) : nullptr;
-    char* pcm_top = pcm ? (dry ? (char*)(uintptr_t)0x1000 : (char*)bc->state) + pcm_head_bytes() : nullptr;
+    char* pcm_top = pcm ? pcm_base() + pcm_head_bytes() : nullptr;
     // patch-parallel: only the image tokens' K rows and V^T columns travel (what distrifuser gathers, modules/pp/attn.py:222-233): they are packed
     // into contiguous send buffers first -- the QKV epilogue writes q|k interleaved and V^T rows padded, with the text tokens behind the image ones
     bf16_t *k_send = nullptr, *v_send = nullptr, *k_g = nullptr, *v_g = nullptr, *k_all = nullptr, *vt_all = nullptr;
@@ -272,17 +296,18 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       v_send = alloc<bf16_t>((size_t)B * d * L);
       k_g = alloc<bf16_t>((size_t)world * B * L * d);
       v_g = alloc<bf16_t>((size_t)world * B * d * L);
-      k_all = alloc<bf16_t>((size_t)B * Ljt * d);
-      vt_all = alloc<bf16_t>((size_t)B * d * ldvt_jt);
+      k_all = alloc<bf16_t>((size_t)B * (Ltot + Lt) * d);
+      vt_all = alloc<bf16_t>((size_t)B * d * vt_ld(Ltot + Lt));
     }
-    // keys of the joint attention per sample: every rank's `L` image tokens in rank order, then the `tail` local-only (text) tokens:
+    // keys of a patch-parallel attention per sample: every rank's `L` image tokens in rank order, then the `tail` local-only (text) tokens:
     // k_all [B][world * L + tail][d], vt_all [B][d][ld_all]
-    auto gather_kv = [&](bf16_t* qk_loc, bf16_t* vt_loc, int ld_loc, int tail, int ld_all) {
+    auto gather_kv = [&](const Seq& s, int ld_all) {
+      const int tail = s.tail, ld_loc = s.ldvt[0];
       const int rows_loc = L + tail, rows_all = Ltot + tail;
       const size_t krow = (size_t)d * 2, qrow = 2 * krow;
       for (int b = 0; b < B && ok(); ++b)               // K half of this sample's image rows
-        copy2d((char*)k_send + (size_t)b * L * krow, krow, (char*)qk_loc + (size_t)b * rows_loc * qrow + krow, qrow, krow, L);
-      copy2d(v_send, (size_t)L * 2, vt_loc, (size_t)ld_loc * 2, (size_t)L * 2, (size_t)B * d);
+        copy2d((char*)k_send + (size_t)b * L * krow, krow, (char*)s.qk + (size_t)b * rows_loc * qrow + krow, qrow, krow, L);
+      copy2d(v_send, (size_t)L * 2, s.vt, (size_t)ld_loc * 2, (size_t)L * 2, (size_t)B * d);
       all_gather(k_send, k_g, (size_t)B * L * krow);
       all_gather(v_send, v_g, (size_t)B * d * L * 2);
       for (int r = 0; r < world && ok(); ++r) {
@@ -291,10 +316,34 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       }
       if (tail) {
         for (int b = 0; b < B && ok(); ++b)
-          copy2d((char*)k_all + ((size_t)b * rows_all + Ltot) * krow, krow, (char*)qk_loc + ((size_t)b * rows_loc + L) * qrow + krow, qrow, krow, tail);
-        copy2d((char*)vt_all + (size_t)Ltot * 2, (size_t)ld_all * 2, (char*)vt_loc + (size_t)L * 2, (size_t)ld_loc * 2, (size_t)MX_VT_LD(tail) * 2,
+          copy2d((char*)k_all + ((size_t)b * rows_all + Ltot) * krow, krow, (char*)s.qk + ((size_t)b * rows_loc + L) * qrow + krow, qrow, krow, tail);
+        copy2d((char*)vt_all + (size_t)Ltot * 2, (size_t)ld_all * 2, (char*)s.vt + (size_t)L * 2, (size_t)ld_loc * 2, (size_t)MX_VT_LD(tail) * 2,
                (size_t)B * d);
       }
+    };
+    // THE ATTENTION of one sequence set (the joint one, attn2's), in the form the mode asks for: patch-parallel -- local queries against the
+    // gathered keys; a mixed batch -- one problem per group; the chunk cache -- one problem per ACTIVE group (act); otherwise one problem.
+    // q carries MX_ATTN_QSCALE(1/8) from the QKV epilogue (RMSNorm + out_scale).
+    auto attend = [&](const Seq& s, const bool* act) {
+      const int Lk = Ltot + s.tail, ld_all = vt_ld(Lk);
+      if (is_pp()) gather_kv(s, ld_all);
+      if (!ok() || quiet()) return;
+      int rc = 0;
+      if (is_pp()) {
+        rc = mx_attention_prescaled(stream, s.qk, 2 * d, k_all, d, vt_all, ld_all, (int64_t)d * ld_all, s.o, d, B, heads, s.len[0], Lk);
+      } else if (ng > 1 || act) {
+        mx_attn_problem pr[MX_MAX_SEGS];
+        int n = 0;
+        for (int g = 0; g < ng; ++g) if (!act || act[g]) {
+          pr[n].q = s.qk + s.row0[g] * 2 * d; pr[n].k = s.qk + s.row0[g] * 2 * d + d; pr[n].vt = s.vt + s.vt0[g]; pr[n].o = s.o + s.row0[g] * d;
+          pr[n].vt_batch_stride = (int64_t)d * s.ldvt[g]; pr[n].B = gB[g]; pr[n].Lq = s.len[g]; pr[n].Lk = s.len[g]; pr[n].ldvt = s.ldvt[g];
+          ++n;
+        }
+        if (n) rc = mx_attention_prescaled_grouped(stream, pr, n, 2 * d, 2 * d, d, heads);
+      } else {
+        rc = mx_attention_prescaled(stream, s.qk, 2 * d, s.qk + d, 2 * d, s.vt, s.ldvt[0], (int64_t)d * s.ldvt[0], s.o, d, B, heads, s.len[0], s.len[0]);
+      }
+      if (rc) fail(std::string("attention: ") + mx_last_error());
     };
 
     // Block-skip cache (mx_mmdit_forward_cached; the reference's per-block CacheManagers, SD3Transformer.py:54-57,151,172,219-228): a block
@@ -307,23 +356,16 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       bc_bytes = bc_scratch + (size_t)c.num_layers * (2 * bc_x + bc_c);
       if (!dry && bc_bytes > bc->state_bytes) fail("block cache: state buffer too small (mx_mmdit_block_cache_bytes)");
     }
+    // how far x is from a state tensor, per sample: the head of the state is the comparison scratch
+    auto x_moved = [&](const char* st, float* mse, const char* msg) {
+      if (mx::launch_sq_diff_partial(stream, x, st, (long)L * d, B, (double*)bc->state, bc_dslot)) return fail(mx_last_error());
+      return bc_read_mse((double*)bc->state, B, 64, mse, msg, [&](size_t s) { return MseRow{(int)s, (double)L * d, s}; });
+    };
     // decides block i; false = reuse.  Leaves the latest input in the cache (cache_manager.py:183)
     auto decide = [&](int i) -> bool {
       char* st = (char*)bc->state + bc_scratch + (size_t)i * (2 * bc_x + bc_c);
       std::vector<float> mse(B, MX_MSE_UNCACHED);
-      if (bc_any_valid) {
-        double* part = (double*)bc->state;
-        std::vector<double> hp((size_t)B * 64);
-        if (mx::launch_sq_diff_partial(stream, x, st, (long)L * d, B, part, bc_dslot)) { fail(mx_last_error()); return true; }
-        if (hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) { fail("block cache: reading the input differences failed"); return true; }
-        for (int s = 0; s < B; ++s) {
-          if (!bc_valid[s]) continue;
-          double t = 0.0;
-          for (int k = 0; k < 64; ++k) t += hp[(size_t)s * 64 + k];
-          mse[s] = (float)(t / ((double)L * d));
-        }
-      }
+      if (bc_any_valid && !x_moved(st, mse.data(), "block cache: reading the input differences failed")) return true;
       std::vector<unsigned char> run(B, 1);
       if (bc->predict(bc->ctx, i, 0, B, 1, h_timesteps.data(), mse.data(), run.data())) { fail("block cache: the predictor failed"); return true; }
       bool any = !bc_all_valid;
@@ -334,17 +376,8 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     auto after = [&](int i, bool ran, bool last) {
       char* st = (char*)bc->state + bc_scratch + (size_t)i * (2 * bc_x + bc_c);
       if (ran && bc_all_valid && bc->observe) {              // how far the block's image-stream output moved since its last run (fitting labels)
-        double* part = (double*)bc->state;
-        std::vector<double> hp((size_t)B * 64);
         std::vector<float> om(B);
-        if (mx::launch_sq_diff_partial(stream, x, st + bc_x, (long)L * d, B, part, bc_dslot)) { fail(mx_last_error()); return; }
-        if (hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) { fail("block cache: reading the output differences failed"); return; }
-        for (int s = 0; s < B; ++s) {
-          double t = 0.0;
-          for (int k = 0; k < 64; ++k) t += hp[(size_t)s * 64 + k];
-          om[s] = (float)(t / ((double)L * d));
-        }
+        if (!x_moved(st + bc_x, om.data(), "block cache: reading the output differences failed")) return;
         bc->observe(bc->ctx, i, B, om.data());
       }
       bool okc = ran ? bc_store(st + bc_x, x, (size_t)L * d * 2) : bc_load(x, st + bc_x, (size_t)L * d * 2);
@@ -352,238 +385,173 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       if (ran) blocks_run |= 1ull << i;
     };
 
+    // ---- the chunk-unit cache's view of the current block (pcm) ----
+    const long row_i = pcm ? (long)(pcm_maxh / ps) * (pcm_maxw / ps) * d : 0, row_c = (long)Lt * d;      // elements of a state row, per stream
+    long maxL = 0; for (int g = 0; g < ng; ++g) maxL = std::max<long>(maxL, image.len[g]);
+    struct {
+      char *in, *out, *octx, *a, *ae, *a2;                   // state regions: block input, outputs of both streams, attn / attn context / attn2 results
+      std::vector<unsigned char> run;                        // per chunk: asks
+      bool gany[MX_MAX_SEGS]; int gask[MX_MAX_SEGS], gtot[MX_MAX_SEGS];        // per group: any chunk asks; asking chunks; chunks
+      std::vector<mx::PcRange> act_img, act_ctx;             // rows of the samples of the active groups, per stream
+      const mx::PcRange *d_act_img, *d_act_ctx;
+    } cb{};
+    // a stream's tensor <-> a state region, sample by sample (to_batch) with the optional gated add: t = res + vec[sample] * state
+    auto state_copy = [&](Stream s, void* t, char* reg, int to_batch, const float* vec, const void* res, int gate) {
+      const bool img = s == kImage;
+      if (ok() && mx::launch_pc_image_copy(stream, t, reg, img ? (void*)pcm_dimg : (void*)pcm_dctx, B, 0, d, img ? row_i : row_c, to_batch, vec, ntot, res,
+                                           img ? maxL * d : row_c, gate)) fail(mx_last_error());
+    };
+    // a range table of the running block to the device (slot: which of the scratch tables)
+    auto upload = [&](const std::vector<mx::PcRange>& v, int slot) -> const mx::PcRange* {
+      mx::PcRange* dst = pcm_dtmp + (size_t)slot * pcm_ncmax();
+      if (!ok() || v.empty()) return dst;
+      pcm_sent.push_back(v);                // (the copy is asynchronous from pageable memory: the table must outlive the block that built it)
+      if (hipMemcpyAsync(dst, pcm_sent.back().data(), v.size() * sizeof(mx::PcRange), hipMemcpyHostToDevice, stream) != hipSuccess)
+        fail("mmdit patch cache: sending a range table failed");
+      return dst;
+    };
+    // Opens block i of the chunk cache: carves its state regions (the sizing walk stops here), decides per chunk, stores the input and, when no
+    // chunk asks, takes both streams from the state.  true: the block runs.
+    auto pcm_open = [&](int i, bool dual, bool last) -> bool {
+      auto region = [&](long row_elems) { char* r = pcm_top; pcm_top += ((size_t)row_elems * pcm_slots * 2 + 255) & ~(size_t)255; return r; };
+      cb.in = region(row_i); cb.out = region(row_i); cb.octx = last ? nullptr : region(row_c);
+      cb.a = region(row_i); cb.ae = last ? nullptr : region(row_c); cb.a2 = dual ? region(row_i) : nullptr;
+      if (dry) return false;
+      if ((size_t)(pcm_top - (char*)bc->state) > bc->state_bytes) return fail("mmdit patch cache: state buffer too small (mx_mmdit_patch_cache_bytes)");
+      const int NC = pcm_nc;
+      if (bc_any_valid && mx::launch_pc_range_sq_diff(stream, x, cb.in, row_i, d, pcm_dchunks, NC, pcm_dpart)) return fail(mx_last_error());
+      cb.run.assign(NC, 1);
+      for (int g = 0; g < MX_MAX_SEGS; ++g) { cb.gask[g] = 0; cb.gtot[g] = 0; }
+      // THE DECISION -- the one place the two modes differ: it leaves run[], gask[] and gtot[]
+      if (bc_dev) {
+        // on the device (mx_block_cache.dev_down): one launch, one record read back (patch_cache.hip pc_decide_kernel; skip_decide.h)
+        mx_skip_decide_args a{};
+        a.forest = bc->dev_down; a.n_in = 1; a.kind = 1; a.units = pcm_dchunks; a.unit_sample = bc_skip.unit_sample; a.partial = pcm_dpart;
+        a.part_len[0] = 64; a.part_elems[0] = (double)d;
+        const unsigned char* flags = nullptr;
+        const int32_t* rec = bc_dev_decide(a, i, true, &flags);
+        if (!rec) return false;
+        cb.run.assign(flags, flags + NC);
+        for (int g = 0; g < MX_MAX_SEGS; ++g) { cb.gask[g] = rec[MX_SKIP_REC_GASK + g]; cb.gtot[g] = rec[MX_SKIP_REC_GTOT + g]; }
+      } else {
+        // on the host: the partial sums come back and the caller's predictor answers
+        std::vector<float> mse(NC, MX_MSE_UNCACHED);
+        if (bc_any_valid && !bc_read_mse(pcm_dpart, NC, 64, mse.data(), "mmdit patch cache: reading the input differences failed",
+                                         [&](size_t j) { return MseRow{pcm_chunk_b[j], (double)pcm_chunks[j].rows * d, j}; })) return false;
+        std::vector<float> tpp(NC);
+        for (int j = 0; j < NC; ++j) tpp[j] = h_timesteps[pcm_chunk_b[j]];
+        if (bc->predict(bc->ctx, i, 0, NC, 1, tpp.data(), mse.data(), cb.run.data())) return fail("mmdit patch cache: the predictor failed");
+        for (int j = 0; j < NC; ++j) {
+          if (!bc_valid[pcm_chunk_b[j]]) cb.run[j] = 1;
+          ++cb.gtot[pcm_chunk_g[j]];
+          if (cb.run[j]) ++cb.gask[pcm_chunk_g[j]];
+        }
+      }
+      bool any = false;
+      for (int g = 0; g < MX_MAX_SEGS; ++g) { cb.gany[g] = cb.gask[g] > 0; any = any || cb.gany[g]; pcm_asked += cb.gask[g]; pcm_total += cb.gtot[g]; }
+      state_copy(kImage, x, cb.in, 0, nullptr, nullptr, 0);                  // the cached input is always the latest one (cache_manager.py:183)
+      if (!any) {                                                             // SD3Transformer.py:219-228: both streams from the block's caches
+        state_copy(kImage, x, cb.out, 1, nullptr, nullptr, 0);
+        if (!last) state_copy(kText, ctx, cb.octx, 1, nullptr, nullptr, 0);
+        return false;
+      }
+      blocks_run |= 1ull << i;
+      cb.act_img.clear(); cb.act_ctx.clear();
+      for (int g = 0; g < ng; ++g) if (cb.gany[g]) for (int k = 0; k < gB[g]; ++k) {
+        const int bb = gb0[g] + k;
+        cb.act_img.push_back(mx::PcRange{pcm_img[bb].row0, image.len[g], pcm_img[bb].slot, 0});
+        cb.act_ctx.push_back(mx::PcRange{(long long)bb * Lt, Lt, pcm_img[bb].slot, 0});
+      }
+      cb.d_act_img = upload(cb.act_img, 0);
+      cb.d_act_ctx = upload(cb.act_ctx, 1);
+      return ok();
+    };
+    // attn2's renewal (attention.py:303-325): a group whose asking ratio is <= 1/16 renews its asking chunks only; the others renew every chunk
+    auto attn2_ranges = [&] {
+      std::vector<mx::PcRange> v;
+      for (int g = 0; g < ng; ++g) if (cb.gany[g]) {
+        const bool sparse = cb.gask[g] * 16 <= cb.gtot[g];
+        if (!sparse) { for (int k = 0; k < gB[g]; ++k) { const int bb = gb0[g] + k; v.push_back(mx::PcRange{pcm_img[bb].row0, image.len[g], pcm_img[bb].slot, 0}); } }
+        else for (int j = 0; j < pcm_nc; ++j) if (pcm_chunk_g[j] == g && cb.run[j]) v.push_back(pcm_chunks[j]);
+      }
+      return v;
+    };
+    // HOW AN ATTENTION PROJECTION'S RESULT REACHES ITS STREAM t (x or ctx): t += gate * (o W^T + bias).  Exact: the gated residual in the GEMM's
+    // epilogue.  Chunk cache: the active groups' rows are materialised without gate or residual (what attn.output / attn.encoder_output
+    // cache, attention.py:407-415), range-copied into the state region, and every row -- fresh or cached -- comes back through the gated copy.
+    // ranges(): the rows to renew, asked for after the GEMM has been issued.
+    auto project = [&](Linear l, const float* gate, char* reg, auto&& ranges) {
+      if (!pcm) { linear(l.plus(l.c, d).gated(gate, ntot)); return; }
+      const bool img = l.stream == kImage;
+      void* t = l.c;
+      l.c = img ? pcm_ti : pcm_tc;
+      linear(l.only(cb.gany));
+      const std::pair<const mx::PcRange*, size_t> r = ranges();
+      if (ok() && mx::launch_pc_range_copy(stream, l.c, reg, img ? row_i : row_c, d, r.first, (int)r.second, 0, img ? maxL * d : row_c)) fail(mx_last_error());
+      state_copy(l.stream, t, reg, 1, gate, t, 1);
+    };
+
     for (int i = 0; i < c.num_layers && ok(); ++i) {
       const std::string b = "transformer_blocks." + std::to_string(i);
       const bool dual = c.dual_attention[i] != 0, last = i == c.num_layers - 1;
-      if (pcm) {
-        const long Lmax = (long)(pcm_maxh / ps) * (pcm_maxw / ps);
-        const long row_i = Lmax * d, row_c = (long)Lt * d;
-        auto region = [&](long row_elems) { char* r = pcm_top; pcm_top += ((size_t)row_elems * pcm_slots * 2 + 255) & ~(size_t)255; return r; };
-        char* r_in = region(row_i); char* r_out = region(row_i); char* r_octx = last ? nullptr : region(row_c);
-        char* r_a = region(row_i); char* r_ae = last ? nullptr : region(row_c); char* r_a2 = dual ? region(row_i) : nullptr;
-        if (dry) continue;
-        if ((size_t)(pcm_top - (char*)bc->state) > bc->state_bytes) { fail("mmdit patch cache: state buffer too small (mx_mmdit_patch_cache_bytes)"); break; }
-        long maxL = 0; for (int g = 0; g < ng; ++g) maxL = std::max<long>(maxL, gL[g]);
-        auto img_copy = [&](void* t, char* reg, int to_batch, const float* vec, const void* res, int gate) {
-          if (ok() && mx::launch_pc_image_copy(stream, t, reg, pcm_dimg, B, 0, d, row_i, to_batch, vec, ntot, res, maxL * d, gate)) fail(mx_last_error()); };
-        auto ctx_copy = [&](void* t, char* reg, int to_batch, const float* vec, const void* res, int gate) {
-          if (ok() && mx::launch_pc_image_copy(stream, t, reg, pcm_dctx, B, 0, d, row_c, to_batch, vec, ntot, res, (long)Lt * d, gate)) fail(mx_last_error()); };
-        // ---- decision, per chunk ----
-        const int NC = pcm_nc;
-        if (bc_any_valid && mx::launch_pc_range_sq_diff(stream, x, r_in, row_i, d, pcm_dchunks, NC, pcm_dpart)) { fail(mx_last_error()); break; }
-        std::vector<unsigned char> run(NC, 1);
-        bool gany[MX_MAX_SEGS] = {false, false, false, false};
-        int gask[MX_MAX_SEGS] = {0, 0, 0, 0}, gtot[MX_MAX_SEGS] = {0, 0, 0, 0};
-        // THE DECISION -- the one place the two modes differ: it leaves run[], gask[] and gtot[]
-        if (bc_dev) {
-          // on the device (mx_block_cache.dev_down): one launch, one record read back (patch_cache.hip pc_decide_kernel; skip_decide.h)
-          mx_skip_decide_args a{};
-          a.forest = bc->dev_down; a.n_in = 1; a.kind = 1; a.units = pcm_dchunks; a.unit_sample = bc_skip.unit_sample; a.partial = pcm_dpart;
-          a.part_len[0] = 64; a.part_elems[0] = (double)d;
-          const unsigned char* flags = nullptr;
-          const int32_t* rec = bc_dev_decide(a, i, true, &flags);
-          if (!rec) break;
-          run.assign(flags, flags + NC);
-          for (int g = 0; g < MX_MAX_SEGS; ++g) { gask[g] = rec[MX_SKIP_REC_GASK + g]; gtot[g] = rec[MX_SKIP_REC_GTOT + g]; }
-        } else {
-          // on the host: the partial sums come back and the caller's predictor answers
-          std::vector<float> mse(NC, MX_MSE_UNCACHED);
-          if (bc_any_valid) {
-            std::vector<double> hp((size_t)NC * 64);
-            if (hipMemcpyAsync(hp.data(), pcm_dpart, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) { fail("mmdit patch cache: reading the input differences failed"); break; }
-            for (int j = 0; j < NC; ++j) {
-              if (!bc_valid[pcm_chunk_b[j]]) continue;
-              double t = 0.0;
-              for (int k = 0; k < 64; ++k) t += hp[(size_t)j * 64 + k];
-              mse[j] = (float)(t / ((double)pcm_chunks[j].rows * d));
-            }
-          }
-          std::vector<float> tpp(NC);
-          for (int j = 0; j < NC; ++j) tpp[j] = h_timesteps[pcm_chunk_b[j]];
-          if (bc->predict(bc->ctx, i, 0, NC, 1, tpp.data(), mse.data(), run.data())) { fail("mmdit patch cache: the predictor failed"); break; }
-          for (int j = 0; j < NC; ++j) {
-            if (!bc_valid[pcm_chunk_b[j]]) run[j] = 1;
-            ++gtot[pcm_chunk_g[j]];
-            if (run[j]) ++gask[pcm_chunk_g[j]];
-          }
-        }
-        bool any = false;
-        for (int g = 0; g < MX_MAX_SEGS; ++g) { gany[g] = gask[g] > 0; any = any || gany[g]; pcm_asked += gask[g]; pcm_total += gtot[g]; }
-        img_copy(x, r_in, 0, nullptr, nullptr, 0);                           // the cached input is always the latest one (cache_manager.py:183)
-        if (!any) {                                                           // SD3Transformer.py:219-228: both streams from the block's caches
-          img_copy(x, r_out, 1, nullptr, nullptr, 0);
-          if (!last) ctx_copy(ctx, r_octx, 1, nullptr, nullptr, 0);
-          continue;
-        }
-        blocks_run |= 1ull << i;
-        const float* mi = mod + off_img[i];
-        const float* mc = mod + off_ctx[i];
-        // ranges of the samples of the active groups (image rows / text rows), uploaded per use
-        auto upload = [&](const std::vector<mx::PcRange>& v, int slot) -> const mx::PcRange* {
-          mx::PcRange* dst = pcm_dtmp + (size_t)slot * pcm_ncmax();
-          if (!ok() || v.empty()) return dst;
-          pcm_sent.push_back(v);                // (advisor, round 4: the loop-local table died before the asynchronous copy had to have read it)
-          if (hipMemcpyAsync(dst, pcm_sent.back().data(), v.size() * sizeof(mx::PcRange), hipMemcpyHostToDevice, stream) != hipSuccess)
-            fail("mmdit patch cache: sending a range table failed");
-          return dst;
-        };
-        std::vector<mx::PcRange> act_img, act_ctx;
-        for (int g = 0; g < ng; ++g) if (gany[g]) for (int k = 0; k < gB[g]; ++k) {
-          const int bb = gb0[g] + k;
-          act_img.push_back(mx::PcRange{pcm_img[bb].row0, gL[g], pcm_img[bb].slot, 0});
-          act_ctx.push_back(mx::PcRange{(long long)bb * Lt, Lt, pcm_img[bb].slot, 0});
-        }
-        const mx::PcRange* d_act_img = upload(act_img, 0);
-        const mx::PcRange* d_act_ctx = upload(act_ctx, 1);
-        lnmod(x, xin, dual ? x2in : nullptr, mi + d, mi, dual ? mi + 7 * d : nullptr, dual ? mi + 6 * d : nullptr, ntot, MI, d, L, true);
-        if (last) lnmod(ctx, cin, nullptr, mc, mc + d, nullptr, nullptr, ntot, MT, d, Lt);
-        else lnmod(ctx, cin, nullptr, mc + d, mc, nullptr, nullptr, ntot, MT, d, Lt);
-        // the q | k | v projections of both streams: all groups (the reference projects every chunk, attention.py:257-285)
-        qkv(xin, b + ".attn.to_qkv", b + ".attn.norm_q.weight", b + ".attn.norm_k.weight", qk_j, vt_j, ldvt_j, MI, d, L, Lj, 0, [&](int g, mx_gemm_seg& q) {
-          q.a = xin + r0[g] * d; q.c = qk_j + jr0[g] * 2 * d; q.vt = vt_j + vj0[g]; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; q.ldvt = gldj[g];
-          q.c_batch_rows = gLj[g]; q.c_row_off = 0; });
-        qkv(cin, b + ".attn.add_qkv", b + ".attn.norm_added_q.weight", b + ".attn.norm_added_k.weight", qk_j, vt_j, ldvt_j, MT, d, Lt, Lj, L, [&](int g, mx_gemm_seg& q) {
-          q.a = cin + (long)gb0[g] * Lt * d; q.c = qk_j + jr0[g] * 2 * d; q.vt = vt_j + vj0[g]; q.M = gB[g] * Lt; q.rows_per_batch = Lt; q.ldvt = gldj[g];
-          q.c_batch_rows = gLj[g]; q.c_row_off = gL[g]; });
-        auto attention_active = [&](bf16_t* qk, bf16_t* vt, bf16_t* o, const long* row0s, const long* vt0s, const int* Ls, const int* lds) {
-          mx_attn_problem pr[MX_MAX_SEGS];
-          int n = 0;
-          for (int g = 0; g < ng; ++g) if (gany[g]) {
-            pr[n].q = qk + row0s[g] * 2 * d; pr[n].k = qk + row0s[g] * 2 * d + d; pr[n].vt = vt + vt0s[g]; pr[n].o = o + row0s[g] * d;
-            pr[n].vt_batch_stride = (int64_t)d * lds[g]; pr[n].B = gB[g]; pr[n].Lq = Ls[g]; pr[n].Lk = Ls[g]; pr[n].ldvt = lds[g];
-            ++n;
-          }
-          if (ok() && n && mx_attention_prescaled_grouped(stream, pr, n, 2 * d, 2 * d, d, heads)) fail(std::string("attention: ") + mx_last_error());
-        };
-        attention_active(qk_j, vt_j, o_j, jr0, vj0, gLj, gldj);
-        act = gany;
-        // to_out of the active groups' image rows, no gate / residual: what attn.output caches (attention.py:407-415)
-        linear(o_j, d, b + ".attn.to_out.0", pcm_ti, d, MI, d, d, 0, nullptr, 0, nullptr, 0, L, Lj, 0, [&](int g, mx_gemm_seg& q) {
-          q.a = o_j + jr0[g] * d; q.c = pcm_ti + r0[g] * d; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; q.a_batch_rows = gLj[g]; q.a_row_off = 0; });
-        act = nullptr;
-        if (ok() && mx::launch_pc_range_copy(stream, pcm_ti, r_a, row_i, d, d_act_img, (int)act_img.size(), 0, maxL * d)) fail(mx_last_error());
-        img_copy(x, r_a, 1, mi + 2 * d, x, 1);                                 // x += gate_msa * attn.output (fresh or cached)   (transformer.py:344-345)
-        if (dual) {
-          qkv(x2in, b + ".attn2.to_qkv", b + ".attn2.norm_q.weight", b + ".attn2.norm_k.weight", qk_i, vt_i, ldvt_i, MI, d, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-            q.a = x2in + r0[g] * d; q.c = qk_i + r0[g] * 2 * d; q.vt = vt_i + vi0[g]; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; q.ldvt = gldi[g]; });
-          attention_active(qk_i, vt_i, o_i, r0, vi0, gL, gldi);
-          act = gany;
-          linear(o_i, d, b + ".attn2.to_out.0", pcm_ti, d, MI, d, d, 0, nullptr, 0, nullptr, 0, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-            q.a = o_i + r0[g] * d; q.c = pcm_ti + r0[g] * d; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; });
-          act = nullptr;
-          // a group whose asking ratio is <= 1/16 renews its asking chunks only (attention.py:303-325); the others renew every chunk
-          std::vector<mx::PcRange> rng2;
-          for (int g = 0; g < ng; ++g) if (gany[g]) {
-            const bool sparse = gask[g] * 16 <= gtot[g];
-            if (!sparse) { for (int k = 0; k < gB[g]; ++k) { const int bb = gb0[g] + k; rng2.push_back(mx::PcRange{pcm_img[bb].row0, gL[g], pcm_img[bb].slot, 0}); } }
-            else for (int j = 0; j < NC; ++j) if (pcm_chunk_g[j] == g && run[j]) rng2.push_back(pcm_chunks[j]);
-          }
-          const mx::PcRange* d_rng2 = upload(rng2, 2);
-          if (ok() && mx::launch_pc_range_copy(stream, pcm_ti, r_a2, row_i, d, d_rng2, (int)rng2.size(), 0, maxL * d)) fail(mx_last_error());
-          img_copy(x, r_a2, 1, mi + 8 * d, x, 1);
-        }
-        lnmod(x, xin, nullptr, mi + 4 * d, mi + 3 * d, nullptr, nullptr, ntot, MI, d, L, true);
-        linear(xin, d, b + ".ff.net.0.proj", ff, 4 * d, MI, 4 * d, d, MX_EPI_GELU_TANH);
-        linear(ff, 4 * d, b + ".ff.net.2", x, d, MI, d, 4 * d, 0, x, d, mi + 5 * d, ntot, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-          q.a = ff + r0[g] * 4 * d; q.c = x + r0[g] * d; q.residual = x + r0[g] * d; q.gate = mi + 5 * d + (long)gb0[g] * ntot; q.M = gB[g] * gL[g];
-          q.rows_per_batch = gL[g]; });
-        if (!last) {
-          act = gany;
-          linear(o_j, d, b + ".attn.to_add_out", pcm_tc, d, MT, d, d, 0, nullptr, 0, nullptr, 0, Lt, Lj, L, [&](int g, mx_gemm_seg& q) {
-            q.a = o_j + jr0[g] * d; q.c = pcm_tc + (long)gb0[g] * Lt * d; q.M = gB[g] * Lt; q.rows_per_batch = Lt; q.a_batch_rows = gLj[g]; q.a_row_off = gL[g]; });
-          act = nullptr;
-          if (ok() && mx::launch_pc_range_copy(stream, pcm_tc, r_ae, row_c, d, d_act_ctx, (int)act_ctx.size(), 0, (long)Lt * d)) fail(mx_last_error());
-          ctx_copy(ctx, r_ae, 1, mc + 2 * d, ctx, 1);                          // ctx += c_gate_msa * attn.encoder_output (fresh or cached)
-          lnmod(ctx, cin, nullptr, mc + 4 * d, mc + 3 * d, nullptr, nullptr, ntot, MT, d, Lt);
-          linear(cin, d, b + ".ff_context.net.0.proj", ffc, 4 * d, MT, 4 * d, d, MX_EPI_GELU_TANH);
-          linear(ffc, 4 * d, b + ".ff_context.net.2", ctx, d, MT, d, 4 * d, 0, ctx, d, mc + 5 * d, ntot, Lt);
-        }
-        img_copy(x, r_out, 0, nullptr, nullptr, 0);
-        if (!last) ctx_copy(ctx, r_octx, 0, nullptr, nullptr, 0);
-        continue;
-      }
-      const bool cached = bc != nullptr && !dry;
-      const bool ran = cached ? decide(i) : true;
+      // WHAT BRACKETS A BLOCK: nothing; the per-sample cache's decide / after around a muted walk; the chunk cache's pcm_open and output stores
+      const bool cached = bc != nullptr && !pcm && !dry;
+      bool ran = true;
+      if (pcm) { if (!pcm_open(i, dual, last)) continue; }
+      else if (cached) ran = decide(i);
       if (!ok()) break;
       mute = !ran;
+      const bool* act = pcm ? cb.gany : nullptr;
       const float* mi = mod + off_img[i];   // chunks: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp[, shift2, scale2, gate2]
       const float* mc = mod + off_ctx[i];
       // AdaLN-Zero(-X) on the image stream, AdaLN-Zero / -continuous on the context stream (transformer.py:316-328)
-      lnmod(x, xin, dual ? x2in : nullptr, mi + d, mi, dual ? mi + 7 * d : nullptr, dual ? mi + 6 * d : nullptr, ntot, MI, d, L, true);
-      if (last) lnmod(ctx, cin, nullptr, mc, mc + d, nullptr, nullptr, ntot, MT, d, Lt);        // continuous: (scale, shift)
-      else lnmod(ctx, cin, nullptr, mc + d, mc, nullptr, nullptr, ntot, MT, d, Lt);
+      lnmod(kImage, x, xin, dual ? x2in : nullptr, mi + d, mi, dual ? mi + 7 * d : nullptr, dual ? mi + 6 * d : nullptr, ntot);
+      if (last) lnmod(kText, ctx, cin, nullptr, mc, mc + d, nullptr, nullptr, ntot);        // continuous: (scale, shift)
+      else lnmod(kText, ctx, cin, nullptr, mc + d, mc, nullptr, nullptr, ntot);
       // joint attention (attention.py:256-372): image rows first, then text rows
-      // (mixed batch: group g's image rows go to rows [0, L_g) of its samples' joint sequences, the text rows behind them)
-      qkv(xin, b + ".attn.to_qkv", b + ".attn.norm_q.weight", b + ".attn.norm_k.weight", qk_j, vt_j, ldvt_j, MI, d, L, Lj, 0, [&](int g, mx_gemm_seg& q) {
-        q.a = xin + r0[g] * d; q.c = qk_j + jr0[g] * 2 * d; q.vt = vt_j + vj0[g]; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; q.ldvt = gldj[g];
-        q.c_batch_rows = gLj[g]; q.c_row_off = 0; });
-      qkv(cin, b + ".attn.add_qkv", b + ".attn.norm_added_q.weight", b + ".attn.norm_added_k.weight", qk_j, vt_j, ldvt_j, MT, d, Lt, Lj, L, [&](int g, mx_gemm_seg& q) {
-        q.a = cin + (long)gb0[g] * Lt * d; q.c = qk_j + jr0[g] * 2 * d; q.vt = vt_j + vj0[g]; q.M = gB[g] * Lt; q.rows_per_batch = Lt; q.ldvt = gldj[g];
-        q.c_batch_rows = gLj[g]; q.c_row_off = gL[g]; });
-      if (is_pp()) {
-        gather_kv(qk_j, vt_j, ldvt_j, Lt, ldvt_jt);
-        attention_qk(qk_j, k_all, d, vt_all, ldvt_jt, o_j, heads, Lj, Ljt);
-      } else if (ng > 1) {
-        mx_attn_problem pr[MX_MAX_SEGS];
-        for (int g = 0; g < ng; ++g) {
-          pr[g].q = qk_j + jr0[g] * 2 * d; pr[g].k = qk_j + jr0[g] * 2 * d + d; pr[g].vt = vt_j + vj0[g]; pr[g].o = o_j + jr0[g] * d;
-          pr[g].vt_batch_stride = (int64_t)d * gldj[g]; pr[g].B = gB[g]; pr[g].Lq = gLj[g]; pr[g].Lk = gLj[g]; pr[g].ldvt = gldj[g];
-        }
-        if (ok() && !quiet() && mx_attention_prescaled_grouped(stream, pr, ng, 2 * d, 2 * d, d, heads)) fail(std::string("attention: ") + mx_last_error());
-      } else
-      attention(qk_j, d, vt_j, ldvt_j, o_j, heads, Lj);
+      // (mixed batch: group g's image rows go to rows [0, L_g) of its samples' joint sequences, the text rows behind them; the chunk cache
+      // projects every chunk, attention.py:257-285)
+      qkv(xin, kImage, b + ".attn.to_qkv", b + ".attn.norm_", joint);
+      qkv(cin, kText, b + ".attn.add_qkv", b + ".attn.norm_added_", joint);
+      attend(joint, act);
       // x += gate_msa * to_out(attn[:, :L])                                   (transformer.py:344-345)
-      linear(o_j, d, b + ".attn.to_out.0", x, d, MI, d, d, 0, x, d, mi + 2 * d, ntot, L, Lj, 0, [&](int g, mx_gemm_seg& q) {
-        q.a = o_j + jr0[g] * d; q.c = x + r0[g] * d; q.residual = x + r0[g] * d; q.gate = mi + 2 * d + (long)gb0[g] * ntot; q.M = gB[g] * gL[g];
-        q.rows_per_batch = gL[g]; q.a_batch_rows = gLj[g]; q.a_row_off = 0; });
+      project(Linear{joint.o, d, b + ".attn.to_out.0", x, d, MI, d, d}.rows(kImage).from(joint), mi + 2 * d, cb.a,
+              [&] { return std::make_pair(cb.d_act_img, cb.act_img.size()); });
       if (dual) {                                                             // attn2: image-only self-attention (:347-357)
-        qkv(x2in, b + ".attn2.to_qkv", b + ".attn2.norm_q.weight", b + ".attn2.norm_k.weight", qk_i, vt_i, ldvt_i, MI, d, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-          q.a = x2in + r0[g] * d; q.c = qk_i + r0[g] * 2 * d; q.vt = vt_i + vi0[g]; q.M = gB[g] * gL[g]; q.rows_per_batch = gL[g]; q.ldvt = gldi[g]; });
-        if (is_pp()) {
-          gather_kv(qk_i, vt_i, ldvt_i, 0, ldvt_it);
-          attention_qk(qk_i, k_all, d, vt_all, ldvt_it, o_i, heads, L, Ltot);
-        } else if (ng > 1) {
-          mx_attn_problem pr[MX_MAX_SEGS];
-          for (int g = 0; g < ng; ++g) {
-            pr[g].q = qk_i + r0[g] * 2 * d; pr[g].k = qk_i + r0[g] * 2 * d + d; pr[g].vt = vt_i + vi0[g]; pr[g].o = o_i + r0[g] * d;
-            pr[g].vt_batch_stride = (int64_t)d * gldi[g]; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = gL[g]; pr[g].ldvt = gldi[g];
-          }
-          if (ok() && !quiet() && mx_attention_prescaled_grouped(stream, pr, ng, 2 * d, 2 * d, d, heads)) fail(std::string("attention: ") + mx_last_error());
-        } else
-        attention(qk_i, d, vt_i, ldvt_i, o_i, heads, L);
-        linear(o_i, d, b + ".attn2.to_out.0", x, d, MI, d, d, 0, x, d, mi + 8 * d, ntot, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-          q.a = o_i + r0[g] * d; q.c = x + r0[g] * d; q.residual = x + r0[g] * d; q.gate = mi + 8 * d + (long)gb0[g] * ntot; q.M = gB[g] * gL[g];
-          q.rows_per_batch = gL[g]; });
+        qkv(x2in, kImage, b + ".attn2.to_qkv", b + ".attn2.norm_", image);
+        attend(image, act);
+        project(Linear{image.o, d, b + ".attn2.to_out.0", x, d, MI, d, d}.rows(kImage), mi + 8 * d, cb.a2,
+                [&] { const std::vector<mx::PcRange> v = attn2_ranges(); return std::make_pair(upload(v, 2), v.size()); });
       }
       // x += gate_mlp * ff(LN(x) * (1 + scale_mlp) + shift_mlp)               (:359-366)
-      lnmod(x, xin, nullptr, mi + 4 * d, mi + 3 * d, nullptr, nullptr, ntot, MI, d, L, true);
-      linear(xin, d, b + ".ff.net.0.proj", ff, 4 * d, MI, 4 * d, d, MX_EPI_GELU_TANH);
-      linear(ff, 4 * d, b + ".ff.net.2", x, d, MI, d, 4 * d, 0, x, d, mi + 5 * d, ntot, L, 0, 0, [&](int g, mx_gemm_seg& q) {
-        q.a = ff + r0[g] * 4 * d; q.c = x + r0[g] * d; q.residual = x + r0[g] * d; q.gate = mi + 5 * d + (long)gb0[g] * ntot; q.M = gB[g] * gL[g];
-        q.rows_per_batch = gL[g]; });
+      lnmod(kImage, x, xin, nullptr, mi + 4 * d, mi + 3 * d, nullptr, nullptr, ntot);
+      linear(Linear{xin, d, b + ".ff.net.0.proj", ff, 4 * d, MI, 4 * d, d}.epilogue(MX_EPI_GELU_TANH));
+      linear(Linear{ff, 4 * d, b + ".ff.net.2", x, d, MI, d, 4 * d}.rows(kImage).plus(x, d).gated(mi + 5 * d, ntot));
       if (!last) {                                                            // context stream (:371-386)
-        linear(o_j, d, b + ".attn.to_add_out", ctx, d, MT, d, d, 0, ctx, d, mc + 2 * d, ntot, Lt, Lj, L, [&](int g, mx_gemm_seg& q) {
-          q.a = o_j + jr0[g] * d; q.c = ctx + (long)gb0[g] * Lt * d; q.residual = ctx + (long)gb0[g] * Lt * d; q.gate = mc + 2 * d + (long)gb0[g] * ntot;
-          q.M = gB[g] * Lt; q.rows_per_batch = Lt; q.a_batch_rows = gLj[g]; q.a_row_off = gL[g]; });
-        lnmod(ctx, cin, nullptr, mc + 4 * d, mc + 3 * d, nullptr, nullptr, ntot, MT, d, Lt);
-        linear(cin, d, b + ".ff_context.net.0.proj", ffc, 4 * d, MT, 4 * d, d, MX_EPI_GELU_TANH);
-        linear(ffc, 4 * d, b + ".ff_context.net.2", ctx, d, MT, d, 4 * d, 0, ctx, d, mc + 5 * d, ntot, Lt);
+        project(Linear{joint.o, d, b + ".attn.to_add_out", ctx, d, MT, d, d}.rows(kText).from(joint), mc + 2 * d, cb.ae,
+                [&] { return std::make_pair(cb.d_act_ctx, cb.act_ctx.size()); });
+        lnmod(kText, ctx, cin, nullptr, mc + 4 * d, mc + 3 * d, nullptr, nullptr, ntot);
+        linear(Linear{cin, d, b + ".ff_context.net.0.proj", ffc, 4 * d, MT, 4 * d, d}.epilogue(MX_EPI_GELU_TANH));
+        linear(Linear{ffc, 4 * d, b + ".ff_context.net.2", ctx, d, MT, d, 4 * d}.rows(kText).plus(ctx, d).gated(mc + 5 * d, ntot));
         dump(b + ".context", ctx, (size_t)MT * d);
       }
       dump(b, x, (size_t)MI * d);
       mute = false;
       if (cached && ok()) after(i, ran, last);
+      if (pcm) {
+        state_copy(kImage, x, cb.out, 0, nullptr, nullptr, 0);
+        if (!last) state_copy(kText, ctx, cb.octx, 0, nullptr, nullptr, 0);
+      }
     }
-    if (pcm) bc_bytes = (size_t)(pcm_top - (dry ? (char*)(uintptr_t)0x1000 : (char*)bc->state));
+    if (pcm) bc_bytes = (size_t)(pcm_top - pcm_base());
     // ---- norm_out (AdaLN-continuous) + proj_out + unpatchify (SD3Transformer.py:238-259) ----
-    lnmod(x, xin, nullptr, mod + off_out, mod + off_out + d, nullptr, nullptr, ntot, MI, d, L, true);
+    lnmod(kImage, x, xin, nullptr, mod + off_out, mod + off_out + d, nullptr, nullptr, ntot);
     const int No = ps * ps * c.out_channels;
     bf16_t* o = alloc<bf16_t>((size_t)MI * No);
-    linear(xin, d, "proj_out", o, No, MI, No, d);
+    linear(Linear{xin, d, "proj_out", o, No, MI, No, d});
     dump("proj_out", o, (size_t)MI * No);
     for (int g = 0; g < ng && ok() && !dry; ++g)
-      if (mx::launch_unpatchify(stream, o + r0[g] * No, g_out[g], io_dtype, gB[g], c.out_channels, gH[g], gW[g], ps, No)) fail(mx_last_error());
+      if (mx::launch_unpatchify(stream, o + image.row0[g] * No, g_out[g], io_dtype, gB[g], c.out_channels, gH[g], gW[g], ps, No)) fail(mx_last_error());
     if (stage && !dry && ok() && !stage_hit) fail(std::string("unknown stage '") + stage + "'");
     // the range tables of the patch cache were copied from pcm_sent asynchronously: they are released only once the stream has read them
     if (!pcm_sent.empty()) { if (!dry && hipStreamSynchronize(stream) != hipSuccess) fail("mmdit patch cache: final synchronisation failed"); pcm_sent.clear(); }

@@ -6,7 +6,8 @@
 //                     the gemm / conv wrapper and the stage dump of the trace entry points.  Copyable (the recording walk copies a plan);
 //   * Groups       -- the resolution groups of a forward (one unless the batch is mixed);
 //   * DenoiserPlan -- PlanBase + Groups + the patch-parallel exchange + the per-sample block-cache bookkeeping shared by the cached entry
-//                     points of the two denoisers (which samples hold state, the slot table, the timesteps, rows in / out of the state);
+//                     points of the two denoisers (which samples hold state, the slot table, the timesteps, rows in / out of the state, the
+//                     comparison partial sums read back as per-row MSEs);
 //   * ForwardCall  -- one forward of a denoiser as named fields, and run_forward, the driver both denoisers share: generic checks -> the
 //                     model's checks -> plan set-up -> recording walk of a stale patch-parallel layout -> eager run or hipGraph replay.
 #pragma once
@@ -199,6 +200,24 @@ struct DenoiserPlan : PlanBase, Groups {
     if (bc_keyed) bc->cached_valid = 0;
     set_error(who + ": reading the timesteps failed");
     return 1;
+  }
+  // Partial sums -> host MSE: reads back `n` rows of `len` doubles from the device buffer `part`, synchronises, and folds each row in index
+  // order -- a plain left-to-right double sum: skip_decide.h and the device decision are bit-compared with it -- into
+  // mse[at] = float(sum / elems).  where(r) = {sample, elems, at} of row r; a row whose sample holds no state is skipped, so its entry
+  // keeps what the caller put there (MX_MSE_UNCACHED).  `msg`: the caller's error text.
+  struct MseRow { int sample; double elems; size_t at; };
+  template <class Where> bool bc_read_mse(const double* part, size_t n, int len, float* mse, const char* msg, Where where) {
+    std::vector<double> hp(n * len);
+    if (hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) return fail(msg);
+    for (size_t r = 0; r < n; ++r) {
+      const MseRow w = where(r);
+      if (!bc_valid[w.sample]) continue;
+      double t = 0.0;
+      for (int k = 0; k < len; ++k) t += hp[r * len + k];
+      mse[w.at] = (float)(t / w.elems);
+    }
+    return true;
   }
   // ---- the decision on the device (mx_block_cache.dev_down; the patch / chunk unit: mx_*_forward_cached_mixed) ----
   // The host keeps what sizes the following launches: per block it reads back ONE record (n_ask, first[], the group counts; the flags when

@@ -1046,16 +1046,10 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         double* part = (double*)bc->state;                       // the head of the state is scratch (bc_scratch_bytes)
         for (int f = 0; f < nf && ok(); ++f)
           if (mx::launch_sq_diff_partial(stream, ins[f].p, in_cache[f], (long)ins[f].per_sample, B, part + (size_t)f * B * 64, bc_dslot)) fail(mx_last_error());
-        std::vector<double> hp((size_t)nf * B * 64);
-        if (ok() && (hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                     hipStreamSynchronize(stream) != hipSuccess)) fail("block cache: reading the input differences failed");
-        for (int f = 0; f < nf; ++f)
-          for (int b = 0; b < B; ++b) {
-            if (!bc_valid[b]) continue;                          // nothing cached for this sample: the marker stays (cache_manager.py:110,139)
-            double t = 0.0;
-            for (int k = 0; k < 64; ++k) t += hp[((size_t)f * B + b) * 64 + k];
-            mse[(size_t)b * nf + f] = (float)(t / (double)ins[f].per_sample);
-          }
+        // feature f's B rows one after the other; a sample with nothing cached keeps the marker (cache_manager.py:110,139)
+        if (ok()) bc_read_mse(part, (size_t)nf * B, 64, mse.data(), "block cache: reading the input differences failed", [&](size_t r) {
+          const size_t f = r / B, b = r % B;
+          return MseRow{(int)b, (double)ins[f].per_sample, b * nf + f}; });
       }
       if (!ok()) return;
       std::vector<unsigned char> run(B, 1);
@@ -1091,16 +1085,10 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         if (!ok()) return;
         if (any && bc_all_valid && bc->observe && o.p == x) {     // how far the block's output moved since its last run (fitting labels)
           double* part = (double*)bc->state;
-          std::vector<double> hp((size_t)B * 64);
           std::vector<float> om(B);
           if (mx::launch_sq_diff_partial(stream, o.p, oc, (long)o.per_sample, B, part, bc_dslot)) { fail(mx_last_error()); return; }
-          if (hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-              hipStreamSynchronize(stream) != hipSuccess) { fail("block cache: reading the output differences failed"); return; }
-          for (int b = 0; b < B; ++b) {
-            double t = 0.0;
-            for (int k = 0; k < 64; ++k) t += hp[(size_t)b * 64 + k];
-            om[b] = (float)(t / (double)o.per_sample);
-          }
+          if (!bc_read_mse(part, B, 64, om.data(), "block cache: reading the output differences failed",
+                           [&](size_t b) { return MseRow{(int)b, (double)o.per_sample, b}; })) return;
           bc->observe(bc->ctx, idx, B, om.data());
         }
         if (any && partial && mx::launch_copy_rows(stream, o.p, oc, o.per_sample * 2, B, bc_dsel(), 0)) { fail(mx_last_error()); return; }

@@ -201,6 +201,24 @@ int main() {
     REQUIRE(say("mx_mmdit_workspace_bytes_cached_mixed(1 x 16, 2 x 32; 37, 0)", mx_mmdit_workspace_bytes_cached_mixed(t, tg, 2, 37, 0)) == 0);
     REQUIRE(say("mx_mmdit_workspace_bytes_cached_mixed(1 x 16, 2 x 32; 37, 32)", mx_mmdit_workspace_bytes_cached_mixed(t, tg, 2, 37, 32)) == 0);  // 16 is not a multiple of 32
     REQUIRE(say("mx_mmdit_workspace_bytes_cached_mixed(no groups)", mx_mmdit_workspace_bytes_cached_mixed(t, nullptr, 0, 37, 8)) == 0);
+    // three resolutions in one cached launch sequence with the state of its four requests, and the patch-parallel plan at 32 and 16 local tokens
+    mx_unet_group t3[3]; std::memset(t3, 0, sizeof(t3));
+    const int tres[3] = {16, 24, 32}, tb[3] = {1, 2, 1};
+    for (int i = 0; i < 3; ++i) { t3[i].batch = tb[i]; t3[i].H = t3[i].W = tres[i]; }
+    REQUIRE(say("mx_mmdit_workspace_bytes_cached_mixed(1 x 16, 2 x 24, 1 x 32; 37, 8)", mx_mmdit_workspace_bytes_cached_mixed(t, t3, 3, 37, 8)) > 0);
+    REQUIRE(say("mx_mmdit_workspace_bytes_mixed(1 x 16, 2 x 24, 1 x 32; 37)", mx_mmdit_workspace_bytes_mixed(t, t3, 3, 37)) > 0);
+    REQUIRE(say("mx_mmdit_patch_cache_bytes(4, 32, 32, 8, 37)", mx_mmdit_patch_cache_bytes(t, 4, 32, 32, 8, 37)) > 0);
+    for (int world : {2, 4}) {
+      const int hl = 16 / world;
+      const size_t ws = say(call("tiny mx_mmdit_workspace_bytes_pp(2, %d, 16, 37, %d)", hl, world), mx_mmdit_workspace_bytes_pp(t, 2, hl, 16, 37, world));
+      REQUIRE(ws > 0);
+      REQUIRE(say(call("tiny mx_mmdit_pp_state_bytes(2, %d, 16, 37, %d)", hl, world), mx_mmdit_pp_state_bytes(t, 2, hl, 16, 37, world)) > 0);
+      mx_pp_comm comm; comm.rank = world - 1; comm.world = world; comm.all_gather = count_gather; comm.ctx = nullptr;
+      begin_exchanges(ws);
+      REQUIRE(say(call("tiny mx_mmdit_pp_comm_plan(2, %d, 16, 37, rank %d of %d)", hl, world - 1, world), (size_t)mx_mmdit_pp_comm_plan(t, 2, hl, 16, 37, &comm)) == 0);
+      say_exchanges("tiny mx_mmdit_pp_comm_plan");
+      REQUIRE(n_exchanges > 0);
+    }
     mx_mmdit_destroy(t);
   }
 
