@@ -11,6 +11,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import lib as _lib
+from .model_slot import _grow_only
 from .weights import PackedWeights
 
 
@@ -111,16 +112,11 @@ class MxCLIPTextEncoder:
         b, l = ids.shape
         if l != self.cfg.max_position_embeddings:
             raise ValueError(f"ids must be padded to {self.cfg.max_position_embeddings} tokens")
-        need = self._lib.mx_clip_workspace_bytes(self._handle, b)
-        if need == 0:
-            raise _lib.MxError("mx_clip_workspace_bytes: " + self._lib.mx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = _grow_only(vars(self), "_ws", self._lib.mx_clip_workspace_bytes(self._handle, b), "mx_clip_workspace_bytes", self.device)
         hidden = torch.empty((b, l, self.cfg.hidden_size), dtype=torch.bfloat16, device=self.device)
         pooled = torch.empty((b, self.cfg.projection_dim), dtype=torch.float32, device=self.device) if self.cfg.projection_dim > 0 else None
         _lib.check(self._lib.mx_clip_encode(self._handle, _lib.current_stream(), ids.data_ptr(), hidden.data_ptr(),
-                                            pooled.data_ptr() if pooled is not None else None, b, self._ws.data_ptr(), self._ws.numel()), "mx_clip_encode")
+                                            pooled.data_ptr() if pooled is not None else None, b, ws.data_ptr(), ws.numel()), "mx_clip_encode")
         return hidden, pooled
 
 

@@ -26,7 +26,10 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import lib as _lib
-from .unet import MxUNet
+from .model_slot import _grow_only
+from .pipeline import SDXLDenoiser
+from .pipeline_sd3 import SD3Denoiser
+from .step_state import StepCache
 
 
 def split_rows(latents: torch.Tensor, rank: int, world: int) -> torch.Tensor:
@@ -125,6 +128,7 @@ class PatchParallelUNet:
     [2n, C, H, W] = [uncond... ; cond...] with 2n rows of every conditioning tensor, runs this rank's branch (n rows) on its row slab over its
     batch group, and gathers over the world; ``forward_gathered`` returns that gather as it lies.  A layout that does not split (no CFG,
     ``split_batch=False``, one rank) changes nothing."""
+    STALE_SYMBOL = "forward_pp_stale"      # the UNet's stale step is a symbol of its own, and it knows corrected_async_gn
 
     def __init__(self, unet, group=None, log: Optional[CommLog] = None, mode: str = "sync", warmup_steps: int = 4,
                  layout: Optional[CfgSplitLayout] = None):
@@ -159,6 +163,14 @@ class PatchParallelUNet:
         self._cb = _lib.ALLGATHER_FN(self._all_gather)     # keep the callback object alive
         self._err: Optional[BaseException] = None
 
+    def _gather_list(self, t: torch.Tensor, group, n: int) -> List[torch.Tensor]:
+        """``t`` of each of the ``n`` ranks of ``group`` (torch.distributed.all_gather), on t's device; through host memory when the backend is
+        gloo (the tests: gloo moves CPU tensors)"""
+        mine = t.cpu() if self.backend == "gloo" else t
+        parts = [torch.empty_like(mine) for _ in range(n)]
+        self.dist.all_gather(parts, mine, group=group)
+        return [p.to(t.device) for p in parts]
+
     # called from inside mx_unet_forward_pp (C -> Python through ctypes); returns 0 on success
     def _all_gather(self, _ctx, _stream, send, recv, nbytes) -> int:
         try:
@@ -168,11 +180,8 @@ class PatchParallelUNet:
                 self.log.calls.append((so, ro, nbytes))
             s = ws[so:so + nbytes]
             r = ws[ro:ro + nbytes * self.world]
-            if self.backend == "gloo":               # tests: through host memory (gloo moves CPU tensors)
-                host = s.cpu()
-                parts = [torch.empty_like(host) for _ in range(self.world)]
-                self.dist.all_gather(parts, host, group=self.group)
-                r.copy_(torch.cat(parts))
+            if self.backend == "gloo":
+                r.copy_(torch.cat(self._gather_list(s, self.group, self.world)))
             else:                                    # RCCL: device to device, ordered with the current stream by torch
                 self.dist.all_gather_into_tensor(r, s, group=self.group)
             return 0
@@ -191,11 +200,8 @@ class PatchParallelUNet:
                 self.log.calls.append((-1, off, nbytes))
             r = st[off:off + nbytes * self.world]
             own = r[self.rank * nbytes:(self.rank + 1) * nbytes]
-            if self.backend == "gloo":               # tests: through host memory, completes at once (a legal schedule of the async contract)
-                host = own.cpu()
-                parts = [torch.empty_like(host) for _ in range(self.world)]
-                self.dist.all_gather(parts, host, group=self.group)
-                r.copy_(torch.cat(parts))
+            if self.backend == "gloo":               # completes at once (a legal schedule of the async contract)
+                r.copy_(torch.cat(self._gather_list(own, self.group, self.world)))
             else:                                    # RCCL on a side stream: the compute stream runs on while the slots travel
                 cur = torch.cuda.current_stream()
                 if self._comm_stream is None:
@@ -239,42 +245,37 @@ class PatchParallelUNet:
         self.last_step_mode = mode
         return _lib.PPStale(self._state.data_ptr(), self._state.numel(), mode, corrected, self._cb_async)
 
-    def forward_local(self, latents_local: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
-                      text_embeds: torch.Tensor, time_ids: torch.Tensor) -> torch.Tensor:
+    def forward_local(self, latents_local: torch.Tensor, timestep: torch.Tensor, *cond: torch.Tensor) -> torch.Tensor:
+        """this rank's rows in, this rank's output rows out; ``cond``: the model's conditioning tensors (its COND) for the batch"""
         u = self.unet
         x = latents_local.contiguous()
         b, _c, hl, w = x.shape
-        dev = u.device
-        ctx_len = encoder_hidden_states.shape[1]
-        ts = timestep.to(device=dev, dtype=torch.float32).reshape(-1)
-        ts = (ts.expand(b) if ts.numel() == 1 else ts).contiguous()
-        ehs = encoder_hidden_states.to(device=dev, dtype=torch.bfloat16).contiguous()
-        te = text_embeds.to(device=dev, dtype=torch.bfloat16).contiguous()
-        ti = time_ids.to(device=dev, dtype=torch.float32).contiguous()
-        need = u._lib.mx_unet_workspace_bytes_pp(u._handle, b, hl, w, ctx_len, self.world)
-        if need == 0:
-            raise _lib.MxError("mx_unet_workspace_bytes_pp: " + u._lib.mx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty((b, u.cfg.out_channels, hl, w), dtype=x.dtype, device=dev)
+        ctx_len = cond[0].shape[1]
+        ts, *cond = u._conditioning(b, timestep, *cond)
+        shape = (b, hl, w, ctx_len, self.world)
+        ws = _grow_only(vars(self), "_ws", u._fn("workspace_bytes_pp")(u._handle, *shape), f"mx_{u.ABI}_workspace_bytes_pp", u.device)
+        out = torch.empty((b, u.cfg.out_channels, hl, w), dtype=x.dtype, device=u.device)
         comm = _lib.PPComm(self.rank, self.world, self._cb, None)
         self._err = None
-        if self.mode == "sync":
-            rc = u._lib.mx_unet_forward_pp(u._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), ts.data_ptr(),
-                                           ehs.data_ptr(), te.data_ptr(), ti.data_ptr(), out.data_ptr(), b, hl, w, ctx_len, C.byref(comm),
-                                           self._ws.data_ptr(), self._ws.numel())
-        else:
-            sneed = u._lib.mx_unet_pp_state_bytes(u._handle, b, hl, w, ctx_len, self.world)
+        stale = None
+        if self.mode != "sync":
+            sneed = u._fn("pp_state_bytes")(u._handle, *shape)
             if sneed == 0:
-                raise _lib.MxError("mx_unet_pp_state_bytes: " + u._lib.mx_last_error().decode())
-            stale = self._stale_desc(sneed, ("unet", b, hl, w, ctx_len, self.world), dev, int(self.mode == "corrected_async_gn"))
-            rc = u._lib.mx_unet_forward_pp_stale(u._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), ts.data_ptr(),
-                                                 ehs.data_ptr(), te.data_ptr(), ti.data_ptr(), out.data_ptr(), b, hl, w, ctx_len,
-                                                 C.byref(comm), C.byref(stale), self._ws.data_ptr(), self._ws.numel())
+                raise _lib.MxError(f"mx_{u.ABI}_pp_state_bytes: " + u._lib.mx_last_error().decode())
+            stale = self._stale_desc(sneed, (u.ABI, *shape), u.device, int(self.STALE_SYMBOL is not None and self.mode == "corrected_async_gn"))
             self.counter += 1
+        head = (u._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), ts.data_ptr(), *(c.data_ptr() for c in cond),
+                out.data_ptr(), b, hl, w, ctx_len, C.byref(comm))
+        stale_ref = None if stale is None else C.byref(stale)
+        if self.STALE_SYMBOL is None:        # one symbol: the stale descriptor, or NULL for a synchronous step
+            rc = u._fn("forward_pp")(*head, stale_ref, ws.data_ptr(), ws.numel())
+        elif stale is None:
+            rc = u._fn("forward_pp")(*head, ws.data_ptr(), ws.numel())
+        else:
+            rc = u._fn(self.STALE_SYMBOL)(*head, stale_ref, ws.data_ptr(), ws.numel())
         if self._err is not None:
             raise self._err
-        _lib.check(rc, "mx_unet_forward_pp")
+        _lib.check(rc, f"mx_{u.ABI}_forward_pp")
         return out
 
     def _single_rank(self, latents, timestep, *cond) -> torch.Tensor:
@@ -301,11 +302,8 @@ class PatchParallelUNet:
         local = local.contiguous()
         if self.log is not None:
             self.log.world_calls.append((local.numel() * local.element_size(), lay.world))
-        if self.backend == "gloo":                   # tests: through host memory
-            host = local.cpu()
-            parts = [torch.empty_like(host) for _ in range(lay.world)]
-            self.dist.all_gather(parts, host)
-            return torch.stack(parts).to(local.device)
+        if self.backend == "gloo":
+            return torch.stack(self._gather_list(local, None, lay.world))
         buf = torch.empty((lay.world, *local.shape), dtype=local.dtype, device=local.device)
         self.dist.all_gather_into_tensor(buf, local)
         return buf
@@ -317,18 +315,12 @@ class PatchParallelUNet:
         npb = self.world
         return buf.view(2, npb, n, c, hs, w).permute(0, 2, 3, 1, 4, 5).reshape(2 * n, c, npb * hs, w)
 
-    def forward(self, latents: torch.Tensor, timestep, encoder_hidden_states, text_embeds, time_ids) -> torch.Tensor:
+    def forward(self, latents: torch.Tensor, timestep, *cond: torch.Tensor) -> torch.Tensor:
         """whole latent in, whole noise prediction out on every rank (distri_sdxl_unet_pp.py:167-195)."""
         if self.layout is not None:
-            return self._forward_split(latents, timestep, encoder_hidden_states, text_embeds, time_ids)
-        local = self.forward_local(split_rows(latents, self.rank, self.world), timestep, encoder_hidden_states, text_embeds, time_ids)
-        if self.backend == "gloo":
-            parts = [torch.empty_like(local.cpu()) for _ in range(self.world)]
-            self.dist.all_gather(parts, local.cpu(), group=self.group)
-            return torch.cat([p.to(local.device) for p in parts], dim=2)
-        parts = [torch.empty_like(local) for _ in range(self.world)]
-        self.dist.all_gather(parts, local, group=self.group)
-        return torch.cat(parts, dim=2)
+            return self._forward_split(latents, timestep, *cond)
+        local = self.forward_local(split_rows(latents, self.rank, self.world), timestep, *cond)
+        return torch.cat(self._gather_list(local, self.group, self.world), dim=2)
 
 
 class PatchParallelSD3(PatchParallelUNet):
@@ -336,50 +328,7 @@ class PatchParallelSD3(PatchParallelUNet):
     modules/pp/attn.py:202-277): rank r owns the image tokens of its latent rows, every rank computes the text stream, each joint block
     all-gathers the image K / V^T.  ``forward(latents, timestep, encoder_hidden_states, pooled)``."""
 
-    def forward_local(self, latents_local: torch.Tensor, timestep: torch.Tensor, encoder_hidden_states: torch.Tensor,
-                      pooled: torch.Tensor) -> torch.Tensor:
-        u = self.unet                                        # an MxSD3Transformer
-        x = latents_local.contiguous()
-        b, _c, hl, w = x.shape
-        dev = u.device
-        lt = encoder_hidden_states.shape[1]
-        ts = timestep.to(device=dev, dtype=torch.float32).reshape(-1)
-        ts = (ts.expand(b) if ts.numel() == 1 else ts).contiguous()
-        ehs = encoder_hidden_states.to(device=dev, dtype=torch.bfloat16).contiguous()
-        pp = pooled.to(device=dev, dtype=torch.bfloat16).contiguous()
-        need = u._lib.mx_mmdit_workspace_bytes_pp(u._handle, b, hl, w, lt, self.world)
-        if need == 0:
-            raise _lib.MxError("mx_mmdit_workspace_bytes_pp: " + u._lib.mx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty((b, u.cfg.out_channels, hl, w), dtype=x.dtype, device=dev)
-        comm = _lib.PPComm(self.rank, self.world, self._cb, None)
-        self._err = None
-        stale_ref = None
-        if self.mode != "sync":
-            sneed = u._lib.mx_mmdit_pp_state_bytes(u._handle, b, hl, w, lt, self.world)
-            if sneed == 0:
-                raise _lib.MxError("mx_mmdit_pp_state_bytes: " + u._lib.mx_last_error().decode())
-            stale = self._stale_desc(sneed, ("mmdit", b, hl, w, lt, self.world), dev, 0)
-            stale_ref = C.byref(stale)
-            self.counter += 1
-        rc = u._lib.mx_mmdit_forward_pp(u._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), ts.data_ptr(),
-                                        ehs.data_ptr(), pp.data_ptr(), out.data_ptr(), b, hl, w, lt, C.byref(comm), stale_ref,
-                                        self._ws.data_ptr(), self._ws.numel())
-        if self._err is not None:
-            raise self._err
-        _lib.check(rc, "mx_mmdit_forward_pp")
-        return out
-
-    def forward(self, latents: torch.Tensor, timestep, encoder_hidden_states, pooled) -> torch.Tensor:
-        if self.layout is not None:
-            return self._forward_split(latents, timestep, encoder_hidden_states, pooled)
-        local = self.forward_local(split_rows(latents, self.rank, self.world), timestep, encoder_hidden_states, pooled)
-        host = self.backend == "gloo"
-        mine = local.cpu() if host else local
-        parts = [torch.empty_like(mine) for _ in range(self.world)]
-        self.dist.all_gather(parts, mine, group=self.group)
-        return torch.cat([p.to(local.device) for p in parts], dim=2)
+    STALE_SYMBOL = None                    # mx_mmdit_forward_pp takes the stale descriptor itself; no corrected GroupNorm (there is none)
 
 
 class PatchParallelDenoiser:
@@ -388,33 +337,21 @@ class PatchParallelDenoiser:
     Every rank holds the whole latents, as in distrifuser, and applies the same kernel to the same gathered bytes: after a step the latents are
     bit-identical on all ranks."""
 
+    hooks = SDXLDenoiser          # the model's side of a step, shared with the one-GPU denoiser: _cond, _scale_input, _scheduler_step_rows
+
     def __init__(self, pp: PatchParallelUNet, guidance_scale: float = 5.0):
-        from .step_state import StepCache
         assert pp.layout is not None, "the step on the gather buffer needs a CfgSplitLayout that splits the CFG batch"
         self.pp = pp
         self.guidance_scale = guidance_scale
         self._cache = StepCache(pp.unet.device)
 
-    def _cond(self, req) -> tuple:
-        return (torch.cat([req.negative_prompt_embeds, req.prompt_embeds], dim=0),
-                torch.cat([req.negative_pooled_prompt_embeds, req.pooled_prompt_embeds], dim=0),
-                torch.cat([req.negative_add_time_ids, req.add_time_ids], dim=0))
-
-    def _scale_input(self, lat: torch.Tensor, sig: torch.Tensor) -> torch.Tensor:
-        from . import ops
-        return ops.euler_scale_input(lat, sig, 2)
-
-    def _step_rows(self, buf, lat, sig, sig_next) -> None:
-        from . import ops
-        ops.cfg_euler_step_rows_(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)
-
     @torch.inference_mode()
     def step(self, req) -> None:
-        e = self._cache.entry((req.resolution, req.request_id, id(req)), [req], lambda: self._cond(req))
+        e = self._cache.entry((req.resolution, req.request_id, id(req)), [req], lambda: self.hooks._cond([req], True))
         lat = self._cache.latents(e, [req])
         sig, sig_next, ts = self._cache.step_scalars(e, [req])
-        buf = self.pp.forward_gathered(self._scale_input(lat, sig), torch.cat([ts, ts], dim=0), *e.cond)
-        self._step_rows(buf, lat, sig, sig_next)
+        buf = self.pp.forward_gathered(self.hooks._scale_input(lat, sig, True), torch.cat([ts, ts], dim=0), *e.cond)
+        self.hooks._scheduler_step_rows(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)
         req.step_index += 1
         req.latents = lat[0:1]
 
@@ -422,17 +359,7 @@ class PatchParallelDenoiser:
 class PatchParallelSD3Denoiser(PatchParallelDenoiser):
     """The same for one ``SD3Request`` of pipeline_sd3.py over a PatchParallelSD3: no input scaling, the flow-match step (mx_cfg_flow_step_rows)."""
 
+    hooks = SD3Denoiser
+
     def __init__(self, pp: PatchParallelSD3, guidance_scale: float = 7.0):
         super().__init__(pp, guidance_scale)
-
-    def _cond(self, req) -> tuple:
-        return (torch.cat([req.negative_prompt_embeds, req.prompt_embeds], dim=0),
-                torch.cat([req.negative_pooled_prompt_embeds, req.pooled_prompt_embeds], dim=0))
-
-    def _scale_input(self, lat: torch.Tensor, sig: torch.Tensor) -> torch.Tensor:
-        from . import ops
-        return ops.euler_scale_input(lat, torch.zeros_like(sig), 2)      # exact x / 1 copy == torch.cat([latents] * 2)
-
-    def _step_rows(self, buf, lat, sig, sig_next) -> None:
-        from . import ops
-        ops.cfg_flow_step_rows_(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)

@@ -9,7 +9,7 @@ duplication, the UNet, the CFG combine and the Euler step -- runs in libmxdenois
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -59,44 +59,62 @@ class Request:
         return self.step_index >= self.num_inference_steps
 
 
-class SDXLDenoiser:
-    def __init__(self, unet: MxUNet, guidance_scale: float = 5.0):
-        self.unet = unet
-        self.guidance_scale = guidance_scale   # reference default (pipeline_..._esymred.py:265)
+@dataclass
+class _Part:
+    """one resolution of a step"""
+    res: str
+    reqs: list
+    entry: object                         # its StepCache entry: .cond, .uid
+    latents: torch.Tensor                 # [n, ...]
+    sigma: torch.Tensor
+    sigma_next: torch.Tensor
+    timesteps: torch.Tensor               # one per model row ([uncond..., cond...] under CFG)
+    x_in: torch.Tensor                    # the model's input rows
+
+
+class Denoiser:
+    """One ``denoising_step`` over a heterogeneous batch of requests, for either model.  A subclass says which request fields make the
+    conditioning (``_cond``), how the model input is made from the latents (``_scale_input``), which scheduler step follows
+    (``_scheduler_step``; ``_scheduler_step_rows`` on a patch-parallel gather buffer), how its model slot is called (``_forward``,
+    ``_forward_mixed``) and whether a batch composition is announced to it (``announces_composition``: MxUNet.set_context_key)."""
+    announces_composition = False
+
+    def __init__(self, model, guidance_scale: float):
+        self._model = model
+        self.guidance_scale = guidance_scale
         self._tables: Dict[int, tuple] = {}
         self.concurrent_resolutions = True
         self._streams: List[torch.cuda.Stream] = []
-        self._cache = StepCache(unet.device)      # per batch composition: conditioning cats, sigma/timestep tables (step_state.py)
+        self._cache = StepCache(model.device)      # per batch composition: conditioning cats, sigma/timestep tables (step_state.py)
         self._mixed_cond: Dict[tuple, tuple] = {}  # per mixed composition: the conditioning of all resolutions concatenated
 
-    def set_timesteps(self, req: Request) -> None:
-        if req.num_inference_steps not in self._tables:
-            self._tables[req.num_inference_steps] = euler_tables(req.num_inference_steps)
-        req.timesteps, req.sigmas, _ = self._tables[req.num_inference_steps]
-        req.step_index = 0
-
-    def init_noise_sigma(self, num_inference_steps: int) -> float:
-        if num_inference_steps not in self._tables:
-            self._tables[num_inference_steps] = euler_tables(num_inference_steps)
-        return self._tables[num_inference_steps][2]
+    @staticmethod
+    def _cond(reqs, do_classifier_free_guidance: bool) -> tuple:
+        """(encoder_hidden_states, pooled) of one resolution's requests; with CFG in the row order [uncond..., cond...]
+        (pipeline_stable_diffusion_xl_esymred.py:322-339, pipeline_stable_diffusion_3_esymred.py:281-292)"""
+        if do_classifier_free_guidance:
+            return (torch.cat([r.negative_prompt_embeds for r in reqs] + [r.prompt_embeds for r in reqs], dim=0),
+                    torch.cat([r.negative_pooled_prompt_embeds for r in reqs] + [r.pooled_prompt_embeds for r in reqs], dim=0))
+        return torch.cat([r.prompt_embeds for r in reqs], dim=0), torch.cat([r.pooled_prompt_embeds for r in reqs], dim=0)
 
     @torch.inference_mode()
-    def denoising_step(self, worker_reqs: Dict[str, List[Request]], do_classifier_free_guidance: bool = True,
+    def denoising_step(self, worker_reqs: Dict[str, list], do_classifier_free_guidance: bool = True,
                        is_sliced: bool = False, patch_size: int = 256) -> None:
         """One timestep for every request in ``worker_reqs`` ({str(res): [requests]}), in place.
 
-        The reference runs the resolutions of a mixed batch as one patch batch; here each resolution is its own launch
-        sequence, and with more than one resolution present the sequences are issued on separate streams: a small batch
-        (one 512-1024 px request fills about a quarter of the CUs) leaves room for the other sequences to run beside it.
-        The caller's stream waits for all of them; ``self.concurrent_resolutions = False`` serialises them."""
+        The reference runs the resolutions of a mixed batch as one patch batch, and so does this: ONE launch sequence for all of them --
+        also with ESYMRED_USE_CACHE=TRUE, where the cache at its reference unit, the patch / token chunk, decides once per block for the
+        patches of every resolution.  Where that does not apply (``mixed_one_sequence = False``, the per-sample cache, more resolutions than
+        a sequence holds) each resolution is its own launch sequence, issued on separate streams: a small batch (one 512-1024 px request fills
+        about a quarter of the CUs) leaves room for the other sequences to run beside it.  The caller's stream waits for all of them;
+        ``self.concurrent_resolutions = False`` serialises them."""
         res_list = [r for r in sorted(worker_reqs.keys(), key=lambda r: int(r)) if worker_reqs[r]]       # :275-276
-        cached_patch_unit = (getattr(self.unet, "_block_caches", None) is not None and is_sliced and 1 <= len(res_list) <= self.unet.max_mixed_groups
-                             and all(int(r) % patch_size == 0 and int(r) > patch_size for r in res_list))
-        if cached_patch_unit or (1 < len(res_list) <= self.unet.max_mixed_groups and self.unet.mixed_one_sequence
-                                 and getattr(self.unet, "_block_caches", None) is None):
-            # ONE launch sequence for all resolutions -- also with ESYMRED_USE_CACHE=TRUE (round 4: the cache at its reference unit, the patch,
-            # decides once per block for the patches of every resolution: MxUNet.forward -> forward_mixed_cached)
-            self._step_mixed(res_list, worker_reqs, do_classifier_free_guidance, is_sliced, patch_size, cached=cached_patch_unit)
+        m = self._model
+        cache_on = getattr(m, "_block_caches", None) is not None
+        cached_unit = (cache_on and is_sliced and 1 <= len(res_list) <= m.max_mixed_groups
+                       and all(int(r) % patch_size == 0 and int(r) > patch_size for r in res_list))
+        if cached_unit or (1 < len(res_list) <= m.max_mixed_groups and m.mixed_one_sequence and not cache_on):
+            self._step(res_list, worker_reqs, do_classifier_free_guidance, is_sliced, patch_size, through_dict=cached_unit)
             return
         if len(res_list) <= 1 or not self.concurrent_resolutions:
             for res in res_list:
@@ -106,7 +124,7 @@ class SDXLDenoiser:
         fork = torch.cuda.Event()
         fork.record(cur)
         while len(self._streams) < len(res_list):
-            self._streams.append(torch.cuda.Stream(device=self.unet.device))
+            self._streams.append(torch.cuda.Stream(device=m.device))
         for i, res in enumerate(res_list):
             side = self._streams[i]
             side.wait_event(fork)
@@ -119,97 +137,112 @@ class SDXLDenoiser:
             for r in worker_reqs[res]:             # (post_inference / VAE) are now known to the allocator
                 r.latents.record_stream(cur)
 
-    def _gather(self, res: str, reqs: List[Request], do_classifier_free_guidance: bool):
-        """the per-resolution gather of :287-339 through the per-composition cache: (entry, latents [n, ...], sigma, sigma_next, timesteps)"""
-        def build_cond():
-            if do_classifier_free_guidance:                              # :322-339 row order [uncond..., cond...]
-                ehs = torch.cat([r.negative_prompt_embeds for r in reqs] + [r.prompt_embeds for r in reqs], dim=0)
-                pooled = torch.cat([r.negative_pooled_prompt_embeds for r in reqs] + [r.pooled_prompt_embeds for r in reqs], dim=0)
-                tids = torch.cat([t for r in reqs for t in (r.negative_add_time_ids, r.add_time_ids)], dim=0)    # interleaved neg/pos per request (:302-305)
-            else:
-                ehs = torch.cat([r.prompt_embeds for r in reqs], dim=0)
-                pooled = torch.cat([r.pooled_prompt_embeds for r in reqs], dim=0)
-                tids = torch.cat([r.add_time_ids for r in reqs], dim=0)
-            return ehs, pooled, tids
-        e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs)), reqs, build_cond)
-        lat = self._cache.latents(e, reqs)
-        sig, sig_next, ts = self._cache.step_scalars(e, reqs)
-        return e, lat, sig, sig_next, ts
-
-    def _step_mixed(self, res_list: List[str], worker_reqs: Dict[str, List[Request]], do_classifier_free_guidance: bool, is_sliced: bool,
-                    patch_size: int, cached: bool = False) -> None:
-        """All resolutions of the batch in ONE launch sequence (MxUNet.forward_mixed): the reference runs them as one patch batch
-        (:369-380 with the dict of all resolutions; modules/unet.py:242-260).  Conditioning rows: ascending resolution, [uncond..., cond...]
-        inside each (:275-276, 327-339)."""
-        here = torch.cuda.current_stream()
-        parts = []
-        for res in res_list:
-            reqs = worker_reqs[res]
-            for r in reqs:
-                r.latents.record_stream(here)
-            e, lat, sig, sig_next, ts = self._gather(res, reqs, do_classifier_free_guidance)
-            rows = 2 * len(reqs) if do_classifier_free_guidance else len(reqs)
-            parts.append((res, reqs, e, lat, sig, sig_next, torch.cat([ts, ts]) if do_classifier_free_guidance else ts,
-                          ops.euler_scale_input(lat, sig, rows)))
-        key = tuple(id(p[2]) for p in parts)                 # the concatenated conditioning lives as long as its per-resolution entries
-        hit = self._mixed_cond.get(key)
-        if hit is None or any(a is not b for a, b in zip(hit[0], [p[2] for p in parts])):
-            cat = tuple(torch.cat([p[2].cond[k] for p in parts], dim=0) for k in range(3))
-            if len(self._mixed_cond) > 32:
-                self._mixed_cond.clear()
-            hit = self._mixed_cond[key] = ([p[2] for p in parts], cat, new_uid())
-        ehs, pooled, tids = hit[1]
-        if cached:        # the model slot's own entry: the dict of all resolutions with the request ids the caches are keyed by (:369-380)
-            out = self.unet.forward({p[0]: p[7] for p in parts}, torch.cat([p[6] for p in parts]), ehs, added_cond_kwargs={"text_embeds": pooled, "time_ids": tids},
-                                    return_dict=False, is_sliced=True, patch_size=patch_size,
-                                    input_indices={p[0]: [str(r.request_id) for r in p[1]] for p in parts})[0]
-            noise = [out[p[0]] for p in parts]
-        else:
-            self.unet.set_context_key(hit[2])       # the composition's text embeddings are fixed: K / V^T of all layers once per composition
-            noise = self.unet.forward_mixed([p[7] for p in parts], torch.cat([p[6] for p in parts]), ehs, pooled, tids,
-                                            gn_patch=(patch_size // 8 if is_sliced else 0))
-        g = self.guidance_scale if do_classifier_free_guidance else 0.0
-        for (res, reqs, _e, lat, sig, sig_next, _ts, _x), nz in zip(parts, noise):
-            ops.cfg_euler_step_(nz, lat, sig, sig_next, g)              # :382-397
-            for i, r in enumerate(reqs):                                 # :399-403
-                r.step_index += 1
-                r.latents = lat[i:i + 1]
-
-    def _step_resolution(self, res: str, reqs: List[Request], do_classifier_free_guidance: bool, is_sliced: bool,
-                         patch_size: int) -> None:
-        n = len(reqs)
+    def _gather(self, res: str, reqs: list, do_classifier_free_guidance: bool) -> _Part:
+        """the per-resolution gather of :287-339 through the per-composition cache, and the model's input rows (:357-360 + the cat of :327).
+        Embeddings are fixed for a request's lifetime: one cat per batch composition, not per step."""
         here = torch.cuda.current_stream()
         for r in reqs:                                                   # latents may have been produced on another stream
             r.latents.record_stream(here)
-
-        def build_cond():
-            if do_classifier_free_guidance:                              # :322-339 row order [uncond..., cond...]
-                ehs = torch.cat([r.negative_prompt_embeds for r in reqs] + [r.prompt_embeds for r in reqs], dim=0)
-                pooled = torch.cat([r.negative_pooled_prompt_embeds for r in reqs] + [r.pooled_prompt_embeds for r in reqs], dim=0)
-                # add_time_ids are interleaved neg/pos per request in the reference (:302-305)
-                tids = torch.cat([t for r in reqs for t in (r.negative_add_time_ids, r.add_time_ids)], dim=0)
-            else:
-                ehs = torch.cat([r.prompt_embeds for r in reqs], dim=0)
-                pooled = torch.cat([r.pooled_prompt_embeds for r in reqs], dim=0)
-                tids = torch.cat([r.add_time_ids for r in reqs], dim=0)
-            return ehs, pooled, tids
-        # embeddings are fixed for a request's lifetime: one cat per batch composition, not per step (:287-316 redo it every step)
-        e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs)), reqs, build_cond)
-        ehs, pooled, tids = e.cond
-        lat = self._cache.latents(e, reqs)                               # :287-312
+        e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs)), reqs,
+                              lambda: self._cond(reqs, do_classifier_free_guidance))
+        lat = self._cache.latents(e, reqs)
         sig, sig_next, ts = self._cache.step_scalars(e, reqs)
-        rows = 2 * n if do_classifier_free_guidance else n
-        ts2 = torch.cat([ts, ts], dim=0) if do_classifier_free_guidance else ts
-        x_in = ops.euler_scale_input(lat, sig, rows)                     # :357-360 (+ the cat of :327)
-        self.unet.set_context_key(e.uid)         # the composition's text embeddings are fixed: K / V^T of all layers once per composition
-        noise = self.unet.forward({res: x_in}, ts2, ehs, added_cond_kwargs={"text_embeds": pooled, "time_ids": tids},
-                                  return_dict=False, is_sliced=is_sliced, patch_size=patch_size,
-                                  input_indices={res: [str(r.request_id) for r in reqs]})[0][res]   # :369-380
+        return _Part(res, reqs, e, lat, sig, sig_next, torch.cat([ts, ts], dim=0) if do_classifier_free_guidance else ts,
+                     self._scale_input(lat, sig, do_classifier_free_guidance))
+
+    def _mixed_composition(self, parts: List[_Part]) -> tuple:
+        """(conditioning of all resolutions concatenated, uid): rows in ascending resolution.  Lives as long as its per-resolution entries."""
+        entries = [p.entry for p in parts]
+        key = tuple(id(e) for e in entries)
+        hit = self._mixed_cond.get(key)
+        if hit is None or any(a is not b for a, b in zip(hit[0], entries)):
+            cat = tuple(torch.cat([e.cond[k] for e in entries], dim=0) for k in range(len(entries[0].cond)))
+            if len(self._mixed_cond) > 32:
+                self._mixed_cond.clear()
+            hit = self._mixed_cond[key] = (entries, cat, new_uid())
+        return hit[1], hit[2]
+
+    def _step(self, res_list: List[str], worker_reqs: Dict[str, list], do_classifier_free_guidance: bool, is_sliced: bool, patch_size: int,
+              through_dict: bool) -> None:
+        """The resolutions ``res_list`` in one call of the model slot.  ``through_dict``: its reference entry ``forward({res: rows}, ...)`` with
+        the request ids the block-skip caches are keyed by (:369-380) -- where the per-sample cache and the unsliced rule live; else
+        ``forward_mixed``, ONE launch sequence.  Conditioning rows: ascending resolution, [uncond..., cond...] inside each (:275-276, 327-339)."""
+        parts = [self._gather(res, worker_reqs[res], do_classifier_free_guidance) for res in res_list]
+        if len(parts) == 1:
+            (cond, uid), ts = (parts[0].entry.cond, parts[0].entry.uid), parts[0].timesteps
+        else:
+            (cond, uid), ts = self._mixed_composition(parts), torch.cat([p.timesteps for p in parts])
+        if self.announces_composition:       # the composition's text embeddings are fixed: K / V^T of all layers once per composition
+            self._model.set_context_key(uid)
+        if through_dict:
+            out = self._forward({p.res: p.x_in for p in parts}, ts, cond, is_sliced=is_sliced, patch_size=patch_size,
+                                input_indices={p.res: [str(r.request_id) for r in p.reqs] for p in parts})
+            noise = [out[p.res] for p in parts]
+        else:
+            noise = self._forward_mixed([p.x_in for p in parts], ts, cond, patch_size // 8 if is_sliced else 0)
         g = self.guidance_scale if do_classifier_free_guidance else 0.0
-        ops.cfg_euler_step_(noise, lat, sig, sig_next, g)                # :382-397
-        for i, r in enumerate(reqs):                                     # :399-403
-            r.step_index += 1
-            r.latents = lat[i:i + 1]
+        for p, nz in zip(parts, noise):
+            self._scheduler_step(nz, p.latents, p.sigma, p.sigma_next, g)          # :382-397
+            for i, r in enumerate(p.reqs):                                         # :399-403
+                r.step_index += 1
+                r.latents = p.latents[i:i + 1]
+
+    def _step_resolution(self, res: str, reqs: list, do_classifier_free_guidance: bool, is_sliced: bool, patch_size: int) -> None:
+        self._step([res], {res: reqs}, do_classifier_free_guidance, is_sliced, patch_size, through_dict=True)
+
+
+class SDXLDenoiser(Denoiser):
+    announces_composition = True
+
+    def __init__(self, unet: MxUNet, guidance_scale: float = 5.0):
+        super().__init__(unet, guidance_scale)     # reference default (pipeline_..._esymred.py:265)
+        self.unet = unet
+
+    def set_timesteps(self, req: Request) -> None:
+        req.timesteps, req.sigmas = self._table(req.num_inference_steps)[:2]
+        req.step_index = 0
+
+    def init_noise_sigma(self, num_inference_steps: int) -> float:
+        return self._table(num_inference_steps)[2]
+
+    def _table(self, num_inference_steps: int) -> tuple:
+        if num_inference_steps not in self._tables:
+            self._tables[num_inference_steps] = euler_tables(num_inference_steps)
+        return self._tables[num_inference_steps]
+
+    @staticmethod
+    def _cond(reqs, do_classifier_free_guidance: bool) -> tuple:
+        if do_classifier_free_guidance:          # add_time_ids are interleaved neg/pos per request in the reference (:302-305)
+            tids = torch.cat([t for r in reqs for t in (r.negative_add_time_ids, r.add_time_ids)], dim=0)
+        else:
+            tids = torch.cat([r.add_time_ids for r in reqs], dim=0)
+        return (*Denoiser._cond(reqs, do_classifier_free_guidance), tids)
+
+    @staticmethod
+    def _scale_input(lat: torch.Tensor, sig: torch.Tensor, do_classifier_free_guidance: bool) -> torch.Tensor:
+        return ops.euler_scale_input(lat, sig, (2 if do_classifier_free_guidance else 1) * lat.shape[0])
+
+    _scheduler_step = staticmethod(ops.cfg_euler_step_)
+    _scheduler_step_rows = staticmethod(ops.cfg_euler_step_rows_)
+
+    def _forward(self, x: Dict[str, torch.Tensor], ts, cond, **kwargs) -> Dict[str, torch.Tensor]:
+        ehs, pooled, tids = cond
+        return self.unet.forward(x, ts, ehs, added_cond_kwargs={"text_embeds": pooled, "time_ids": tids}, return_dict=False, **kwargs)[0]
+
+    def _forward_mixed(self, xs: List[torch.Tensor], ts, cond, gn_patch: int) -> List[torch.Tensor]:
+        return self.unet.forward_mixed(xs, ts, *cond, gn_patch=gn_patch)
+
+
+def _synthetic_embeds(seed: int, shared: Optional[dict], ctx_len: int, ehs_dim: int, pooled_dim: int, device, dtype) -> tuple:
+    """(prompt, negative prompt, pooled, negative pooled) embeddings ~N(0,1) from ``seed``; made once per ``shared`` dict"""
+    if shared is None or "pe" not in shared:
+        ge = torch.Generator(device="cpu").manual_seed(seed)
+        made = [torch.randn(*shape, generator=ge).to(device=device, dtype=dtype)
+                for shape in ((1, ctx_len, ehs_dim), (1, ctx_len, ehs_dim), (1, pooled_dim), (1, pooled_dim))]
+        if shared is None:
+            return tuple(made)
+        shared.update(zip(("pe", "ne", "pp", "npp"), made))
+    return shared["pe"], shared["ne"], shared["pp"], shared["npp"]
 
 
 def synthetic_request(rid: int, resolution: int, steps: int, cfg, denoiser: SDXLDenoiser, device, dtype=torch.bfloat16,
@@ -217,16 +250,7 @@ def synthetic_request(rid: int, resolution: int, steps: int, cfg, denoiser: SDXL
     """Fixed-prompt synthetic request: embeddings ~N(0,1) from the reference seed, time ids
     (res, res, 0, 0, res, res) (pipeline_..._esymred.py:181-187), latents randn * init_noise_sigma."""
     g = torch.Generator(device="cpu").manual_seed(seed + 17 * rid)
-    if shared is None or "pe" not in shared:
-        ge = torch.Generator(device="cpu").manual_seed(seed)
-        pe = torch.randn(1, 77, cfg.cross_attention_dim, generator=ge).to(device=device, dtype=dtype)
-        ne = torch.randn(1, 77, cfg.cross_attention_dim, generator=ge).to(device=device, dtype=dtype)
-        pp = torch.randn(1, cfg.text_embed_dim, generator=ge).to(device=device, dtype=dtype)
-        npp = torch.randn(1, cfg.text_embed_dim, generator=ge).to(device=device, dtype=dtype)
-        if shared is not None:
-            shared.update(pe=pe, ne=ne, pp=pp, npp=npp)
-    else:
-        pe, ne, pp, npp = shared["pe"], shared["ne"], shared["pp"], shared["npp"]
+    pe, ne, pp, npp = _synthetic_embeds(seed, shared, 77, cfg.cross_attention_dim, cfg.text_embed_dim, device, dtype)
     r = float(resolution)
     tid = torch.tensor([[r, r, 0.0, 0.0, r, r]], device=device, dtype=torch.float32)
     lat = torch.randn(1, cfg.in_channels, resolution // 8, resolution // 8, generator=g)

@@ -10,6 +10,7 @@ from typing import Dict, List, Sequence, Tuple
 import torch
 
 from . import lib as _lib
+from .model_slot import _grow_only
 from .weights import PackedWeights, _geglu_interleave
 
 LOG2E = 1.4426950408889634
@@ -126,14 +127,9 @@ class MxT5Encoder:
         b, l = ids.shape
         if l not in self.seq_lens:
             raise ValueError(f"sequence length {l} was not prepared (seq_lens = {self.seq_lens})")
-        need = self._lib.mx_t5_workspace_bytes(self._handle, b, l)
-        if need == 0:
-            raise _lib.MxError("mx_t5_workspace_bytes: " + self._lib.mx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = _grow_only(vars(self), "_ws", self._lib.mx_t5_workspace_bytes(self._handle, b, l), "mx_t5_workspace_bytes", self.device)
         out = torch.empty((b, l, self.cfg.d_model), dtype=torch.bfloat16, device=self.device)
-        _lib.check(self._lib.mx_t5_encode(self._handle, _lib.current_stream(), ids.data_ptr(), out.data_ptr(), b, l, self._ws.data_ptr(), self._ws.numel()),
+        _lib.check(self._lib.mx_t5_encode(self._handle, _lib.current_stream(), ids.data_ptr(), out.data_ptr(), b, l, ws.data_ptr(), ws.numel()),
                    "mx_t5_encode")
         return out
 

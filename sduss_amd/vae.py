@@ -10,6 +10,7 @@ from typing import Dict, List, Tuple
 import torch
 
 from . import lib as _lib
+from .model_slot import _grow_only
 from .weights import PackedWeights, _conv_pack
 
 PAD = 64   # latent channels are zero-padded to one K tile
@@ -122,16 +123,11 @@ class MxVAEDecoder:
     def decode(self, latents: torch.Tensor) -> torch.Tensor:
         x = latents.contiguous()
         b, _c, h, w = x.shape
-        need = self._lib.mx_vae_workspace_bytes(self._handle, b, h, w)
-        if need == 0:
-            raise _lib.MxError("mx_vae_workspace_bytes: " + self._lib.mx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = _grow_only(vars(self), "_ws", self._lib.mx_vae_workspace_bytes(self._handle, b, h, w), "mx_vae_workspace_bytes", self.device)
         f = 2 ** (len(self.cfg.block_out_channels) - 1)
         out = torch.empty((b, self.cfg.out_channels, f * h, f * w), dtype=self.out_dtype, device=self.device)
         _lib.check(self._lib.mx_vae_decode(self._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), out.data_ptr(),
-                                           _lib.torch_dtype_code(self.out_dtype), b, h, w, self._ws.data_ptr(), self._ws.numel()), "mx_vae_decode")
+                                           _lib.torch_dtype_code(self.out_dtype), b, h, w, ws.data_ptr(), ws.numel()), "mx_vae_decode")
         return out
 
 

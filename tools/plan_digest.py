@@ -229,9 +229,64 @@ def mmdit_cases():
     print(f"mmdit forward_mixed_cached on the device blocks run {[hex(h) for h in pcd.history]}, {pcd.patches_asked} of {pcd.patches_total} chunk-blocks asked", flush=True)
 
 
+def denoiser_cases(model):
+    """SDXLDenoiser / SD3Denoiser over the tiny model, through the public API only: the sha256 of every request's latents after every step.
+    Latents of 16 / 24 / 32 pixels, patch_size 64 (every resolution a multiple of the patch and larger: the cached-unit route), requests of 4 and 6
+    steps and of their own embeddings, so that the per-request scalars and the row order show."""
+    from sduss_amd.pipeline import SDXLDenoiser, synthetic_request
+    from sduss_amd.pipeline_sd3 import SD3Denoiser, synthetic_sd3_request
+    if model == "unet":
+        cfg = UNetConfig.tiny()
+        net = MxUNet(cfg, ref.init_params(ref.UNetConfig.tiny()), device="cuda:0")
+        new_denoiser = lambda: SDXLDenoiser(net)
+        request = lambda den, rid, res: synthetic_request(rid, res, 4 + 2 * (rid % 2), cfg, den, "cuda:0", seed=500 + rid)
+    else:
+        cfg = MMDiTConfig.tiny()
+        net = MxSD3Transformer(cfg, mref.init_params(mref.MMDiTConfig.tiny()), device="cuda:0")
+        new_denoiser = lambda: SD3Denoiser(net)
+        request = lambda den, rid, res: synthetic_sd3_request(rid, res, 4 + 2 * (rid % 2), cfg, den, "cuda:0", seed=500 + rid, ctx_len=20)
+    one, three = [(256, 2)], [(128, 1), (192, 2), (256, 1)]
+
+    def run(what, spec, steps, drop=None, masks=None, concurrent=True, **step_kwargs):
+        den = new_denoiser()
+        den.concurrent_resolutions = concurrent
+        rids = iter(range(sum(n for _res, n in spec)))
+        batch = {str(res): [request(den, next(rids), res) for _ in range(n)] for res, n in spec}
+        for k in range(steps):
+            if masks is not None:
+                pred.mask = masks[k]
+            den.denoising_step(batch, patch_size=64, **step_kwargs)
+            for reqs in batch.values():
+                for r in reqs:
+                    say(f"{model} denoiser {what} step {k + 1} request {r.request_id}", r.latents)
+            if drop is not None and k + 1 == drop[1]:
+                del batch[drop[0]]
+
+    run("one resolution, CFG", one, 3, is_sliced=False)
+    run("one resolution, no CFG", one, 2, is_sliced=False, do_classifier_free_guidance=False)
+    run("three resolutions, one sequence, 192 px leaves after step 2", three, 3, drop=("192", 2), is_sliced=True)
+    net.mixed_one_sequence = False
+    for concurrent in (True, False):
+        run(f"three resolutions, one sequence per resolution, {'side streams' if concurrent else 'serial'}", three, 2, concurrent=concurrent, is_sliced=True)
+    net.mixed_one_sequence = True
+
+    pred = Script()
+    asks = (np.ones, np.zeros, np.ones)
+    net.enable_block_cache(pred, forced_after=1 << 30)
+    run("block cache, patch / chunk unit, all / none / all ask", three, 3, masks=asks, is_sliced=True)
+    pc = net._patch_cache
+    print(f"{model} denoiser patch / chunk unit blocks run {[hex(h) for h in pc.history]}, {pc.patches_asked} of {pc.patches_total} asked", flush=True)
+    net.enable_block_cache(pred, forced_after=1 << 30)
+    run("block cache, per-sample unit, all / none / all ask", one, 3, masks=asks, is_sliced=False)
+    print(f"{model} denoiser per-sample unit blocks run {[hex(h) for h in net._block_caches['256'].history]}", flush=True)
+    net.disable_block_cache()
+
+
 if __name__ == "__main__":
     tiny_cases()
     pp_cases()
     base_width_case()
     mmdit_cases()
     pp_cases("mmdit")
+    denoiser_cases("unet")
+    denoiser_cases("mmdit")
