@@ -444,6 +444,21 @@ extern "C" int mx_groupnorm_nhwc_grouped(void* stream, const mx_gn_problem* prob
   using namespace mx;
   MX_CHECK(probs && n >= 1 && n <= MX_MAX_SEGS && gamma && beta && workspace, "groupnorm: grouped launch needs 1..MX_MAX_SEGS problems and its operands");
   MX_CHECK(groups > 0 && C % groups == 0, "groupnorm: C % groups != 0");
+  // A problem whose patch covers its image is exact (gn_fill) and, launched alone, folds in its apply pass; grouped with sliced problems it would go
+  // through their separate fold launch instead and differ from its own launch in the last bits.  Such a launch runs as two, the exact problems and
+  // the sliced ones, each as they would alone: what a problem computes never depends on what it is grouped with.
+  if (patch > 0 && groups <= kFoldGroups && n > 1) {
+    mx_gn_problem ex[MX_MAX_SEGS], sl[MX_MAX_SEGS];
+    int ne = 0, ns = 0;
+    for (int i = 0; i < n; ++i) {
+      if (patch >= probs[i].H && patch >= probs[i].W) ex[ne++] = probs[i]; else sl[ns++] = probs[i];
+    }
+    if (ne > 0 && ns > 0) {
+      if (mx_groupnorm_nhwc_grouped(stream, ex, ne, C1, gamma, beta, C, groups, eps, silu, patch, workspace)) return 1;
+      return mx_groupnorm_nhwc_grouped(stream, sl, ns, C1, gamma, beta, C, groups, eps, silu, patch,
+                                       (char*)workspace + mx_groupnorm_nhwc_grouped_workspace_bytes(ex, ne, C));
+    }
+  }
   GnGroup G;
   G.n = n;
   char* ws = (char*)workspace;
