@@ -563,6 +563,20 @@ size_t mx_vae_workspace_bytes(const mx_vae* v, int batch, int H, int W);
 int mx_vae_validate(const mx_vae* v, int batch, int H, int W);
 int mx_vae_decode(mx_vae* v, void* stream, const void* latents, int io_dtype, void* out, int out_dtype, int batch, int H, int W,
                   void* workspace, size_t workspace_bytes);
+/* The same decode ending in the image the client receives (image_processor.postprocess(output_type="pil"), :455): out is
+ * uint8 [batch, 8H, 8W, 3] (interleaved RGB; 8 = 2^(n_levels - 1)).  The plan is mx_vae_decode's up to conv_norm_out; then one launch
+ * (mx_conv3x3_rgb8 below) stands in for conv_out and the NCHW float store, so every byte is rounded once from the fp32 accumulator.
+ * Needs out_channels == 3.  Sized by mx_vae_workspace_bytes as well: this path never takes more workspace than mx_vae_decode. */
+int mx_vae_decode_rgb8(mx_vae* v, void* stream, const void* latents, int io_dtype, void* out, int batch, int H, int W, void* workspace,
+                       size_t workspace_bytes);
+/* 3x3 convolution (pad 1, stride 1) to three channels with the 8-bit image epilogue, the operator on its own (csrc/conv_rgb8.hip; not a
+ * route of mx_conv3x3):
+ *   x NHWC bf16 [B, H, W, Cin], Cin % 64 == 0;  w packed bf16 [4, 9 Cin] ((kh, kw, cin) order; row 3 is padding and is not read);
+ *   bias fp32 [4] (entry 3 unused);  x, w and bias 16-byte aligned;  out uint8 [B, H, W, 3], contiguous.
+ * Per element in fp32: y = acc + bias;  t = y * 0.5 + 0.5;  t = min(max(t, 0), 1) with NaN -> 0;  out = rint(t * 255) (half to even).
+ * Rows leave as dwords when W % 4 == 0 and out is 4-byte aligned, as bytes otherwise.  Refused without a launch: null operands, sizes
+ * <= 0, Cin % 64 != 0, B H W Cin >= 2^31 (32-bit source offsets), weights + one staged chunk past 64 KB of LDS. */
+int mx_conv3x3_rgb8(void* stream, const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int Cin);
 
 /* ------------------------------------------------------------------------------------------
  * CLIP text encoder (csrc/clip_text.cpp): what diffusers' encode_prompt runs per prompt before the denoising loop

@@ -34,6 +34,7 @@ struct mx_vae {
 
 namespace {
 constexpr int kPad = 64;   // the 4 latent channels are zero-padded to one K tile
+constexpr int kRgb8 = -1;  // run()'s out_dtype of mx_vae_decode_rgb8
 
 struct Plan : mx::PlanBase {
   mx_vae* u; int B, H, W;
@@ -112,6 +113,7 @@ struct Plan : mx::PlanBase {
     return out;
   }
 
+  // out_dtype >= 0: images [B, out_channels, 8H, 8W] of that dtype in [-1, 1];  out_dtype < 0 (kRgb8): uint8 [B, 8H, 8W, 3]
   bool run(const void* latents, int io_dtype, void* outp, int out_dtype) {
     const mx_vae_config& c = u->cfg;
     const int nlev = c.n_levels;
@@ -144,6 +146,11 @@ struct Plan : mx::PlanBase {
     bf16_t* n = alloc<bf16_t>(M * C);
     groupnorm(x, n, "decoder.conv_norm_out", h, wd, C, true);
     const int ldo = (c.out_channels + 3) / 4 * 4;
+    if (out_dtype == kRgb8) {                          // conv_out + postprocess + 8-bit store in one launch; no bf16 image, no transpose
+      const bf16_t* wgt = wb("decoder.conv_out.weight", (size_t)ldo * 9 * C); const float* bias = wf("decoder.conv_out.bias", ldo);
+      if (ok() && !dry && mx_conv3x3_rgb8(stream, n, wgt, bias, outp, B, h, wd, C)) fail(std::string("conv3x3_rgb8: ") + mx_last_error());
+      return ok();
+    }
     bf16_t* o = alloc<bf16_t>(M * ldo);
     conv(n, h, wd, C, "decoder.conv_out", o, ldo, 0);
     if (ok() && !dry && mx::launch_nhwc_to_nchw(stream, o, outp, out_dtype, B, c.out_channels, h * wd, ldo)) fail(mx_last_error());
@@ -157,7 +164,7 @@ int run_impl(mx_vae* u, void* stream, const void* latents, int io_dtype, void* o
   MX_CHECK(batch > 0 && H > 0 && W > 0, "vae: bad shape");
   if (!dry) {
     MX_CHECK(latents && out && ws && u->weights.blob, "vae: null operand or weights not set");
-    MX_CHECK(io_dtype >= 0 && io_dtype <= 2 && out_dtype >= 0 && out_dtype <= 2, "vae: bad dtype");
+    MX_CHECK(io_dtype >= 0 && io_dtype <= 2 && out_dtype >= kRgb8 && out_dtype <= 2, "vae: bad dtype");
   }
   Plan p;
   p.u = u; p.B = batch; p.H = H; p.W = W; p.lookup = lookup;
@@ -194,5 +201,12 @@ extern "C" int mx_vae_validate(const mx_vae* u, int batch, int H, int W) {
 }
 extern "C" int mx_vae_decode(mx_vae* u, void* stream, const void* latents, int io_dtype, void* out, int out_dtype, int batch, int H, int W,
                              void* workspace, size_t workspace_bytes) {
+  MX_CHECK(out_dtype >= 0, "vae: bad dtype");
   return run_impl(u, stream, latents, io_dtype, out, out_dtype, batch, H, W, workspace, workspace_bytes, false, false, nullptr);
+}
+extern "C" int mx_vae_decode_rgb8(mx_vae* u, void* stream, const void* latents, int io_dtype, void* out, int batch, int H, int W, void* workspace,
+                                  size_t workspace_bytes) {
+  MX_CHECK(u != nullptr, "vae_decode_rgb8: null handle");
+  MX_CHECK(u->cfg.out_channels == 3, "vae_decode_rgb8: an RGB image needs out_channels == 3");
+  return run_impl(u, stream, latents, io_dtype, out, kRgb8, batch, H, W, workspace, workspace_bytes, false, false, nullptr);
 }

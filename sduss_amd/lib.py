@@ -254,6 +254,8 @@ SYMBOLS = {
     "mx_vae_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "mx_vae_validate": (_i, [_vp, _i, _i, _i]),
     "mx_vae_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz]),
+    "mx_vae_decode_rgb8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz]),
+    "mx_conv3x3_rgb8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "mx_clip_create": (_vp, [C.POINTER(CLIPConfigC)]),
     "mx_clip_destroy": (None, [_vp]),
     "mx_clip_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),

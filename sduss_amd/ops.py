@@ -1,4 +1,4 @@
-"""Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_attention,
+"""Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_attention,
 mx_layernorm, mx_groupnorm_nhwc, scheduler steps).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
@@ -177,6 +177,21 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stri
     if want_gn_partials:
         return c, part
     return c
+
+
+def conv3x3_rgb8(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x NHWC bf16 [B,H,W,Cin] (Cin % 64 == 0); w bf16 [4, 9*Cin] tap-major (row 3 padding); bias fp32 [4] -> uint8 [B,H,W,3] =
+    rint(255 clamp((conv + bias) / 2 + 0.5, 0, 1)), rounded once from the fp32 accumulator (mx_conv3x3_rgb8).  ``out``: write into this
+    contiguous uint8 [B,H,W,3] tensor (a view into a guarded buffer, say) instead of allocating."""
+    l = _lib.load()
+    _bf16(x); _bf16(w)
+    b, h, wd, cin = x.shape
+    assert w.shape == (4, 9 * cin) and bias.dtype == torch.float32 and bias.numel() == 4 and bias.is_contiguous()
+    if out is None:
+        out = torch.empty((b, h, wd, 3), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.shape == (b, h, wd, 3) and out.is_contiguous() and out.device == x.device
+    _lib.check(l.mx_conv3x3_rgb8(_lib.current_stream(), x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), b, h, wd, cin), "mx_conv3x3_rgb8")
+    return out
 
 
 ATTN_QSCALE = 0.125 * 1.4426950408889634     # MX_ATTN_QSCALE(1/sqrt(64))

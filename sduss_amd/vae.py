@@ -1,4 +1,4 @@
-"""The VAE decoder behind the C ABI (``mx_vae_decode``): what ``post_inference`` calls as ``self.vae.decode``
+"""The VAE decoder behind the C ABI (``mx_vae_decode``, ``mx_vae_decode_rgb8``): what ``post_inference`` calls as ``self.vae.decode``
 (sduss/model_executor/diffusers/pipelines/stable_diffusion_xl/pipeline_stable_diffusion_xl_esymred.py:406-463).
 SURVEY.md section 8f rank 2 ("next" row): the step after the denoising loop, on the same HIP kernels as the UNet."""
 from __future__ import annotations
@@ -90,7 +90,8 @@ def pack_vae(cfg: VAEConfig, P: Dict[str, torch.Tensor]) -> List[Tuple[str, torc
 
 class MxVAEDecoder:
     """``decode(latents) -> images`` with latents [B, 4 | 16, H, W] as the denoising loop leaves them (``latents / scaling_factor
-    (+ shift_factor)`` of post_inference, SDXL :440 / SD3 :408, is folded into the packed weights) and images [B, 3, 8H, 8W] in [-1, 1]."""
+    (+ shift_factor)`` of post_inference, SDXL :440 / SD3 :408, is folded into the packed weights) and images [B, 3, 8H, 8W] in [-1, 1];
+    ``decode_images(latents) -> uint8 [B, 8H, 8W, 3]``, the same decode ending in the 8-bit image of image_processor.postprocess."""
 
     def __init__(self, cfg: VAEConfig, params: Dict[str, torch.Tensor], device="cuda:0", out_dtype=torch.float32):
         self.cfg = cfg
@@ -130,14 +131,57 @@ class MxVAEDecoder:
                                            _lib.torch_dtype_code(self.out_dtype), b, h, w, ws.data_ptr(), ws.numel()), "mx_vae_decode")
         return out
 
+    @torch.inference_mode()
+    def decode_images(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents -> the 8-bit images the client receives, uint8 [B, 8H, 8W, 3] on the device (mx_vae_decode_rgb8): the decoder with
+        image_processor.postprocess in its last launch, rint(255 clamp(x / 2 + 0.5, 0, 1)) of the fp32 accumulator"""
+        x = latents.contiguous()
+        b, _c, h, w = x.shape
+        ws = _grow_only(vars(self), "_ws", self._lib.mx_vae_workspace_bytes(self._handle, b, h, w), "mx_vae_workspace_bytes", self.device)
+        f = 2 ** (len(self.cfg.block_out_channels) - 1)
+        out = torch.empty((b, f * h, f * w, 3), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.mx_vae_decode_rgb8(self._handle, _lib.current_stream(), x.data_ptr(), _lib.torch_dtype_code(x.dtype), out.data_ptr(),
+                                                b, h, w, ws.data_ptr(), ws.numel()), "mx_vae_decode_rgb8")
+        return out
 
-def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list]) -> Dict[str, torch.Tensor]:
-    """mirror of post_inference (:406-463) up to the tensor stage: gather the finished requests' latents per resolution, decode,
-    postprocess to [0, 1]; returns {resolution: images [n, 3, res, res]}"""
+    def images_to_host(self, images: Dict[str, torch.Tensor]) -> Dict[str, "numpy.ndarray"]:  # noqa: F821
+        """device uint8 images per resolution -> numpy views [n, res, res, 3] into ONE grow-only pinned host buffer: non-blocking copies on
+        the current stream, one event, one wait.  The views are valid until the next call."""
+        need = sum(t.numel() for t in images.values())
+        pin = getattr(self, "_pin", None)
+        if pin is None or pin.numel() < need:
+            self._pin = None
+            pin = self._pin = torch.empty(max(need, 1), dtype=torch.uint8, pin_memory=True)
+        if getattr(self, "_pin_event", None) is None:
+            self._pin_event = torch.cuda.Event()
+        host, at = {}, 0
+        for res, t in images.items():
+            assert t.dtype == torch.uint8 and t.is_contiguous()
+            host[res] = pin[at:at + t.numel()].view(t.shape)
+            host[res].copy_(t, non_blocking=True)
+            at += t.numel()
+        self._pin_event.record()
+        self._pin_event.synchronize()
+        return {res: h.numpy() for res, h in host.items()}
+
+
+OUTPUT_TYPES = ("pt", "uint8", "pil")
+
+
+def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list], output_type: str = "pt") -> Dict[str, object]:
+    """mirror of post_inference (:406-463): gather the finished requests' latents per resolution, decode, postprocess.
+      "pt"     {resolution: fp32 images [n, 3, res, res] in [0, 1]} on the device (the tensor stage);
+      "uint8"  {resolution: uint8 images [n, res, res, 3]} on the device (MxVAEDecoder.decode_images);
+      "pil"    {resolution: [PIL.Image, ...]}, the reference's default: the "uint8" images through the decoder's pinned host buffer."""
+    if output_type not in OUTPUT_TYPES:
+        raise ValueError(f"post_inference: output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
     images = {}
     for res, reqs in worker_reqs.items():
         if not reqs:
             continue
         lat = torch.cat([r.latents for r in reqs], dim=0)
-        images[res] = (vae.decode(lat) / 2 + 0.5).clamp(0, 1)
+        images[res] = (vae.decode(lat) / 2 + 0.5).clamp(0, 1) if output_type == "pt" else vae.decode_images(lat)
+    if output_type == "pil":
+        from PIL import Image
+        return {res: [Image.fromarray(a) for a in arr] for res, arr in vae.images_to_host(images).items()}      # (an RGB fromarray copies)
     return images
