@@ -579,6 +579,55 @@ int mx_vae_decode_rgb8(mx_vae* v, void* stream, const void* latents, int io_dtyp
 int mx_conv3x3_rgb8(void* stream, const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int Cin);
 
 /* ------------------------------------------------------------------------------------------
+ * The step before the loop for a request that starts from an image: the VAE encoder (AutoencoderKL.encode + the posterior + the latent
+ * scaling), so that image-to-image, inpainting preparation and refiner hand-offs get their starting latents from this library
+ * (prepare_inference takes a request's latents from the caller: pipeline_stable_diffusion_xl_esymred.py:154-168).
+ * The same handle as the decoder: its weight table may hold "encoder.*" and "quant_conv.*" tensors (sduss_amd/vae.py, pack_vae_encoder);
+ * quant_conv (a padded [64, 64] linear over the moments) runs when the table names it -- SD3's AutoencoderKL has none.
+ * The encoder's downsampler pads asymmetrically (F.pad(x, (0, 1, 0, 1)), stride 2, pad 0); rotated by 180 degrees that is the library's
+ * stride-2 pad-1 conv, so the plan runs in the rotated orientation: the first launch reads the image backwards, every 3x3 weight is rotated
+ * at pack time, the last launch reads the moments backwards ("The encoder runs rotated").
+ *   image    MX_IMAGE_RGB8_HWC: uint8 [batch, H, W, 3] as a client sends it (value = 2 (u / 255) - 1 in fp32, then one rounding to bf16);
+ *            MX_IMAGE_F32_CHW:  fp32 [batch, 3, H, W] in [-1, 1] (image_processor.preprocess);  H, W: image pixels, multiples of 2^(n_levels - 1)
+ *   latents  [batch, latent_channels, H / f, W / f] of io_dtype, NCHW, f = 2^(n_levels - 1): (z - shift_factor) * scaling_factor with
+ *            z = the posterior's mode (posterior_noise NULL) or mean + std * posterior_noise; with start_noise, then
+ *            keep[b] * latents + sigma[b] * start_noise (the noise of the start step: Euler add_noise keep = 1, flow-match scale_noise keep = 1 - sigma)
+ *   posterior_noise, start_noise: NCHW of io_dtype, shaped as latents, or NULL;  keep, sigma: fp32 [batch], needed with start_noise.
+ * Refused without a launch: out_channels != 3, H or W not a multiple of 2^(n_levels - 1), null operands, a workspace smaller than
+ * the sizing walk's answer.
+ * ------------------------------------------------------------------------------------------ */
+enum { MX_IMAGE_RGB8_HWC = 0, MX_IMAGE_F32_CHW = 1 };
+typedef struct mx_vae_encode_args {
+  const void* image;
+  int image_format;               /* MX_IMAGE_* */
+  const void* posterior_noise;    /* optional */
+  const void* start_noise;        /* optional */
+  const float* keep;              /* with start_noise */
+  const float* sigma;             /* with start_noise */
+  void* latents;
+  int io_dtype;                   /* of latents and both noises */
+  float scaling_factor, shift_factor;
+} mx_vae_encode_args;
+size_t mx_vae_encode_workspace_bytes(const mx_vae* v, int batch, int H, int W);
+int mx_vae_encode_validate(const mx_vae* v, int batch, int H, int W);
+int mx_vae_encode(mx_vae* v, void* stream, const mx_vae_encode_args* args, int batch, int H, int W, void* workspace, size_t workspace_bytes);
+/* The encoder's conv_in on its own (csrc/conv_rgb_in.hip; not a route of the generic 3x3 conv): 3x3, pad 1, stride 1, the image's 3 channels -> N.
+ *   image as above;  w bf16 [N, 32], column (ky 3 + kx) 3 + c for the 27 taps, columns 27..31 padding that is read as zero whatever it holds;
+ *   bias fp32 [N];  y NHWC bf16 [B, H, W, N] = bf16(acc + bias), N % 16 == 0;  w, bias and y 16-byte aligned.
+ *   rotate = 1: output pixel (y, x) is the conv centred on image pixel (H-1-y, W-1-x) of the image rotated by 180 degrees;  0: the plain conv.
+ * Refused without a launch: null operands, sizes <= 0, N % 16 != 0, a bad format or rotate, misaligned operands, 3 B H W >= 2^31. */
+int mx_conv3x3_rgb_in(void* stream, const void* image, int image_format, const void* w, const float* bias, void* y, int B, int H, int W, int N,
+                      int rotate);
+/* The encoder's last launch on its own (csrc/elementwise.hip): moments bf16 [B h w, ld], columns [0, lc) mean and [lc, 2 lc) logvar -> latents
+ * NCHW [B, lc, h, w] of io_dtype.  Per element in fp32, each operation rounded on its own:
+ *   z = mean                                                       posterior_noise NULL
+ *   z = mean + expf{0.5f * min[max[logvar, -30], 20]} * eps        otherwise
+ *   lat = {z - shift} * scaling;   lat = keep[b] * lat + sigma[b] * start_noise     (start_noise given: mul, mul, add)
+ * rotate = 1: element (b, c, y, x) comes from moments row (h-1-y) w + (w-1-x) of image b. */
+int mx_vae_latent_finish(void* stream, const void* moments, int ld, void* out, int io_dtype, int B, int lc, int h, int w, float scaling, float shift,
+                         const void* posterior_noise, const void* start_noise, const float* keep, const float* sigma, int rotate);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP text encoder (csrc/clip_text.cpp): what diffusers' encode_prompt runs per prompt before the denoising loop
  * (prepare_inference, pipeline_stable_diffusion_xl_esymred.py:118-140): transformers CLIPTextModel (SDXL text_encoder: ViT-L, quick_gelu,
  * no projection) and CLIPTextModelWithProjection (text_encoder_2: OpenCLIP bigG, gelu, text_projection).  Packed weights keep the

@@ -606,3 +606,63 @@ int launch_copy_rows(hipStream_t s, void* batch, void* slotted, size_t bytes_per
   return 0;
 }
 }  // namespace mx
+
+// ------------------------------------------------------------------------------------------
+// The last launch of the VAE encoder (vae_sdxl.cpp, EncodePlan): moments -> the latents a request starts from.
+// DiagonalGaussianDistribution.mode / .sample, (z - shift_factor) * scaling_factor and, for a request that starts inside the schedule, the start
+// step's noise (EulerDiscreteScheduler.add_noise: keep = 1, sigma = sigma[t_start]; the flow-match scale_noise: keep = 1 - sigma), stored NCHW.
+// Every operation in fp32, rounded on its own (this translation unit contracts nothing); one rounding to the io dtype at the store.
+// ------------------------------------------------------------------------------------------
+namespace mx {
+template <typename T>
+__global__ void vae_latent_finish_kernel(const bf16_t* __restrict__ moments, int ld, T* __restrict__ out, int B, int lc, int h, int w, float scaling, float shift,
+                                         const T* __restrict__ posterior_noise, const T* __restrict__ start_noise, const float* __restrict__ keep,
+                                         const float* __restrict__ sigma, int rotate) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;  // over B*lc*h*w, x fastest: the NCHW element
+  const long total = (long)B * lc * h * w;
+  if (idx >= total) return;
+  const int x = (int)(idx % w);
+  long r = idx / w;
+  const int y = (int)(r % h); r /= h;
+  const int c = (int)(r % lc);
+  const int b = (int)(r / lc);
+  const long row = (long)b * h * w + (rotate ? (long)(h - 1 - y) * w + (w - 1 - x) : (long)y * w + x);
+  float z = bf16_to_f32(moments[row * ld + c]);
+  if (posterior_noise) {
+    float lv = bf16_to_f32(moments[row * ld + lc + c]);
+    lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+    const float sd = expf(0.5f * lv);
+    const float t = sd * load_as_f32<T>(posterior_noise, idx);
+    z = z + t;
+  }
+  float lat = (z - shift) * scaling;
+  if (start_noise) {
+    const float a = keep[b] * lat;
+    const float n = sigma[b] * load_as_f32<T>(start_noise, idx);
+    lat = a + n;
+  }
+  store_from_f32<T>(out, idx, lat);
+}
+}  // namespace mx
+
+extern "C" int mx_vae_latent_finish(void* stream, const void* moments, int ld, void* out, int io_dtype, int B, int lc, int h, int w, float scaling, float shift,
+                                    const void* posterior_noise, const void* start_noise, const float* keep, const float* sigma, int rotate) {
+  MX_CHECK(moments && out, "vae_latent_finish: null operand");
+  MX_CHECK(B > 0 && lc > 0 && h > 0 && w > 0, "vae_latent_finish: sizes must be positive");
+  MX_CHECK(ld >= 2 * lc, "vae_latent_finish: ld must hold the mean and the logvar columns");
+  MX_CHECK(rotate == 0 || rotate == 1, "vae_latent_finish: rotate must be 0 or 1");
+  MX_CHECK(!start_noise || (keep && sigma), "vae_latent_finish: start_noise needs keep and sigma");
+  MX_CHECK((long)B * h * w * ld < 2147483647L, "vae_latent_finish: the moments exceed 32-bit offsets");
+  const long total = (long)B * lc * h * w;
+  dim3 grid((unsigned)mx::cdiv64(total, 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+#define MX_FINISH(T) hipLaunchKernelGGL((mx::vae_latent_finish_kernel<T>), grid, block, 0, s, (const mx::bf16_t*)moments, ld, (T*)out, B, lc, h, w, scaling, shift, \
+                                        (const T*)posterior_noise, (const T*)start_noise, keep, sigma, rotate)
+  if (io_dtype == MX_F32) MX_FINISH(float);
+  else if (io_dtype == MX_F16) MX_FINISH(_Float16);
+  else if (io_dtype == MX_BF16) MX_FINISH(mx::bf16_t);
+  else MX_CHECK(false, "vae_latent_finish: bad dtype");
+#undef MX_FINISH
+  MX_LAUNCH_CHECK();
+  return 0;
+}

@@ -44,10 +44,11 @@ struct Plan : mx::PlanBase {
     d.a = a; d.lda = lda; d.w = wgt; d.bias = bias; d.c = c; d.ldc = ldc; d.M = M; d.N = N; d.K = K; d.residual = residual; d.ldr = ldr; d.out_scale = out_scale;
     return gemm(d, false);
   }
-  bool conv(const bf16_t* x, int h, int wd, int Cin, const std::string& prefix, bf16_t* out, int Cout, int up, const void* residual = nullptr) {
+  bool conv(const bf16_t* x, int h, int wd, int Cin, const std::string& prefix, bf16_t* out, int Cout, int up, const void* residual = nullptr, int stride = 1) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
     d.a = x; d.w = wb(prefix + ".weight", (size_t)Cout * 9 * Cin); d.bias = wf(prefix + ".bias", Cout);
-    d.c = out; d.ldc = Cout; d.B = B; d.Hin = h; d.Win = wd; d.Cin = Cin; d.Hout = h << up; d.Wout = wd << up; d.stride = 1; d.up = up;
+    d.c = out; d.ldc = Cout; d.B = B; d.Hin = h; d.Win = wd; d.Cin = Cin; d.Hout = ((h << up) + stride - 1) / stride; d.Wout = ((wd << up) + stride - 1) / stride;
+    d.stride = stride; d.up = up;
     d.M = B * d.Hout * d.Wout; d.N = Cout; d.K = 9 * Cin; d.rows_per_batch = d.Hout * d.Wout; d.residual = residual; d.ldr = Cout;
     return gemm(d, true);
   }
@@ -158,6 +159,79 @@ struct Plan : mx::PlanBase {
   }
 };
 
+// The ENCODER (AutoencoderKL.encode -> posterior -> scaled latents), the decoder's graph walked the other way on the same wrappers:
+//   conv_in -> down blocks (layers_per_block resnets each, a stride-2 conv between them) -> mid: resnet, attention, resnet -> GroupNorm + SiLU
+//   -> conv_out (2 lc moments, stored 64 wide) -> quant_conv (1x1 as a padded [64, 64] linear; SD3 has none) -> mode / sample, shift, scale, start noise.
+// diffusers' Downsample2D pads (0, 1, 0, 1) and convolves with stride 2, pad 0.  Rotated by 180 degrees that is the stride-2 PAD-1 conv of the
+// library's loader, and a pad-1 stride-1 conv commutes with the rotation when its weights are rotated too; GroupNorm, 1x1 convs and attention over
+// all tokens do not see pixel order.  So the whole plan runs in the rotated orientation: the first launch reads the image backwards
+// (mx_conv3x3_rgb_in, rotate = 1), the packer has rotated every 3x3 weight (vae.py, pack_vae_encoder), the last launch reads the moments backwards.
+// H, W here are IMAGE pixels.
+struct EncodePlan : Plan {
+  bool run_encode(const mx_vae_encode_args& a) {
+    const mx_vae_config& c = u->cfg;
+    const int nlev = c.n_levels, lc = c.latent_channels;
+    int h = H, wd = W;
+    int C = c.block_out_channels[0];
+    bf16_t* x = alloc<bf16_t>((size_t)B * h * wd * C);
+    {
+      const bf16_t* wgt = wb("encoder.conv_in.weight", (size_t)C * 32); const float* bias = wf("encoder.conv_in.bias", C);
+      if (ok() && !dry && mx_conv3x3_rgb_in(stream, a.image, a.image_format, wgt, bias, x, B, h, wd, C, 1)) fail(std::string("conv3x3_rgb_in: ") + mx_last_error());
+    }
+    for (int i = 0; i < nlev && ok(); ++i) {
+      const int Cout = c.block_out_channels[i];
+      for (int j = 0; j < c.layers_per_block && ok(); ++j) {
+        x = resnet("encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), x, h, wd, C, Cout);
+        C = Cout;
+      }
+      if (i != nlev - 1) {
+        bf16_t* d = alloc<bf16_t>((size_t)B * (h / 2) * (wd / 2) * C);
+        conv(x, h, wd, C, "encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv", d, C, 0, nullptr, 2);
+        h /= 2; wd /= 2;
+        x = d;
+      }
+    }
+    x = resnet("encoder.mid_block.resnets.0", x, h, wd, C, C);
+    x = attention("encoder.mid_block.attentions.0", x, h, wd, C);
+    x = resnet("encoder.mid_block.resnets.1", x, h, wd, C, C);
+    const size_t M = (size_t)B * h * wd;
+    bf16_t* n = alloc<bf16_t>(M * C);
+    groupnorm(x, n, "encoder.conv_norm_out", h, wd, C, true);
+    bf16_t* mom = alloc<bf16_t>(M * kPad);               // the 2 lc moments in columns [0, 2 lc) of 64 (rows 2 lc .. 63 of the packed conv_out are zero)
+    conv(n, h, wd, C, "encoder.conv_out", mom, kPad, 0);
+    bf16_t* q = alloc<bf16_t>(M * kPad);                 // (sized whether or not the table names a quant_conv: the sizing walk may run before the weights are set)
+    if (u->weights.table.count("quant_conv.weight")) {   // SD3's AutoencoderKL has none: conv_out's moments are the posterior's
+      linear(mom, kPad, wb("quant_conv.weight", (size_t)kPad * kPad), wf("quant_conv.bias", kPad), q, kPad, (int)M, kPad, kPad);
+      mom = q;
+    }
+    if (ok() && !dry && mx_vae_latent_finish(stream, mom, kPad, a.latents, a.io_dtype, B, lc, h, wd, a.scaling_factor, a.shift_factor, a.posterior_noise,
+                                             a.start_noise, a.keep, a.sigma, 1))
+      fail(std::string("vae_latent_finish: ") + mx_last_error());
+    return ok();
+  }
+};
+
+int encode_impl(mx_vae* u, void* stream, const mx_vae_encode_args* a, int batch, int H, int W, void* ws, size_t ws_bytes, bool dry, bool lookup, size_t* peak) {
+  MX_CHECK(u != nullptr, "vae_encode: null handle");
+  MX_CHECK(batch > 0 && H > 0 && W > 0, "vae_encode: bad shape");
+  MX_CHECK(u->cfg.out_channels == 3, "vae_encode: an RGB image needs out_channels == 3");
+  MX_CHECK(2 * u->cfg.latent_channels <= kPad, "vae_encode: the moments must fit 64 columns");
+  const int f = 1 << (u->cfg.n_levels - 1);
+  MX_CHECK(H % f == 0 && W % f == 0, "vae_encode: H and W must be multiples of 2^(n_levels - 1) = " + std::to_string(f));
+  mx_vae_encode_args none; std::memset(&none, 0, sizeof(none));
+  if (!dry) {
+    MX_CHECK(a && a->image && a->latents && ws && u->weights.blob, "vae_encode: null operand or weights not set");
+    MX_CHECK(a->io_dtype >= 0 && a->io_dtype <= 2, "vae_encode: bad dtype");
+    MX_CHECK(a->image_format == MX_IMAGE_RGB8_HWC || a->image_format == MX_IMAGE_F32_CHW, "vae_encode: bad image format");
+    MX_CHECK(!a->start_noise || (a->keep && a->sigma), "vae_encode: start_noise needs keep and sigma");
+  }
+  EncodePlan p;
+  p.u = u; p.B = batch; p.H = H; p.W = W; p.lookup = lookup;
+  if (dry) p.begin_dry(u->weights); else p.begin(u->weights, (hipStream_t)stream, ws, ws_bytes);
+  const bool okr = p.run_encode(dry ? none : *a);
+  return p.finish(okr, peak);
+}
+
 int run_impl(mx_vae* u, void* stream, const void* latents, int io_dtype, void* out, int out_dtype, int batch, int H, int W, void* ws, size_t ws_bytes,
              bool dry, bool lookup, size_t* peak) {
   MX_CHECK(u != nullptr, "vae: null handle");
@@ -209,4 +283,16 @@ extern "C" int mx_vae_decode_rgb8(mx_vae* u, void* stream, const void* latents, 
   MX_CHECK(u != nullptr, "vae_decode_rgb8: null handle");
   MX_CHECK(u->cfg.out_channels == 3, "vae_decode_rgb8: an RGB image needs out_channels == 3");
   return run_impl(u, stream, latents, io_dtype, out, kRgb8, batch, H, W, workspace, workspace_bytes, false, false, nullptr);
+}
+extern "C" size_t mx_vae_encode_workspace_bytes(const mx_vae* u, int batch, int H, int W) {
+  size_t peak = 0;
+  if (encode_impl(const_cast<mx_vae*>(u), nullptr, nullptr, batch, H, W, nullptr, 0, true, false, &peak)) return 0;
+  return peak + 4096;
+}
+extern "C" int mx_vae_encode_validate(const mx_vae* u, int batch, int H, int W) {
+  MX_CHECK(u && u->weights.blob, "vae_encode_validate: weights not set");
+  return encode_impl(const_cast<mx_vae*>(u), nullptr, nullptr, batch, H, W, nullptr, 0, true, true, nullptr);
+}
+extern "C" int mx_vae_encode(mx_vae* u, void* stream, const mx_vae_encode_args* args, int batch, int H, int W, void* workspace, size_t workspace_bytes) {
+  return encode_impl(u, stream, args, batch, H, W, workspace, workspace_bytes, false, false, nullptr);
 }

@@ -158,6 +158,16 @@ class VAEConfigC(C.Structure):
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int), ("norm_eps", C.c_float)]
 
 
+IMAGE_RGB8_HWC, IMAGE_F32_CHW = 0, 1
+
+
+class VAEEncodeArgs(C.Structure):
+    """mx_vae_encode_args"""
+    _fields_ = [("image", C.c_void_p), ("image_format", C.c_int), ("posterior_noise", C.c_void_p), ("start_noise", C.c_void_p),
+                ("keep", C.c_void_p), ("sigma", C.c_void_p), ("latents", C.c_void_p), ("io_dtype", C.c_int),
+                ("scaling_factor", C.c_float), ("shift_factor", C.c_float)]
+
+
 class WeightEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -256,6 +266,11 @@ SYMBOLS = {
     "mx_vae_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz]),
     "mx_vae_decode_rgb8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz]),
     "mx_conv3x3_rgb8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "mx_vae_encode_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "mx_vae_encode_validate": (_i, [_vp, _i, _i, _i]),
+    "mx_vae_encode": (_i, [_vp, _vp, C.POINTER(VAEEncodeArgs), _i, _i, _i, _vp, _sz]),
+    "mx_conv3x3_rgb_in": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "mx_vae_latent_finish": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _i]),
     "mx_clip_create": (_vp, [C.POINTER(CLIPConfigC)]),
     "mx_clip_destroy": (None, [_vp]),
     "mx_clip_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),

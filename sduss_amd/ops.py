@@ -1,4 +1,4 @@
-"""Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_attention,
+"""Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
 mx_layernorm, mx_groupnorm_nhwc, scheduler steps).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
@@ -191,6 +191,52 @@ def conv3x3_rgb8(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: Opti
         out = torch.empty((b, h, wd, 3), dtype=torch.uint8, device=x.device)
     assert out.dtype == torch.uint8 and out.shape == (b, h, wd, 3) and out.is_contiguous() and out.device == x.device
     _lib.check(l.mx_conv3x3_rgb8(_lib.current_stream(), x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), b, h, wd, cin), "mx_conv3x3_rgb8")
+    return out
+
+
+def conv3x3_rgb_in(image: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, rotate: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """image uint8 [B,H,W,3] (a client's bytes; value 2 (u / 255) - 1) or fp32 [B,3,H,W] in [-1, 1]; w bf16 [N, 32], column (ky 3 + kx) 3 + c, columns
+    27..31 read as zero; bias fp32 [N] -> NHWC bf16 [B,H,W,N], the pad-1 3x3 conv (mx_conv3x3_rgb_in).  ``rotate``: of the image rotated by 180
+    degrees.  ``out``: write into this contiguous bf16 [B,H,W,N] tensor instead of allocating."""
+    l = _lib.load()
+    _bf16(w)
+    assert image.is_cuda and image.is_contiguous()
+    if image.dtype == torch.uint8:
+        fmt = _lib.IMAGE_RGB8_HWC
+        b, h, wd, c = image.shape
+    else:
+        assert image.dtype == torch.float32, "expected a uint8 [B,H,W,3] or an fp32 [B,3,H,W] image"
+        fmt = _lib.IMAGE_F32_CHW
+        b, c, h, wd = image.shape
+    n = w.shape[0]
+    assert c == 3 and w.shape == (n, 32) and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
+    if out is None:
+        out = torch.empty((b, h, wd, n), dtype=torch.bfloat16, device=image.device)
+    assert out.dtype == torch.bfloat16 and out.shape == (b, h, wd, n) and out.is_contiguous() and out.device == image.device
+    _lib.check(l.mx_conv3x3_rgb_in(_lib.current_stream(), image.data_ptr(), fmt, w.data_ptr(), bias.data_ptr(), out.data_ptr(), b, h, wd, n, int(rotate)),
+               "mx_conv3x3_rgb_in")
+    return out
+
+
+def vae_latent_finish(moments: torch.Tensor, lc: int, h: int, w: int, scaling: float, shift: float, dtype: torch.dtype,
+                      posterior_noise: Optional[torch.Tensor] = None, start_noise: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                      sigma: Optional[torch.Tensor] = None, rotate: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moments bf16 [B h w, ld] (columns [0, lc) mean, [lc, 2 lc) logvar) -> latents [B, lc, h, w] of ``dtype``: the posterior's mode, or its sample with
+    ``posterior_noise``; (z - shift) * scaling; with ``start_noise``: keep[b] * latents + sigma[b] * start_noise (mx_vae_latent_finish)."""
+    l = _lib.load()
+    assert moments.is_cuda and moments.dtype == torch.bfloat16 and moments.ndim == 2 and moments.stride(1) == 1
+    ld = moments.stride(0)
+    b = moments.shape[0] // (h * w)
+    assert moments.shape[0] == b * h * w and moments.shape[1] >= 2 * lc
+    if out is None:
+        out = torch.empty((b, lc, h, w), dtype=dtype, device=moments.device)
+    assert out.dtype == dtype and out.shape == (b, lc, h, w) and out.is_contiguous()
+    for t in (posterior_noise, start_noise):
+        assert t is None or (t.is_cuda and t.dtype == dtype and t.shape == out.shape and t.is_contiguous())
+    for t in (keep, sigma):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.numel() == b and t.is_contiguous())
+    _lib.check(l.mx_vae_latent_finish(_lib.current_stream(), moments.data_ptr(), ld, out.data_ptr(), _lib.torch_dtype_code(dtype), b, lc, h, w, scaling, shift,
+                                      _p(posterior_noise), _p(start_noise), _p(keep), _p(sigma), int(rotate)), "mx_vae_latent_finish")
     return out
 
 

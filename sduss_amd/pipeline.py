@@ -72,6 +72,13 @@ class _Part:
     x_in: torch.Tensor                    # the model's input rows
 
 
+def start_step(num_inference_steps: int, strength: float) -> int:
+    """the step an image-to-image request starts at, diffusers' ``get_timesteps``: init = min(int(steps * strength), steps),
+    t_start = max(steps - init, 0).  strength 1 starts at step 0 (pure noise at the first sigma), strength 0 at ``steps`` (nothing left to do)."""
+    init = min(int(num_inference_steps * strength), num_inference_steps)
+    return max(num_inference_steps - init, 0)
+
+
 class Denoiser:
     """One ``denoising_step`` over a heterogeneous batch of requests, for either model.  A subclass says which request fields make the
     conditioning (``_cond``), how the model input is made from the latents (``_scale_input``), which scheduler step follows
@@ -136,6 +143,29 @@ class Denoiser:
         for res in res_list:                       # the new latents were allocated on side streams: consumers on `cur`
             for r in worker_reqs[res]:             # (post_inference / VAE) are now known to the allocator
                 r.latents.record_stream(cur)
+
+    @staticmethod
+    def _start_mix(sigma: np.float32) -> tuple:
+        """(keep, sigma) of the start step's noise: latents = keep * clean + sigma * noise"""
+        raise NotImplementedError
+
+    def start_from_image(self, req, encoder, image: torch.Tensor, strength: float, posterior_noise: Optional[torch.Tensor] = None,
+                         start_noise: Optional[torch.Tensor] = None) -> None:
+        """Make ``req`` an image-to-image request: it starts at step t_start = ``start_step(steps, strength)`` of its schedule from the latents of
+        ``image`` (uint8 [1, H, W, 3] as a client sends it, or float [1, 3, H, W] in [-1, 1]) noised to that step's sigma.  ONE call of the
+        encoder (vae.MxVAEEncoder): posterior (its mode; its sample with ``posterior_noise``), latent scaling and the start noise leave its last
+        launch together.  ``start_noise``: N(0, 1) shaped as the latents; drawn here when None.  The step itself does not change: a batch already
+        holds requests at different ``step_index``."""
+        self.set_timesteps(req)
+        t_start = start_step(req.num_inference_steps, strength)
+        keep, sigma = self._start_mix(np.float32(req.sigmas[t_start]))
+        f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
+        h, w = (image.shape[1], image.shape[2]) if image.dtype == torch.uint8 else (image.shape[2], image.shape[3])
+        if start_noise is None:
+            start_noise = torch.randn((image.shape[0], encoder.cfg.latent_channels, h // f, w // f), device=encoder.device, dtype=encoder.out_dtype)
+        enc = encoder.encode_images if image.dtype == torch.uint8 else encoder.encode
+        req.latents = enc(image, posterior_noise=posterior_noise, start_noise=start_noise, keep=float(keep), sigma=float(sigma))
+        req.step_index = t_start
 
     def _gather(self, res: str, reqs: list, do_classifier_free_guidance: bool) -> _Part:
         """the per-resolution gather of :287-339 through the per-composition cache, and the model's input rows (:357-360 + the cat of :327).
@@ -221,6 +251,10 @@ class SDXLDenoiser(Denoiser):
     @staticmethod
     def _scale_input(lat: torch.Tensor, sig: torch.Tensor, do_classifier_free_guidance: bool) -> torch.Tensor:
         return ops.euler_scale_input(lat, sig, (2 if do_classifier_free_guidance else 1) * lat.shape[0])
+
+    @staticmethod
+    def _start_mix(sigma: np.float32) -> tuple:
+        return np.float32(1.0), sigma                        # EulerDiscreteScheduler.add_noise: original + sigma * noise
 
     _scheduler_step = staticmethod(ops.cfg_euler_step_)
     _scheduler_step_rows = staticmethod(ops.cfg_euler_step_rows_)

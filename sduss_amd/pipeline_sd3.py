@@ -68,6 +68,10 @@ class SD3Denoiser(Denoiser):
             return ops.euler_scale_input(lat, torch.zeros_like(sig), 2 * lat.shape[0])  # exact x/1 copy == torch.cat([latents] * 2)
         return lat
 
+    @staticmethod
+    def _start_mix(sigma: np.float32) -> tuple:
+        return np.float32(1.0) - sigma, sigma                # FlowMatchEulerDiscreteScheduler.scale_noise: (1 - sigma) * sample + sigma * noise
+
     _scheduler_step = staticmethod(ops.cfg_flow_step_)                 # :362-372
     _scheduler_step_rows = staticmethod(ops.cfg_flow_step_rows_)
 

@@ -1,6 +1,7 @@
-"""The VAE decoder behind the C ABI (``mx_vae_decode``, ``mx_vae_decode_rgb8``): what ``post_inference`` calls as ``self.vae.decode``
+"""The VAE behind the C ABI.  The decoder (``mx_vae_decode``, ``mx_vae_decode_rgb8``): what ``post_inference`` calls as ``self.vae.decode``
 (sduss/model_executor/diffusers/pipelines/stable_diffusion_xl/pipeline_stable_diffusion_xl_esymred.py:406-463).
-SURVEY.md section 8f rank 2 ("next" row): the step after the denoising loop, on the same HIP kernels as the UNet."""
+SURVEY.md section 8f rank 2 ("next" row): the step after the denoising loop, on the same HIP kernels as the UNet.
+The encoder (``mx_vae_encode``): images -> the latents a request starts from, which ``prepare_inference`` takes from the caller (:154-168)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -88,6 +89,134 @@ def pack_vae(cfg: VAEConfig, P: Dict[str, torch.Tensor]) -> List[Tuple[str, torc
     return out
 
 
+def conv_in_pack(w: torch.Tensor) -> torch.Tensor:
+    """encoder.conv_in weight [N, 3, 3, 3] (O, I, kh, kw) -> [N, 32]: column (ky 3 + kx) 3 + c for the 27 taps, columns 27..31 zero (mx_conv3x3_rgb_in)"""
+    n = w.shape[0]
+    assert tuple(w.shape) == (n, 3, 3, 3)
+    return torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(n, 27), (0, 5)).contiguous()
+
+
+def rot180(t: torch.Tensor) -> torch.Tensor:
+    """rotation of the spatial grid (the last two dims) by 180 degrees"""
+    return t.flip(-2, -1)
+
+
+def pack_vae_encoder(cfg: VAEConfig, P: Dict[str, torch.Tensor]) -> List[Tuple[str, torch.Tensor]]:
+    """HF-named AutoencoderKL params (encoder.* and quant_conv.*) -> packed tensors of the encoder plan (csrc/vae_sdxl.cpp, EncodePlan).
+    The plan runs in the orientation rotated by 180 degrees, where the encoder's (0, 1, 0, 1)-padded stride-2 downsampler is a pad-1 conv:
+        conv(pad(x, (0, 1, 0, 1)), w, stride 2, pad 0) == rot(conv(rot(x), rot(w), stride 2, pad 1))      (H, W even)
+        conv(x, w, stride 1, pad 1)                    == rot(conv(rot(x), rot(w), stride 1, pad 1))
+    so every 3x3 weight is rotated here, once; nothing is rounded that was not bf16 already.  conv_out keeps its 2 lc rows in a [64, 9 C] matrix and
+    quant_conv (1x1) is a padded [64, 64] linear, so the moments sit in the first 2 lc of 64 columns."""
+    bf, f32 = torch.bfloat16, torch.float32
+    out: List[Tuple[str, torch.Tensor]] = []
+    m = 2 * cfg.latent_channels
+    assert m <= PAD
+    if cfg.use_post_quant_conv:                               # (the two quant convs come and go together: SD3's AutoencoderKL has neither)
+        w = torch.zeros(PAD, PAD, dtype=f32); b = torch.zeros(PAD, dtype=f32)
+        w[:m, :m] = P["quant_conv.weight"].reshape(m, m).to(f32); b[:m] = P["quant_conv.bias"].to(f32)
+        out.append(("quant_conv.weight", w.to(bf))); out.append(("quant_conv.bias", b))
+    for name, t in P.items():
+        if not name.startswith("encoder."):
+            continue
+        if name == "encoder.conv_in.weight":
+            out.append((name, conv_in_pack(rot180(t)).to(bf)))
+        elif name == "encoder.conv_out.weight":
+            out.append((name, torch.nn.functional.pad(_conv_pack(rot180(t)), (0, 0, 0, PAD - m)).to(bf).contiguous()))
+        elif name == "encoder.conv_out.bias":
+            out.append((name, torch.nn.functional.pad(t.to(f32), (0, PAD - m)).contiguous()))
+        elif t.ndim == 4 and t.shape[-1] == 3:
+            out.append((name, _conv_pack(rot180(t)).to(bf)))
+        elif t.ndim == 4:                                     # 1x1 conv_shortcut
+            out.append((name, t.reshape(t.shape[0], t.shape[1]).to(bf).contiguous()))
+        elif t.ndim == 2:
+            out.append((name, t.to(bf).contiguous()))
+        else:
+            out.append((name, t.to(f32).contiguous()))
+    return out
+
+
+def _config_c(cfg: VAEConfig) -> "_lib.VAEConfigC":
+    cc = _lib.VAEConfigC()
+    cc.latent_channels, cc.out_channels, cc.n_levels = cfg.latent_channels, cfg.out_channels, len(cfg.block_out_channels)
+    for i, v in enumerate(cfg.block_out_channels):
+        cc.block_out_channels[i] = v
+    cc.layers_per_block, cc.norm_num_groups, cc.norm_eps = cfg.layers_per_block, cfg.norm_num_groups, cfg.norm_eps
+    return cc
+
+
+class MxVAEEncoder:
+    """``encode(images) -> latents`` with images fp32 [B, 3, H, W] in [-1, 1] (image_processor.preprocess) and ``encode_images(images)`` with the
+    client's uint8 [B, H, W, 3]; latents [B, 4 | 16, H / 8, W / 8] in ``out_dtype`` as the denoising loop expects them: (z - shift_factor) *
+    scaling_factor with z the posterior's mode, or its sample when ``posterior_noise`` (shaped and typed as the latents) is given.
+    ``start_noise`` with ``keep`` / ``sigma`` (fp32 [B]): the latents leave as keep * latents + sigma * start_noise, the noise of the step an
+    image-to-image request starts at, in the same launch (Denoiser.start_from_image)."""
+
+    def __init__(self, cfg: VAEConfig, params: Dict[str, torch.Tensor], device="cuda:0", out_dtype=torch.bfloat16):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.out_dtype = out_dtype
+        self._lib = _lib.load()
+        self._handle = self._lib.mx_vae_create(C.byref(_config_c(cfg)))
+        if not self._handle:
+            raise _lib.MxError("mx_vae_create: " + self._lib.mx_last_error().decode())
+        self.weights = PackedWeights(pack_vae_encoder(cfg, params), self.device)
+        _lib.check(self._lib.mx_vae_set_weights(self._handle, self.weights.blob.data_ptr(), self.weights.blob.numel(), self.weights.table,
+                                                len(self.weights.names)), "mx_vae_set_weights")
+        self._ws = None
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            self._lib.mx_vae_destroy(h)
+            self._handle = None
+
+    def validate(self, batch: int, h: int, w: int) -> None:
+        _lib.check(self._lib.mx_vae_encode_validate(self._handle, batch, h, w), "mx_vae_encode_validate")
+
+    def _encode(self, image: torch.Tensor, fmt: int, b: int, h: int, w: int, posterior_noise, start_noise, keep, sigma) -> torch.Tensor:
+        f = 2 ** (len(self.cfg.block_out_channels) - 1)
+        ws = _grow_only(vars(self), "_ws", self._lib.mx_vae_encode_workspace_bytes(self._handle, b, h, w), "mx_vae_encode_workspace_bytes", self.device)
+        out = torch.empty((b, self.cfg.latent_channels, h // f, w // f), dtype=self.out_dtype, device=self.device)
+        a = _lib.VAEEncodeArgs()
+        a.image, a.image_format, a.latents, a.io_dtype = image.data_ptr(), fmt, out.data_ptr(), _lib.torch_dtype_code(self.out_dtype)
+        a.scaling_factor, a.shift_factor = self.cfg.scaling_factor, self.cfg.shift_factor
+        keepalive = []
+        for field, t in (("posterior_noise", posterior_noise), ("start_noise", start_noise)):
+            if t is not None:
+                if t.shape != out.shape:
+                    raise _lib.MxError(f"mx_vae_encode: {field} has shape {tuple(t.shape)}, the latents {tuple(out.shape)}")
+                t = t.to(device=self.device, dtype=self.out_dtype).contiguous()
+                keepalive.append(t)
+                setattr(a, field, t.data_ptr())
+        if start_noise is not None:
+            if keep is None or sigma is None:
+                raise _lib.MxError("mx_vae_encode: start_noise needs keep and sigma")
+            for field, t in (("keep", keep), ("sigma", sigma)):
+                t = torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device).expand(b).contiguous()
+                keepalive.append(t)
+                setattr(a, field, t.data_ptr())
+        _lib.check(self._lib.mx_vae_encode(self._handle, _lib.current_stream(), C.byref(a), b, h, w, ws.data_ptr(), ws.numel()), "mx_vae_encode")
+        return out
+
+    @torch.inference_mode()
+    def encode(self, images: torch.Tensor, posterior_noise=None, start_noise=None, keep=None, sigma=None) -> torch.Tensor:
+        x = images.to(device=self.device, dtype=torch.float32).contiguous()
+        b, c, h, w = x.shape
+        if c != 3:
+            raise _lib.MxError(f"mx_vae_encode: expected [B, 3, H, W] images, got {tuple(x.shape)}")
+        return self._encode(x, _lib.IMAGE_F32_CHW, b, h, w, posterior_noise, start_noise, keep, sigma)
+
+    @torch.inference_mode()
+    def encode_images(self, images: torch.Tensor, posterior_noise=None, start_noise=None, keep=None, sigma=None) -> torch.Tensor:
+        """the client's 8-bit images, uint8 [B, H, W, 3]: the first launch reads the bytes themselves (mx_conv3x3_rgb_in)"""
+        if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[-1] != 3:
+            raise _lib.MxError(f"mx_vae_encode: expected uint8 [B, H, W, 3] images, got {images.dtype} {tuple(images.shape)}")
+        x = images.to(self.device).contiguous()
+        b, h, w, _c = x.shape
+        return self._encode(x, _lib.IMAGE_RGB8_HWC, b, h, w, posterior_noise, start_noise, keep, sigma)
+
+
 class MxVAEDecoder:
     """``decode(latents) -> images`` with latents [B, 4 | 16, H, W] as the denoising loop leaves them (``latents / scaling_factor
     (+ shift_factor)`` of post_inference, SDXL :440 / SD3 :408, is folded into the packed weights) and images [B, 3, 8H, 8W] in [-1, 1];
@@ -98,12 +227,7 @@ class MxVAEDecoder:
         self.device = torch.device(device)
         self.out_dtype = out_dtype
         self._lib = _lib.load()
-        cc = _lib.VAEConfigC()
-        cc.latent_channels, cc.out_channels, cc.n_levels = cfg.latent_channels, cfg.out_channels, len(cfg.block_out_channels)
-        for i, v in enumerate(cfg.block_out_channels):
-            cc.block_out_channels[i] = v
-        cc.layers_per_block, cc.norm_num_groups, cc.norm_eps = cfg.layers_per_block, cfg.norm_num_groups, cfg.norm_eps
-        self._handle = self._lib.mx_vae_create(C.byref(cc))
+        self._handle = self._lib.mx_vae_create(C.byref(_config_c(cfg)))
         if not self._handle:
             raise _lib.MxError("mx_vae_create: " + self._lib.mx_last_error().decode())
         self.weights = PackedWeights(pack_vae(cfg, params), self.device)
