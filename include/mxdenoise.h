@@ -872,6 +872,52 @@ int mx_cfg_euler_step_rows(void* stream, const void* gathered, void* latents, co
 int mx_cfg_flow_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next,
                           float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype);
 
+/* ------------------------------------------------------------------------------------------
+ * Inpainting (sduss_amd/csrc/inpaint.hip): repaint the masked part of an image, keep the rest.  diffusers' 4-channel rule of
+ * StableDiffusionXLInpaintPipeline / StableDiffusion3InpaintPipeline, which needs no 9-channel UNet: after every scheduler step
+ *     init_proper = add_noise / scale_noise(image_latents, noise, t_next);   latents = (1 - mask) * init_proper + mask * latents.
+ * ------------------------------------------------------------------------------------------ */
+/* The inpainting rows of one masked step launch.  Plain and inpainting requests step together: row r of the latents is an inpainting row when
+ * slot[r] is in [0, k), and then reads row slot[r] of init / noise / mask.  The slots live in device memory, where the host cannot check them: any
+ * other value (-1 by convention) makes a plain row and is never used as an index. */
+typedef struct {
+  int k;                 /* inpainting rows in this launch; 0 = none (the four pointers are then not read) */
+  const int* slot;       /* device int32 [n_lat]: row -> index in [0, k), or -1 for a plain row */
+  const void* init;      /* [k, C, hw] of dtype: the image's clean latents */
+  const void* noise;     /* [k, C, hw] of dtype: the request's fixed N(0,1) noise */
+  const uint8_t* mask;   /* [k, hw]: non-zero = repaint, 0 = keep */
+} mx_inpaint_rows;
+/* mx_cfg_euler_step / mx_cfg_flow_step with the kept region put back in the same launch.
+ *   noise_pred [2 n_lat | n_lat][C][hw] of `dtype` as for the plain steps (guidance_scale <= 0 reads the first n_lat rows only);
+ *   latents    [n_lat][C][hw] of `dtype`, in place; sigma, sigma_next fp32 [n_lat].
+ * Per element of row r the stepped value is the plain step's, by the same device functions in the same order (sduss_amd/csrc/step_math.h), so a
+ * launch with k = 0 or no slot in [0, k) leaves the bits of the plain step.  Where j = slot[r] is in [0, k) and mask[j][p] == 0 the element becomes
+ *     keep * init[j][c][p] + sigma_next[r] * noise[j][c][p]      keep = 1 (Euler: EulerDiscreteScheduler.add_noise), 1 - sigma_next[r] (flow: scale_noise)
+ * instead: two fp32 products and one sum, each rounded on its own, one rounding to `dtype` at the store; the mask is binary, so the selection equals
+ * (1 - m) a + m b for finite values.  After the last step (sigma_next = 0) that is init itself (a -0 of init may come back as +0).
+ * Refused, with nothing launched: a null operand or `rows`, a non-positive size, a bad dtype, k < 0, k > 0 with a null slot / init / noise / mask.
+ * Offsets are 64-bit.  16-byte accesses when latents, noise_pred, init and noise are 16-byte aligned, the mask is aligned to the elements of a
+ * vector and hw is a whole number of vectors (a vector then lies in one plane and its mask bytes are one load); element accesses otherwise. */
+int mx_cfg_euler_step_masked(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                             int n_lat, int C, int hw, int dtype, const mx_inpaint_rows* rows);
+int mx_cfg_flow_step_masked(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                            int n_lat, int C, int hw, int dtype, const mx_inpaint_rows* rows);
+/* out[r][e] = keep[r] * init[r][e] + sigma[r] * noise[r][e] for n rows of `elems` elements of `dtype`; keep, sigma fp32 [n].  The arithmetic of the kept
+ * region above (one device function): a request's starting latents from its clean latents as they are stored, i.e. already rounded to `dtype`.
+ * Refused: a null operand, a non-positive size, a bad dtype, out == init or out == noise.  16-byte accesses when the three tensors are 16-byte aligned
+ * and elems is a whole number of vectors, element accesses otherwise. */
+int mx_inpaint_renoise(void* stream, const void* init, const void* noise, void* out, const float* keep, const float* sigma, int n, int64_t elems,
+                       int dtype);
+/* A client's mask on the latent grid: mask uint8 [B][H][W] -> out uint8 [B][H / f][W / f], out[b][y][x] = mask[b][f y][f x] >= 128 (1 = repaint, 0 = keep).
+ * diffusers' mask processor: binarise at 0.5 of 255 (exact on bytes: 127 -> 0, 128 -> 1), then the nearest interpolation to the latent grid, which for an
+ * integer factor takes source pixel (f y, f x).  Refused: a null operand, a non-positive size, H or W no multiple of f. */
+int mx_mask_to_latent(void* stream, const uint8_t* mask, uint8_t* out, int B, int H, int W, int f);
+/* Outside the mask the client gets its own pixels back, not their VAE round trip: decoded uint8 [B][H][W][3] in place, pixel (b, y, x) becomes
+ * original's where mask[b][y][x] < 128 (original uint8 [B][H][W][3], mask uint8 [B][H][W], the full-resolution mask as the client sent it).  Any H, W.
+ * Dword accesses over whole groups of four pixels when the three bases are 4-byte aligned, bytes otherwise and for the pixels past the last group.
+ * Refused: a null operand, a non-positive size, decoded == original. */
+int mx_rgb8_paste(void* stream, uint8_t* decoded, const uint8_t* original, const uint8_t* mask, int B, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

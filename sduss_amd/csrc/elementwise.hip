@@ -9,24 +9,9 @@
 // translation unit (HIP's __fmul_rn/__fadd_rn are plain operators in inlined headers and do get contracted; so plain operators here, plus
 // -ffp-contract=off for this file in the Makefile).
 #pragma clang fp contract(off)
+#include "step_math.h"   // load_as_f32 / store_from_f32, cfg_combine, euler_update, flow_update, renoise: shared with inpaint.hip
 
 namespace mx {
-
-template <typename T> __device__ __forceinline__ float load_as_f32(const T* p, long i);
-template <> __device__ __forceinline__ float load_as_f32<float>(const float* p, long i) { return p[i]; }
-template <> __device__ __forceinline__ float load_as_f32<bf16_t>(const bf16_t* p, long i) { return bf16_to_f32(p[i]); }
-template <> __device__ __forceinline__ float load_as_f32<_Float16>(const _Float16* p, long i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void store_from_f32(T* p, long i, float v);
-template <> __device__ __forceinline__ void store_from_f32<float>(float* p, long i, float v) { p[i] = v; }
-template <> __device__ __forceinline__ void store_from_f32<bf16_t>(bf16_t* p, long i, float v) { p[i] = f32_to_bf16(v); }
-template <> __device__ __forceinline__ void store_from_f32<_Float16>(_Float16* p, long i, float v) { p[i] = (_Float16)v; }
-
-// value after a round trip through T (emulates an op whose result tensor has dtype T)
-template <typename T> __device__ __forceinline__ float rnd(float v) {
-  T tmp;
-  store_from_f32<T>(&tmp, 0, v);
-  return load_as_f32<T>(&tmp, 0);
-}
 
 // NCHW latents of any io dtype -> NHWC bf16 with the channel dim zero-padded to CP (=64), so conv_in
 // runs on the same implicit-GEMM kernel as every other conv (unet.py:344).
@@ -126,23 +111,6 @@ __global__ void euler_scale_input_kernel(const T* __restrict__ lat, T* __restric
   store_from_f32<T>(out, idx, load_as_f32<T>(lat, (long)src * elems + e) / denom);
 }
 
-// The per-element arithmetic of the two CFG steps, shared by the kernels over a [2 n, elems] prediction and the ones that read the world
-// gather of the split-batch patch parallelism where it lies (cfg_step_rows_kernel): the same operations in the same order, so the same bits.
-// the combine runs in the model dtype (pipeline_..._esymred.py:383-385; pipeline_stable_diffusion_3_esymred.py:365-367): one rounding per op
-template <typename T> __device__ __forceinline__ float cfg_combine(float u, float t, float g) { return rnd<T>(u + rnd<T>(g * rnd<T>(t - u))); }
-// epsilon Euler step (scheduling_euler_discrete.py:210-268): separate IEEE ops (no fma contraction) so the fp32 chain matches torch's op-by-op evaluation
-__device__ __forceinline__ float euler_update(float x, float eps, float s, float sn) {
-  const float pred_x0 = (x - (s * eps));
-  const float d = ((x - pred_x0) / s);
-  const float step = d * (sn - s);
-  return x + step;
-}
-// flow-match Euler step: x + (sigma_next - sigma) * v
-__device__ __forceinline__ float flow_update(float x, float v, float s, float sn) {
-  const float step = (sn - s) * v;
-  return x + step;
-}
-
 // CFG combine + epsilon Euler step, fp32 math (pipeline_..._esymred.py:382-385; scheduling_euler_discrete.py:210-268)
 template <typename T>
 __global__ void cfg_euler_step_kernel(const T* __restrict__ noise, T* __restrict__ lat, const float* __restrict__ sigma,
@@ -161,9 +129,6 @@ __global__ void cfg_euler_step_kernel(const T* __restrict__ noise, T* __restrict
   const float x = load_as_f32<T>(lat, idx);
   store_from_f32<T>(lat, idx, euler_update(x, eps, sigma[row], sigma_next[row]));
 }
-
-// V elements of T moved as one access (16 bytes on the vector path, one element on the other)
-template <typename T, int V> struct alignas(sizeof(T) * V) elem_vec { T v[V]; };
 
 // The same two steps on the world gather of the split-batch patch parallelism (patch_parallel.py, distri_sdxl_unet_pp.py:163-170), read where it
 // lies: gathered [2 S][n_lat][C][H / S][W], slot k < S the unconditional and slot S + k the conditional prediction of latent rows
@@ -637,9 +602,7 @@ __global__ void vae_latent_finish_kernel(const bf16_t* __restrict__ moments, int
   }
   float lat = (z - shift) * scaling;
   if (start_noise) {
-    const float a = keep[b] * lat;
-    const float n = sigma[b] * load_as_f32<T>(start_noise, idx);
-    lat = a + n;
+    lat = renoise(lat, load_as_f32<T>(start_noise, idx), keep[b], sigma[b]);
   }
   store_from_f32<T>(out, idx, lat);
 }

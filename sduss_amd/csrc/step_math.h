@@ -1,0 +1,56 @@
+// The per-element arithmetic of the scheduler steps, one definition for every translation unit that steps latents (elementwise.hip, inpaint.hip):
+// the io-dtype loads and stores, the CFG combine, the two Euler updates and the re-noising of clean latents.  Every function is a chain of separately
+// rounded IEEE fp32 operations that torch evaluates identically op by op, so an including file must not contract mul + add into FMA: it is built with
+// -ffp-contract=off (Makefile) and the pragma below covers everything that follows the include.
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace mx {
+
+template <typename T> __device__ __forceinline__ float load_as_f32(const T* p, long i);
+template <> __device__ __forceinline__ float load_as_f32<float>(const float* p, long i) { return p[i]; }
+template <> __device__ __forceinline__ float load_as_f32<bf16_t>(const bf16_t* p, long i) { return bf16_to_f32(p[i]); }
+template <> __device__ __forceinline__ float load_as_f32<_Float16>(const _Float16* p, long i) { return (float)p[i]; }
+template <typename T> __device__ __forceinline__ void store_from_f32(T* p, long i, float v);
+template <> __device__ __forceinline__ void store_from_f32<float>(float* p, long i, float v) { p[i] = v; }
+template <> __device__ __forceinline__ void store_from_f32<bf16_t>(bf16_t* p, long i, float v) { p[i] = f32_to_bf16(v); }
+template <> __device__ __forceinline__ void store_from_f32<_Float16>(_Float16* p, long i, float v) { p[i] = (_Float16)v; }
+
+// value after a round trip through T (emulates an op whose result tensor has dtype T)
+template <typename T> __device__ __forceinline__ float rnd(float v) {
+  T tmp;
+  store_from_f32<T>(&tmp, 0, v);
+  return load_as_f32<T>(&tmp, 0);
+}
+
+// V elements of T moved as one access (16 bytes on the vector path, one element on the other)
+template <typename T, int V> struct alignas(sizeof(T) * V) elem_vec { T v[V]; };
+
+// The per-element arithmetic of the two CFG steps, shared by the kernels over a [2 n, elems] prediction, the ones that read the world
+// gather of the split-batch patch parallelism where it lies (cfg_step_rows_kernel) and the masked step of inpainting (cfg_step_masked_kernel): the
+// same operations in the same order, so the same bits.
+// the combine runs in the model dtype (pipeline_..._esymred.py:383-385; pipeline_stable_diffusion_3_esymred.py:365-367): one rounding per op
+template <typename T> __device__ __forceinline__ float cfg_combine(float u, float t, float g) { return rnd<T>(u + rnd<T>(g * rnd<T>(t - u))); }
+// epsilon Euler step (scheduling_euler_discrete.py:210-268): separate IEEE ops (no fma contraction) so the fp32 chain matches torch's op-by-op evaluation
+__device__ __forceinline__ float euler_update(float x, float eps, float s, float sn) {
+  const float pred_x0 = (x - (s * eps));
+  const float d = ((x - pred_x0) / s);
+  const float step = d * (sn - s);
+  return x + step;
+}
+// flow-match Euler step: x + (sigma_next - sigma) * v
+__device__ __forceinline__ float flow_update(float x, float v, float s, float sn) {
+  const float step = (sn - s) * v;
+  return x + step;
+}
+// clean latents noised to a sigma: keep * init + sigma * noise, two products and one sum (EulerDiscreteScheduler.add_noise: keep = 1; the flow-match
+// scale_noise: keep = 1 - sigma).  The start noise of an image-to-image request (vae_latent_finish_kernel) and the kept region of an inpainting one.
+__device__ __forceinline__ float renoise(float init, float noise, float keep, float sigma) {
+  const float a = keep * init;
+  const float n = sigma * noise;
+  return a + n;
+}
+
+}  // namespace mx

@@ -168,6 +168,11 @@ class VAEEncodeArgs(C.Structure):
                 ("scaling_factor", C.c_float), ("shift_factor", C.c_float)]
 
 
+class InpaintRows(C.Structure):
+    """mx_inpaint_rows: the inpainting rows of one masked step launch"""
+    _fields_ = [("k", C.c_int), ("slot", C.c_void_p), ("init", C.c_void_p), ("noise", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class WeightEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -291,6 +296,11 @@ SYMBOLS = {
     "mx_cfg_euler_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i64, _i]),
     "mx_cfg_euler_step_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
     "mx_cfg_flow_step_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
+    "mx_cfg_euler_step_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, C.POINTER(InpaintRows)]),
+    "mx_cfg_flow_step_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, C.POINTER(InpaintRows)]),
+    "mx_inpaint_renoise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i]),
+    "mx_mask_to_latent": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "mx_rgb8_paste": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
 }
 
 _lib: Optional[C.CDLL] = None

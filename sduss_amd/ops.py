@@ -1,5 +1,5 @@
 """Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
-mx_layernorm, mx_groupnorm_nhwc, scheduler steps).  They allocate outputs with torch and pass raw pointers + the current
+mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
 
@@ -435,3 +435,103 @@ def cfg_flow_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: to
                         guidance_scale: float, n_slabs: int) -> torch.Tensor:
     """The flow-match step on the same layout (mx_cfg_flow_step_rows)."""
     return _cfg_step_rows_("mx_cfg_flow_step_rows", gathered, latents, sigma, sigma_next, guidance_scale, n_slabs)
+
+
+# ---- inpainting (csrc/inpaint.hip) ----
+
+def _need(cond: bool, what: str) -> None:
+    if not cond:
+        raise _lib.MxError(what)
+
+
+def _cfg_step_masked_(fn_name: str, noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                      guidance_scale: float, slot: Optional[torch.Tensor], init: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                      mask: Optional[torch.Tensor]) -> torch.Tensor:
+    l = _lib.load()
+    _need(latents.ndim == 4 and latents.is_contiguous(), f"{fn_name}: latents must be a contiguous [n, C, h, w] tensor")
+    n_lat, c, h, w = latents.shape
+    rows = (2 if guidance_scale > 0 else 1) * n_lat
+    _need(noise_pred.is_contiguous() and noise_pred.dtype == latents.dtype and noise_pred.device == latents.device
+          and noise_pred.numel() == rows * c * h * w, f"{fn_name}: the prediction must be contiguous [{rows}, {c}, {h}, {w}] of the latents' dtype")
+    for name, t in (("sigma", sigma), ("sigma_next", sigma_next)):
+        _need(t.numel() == n_lat, f"{fn_name}: {name} must hold one value per latent row")
+    r = _lib.InpaintRows()
+    if init is not None:
+        k = init.shape[0]
+        _need(slot is not None and noise is not None and mask is not None, f"{fn_name}: inpainting rows need slot, init, noise and mask")
+        _need(slot.dtype == torch.int32 and slot.numel() == n_lat and slot.is_contiguous() and slot.device == latents.device,
+              f"{fn_name}: slot must be a contiguous int32 [{n_lat}] on the latents' device")
+        for name, t in (("init", init), ("noise", noise)):
+            _need(t.dtype == latents.dtype and tuple(t.shape) == (k, c, h, w) and t.is_contiguous() and t.device == latents.device,
+                  f"{fn_name}: {name} must be contiguous [{k}, {c}, {h}, {w}] of the latents' dtype, got {t.dtype} {tuple(t.shape)}")
+        _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (k, h, w) and mask.is_contiguous() and mask.device == latents.device,
+              f"{fn_name}: mask must be contiguous uint8 [{k}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+        r.k, r.slot, r.init, r.noise, r.mask = k, slot.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr()
+    else:
+        _need(slot is None and noise is None and mask is None, f"{fn_name}: slot, noise and mask come with init")
+    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
+    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+    _lib.check(getattr(l, fn_name)(_lib.current_stream(), noise_pred.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
+                                   float(guidance_scale), n_lat, c, h * w, _lib.torch_dtype_code(latents.dtype), C.byref(r)), fn_name)
+    return latents
+
+
+def cfg_euler_step_masked_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float,
+                           slot: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                           mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: cfg_euler_step_ on latents [n, C, h, w] with the kept region of the inpainting rows put back in the same launch
+    (mx_cfg_euler_step_masked).  slot int32 [n]: row -> its row of init / noise [k, C, h, w] and mask uint8 [k, h, w] (non-zero = repaint), or -1 for a
+    plain row; where the mask is 0 the element becomes init + sigma_next * noise.  Without init every row is plain."""
+    return _cfg_step_masked_("mx_cfg_euler_step_masked", noise_pred, latents, sigma, sigma_next, guidance_scale, slot, init, noise, mask)
+
+
+def cfg_flow_step_masked_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float,
+                          slot: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                          mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The flow-match step on the same layout: kept elements become (1 - sigma_next) * init + sigma_next * noise (mx_cfg_flow_step_masked)."""
+    return _cfg_step_masked_("mx_cfg_flow_step_masked", noise_pred, latents, sigma, sigma_next, guidance_scale, slot, init, noise, mask)
+
+
+def inpaint_renoise(init: torch.Tensor, noise: torch.Tensor, keep, sigma) -> torch.Tensor:
+    """keep[r] * init[r] + sigma[r] * noise[r] over the rows of init [n, ...], fp32 ops rounded once to init's dtype (mx_inpaint_renoise);
+    keep / sigma: fp32 [n] tensors or scalars."""
+    l = _lib.load()
+    _need(init.is_cuda and init.ndim >= 2 and init.is_contiguous(), "mx_inpaint_renoise: init must be a contiguous CUDA tensor [n, ...]")
+    _need(noise.dtype == init.dtype and noise.shape == init.shape and noise.is_contiguous() and noise.device == init.device,
+          f"mx_inpaint_renoise: noise must be contiguous {tuple(init.shape)} of dtype {init.dtype}, got {noise.dtype} {tuple(noise.shape)}")
+    n = init.shape[0]
+    scal = []
+    for name, t in (("keep", keep), ("sigma", sigma)):
+        t = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+        _need(t.numel() in (1, n), f"mx_inpaint_renoise: {name} must hold one value, or one per row")
+        scal.append(t.to(init.device).expand(n).contiguous())
+    out = torch.empty_like(init)
+    _lib.check(l.mx_inpaint_renoise(_lib.current_stream(), init.data_ptr(), noise.data_ptr(), out.data_ptr(), scal[0].data_ptr(), scal[1].data_ptr(),
+                                    n, init[0].numel(), _lib.torch_dtype_code(init.dtype)), "mx_inpaint_renoise")
+    return out
+
+
+def mask_to_latent(mask: torch.Tensor, factor: int) -> torch.Tensor:
+    """a client's mask uint8 [B, H, W] -> uint8 [B, H / factor, W / factor] of 0 / 1: mask[b, factor y, factor x] >= 128 (mx_mask_to_latent)"""
+    l = _lib.load()
+    _need(mask.is_cuda and mask.dtype == torch.uint8 and mask.ndim == 3 and mask.is_contiguous(),
+          f"mx_mask_to_latent: expected a contiguous CUDA uint8 [B, H, W] mask, got {mask.dtype} {tuple(mask.shape)}")
+    b, h, w = mask.shape
+    _need(factor > 0 and h % factor == 0 and w % factor == 0, f"mx_mask_to_latent: {h} x {w} is no multiple of the factor {factor}")
+    out = torch.empty((b, h // factor, w // factor), dtype=torch.uint8, device=mask.device)
+    _lib.check(l.mx_mask_to_latent(_lib.current_stream(), mask.data_ptr(), out.data_ptr(), b, h, w, int(factor)), "mx_mask_to_latent")
+    return out
+
+
+def rgb8_paste_(decoded: torch.Tensor, original: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """In place: decoded uint8 [B, H, W, 3] takes original's pixel wherever mask uint8 [B, H, W] is below 128 (mx_rgb8_paste)"""
+    l = _lib.load()
+    _need(decoded.is_cuda and decoded.dtype == torch.uint8 and decoded.ndim == 4 and decoded.shape[-1] == 3 and decoded.is_contiguous(),
+          f"mx_rgb8_paste: expected a contiguous CUDA uint8 [B, H, W, 3] image, got {decoded.dtype} {tuple(decoded.shape)}")
+    b, h, w, _c = decoded.shape
+    _need(original.dtype == torch.uint8 and original.shape == decoded.shape and original.is_contiguous() and original.device == decoded.device,
+          f"mx_rgb8_paste: the original must be contiguous uint8 {tuple(decoded.shape)}, got {original.dtype} {tuple(original.shape)}")
+    _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (b, h, w) and mask.is_contiguous() and mask.device == decoded.device,
+          f"mx_rgb8_paste: the mask must be contiguous uint8 [{b}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+    _lib.check(l.mx_rgb8_paste(_lib.current_stream(), decoded.data_ptr(), original.data_ptr(), mask.data_ptr(), b, h, w), "mx_rgb8_paste")
+    return decoded

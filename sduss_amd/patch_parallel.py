@@ -347,6 +347,8 @@ class PatchParallelDenoiser:
 
     @torch.inference_mode()
     def step(self, req) -> None:
+        if getattr(req, "inpaint", None) is not None:        # the step on the gather buffer has no masked form
+            raise _lib.MxError("inpainting is not available under patch parallelism")
         e = self._cache.entry((req.resolution, req.request_id, id(req)), [req], lambda: self.hooks._cond([req], True))
         lat = self._cache.latents(e, [req])
         sig, sig_next, ts = self._cache.step_scalars(e, [req])

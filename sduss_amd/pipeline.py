@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .step_state import StepCache, new_uid
+from .lib import MxError
+from .step_state import StepCache, _upload, new_uid
 from .unet import MxUNet
 
 
@@ -33,6 +34,18 @@ def euler_tables(num_inference_steps: int, num_train_timesteps: int = 1000, beta
     sigmas = np.interp(timesteps, np.arange(0, len(sig)), sig)
     sigmas = np.concatenate([sigmas, [0.0]]).astype(np.float32)
     return timesteps, sigmas, float((sigmas.max() ** 2 + 1) ** 0.5)
+
+
+@dataclass
+class InpaintState:
+    """What an inpainting request carries beside its latents (Denoiser.start_inpaint): after every step the kept region of the latents becomes
+    ``init`` noised with ``noise`` to the step's next sigma."""
+    init: torch.Tensor                    # [1, C, h, w] model dtype: the image's clean latents
+    noise: torch.Tensor                   # [1, C, h, w] model dtype: the request's fixed N(0, 1) noise
+    mask: torch.Tensor                    # uint8 [1, h, w] on the latent grid: 1 = repaint, 0 = keep
+    image_u8: Optional[torch.Tensor]      # uint8 [1, H, W, 3]: the client's image (None when it came as floats)
+    mask_u8: torch.Tensor                 # uint8 [1, H, W]: the client's mask, >= 128 = repaint
+    paste: bool                           # post_inference gives the client's own pixels back outside the mask
 
 
 @dataclass
@@ -54,6 +67,7 @@ class Request:
     arrival: float = 0.0
     start: Optional[float] = None
     finish: Optional[float] = None
+    inpaint: Optional[InpaintState] = None
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -82,7 +96,8 @@ def start_step(num_inference_steps: int, strength: float) -> int:
 class Denoiser:
     """One ``denoising_step`` over a heterogeneous batch of requests, for either model.  A subclass says which request fields make the
     conditioning (``_cond``), how the model input is made from the latents (``_scale_input``), which scheduler step follows
-    (``_scheduler_step``; ``_scheduler_step_rows`` on a patch-parallel gather buffer), how its model slot is called (``_forward``,
+    (``_scheduler_step``; ``_scheduler_step_rows`` on a patch-parallel gather buffer; ``_scheduler_step_masked`` for a resolution with inpainting
+    requests), how its model slot is called (``_forward``,
     ``_forward_mixed``) and whether a batch composition is announced to it (``announces_composition``: MxUNet.set_context_key)."""
     announces_composition = False
 
@@ -167,6 +182,51 @@ class Denoiser:
         req.latents = enc(image, posterior_noise=posterior_noise, start_noise=start_noise, keep=float(keep), sigma=float(sigma))
         req.step_index = t_start
 
+    def _inpaint_start_mix(self, req, t_start: int, strength: float) -> tuple:
+        """(keep, sigma) of an inpainting request's starting latents = keep * init + sigma * noise"""
+        return self._start_mix(np.float32(req.sigmas[t_start]))
+
+    def start_inpaint(self, req, encoder, image: torch.Tensor, mask: torch.Tensor, strength: float = 1.0, posterior_noise: Optional[torch.Tensor] = None,
+                      noise: Optional[torch.Tensor] = None, paste: bool = False) -> None:
+        """Make ``req`` an inpainting request (diffusers' 4-channel rule, for the base checkpoints): the part of ``image`` where ``mask`` (uint8
+        [1, H, W] as a client sends it) is >= 128 is repainted, the rest is kept.  ``image`` as for ``start_from_image``.  ONE call of the encoder,
+        with no start noise: its result, the clean latents in the model dtype, stays on the request (``req.inpaint.init``, diffusers' image_latents)
+        beside the fixed ``noise`` (N(0, 1) shaped as the latents; drawn here when None) and the mask on the latent grid.  The request starts at step
+        t_start = ``start_step(steps, strength)`` from init noised to that step's sigma; at strength >= 1 from pure noise (is_strength_max).  Every
+        step then puts the kept region back inside its scheduler launch (``_scheduler_step_masked``).  ``paste``: post_inference returns the
+        client's own pixels outside the mask, which needs the uint8 image."""
+        u8 = image.dtype == torch.uint8
+        if paste and not u8:
+            raise MxError("start_inpaint: paste=True needs the client's uint8 [1, H, W, 3] image")
+        h, w = (image.shape[1], image.shape[2]) if u8 else (image.shape[2], image.shape[3])
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (image.shape[0], h, w):
+            raise MxError(f"start_inpaint: expected a uint8 mask {(image.shape[0], h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+        self.set_timesteps(req)
+        t_start = start_step(req.num_inference_steps, strength)
+        f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
+        init = (encoder.encode_images if u8 else encoder.encode)(image, posterior_noise=posterior_noise)
+        mask_u8 = mask.to(encoder.device).contiguous()
+        if noise is None:
+            noise = torch.randn(init.shape, device=encoder.device, dtype=encoder.out_dtype)
+        noise = noise.to(device=encoder.device, dtype=encoder.out_dtype).contiguous()
+        req.inpaint = InpaintState(init, noise, ops.mask_to_latent(mask_u8, f), image.to(encoder.device).contiguous() if u8 else None, mask_u8, paste)
+        req.latents = ops.inpaint_renoise(init, noise, *self._inpaint_start_mix(req, t_start, strength))
+        req.step_index = t_start
+
+    @staticmethod
+    def _inpaint_rows(reqs) -> Optional[tuple]:
+        """(slot, init, noise, mask) of one resolution's requests as the masked step reads them: the inpainting requests' tensors packed in batch
+        order and, per batch row, its index among them or -1 (mx_inpaint_rows).  None when no request inpaints."""
+        states = [getattr(r, "inpaint", None) for r in reqs]
+        rows = [s for s in states if s is not None]
+        if not rows:
+            return None
+        order = iter(range(len(rows)))
+        slot = [next(order) if s is not None else -1 for s in states]
+        dev = rows[0].init.device
+        return (_upload(torch.tensor(slot, dtype=torch.int32), dev), torch.cat([s.init for s in rows], dim=0).contiguous(),
+                torch.cat([s.noise for s in rows], dim=0).contiguous(), torch.cat([s.mask for s in rows], dim=0).contiguous())
+
     def _gather(self, res: str, reqs: list, do_classifier_free_guidance: bool) -> _Part:
         """the per-resolution gather of :287-339 through the per-composition cache, and the model's input rows (:357-360 + the cat of :327).
         Embeddings are fixed for a request's lifetime: one cat per batch composition, not per step."""
@@ -174,7 +234,7 @@ class Denoiser:
         for r in reqs:                                                   # latents may have been produced on another stream
             r.latents.record_stream(here)
         e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs)), reqs,
-                              lambda: self._cond(reqs, do_classifier_free_guidance))
+                              lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs))
         lat = self._cache.latents(e, reqs)
         sig, sig_next, ts = self._cache.step_scalars(e, reqs)
         return _Part(res, reqs, e, lat, sig, sig_next, torch.cat([ts, ts], dim=0) if do_classifier_free_guidance else ts,
@@ -212,7 +272,10 @@ class Denoiser:
             noise = self._forward_mixed([p.x_in for p in parts], ts, cond, patch_size // 8 if is_sliced else 0)
         g = self.guidance_scale if do_classifier_free_guidance else 0.0
         for p, nz in zip(parts, noise):
-            self._scheduler_step(nz, p.latents, p.sigma, p.sigma_next, g)          # :382-397
+            if p.entry.inpaint is None:
+                self._scheduler_step(nz, p.latents, p.sigma, p.sigma_next, g)      # :382-397
+            else:                                                                  # the same step, the kept region of the inpainting rows put back
+                self._scheduler_step_masked(nz, p.latents, p.sigma, p.sigma_next, g, *p.entry.inpaint)
             for i, r in enumerate(p.reqs):                                         # :399-403
                 r.step_index += 1
                 r.latents = p.latents[i:i + 1]
@@ -258,6 +321,12 @@ class SDXLDenoiser(Denoiser):
 
     _scheduler_step = staticmethod(ops.cfg_euler_step_)
     _scheduler_step_rows = staticmethod(ops.cfg_euler_step_rows_)
+    _scheduler_step_masked = staticmethod(ops.cfg_euler_step_masked_)
+
+    def _inpaint_start_mix(self, req, t_start: int, strength: float) -> tuple:
+        if strength >= 1.0:                                  # is_strength_max: pure noise times init_noise_sigma, nothing of the image
+            return np.float32(0.0), np.float32(self.init_noise_sigma(req.num_inference_steps))
+        return super()._inpaint_start_mix(req, t_start, strength)
 
     def _forward(self, x: Dict[str, torch.Tensor], ts, cond, **kwargs) -> Dict[str, torch.Tensor]:
         ehs, pooled, tids = cond

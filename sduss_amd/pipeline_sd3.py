@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .pipeline import Denoiser, _synthetic_embeds
+from .pipeline import Denoiser, InpaintState, _synthetic_embeds
 from .transformer_sd3 import MxSD3Transformer
 
 
@@ -44,6 +44,7 @@ class SD3Request:
     arrival: float = 0.0
     start: Optional[float] = None
     finish: Optional[float] = None
+    inpaint: Optional[InpaintState] = None
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -74,6 +75,7 @@ class SD3Denoiser(Denoiser):
 
     _scheduler_step = staticmethod(ops.cfg_flow_step_)                 # :362-372
     _scheduler_step_rows = staticmethod(ops.cfg_flow_step_rows_)
+    _scheduler_step_masked = staticmethod(ops.cfg_flow_step_masked_)
 
     def _forward(self, x: Dict[str, torch.Tensor], ts, cond, **kwargs) -> Dict[str, torch.Tensor]:
         ehs, pooled = cond

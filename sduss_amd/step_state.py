@@ -11,7 +11,7 @@ skips a request (bench.py keeps its batch full by resetting step_index) is follo
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Callable, List, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -25,7 +25,7 @@ def _upload(host: torch.Tensor, device) -> torch.Tensor:
 
 
 class _Entry:
-    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid")
+    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid", "inpaint")
 
 _next_uid = [0]
 
@@ -42,7 +42,9 @@ class StepCache:
         self.max_entries = max_entries
         self._entries: "OrderedDict[tuple, _Entry]" = OrderedDict()
 
-    def entry(self, key: tuple, reqs: Sequence, build_cond: Callable[[], tuple]) -> _Entry:
+    def entry(self, key: tuple, reqs: Sequence, build_cond: Callable[[], tuple], build_inpaint: Optional[Callable[[], tuple]] = None) -> _Entry:
+        """the entry of a batch composition, built on first use.  ``build_inpaint``: the packed rows of its inpainting requests (Denoiser._inpaint_rows;
+        None for a composition without one), fixed for the composition like ``cond``."""
         e = self._entries.get(key)
         if e is not None:
             self._entries.move_to_end(key)
@@ -50,6 +52,7 @@ class StepCache:
         e = _Entry()
         e.uid = new_uid()
         e.cond = build_cond()
+        e.inpaint = build_inpaint() if build_inpaint is not None else None
         n = len(reqs)
         s_max = max(len(r.timesteps) for r in reqs)
         tab = np.zeros((3, n, s_max), dtype=np.float32)

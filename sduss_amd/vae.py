@@ -11,6 +11,7 @@ from typing import Dict, List, Tuple
 import torch
 
 from . import lib as _lib
+from . import ops
 from .model_slot import _grow_only
 from .weights import PackedWeights, _conv_pack
 
@@ -295,7 +296,8 @@ OUTPUT_TYPES = ("pt", "uint8", "pil")
 def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list], output_type: str = "pt") -> Dict[str, object]:
     """mirror of post_inference (:406-463): gather the finished requests' latents per resolution, decode, postprocess.
       "pt"     {resolution: fp32 images [n, 3, res, res] in [0, 1]} on the device (the tensor stage);
-      "uint8"  {resolution: uint8 images [n, res, res, 3]} on the device (MxVAEDecoder.decode_images);
+      "uint8"  {resolution: uint8 images [n, res, res, 3]} on the device (MxVAEDecoder.decode_images); an inpainting request with
+               ``inpaint.paste`` keeps the client's own pixels outside its mask (mx_rgb8_paste);
       "pil"    {resolution: [PIL.Image, ...]}, the reference's default: the "uint8" images through the decoder's pinned host buffer."""
     if output_type not in OUTPUT_TYPES:
         raise ValueError(f"post_inference: output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
@@ -304,7 +306,14 @@ def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list], output_type:
         if not reqs:
             continue
         lat = torch.cat([r.latents for r in reqs], dim=0)
-        images[res] = (vae.decode(lat) / 2 + 0.5).clamp(0, 1) if output_type == "pt" else vae.decode_images(lat)
+        if output_type == "pt":
+            images[res] = (vae.decode(lat) / 2 + 0.5).clamp(0, 1)
+            continue
+        images[res] = vae.decode_images(lat)
+        for i, r in enumerate(reqs):       # an inpainting request that asked for it gets its own pixels back outside the mask, on the device
+            s = getattr(r, "inpaint", None)
+            if s is not None and s.paste:
+                ops.rgb8_paste_(images[res][i:i + 1], s.image_u8, s.mask_u8)
     if output_type == "pil":
         from PIL import Image
         return {res: [Image.fromarray(a) for a in arr] for res, arr in vae.images_to_host(images).items()}      # (an RGB fromarray copies)
