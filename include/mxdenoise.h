@@ -918,6 +918,40 @@ int mx_mask_to_latent(void* stream, const uint8_t* mask, uint8_t* out, int B, in
  * Refused: a null operand, a non-positive size, decoded == original. */
 int mx_rgb8_paste(void* stream, uint8_t* decoded, const uint8_t* original, const uint8_t* mask, int B, int H, int W);
 
+/* ------------------------------------------------------------------------------------------
+ * Resize of a client's 8-bit image or mask to the request's resolution (sduss_amd/csrc/image_resize.hip, resize_coeffs.cpp), bit-equal to
+ * Pillow's Image.resize for modes "RGB" and "L" -- what diffusers' VaeImageProcessor.preprocess does in front of the VAE, and its mask
+ * processor in front of the binarisation.  Pillow's 8-bit resampler (ImagingResample) is integer arithmetic on integer coefficient tables:
+ *   per axis, scale = in / out, fs = max(scale, 1), support = filter_support * fs, and per output index xx (all in double, int() truncates)
+ *     center = (xx + 0.5) * scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in), n = xmax - xmin,
+ *     w[j] = filter((j + xmin - center + 0.5) * (1 / fs)) for j < n, ww = sum of w[j] in index order, w[j] /= ww when ww != 0,
+ *     k[j] = int(w[j] * 2^22 +- 0.5) (- for negative w);
+ *   one output byte = clip(((1 << 21) + sum_j src[xmin + j] * k[j]) >> 22, 0, 255), int32 sum, arithmetic shift;
+ *   horizontal first into bytes, then vertical over those bytes; a pass whose in == out is skipped; channels are independent.
+ * The filter values double as PIL.Image.Resampling's.
+ * ------------------------------------------------------------------------------------------ */
+#define MX_RESIZE_LANCZOS 1     /* sinc(x) sinc(x / 3) on -3 <= x < 3, support 3 */
+#define MX_RESIZE_BILINEAR 2    /* support 1 */
+#define MX_RESIZE_BICUBIC 3     /* a = -0.5, support 2 */
+#define MX_RESIZE_PRECISION_BITS 22
+#define MX_RESIZE_MAX_SIZE (1 << 24)
+/* One axis' tables on the host, no GPU needed: bounds[out][2] = (xmin, n) and k[out][ksize] with ksize = 2 * ceil(support) + 1 (entries past n are
+ * zero); `cap` = the int32 entries k holds.  Returns ksize; with bounds == k == NULL that is all it does (the size query).  Returns -1, with
+ * the reason in the last error, for a size outside [1, MX_RESIZE_MAX_SIZE], an unknown filter, one null table, or cap < out * ksize.  The device
+ * never evaluates a filter: these tables, uploaded once, are the only source of coefficients. */
+int mx_resize_coeffs(int in, int out, int filter, int32_t* bounds, int32_t* k, int cap);
+/* A resize plan: both axes' tables in library-owned device memory (built and uploaded here, once, off the hot path; an axis whose in == out gets
+ * the identity table, which copies exactly) and the tile shape the launch uses.  NULL, with the reason in the last error, for a non-positive
+ * or too large size, an unknown filter, a failed allocation or copy, or a downscale so steep (thousands to one) that the
+ * input bytes under the taps of four output bytes of one row do not fit a workgroup's LDS. */
+typedef struct mx_resize mx_resize;
+mx_resize* mx_resize_create(int in_h, int in_w, int out_h, int out_w, int filter);
+void mx_resize_destroy(mx_resize* r);
+/* src uint8 [B][in_h][in_w][C] -> dst uint8 [B][out_h][out_w][C], C = 1 or 3, both passes in ONE launch: the horizontally filtered bytes live in
+ * LDS only.  No allocation, copy or synchronisation inside the call; any alignment of src and dst (whole-dword accesses where a row allows them).
+ * Refused, with nothing launched: a null operand, B <= 0, C other than 1 or 3, src == dst, more tiles than one launch holds. */
+int mx_resize_u8(mx_resize* r, void* stream, const uint8_t* src, uint8_t* dst, int B, int C);
+
 #ifdef __cplusplus
 }
 #endif

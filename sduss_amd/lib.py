@@ -159,6 +159,7 @@ class VAEConfigC(C.Structure):
 
 
 IMAGE_RGB8_HWC, IMAGE_F32_CHW = 0, 1
+RESIZE_FILTERS = {"lanczos": 1, "bilinear": 2, "bicubic": 3}      # MX_RESIZE_*: PIL.Image.Resampling's values
 
 
 class VAEEncodeArgs(C.Structure):
@@ -301,6 +302,10 @@ SYMBOLS = {
     "mx_inpaint_renoise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i]),
     "mx_mask_to_latent": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "mx_rgb8_paste": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
+    "mx_resize_coeffs": (_i, [_i, _i, _i, _vp, _vp, _i]),
+    "mx_resize_create": (_vp, [_i, _i, _i, _i, _i]),
+    "mx_resize_destroy": (None, [_vp]),
+    "mx_resize_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,8 +1,9 @@
 """Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
-mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries).  They allocate outputs with torch and pass raw pointers + the current
+mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries, the image resize).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Optional
 
@@ -535,3 +536,48 @@ def rgb8_paste_(decoded: torch.Tensor, original: torch.Tensor, mask: torch.Tenso
           f"mx_rgb8_paste: the mask must be contiguous uint8 [{b}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
     _lib.check(l.mx_rgb8_paste(_lib.current_stream(), decoded.data_ptr(), original.data_ptr(), mask.data_ptr(), b, h, w), "mx_rgb8_paste")
     return decoded
+
+
+class _ResizePlans:
+    """mx_resize plans of one device, least recently used out first: a serving slot sees a handful of (client size, request size) pairs"""
+    CAPACITY = 16
+
+    def __init__(self):
+        self._plans = collections.OrderedDict()
+
+    def get(self, key: tuple) -> int:
+        l = _lib.load()
+        h = self._plans.get(key)
+        if h is not None:
+            self._plans.move_to_end(key)
+            return h
+        h = l.mx_resize_create(*key)
+        if not h:
+            _lib.check(1, "mx_resize_create")
+        self._plans[key] = h
+        if len(self._plans) > self.CAPACITY:
+            # the evicted plan's tables may still be read by a launch in flight: hipFree waits for the device before it releases them
+            l.mx_resize_destroy(self._plans.popitem(last=False)[1])
+        return h
+
+
+_resize_plans = {}
+
+
+def resize_u8(x: torch.Tensor, size, resample: str = "lanczos") -> torch.Tensor:
+    """uint8 [B, H, W, 3] or [B, H, W] -> [B, size[0], size[1](, 3)], bit-equal to Pillow's Image.resize((size[1], size[0]), resample) of every
+    image (mx_resize_u8: both passes in one launch); ``resample``: "lanczos" (diffusers' VaeImageProcessor default), "bicubic" or "bilinear".
+    The plan (the coefficient tables in device memory) is made on first use and kept per device."""
+    l = _lib.load()
+    _need(x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and (x.ndim == 3 or (x.ndim == 4 and x.shape[-1] == 3)),
+          f"mx_resize_u8: expected a contiguous CUDA uint8 [B, H, W, 3] or [B, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    _need(resample in _lib.RESIZE_FILTERS, f"mx_resize_u8: resample must be one of {sorted(_lib.RESIZE_FILTERS)}, got {resample!r}")
+    oh, ow = (int(s) for s in size)
+    b, h, w = x.shape[:3]
+    _need(b > 0 and h > 0 and w > 0 and oh > 0 and ow > 0, f"mx_resize_u8: sizes must be positive, got {tuple(x.shape)} -> {(oh, ow)}")
+    c = 3 if x.ndim == 4 else 1
+    with torch.cuda.device(x.device):
+        plan = _resize_plans.setdefault(x.device.index, _ResizePlans()).get((h, w, oh, ow, _lib.RESIZE_FILTERS[resample]))
+        out = torch.empty((b, oh, ow) + tuple(x.shape[3:]), dtype=torch.uint8, device=x.device)
+        _lib.check(l.mx_resize_u8(plan, _lib.current_stream(), x.data_ptr(), out.data_ptr(), b, c), "mx_resize_u8")
+    return out

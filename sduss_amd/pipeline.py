@@ -164,13 +164,24 @@ class Denoiser:
         """(keep, sigma) of the start step's noise: latents = keep * clean + sigma * noise"""
         raise NotImplementedError
 
+    @staticmethod
+    def _resize_client_u8(what: str, t: torch.Tensor, size, resample: str, device) -> torch.Tensor:
+        """a client's uint8 image [1, H, W, 3] or mask [1, H, W] at the request's (H, W): Pillow's resize on the device (ops.resize_u8)"""
+        if t.dtype != torch.uint8:
+            raise MxError(f"{what}: size= resizes the client's uint8 image; a float image must come at the request's resolution")
+        return ops.resize_u8(t.to(device).contiguous(), size, resample)
+
     def start_from_image(self, req, encoder, image: torch.Tensor, strength: float, posterior_noise: Optional[torch.Tensor] = None,
-                         start_noise: Optional[torch.Tensor] = None) -> None:
+                         start_noise: Optional[torch.Tensor] = None, size=None, resample: str = "lanczos") -> None:
         """Make ``req`` an image-to-image request: it starts at step t_start = ``start_step(steps, strength)`` of its schedule from the latents of
         ``image`` (uint8 [1, H, W, 3] as a client sends it, or float [1, 3, H, W] in [-1, 1]) noised to that step's sigma.  ONE call of the
         encoder (vae.MxVAEEncoder): posterior (its mode; its sample with ``posterior_noise``), latent scaling and the start noise leave its last
         launch together.  ``start_noise``: N(0, 1) shaped as the latents; drawn here when None.  The step itself does not change: a batch already
-        holds requests at different ``step_index``."""
+        holds requests at different ``step_index``.  ``size`` = (H, W): the uint8 image comes at the client's size and is resized to the request's
+        first, as diffusers' VaeImageProcessor.preprocess does with Pillow (``resample``: "lanczos" | "bicubic" | "bilinear"), on the device and
+        to the same bytes; None: the image has the request's size already."""
+        if size is not None:
+            image = self._resize_client_u8("start_from_image", image, size, resample, encoder.device)
         self.set_timesteps(req)
         t_start = start_step(req.num_inference_steps, strength)
         keep, sigma = self._start_mix(np.float32(req.sigmas[t_start]))
@@ -187,14 +198,22 @@ class Denoiser:
         return self._start_mix(np.float32(req.sigmas[t_start]))
 
     def start_inpaint(self, req, encoder, image: torch.Tensor, mask: torch.Tensor, strength: float = 1.0, posterior_noise: Optional[torch.Tensor] = None,
-                      noise: Optional[torch.Tensor] = None, paste: bool = False) -> None:
+                      noise: Optional[torch.Tensor] = None, paste: bool = False, size=None, resample: str = "lanczos") -> None:
         """Make ``req`` an inpainting request (diffusers' 4-channel rule, for the base checkpoints): the part of ``image`` where ``mask`` (uint8
         [1, H, W] as a client sends it) is >= 128 is repainted, the rest is kept.  ``image`` as for ``start_from_image``.  ONE call of the encoder,
         with no start noise: its result, the clean latents in the model dtype, stays on the request (``req.inpaint.init``, diffusers' image_latents)
         beside the fixed ``noise`` (N(0, 1) shaped as the latents; drawn here when None) and the mask on the latent grid.  The request starts at step
         t_start = ``start_step(steps, strength)`` from init noised to that step's sigma; at strength >= 1 from pure noise (is_strength_max).  Every
         step then puts the kept region back inside its scheduler launch (``_scheduler_step_masked``).  ``paste``: post_inference returns the
-        client's own pixels outside the mask, which needs the uint8 image."""
+        client's own pixels outside the mask, which needs the uint8 image.  ``size`` = (H, W): image and mask come at the client's size and are
+        resized to the request's first (``start_from_image``), the mask as a grey image by the same filter -- diffusers' mask processor, whose
+        binarisation is then the >= 128 rule on the resized mask; the request keeps the resized pair, so ``paste`` works at the request's size."""
+        if size is not None:
+            client = tuple(image.shape[:3])
+            image = self._resize_client_u8("start_inpaint", image, size, resample, encoder.device)
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != client:
+                raise MxError(f"start_inpaint: expected a uint8 mask {client}, got {mask.dtype} {tuple(mask.shape)}")
+            mask = ops.resize_u8(mask.to(encoder.device).contiguous(), size, resample)
         u8 = image.dtype == torch.uint8
         if paste and not u8:
             raise MxError("start_inpaint: paste=True needs the client's uint8 [1, H, W, 3] image")
