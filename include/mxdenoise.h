@@ -952,6 +952,58 @@ void mx_resize_destroy(mx_resize* r);
  * Refused, with nothing launched: a null operand, B <= 0, C other than 1 or 3, src == dst, more tiles than one launch holds. */
 int mx_resize_u8(mx_resize* r, void* stream, const uint8_t* src, uint8_t* dst, int B, int C);
 
+/* ------------------------------------------------------------------------------------------
+ * Inpainting only the masked region of a client-size photo (sduss_amd/csrc/inpaint_overlay.hip, inpaint_region.cpp): diffusers'
+ * VaeImageProcessor.blur, get_crop_region and apply_overlay, which are Pillow calls on the host there.  All of it is integer arithmetic on bytes
+ * and bit-equal to Pillow.
+ * ------------------------------------------------------------------------------------------ */
+#define MX_BLUR_MAX_RADIUS 1024
+#define MX_BLUR_MAX_WIDTH 16384    /* a row and its blurred copy live in a workgroup's LDS */
+/* The box of Pillow's ImageFilter.GaussianBlur(radius) (src/libImaging/BoxBlur.c), host only, no GPU needed.  Pillow blurs with three box passes
+ * per axis; one pass over a line in[0..n) is
+ *     out[x] = (ww * sum_{d=-r..r} in[clamp(x + d)] + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + 2^23) >> 24,   clamp to [0, n - 1],
+ * with, in single precision and in this order,
+ *     sigma2 = radius * radius / 3;  L = sqrt(12 * sigma2 + 1);  l = floor((L - 1) / 2);
+ *     a = (2 l + 1) * (l * (l + 1) - 3 * sigma2) / (6 * (sigma2 - (l + 1) * (l + 1)));  fr = l + a;
+ *     r = (int)fr;  ww = (uint32)((float)(1 << 24) / (fr * 2 + 1));  fw = ((1 << 24) - (2 r + 1) * ww) / 2.
+ * (Pillow forms L in double; that moves l only where 12 sigma2 + 1 is an odd square to the last place, and there the two boxes, (r, ww, ww) and
+ * (r + 1, ww, 0), are the same filter.)  Returns 0, or 1 with the reason in the last error for a null result or a radius outside
+ * (0, MX_BLUR_MAX_RADIUS]. */
+int mx_blur_box_params(float radius, int* r, uint32_t* ww, uint32_t* fw);
+/* src uint8 [B][H][W] -> dst, every plane bit-equal to Image.fromarray(plane, "L").filter(ImageFilter.GaussianBlur(radius)): three box passes along
+ * the rows, then three along the columns, each rounded to bytes on its own (so they cannot be merged).  radius <= 0 copies.  Four launches: the row
+ * passes in one (a line stays in LDS between them), one per column pass through `scratch` (B * H * W bytes of device memory from the caller; may be
+ * NULL when radius <= 0).  No allocation or synchronisation inside the call.  Dword accesses when W % 4 == 0 and the buffers are 4-byte aligned.
+ * Refused, with nothing launched: a null src or dst, a null scratch at a positive radius, a non-positive size, W > MX_BLUR_MAX_WIDTH, a radius that
+ * is NaN or above MX_BLUR_MAX_RADIUS, dst or scratch overlapping another buffer. */
+int mx_gaussian_blur_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, float radius);
+/* mask uint8 [B][H][W] -> box int32 [B][4] in device memory: (x_min, y_min, x_max + 1, y_max + 1) over the non-zero bytes of each plane, PIL's
+ * Image.getbbox; an empty plane gives (W, H, 0, 0).  One memset of the record and one launch: integer minima and maxima by atomics, so the result
+ * does not depend on their order.  Refused: a null operand, a non-positive size, a misaligned record. */
+int mx_mask_bbox_u8(void* stream, const uint8_t* mask, int32_t* box, int B, int H, int W);
+/* diffusers' get_crop_region applied to the bounding box (x1, y1, x2, y2) of a mask of mask_w x mask_h, for an image to be processed at
+ * width x height.  Host only.  In Python's terms (ints; / is the double division, int() truncates):
+ *     x1 = max(x1 - pad, 0); y1 = max(y1 - pad, 0); x2 = min(x2 + pad, mask_w); y2 = min(y2 + pad, mask_h)
+ *     if (x2 - x1) / (y2 - y1) > width / height:
+ *         diff = int((x2 - x1) / (width / height) - (y2 - y1));  y1 -= diff // 2;  y2 += diff - diff // 2
+ *         if y2 >= mask_h: d = y2 - mask_h; y2 -= d; y1 -= d
+ *         if y1 < 0: y2 -= y1; y1 = 0
+ *         if y2 >= mask_h: y2 = mask_h
+ *     else: the same on x with diff = int((y2 - y1) * (width / height) - (x2 - x1)) and mask_w
+ * out[4] = (x1, y1, x2, y2).  Returns 0, or 1 with the reason in the last error: a null result, a non-positive size, a negative pad, an empty box
+ * (what an empty mask gives), a box that does not lie inside the mask. */
+int mx_crop_region(int x1, int y1, int x2, int y2, int mask_w, int mask_h, int width, int height, int pad, int32_t* out);
+/* The client's image with the repainted crop blended in: decoded uint8 [B][h][w][3] (the decoder's image, resized to the region), original uint8
+ * [B][H][W][3], mask uint8 [B][H][W] soft (255 = repaint), the region at (x, y) .. (x + w, y + h) -> out uint8 [B][H][W][3], ONE launch that writes
+ * every byte.  Outside the box out is original; inside it is what diffusers' apply_overlay computes with Pillow (paste of the premultiplied original
+ * under the inverted mask, then alpha_composite), per channel with A = 255 - m, d the decoded and o the original byte:
+ *     t = o * A + 128;  p = ((t >> 8) + t) >> 8;  c = min(255, (255 * p) / A)            (A = 0: the result is d)
+ *     u = c * (A * 128) + d * (255 * 128 - A * 128) + (0x80 << 7);  out = (((u >> 8) + u) >> 8) >> 7
+ * which is o itself where m = 0 and, on a 0 / 255 mask, the hard paste of mx_rgb8_paste.  Dword accesses when original, mask and out are 4-byte
+ * aligned.  Refused: a null operand, a non-positive size, a box that does not lie inside the image, out overlapping an input. */
+int mx_rgb8_overlay(void* stream, const uint8_t* decoded, const uint8_t* original, const uint8_t* mask, uint8_t* out, int B, int H, int W, int x, int y,
+                    int w, int h);
+
 #ifdef __cplusplus
 }
 #endif

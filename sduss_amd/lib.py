@@ -306,6 +306,11 @@ SYMBOLS = {
     "mx_resize_create": (_vp, [_i, _i, _i, _i, _i]),
     "mx_resize_destroy": (None, [_vp]),
     "mx_resize_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "mx_blur_box_params": (_i, [_f, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mx_gaussian_blur_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f]),
+    "mx_mask_bbox_u8": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "mx_crop_region": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "mx_rgb8_overlay": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
 }
 
 _lib: Optional[C.CDLL] = None

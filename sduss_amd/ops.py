@@ -1,5 +1,5 @@
 """Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
-mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries, the image resize).  They allocate outputs with torch and pass raw pointers + the current
+mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries, the image resize, the mask blur / bounding box / overlay).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
 
@@ -580,4 +580,73 @@ def resize_u8(x: torch.Tensor, size, resample: str = "lanczos") -> torch.Tensor:
         plan = _resize_plans.setdefault(x.device.index, _ResizePlans()).get((h, w, oh, ow, _lib.RESIZE_FILTERS[resample]))
         out = torch.empty((b, oh, ow) + tuple(x.shape[3:]), dtype=torch.uint8, device=x.device)
         _lib.check(l.mx_resize_u8(plan, _lib.current_stream(), x.data_ptr(), out.data_ptr(), b, c), "mx_resize_u8")
+    return out
+
+
+# ---- inpainting only the masked region (csrc/inpaint_overlay.hip, inpaint_region.cpp) ----
+
+def _need_mask(what: str, mask: torch.Tensor) -> tuple:
+    _need(mask.is_cuda and mask.dtype == torch.uint8 and mask.ndim == 3 and mask.is_contiguous() and mask.numel() > 0,
+          f"{what}: expected a contiguous CUDA uint8 [B, H, W] mask, got {mask.dtype} {tuple(mask.shape)} on {mask.device.type}")
+    return tuple(mask.shape)
+
+
+def blur_box_params(radius: float) -> tuple:
+    """(r, ww, fw) of one box pass of Pillow's GaussianBlur(radius) (mx_blur_box_params); host only"""
+    r, ww, fw = C.c_int(), C.c_uint32(), C.c_uint32()
+    _lib.check(_lib.load().mx_blur_box_params(float(radius), C.byref(r), C.byref(ww), C.byref(fw)), "mx_blur_box_params")
+    return r.value, ww.value, fw.value
+
+
+def gaussian_blur_u8(mask: torch.Tensor, radius: float) -> torch.Tensor:
+    """uint8 [B, H, W] -> a new tensor of the same shape, every plane bit-equal to Pillow's ``Image.filter(ImageFilter.GaussianBlur(radius))`` --
+    diffusers' VaeImageProcessor.blur (mx_gaussian_blur_u8: the three row passes in one launch, one launch per column pass); radius <= 0 copies"""
+    l = _lib.load()
+    b, h, w = _need_mask("mx_gaussian_blur_u8", mask)
+    with torch.cuda.device(mask.device):
+        out = torch.empty_like(mask)
+        scratch = torch.empty_like(mask) if radius > 0 else None
+        _lib.check(l.mx_gaussian_blur_u8(_lib.current_stream(), mask.data_ptr(), out.data_ptr(), _p(scratch), b, h, w, float(radius)), "mx_gaussian_blur_u8")
+    return out
+
+
+def mask_bbox(mask: torch.Tensor) -> torch.Tensor:
+    """uint8 [B, H, W] -> int32 [B, 4] on the device: (x_min, y_min, x_max + 1, y_max + 1) over the non-zero bytes of each plane, (W, H, 0, 0) for an
+    empty one (mx_mask_bbox_u8)"""
+    l = _lib.load()
+    b, h, w = _need_mask("mx_mask_bbox_u8", mask)
+    with torch.cuda.device(mask.device):
+        out = torch.empty((b, 4), dtype=torch.int32, device=mask.device)
+        _lib.check(l.mx_mask_bbox_u8(_lib.current_stream(), mask.data_ptr(), out.data_ptr(), b, h, w), "mx_mask_bbox_u8")
+    return out
+
+
+def crop_region(bbox, mask_size, size, pad: int) -> tuple:
+    """diffusers' get_crop_region applied to a mask's bounding box (mx_crop_region; host only): ``bbox`` = (x1, y1, x2, y2) as one row of mask_bbox
+    gives it, ``mask_size`` = (H, W) of the mask, ``size`` = (H, W) the crop will be processed at -> (x1, y1, x2, y2) inside the mask with about that
+    aspect.  An empty box, what an empty mask gives, is refused."""
+    x1, y1, x2, y2 = (int(v) for v in bbox)
+    out = (C.c_int32 * 4)()
+    _lib.check(_lib.load().mx_crop_region(x1, y1, x2, y2, int(mask_size[1]), int(mask_size[0]), int(size[1]), int(size[0]), int(pad), out), "mx_crop_region")
+    return tuple(out)
+
+
+def rgb8_overlay(decoded: torch.Tensor, original: torch.Tensor, mask: torch.Tensor, x: int = 0, y: int = 0) -> torch.Tensor:
+    """decoded uint8 [B, h, w, 3] blended into original uint8 [B, H, W, 3] at (x, y) under the soft mask uint8 [B, H, W] (255 = repaint) -> a new
+    uint8 [B, H, W, 3]: original's bytes outside the box, diffusers' apply_overlay inside (mx_rgb8_overlay, one launch)"""
+    l = _lib.load()
+    _need(original.is_cuda and original.dtype == torch.uint8 and original.ndim == 4 and original.shape[-1] == 3 and original.is_contiguous()
+          and original.numel() > 0,
+          f"mx_rgb8_overlay: expected a contiguous CUDA uint8 [B, H, W, 3] original, got {original.dtype} {tuple(original.shape)} on {original.device.type}")
+    b, hh, ww, _c = original.shape
+    _need(decoded.dtype == torch.uint8 and decoded.ndim == 4 and decoded.shape[0] == b and decoded.shape[-1] == 3 and decoded.is_contiguous()
+          and decoded.device == original.device and decoded.numel() > 0,
+          f"mx_rgb8_overlay: the decoded image must be contiguous uint8 [{b}, h, w, 3] on the original's device, got {decoded.dtype} {tuple(decoded.shape)}")
+    _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (b, hh, ww) and mask.is_contiguous() and mask.device == original.device,
+          f"mx_rgb8_overlay: the mask must be contiguous uint8 [{b}, {hh}, {ww}], got {mask.dtype} {tuple(mask.shape)}")
+    h, w = decoded.shape[1:3]
+    with torch.cuda.device(original.device):
+        out = torch.empty_like(original)
+        _lib.check(l.mx_rgb8_overlay(_lib.current_stream(), decoded.data_ptr(), original.data_ptr(), mask.data_ptr(), out.data_ptr(), b, hh, ww,
+                                     int(x), int(y), w, h), "mx_rgb8_overlay")
     return out

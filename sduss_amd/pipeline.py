@@ -46,6 +46,10 @@ class InpaintState:
     image_u8: Optional[torch.Tensor]      # uint8 [1, H, W, 3]: the client's image (None when it came as floats)
     mask_u8: torch.Tensor                 # uint8 [1, H, W]: the client's mask, >= 128 = repaint
     paste: bool                           # post_inference gives the client's own pixels back outside the mask
+    full_image_u8: Optional[torch.Tensor] = None   # uint8 [1, Hc, Wc, 3]: the client's whole image, of a request that repaints a crop of it
+    full_mask_u8: Optional[torch.Tensor] = None    # uint8 [1, Hc, Wc]: the client's whole mask, soft (after the blur)
+    region: Optional[tuple] = None                 # (x1, y1, x2, y2) of the crop in the client's image; image_u8 / mask_u8 are that crop resized
+    overlay: bool = False                          # the result is blended into the client's image under the soft mask (mx_rgb8_overlay)
 
 
 @dataclass
@@ -198,7 +202,8 @@ class Denoiser:
         return self._start_mix(np.float32(req.sigmas[t_start]))
 
     def start_inpaint(self, req, encoder, image: torch.Tensor, mask: torch.Tensor, strength: float = 1.0, posterior_noise: Optional[torch.Tensor] = None,
-                      noise: Optional[torch.Tensor] = None, paste: bool = False, size=None, resample: str = "lanczos") -> None:
+                      noise: Optional[torch.Tensor] = None, paste: bool = False, size=None, resample: str = "lanczos", blur: float = 0.0,
+                      crop_pad: Optional[int] = None, overlay: bool = False) -> None:
         """Make ``req`` an inpainting request (diffusers' 4-channel rule, for the base checkpoints): the part of ``image`` where ``mask`` (uint8
         [1, H, W] as a client sends it) is >= 128 is repainted, the rest is kept.  ``image`` as for ``start_from_image``.  ONE call of the encoder,
         with no start noise: its result, the clean latents in the model dtype, stays on the request (``req.inpaint.init``, diffusers' image_latents)
@@ -207,7 +212,45 @@ class Denoiser:
         step then puts the kept region back inside its scheduler launch (``_scheduler_step_masked``).  ``paste``: post_inference returns the
         client's own pixels outside the mask, which needs the uint8 image.  ``size`` = (H, W): image and mask come at the client's size and are
         resized to the request's first (``start_from_image``), the mask as a grey image by the same filter -- diffusers' mask processor, whose
-        binarisation is then the >= 128 rule on the resized mask; the request keeps the resized pair, so ``paste`` works at the request's size."""
+        binarisation is then the >= 128 rule on the resized mask; the request keeps the resized pair, so ``paste`` works at the request's size.
+
+        Repainting only the masked region of a large photo, diffusers' ``padding_mask_crop`` with a blurred mask -- all on the device, to Pillow's bytes:
+        ``blur`` > 0: the client's mask goes through Pillow's GaussianBlur(blur) first, at the client's size (diffusers' VaeImageProcessor.blur, which
+        its user calls before the pipeline); the latent mask is then the >= 128 rule on the soft mask.
+        ``overlay``: the result is blended into the client's image under the soft mask (apply_overlay: post_inference "uint8" / "pil"), where ``paste``
+        cuts at 128; needs the uint8 image.
+        ``crop_pad`` (implies ``overlay``): the bounding box of the soft mask (ops.mask_bbox: one 16-byte read-back here, off the step path), padded by
+        ``crop_pad`` and grown to the request's aspect (ops.crop_region, diffusers' get_crop_region), is cut out of image and mask, and that pair, resized
+        to the request's size (``size``, or the size of the request's latents) by ``resample``, is what the request encodes and repaints; an empty mask
+        is refused.  ``req.inpaint`` keeps the client's whole image, the soft whole mask and the region, and ``vae.finish_cropped`` resizes the decoded
+        image back to the region and blends it into the whole image.  Two departures from diffusers, whose pipeline is not available to compare with:
+        the crop is resized straight to the request's size and the decoded image straight to the region's, both by ``resample``, where diffusers goes
+        through _resize_and_fill and _resize_and_crop -- those differ by edge pixels when the integer truncation of the crop rule leaves the region's
+        aspect a pixel off the request's."""
+        full_image = full_mask = region = None
+        if blur > 0 or crop_pad is not None or overlay:
+            if image.dtype != torch.uint8 or image.ndim != 4 or image.shape[-1] != 3:
+                raise MxError("start_inpaint: blur, crop_pad and overlay work on the client's uint8 [1, H, W, 3] image")
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(image.shape[:3]):
+                raise MxError(f"start_inpaint: expected a uint8 mask {tuple(image.shape[:3])}, got {mask.dtype} {tuple(mask.shape)}")
+            image, mask = image.to(encoder.device).contiguous(), mask.to(encoder.device).contiguous()
+        if blur > 0:
+            mask = ops.gaussian_blur_u8(mask, blur)
+        if crop_pad is not None:
+            if image.shape[0] != 1:
+                raise MxError("start_inpaint: crop_pad takes one image")
+            overlay = True
+            f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
+            target = tuple(int(s) for s in size) if size is not None else (f * req.latents.shape[-2], f * req.latents.shape[-1])
+            box = ops.mask_bbox(mask)[0].tolist()                 # the one read-back of a request's start
+            if box[2] <= box[0] or box[3] <= box[1]:
+                raise MxError("start_inpaint: crop_pad needs a mask with something to repaint; this one is empty")
+            region = ops.crop_region(box, mask.shape[1:], target, crop_pad)
+            full_image, full_mask = image, mask
+            x1, y1, x2, y2 = region
+            image = ops.resize_u8(image[:, y1:y2, x1:x2].contiguous(), target, resample)
+            mask = ops.resize_u8(mask[:, y1:y2, x1:x2].contiguous(), target, resample)
+            size = None
         if size is not None:
             client = tuple(image.shape[:3])
             image = self._resize_client_u8("start_inpaint", image, size, resample, encoder.device)
@@ -228,7 +271,8 @@ class Denoiser:
         if noise is None:
             noise = torch.randn(init.shape, device=encoder.device, dtype=encoder.out_dtype)
         noise = noise.to(device=encoder.device, dtype=encoder.out_dtype).contiguous()
-        req.inpaint = InpaintState(init, noise, ops.mask_to_latent(mask_u8, f), image.to(encoder.device).contiguous() if u8 else None, mask_u8, paste)
+        req.inpaint = InpaintState(init, noise, ops.mask_to_latent(mask_u8, f), image.to(encoder.device).contiguous() if u8 else None, mask_u8, paste,
+                                   full_image, full_mask, region, overlay)
         req.latents = ops.inpaint_renoise(init, noise, *self._inpaint_start_mix(req, t_start, strength))
         req.step_index = t_start
 

@@ -293,12 +293,32 @@ class MxVAEDecoder:
 OUTPUT_TYPES = ("pt", "uint8", "pil")
 
 
+def finish_cropped(req, decoded_row: torch.Tensor, resample: str = "lanczos") -> torch.Tensor:
+    """The client-size result of a request that repainted a crop (Denoiser.start_inpaint with ``crop_pad``): ``decoded_row`` uint8 [1, res, res, 3],
+    the request's decoded image, is resized to the region's (h, w) (ops.resize_u8, Pillow's bytes) and blended into the client's whole image under
+    the soft whole mask (ops.rgb8_overlay, diffusers' apply_overlay with crop_coords) -> uint8 [1, H_client, W_client, 3] on the device.  Pixels
+    whose soft mask is 0, everything outside the region among them, are the client's own bytes.  The resize goes straight to the region's size
+    (start_inpaint's docstring: diffusers' _resize_and_crop differs by edge pixels where the region's aspect is a pixel off)."""
+    s = getattr(req, "inpaint", None)
+    if s is None or s.region is None:
+        raise _lib.MxError("finish_cropped: the request was not started with crop_pad")
+    x1, y1, x2, y2 = s.region
+    if decoded_row.dtype != torch.uint8 or decoded_row.ndim != 4 or decoded_row.shape[0] != 1 or decoded_row.shape[-1] != 3:
+        raise _lib.MxError(f"finish_cropped: expected the request's decoded uint8 [1, H, W, 3] image, got {decoded_row.dtype} {tuple(decoded_row.shape)}")
+    small = ops.resize_u8(decoded_row.contiguous(), (y2 - y1, x2 - x1), resample)
+    return ops.rgb8_overlay(small, s.full_image_u8, s.full_mask_u8, x1, y1)
+
+
 def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list], output_type: str = "pt") -> Dict[str, object]:
     """mirror of post_inference (:406-463): gather the finished requests' latents per resolution, decode, postprocess.
       "pt"     {resolution: fp32 images [n, 3, res, res] in [0, 1]} on the device (the tensor stage);
       "uint8"  {resolution: uint8 images [n, res, res, 3]} on the device (MxVAEDecoder.decode_images); an inpainting request with
-               ``inpaint.paste`` keeps the client's own pixels outside its mask (mx_rgb8_paste);
-      "pil"    {resolution: [PIL.Image, ...]}, the reference's default: the "uint8" images through the decoder's pinned host buffer."""
+               ``inpaint.paste`` keeps the client's own pixels outside its mask (mx_rgb8_paste), one with ``inpaint.overlay`` has the client's
+               image blended in under its soft mask (mx_rgb8_overlay).  A request that repainted a crop (``inpaint.region``) stays as decoded
+               here, at the request's size: its result has the client's size, which a [n, res, res, 3] tensor cannot hold -- ``finish_cropped``
+               makes it from this row;
+      "pil"    {resolution: [PIL.Image, ...]}, the reference's default: the "uint8" images through the decoder's pinned host buffer; a request
+               that repainted a crop comes back at the client's size (``finish_cropped``)."""
     if output_type not in OUTPUT_TYPES:
         raise ValueError(f"post_inference: output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
     images = {}
@@ -314,7 +334,15 @@ def post_inference(vae: MxVAEDecoder, worker_reqs: Dict[str, list], output_type:
             s = getattr(r, "inpaint", None)
             if s is not None and s.paste:
                 ops.rgb8_paste_(images[res][i:i + 1], s.image_u8, s.mask_u8)
+            if s is not None and s.overlay and s.region is None:
+                with torch.inference_mode():                               # (the decoder's images are inference tensors)
+                    images[res][i:i + 1] = ops.rgb8_overlay(images[res][i:i + 1], s.image_u8, s.mask_u8)
     if output_type == "pil":
         from PIL import Image
-        return {res: [Image.fromarray(a) for a in arr] for res, arr in vae.images_to_host(images).items()}      # (an RGB fromarray copies)
+        full = {(res, i): finish_cropped(r, images[res][i:i + 1]) for res, reqs in worker_reqs.items() for i, r in enumerate(reqs)
+                if getattr(getattr(r, "inpaint", None), "region", None) is not None}
+        pil = {res: [Image.fromarray(a) for a in arr] for res, arr in vae.images_to_host(images).items()}       # (an RGB fromarray copies)
+        for (res, i), t in full.items():                                   # a size of its own: a copy of its own
+            pil[res][i] = Image.fromarray(t[0].cpu().numpy())
+        return pil
     return images
