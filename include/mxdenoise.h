@@ -919,6 +919,52 @@ int mx_mask_to_latent(void* stream, const uint8_t* mask, uint8_t* out, int B, in
 int mx_rgb8_paste(void* stream, uint8_t* decoded, const uint8_t* original, const uint8_t* mask, int B, int H, int W);
 
 /* ------------------------------------------------------------------------------------------
+ * Second-order multistep samplers (sduss_amd/csrc/sampler_step.hip, sampler_coeffs.cpp): DPM-Solver++ 2M for the epsilon model and the second-order
+ * Adams-Bashforth step (AB2) for both models, beside the model's own Euler step in ONE launch over a batch whose requests use different samplers.
+ * Both are linear in the latent x, this step's quantity D and the previous step's D:
+ *     x_next = cx * x + c0 * D + c1 * D_prev        D = x - sigma * m  (the data prediction, DPM-Solver++)   or   D = m  (the derivative, AB2)
+ * with m the guided model output.  The latents keep the Euler scaling (k-diffusion's variance-exploding form of sample_dpmpp_2m, equal to diffusers'
+ * variance-preserving DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint, lower_order_final), so mx_euler_scale_input, the start noise of
+ * image-to-image and the re-noising of inpainting are unchanged.  The three coefficients of every step are made on the host (mx_sampler_coeffs).
+ * ------------------------------------------------------------------------------------------ */
+enum { MX_SAMPLER_EULER = 0, MX_SAMPLER_DPMPP_2M = 1, MX_SAMPLER_AB2 = 2 };
+/* The multistep rows of one step launch.  Everything lives in device memory. */
+typedef struct {
+  const int*   kind;   /* device int32 [n_lat]: 0 = the model's Euler step, 1 = multistep on D = x - sigma*m, 2 = multistep on D = m; anything else = 0 */
+  const float* coef;   /* device fp32 [n_lat][3]: cx, c0, c1 of this step (read for kind 1 / 2 only) */
+  float*       hist;   /* device fp32 [n_lat][C][hw]: D of each row's previous step, read where c1 != 0, then overwritten with this step's D (kind 1 / 2 only) */
+} mx_multistep_rows;
+/* One scheduler step over rows of different samplers, with the kept region of inpainting rows put back in the same launch.
+ *   noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype: as for mx_cfg_euler_step_masked; flow != 0 selects the flow-match
+ *   Euler step for kind-0 rows and the flow keep factor 1 - sigma_next of the kept region.
+ * Per element of row r, in fp32 with one rounding per operation (no contraction), m = the CFG combine of mx_cfg_euler_step:
+ *   kind 0 (and any kind other than 1 or 2): the Euler / flow step by the device functions of the plain steps: their bits; hist is not touched.
+ *   kind 1: D = x - (sigma*m);   kind 2: D = m;   acc = (cx*x) + (c0*D);   where c1 != 0: acc = acc + (c1*hist);   latent = acc rounded once to
+ *   `dtype`;   hist = D (fp32).  hist is not read where c1 == 0: on a request's first step it holds uninitialised memory.
+ *   An inpainting row (`inpaint`: NULL or k = 0 for none) then takes keep * init + sigma_next * noise where its mask is 0, exactly as
+ *   mx_cfg_*_step_masked; hist receives D there too (diffusers does not mask its model_outputs either).
+ * Refused, with nothing launched: a null operand, `ms` or member of it, a non-positive size, a bad dtype, hist aliasing latents or noise_pred,
+ * an `inpaint` with k < 0 or with k > 0 and a null member.  Offsets are 64-bit.  16-byte accesses when latents, noise_pred, hist (and init, noise;
+ * the mask to a vector's elements) are 16-byte aligned and hw is a whole number of vectors -- a vector of 8 bf16 / f16 elements is two 16-byte
+ * accesses of hist -- element accesses otherwise. */
+int mx_cfg_multistep_step(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                          int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms, const mx_inpaint_rows* inpaint /* NULL or k = 0: none */);
+/* The coefficients of every step of a schedule, on the host (plain C++, double arithmetic rounded to float once; no GPU needed).
+ *   sigmas [n_steps + 1], strictly decreasing, non-negative, the last may be 0;   out [n_steps][4] = (cx, c0 first order, c0 second order, c1 second
+ *   order) of the step from s = sigmas[i] to sn = sigmas[i + 1].  A row steps second order when it holds the previous step's D, first order otherwise;
+ *   step 0 has no second order: its last two entries repeat the first-order ones with c1 = 0.
+ * MX_SAMPLER_DPMPP_2M (flow = 0 only): lambda(sigma) = -log sigma, h = lambda(sn) - lambda(s), E = -expm1(-h), cx = sn / s; first order c0 = E;
+ *   second order with r = (lambda(s) - lambda(sigmas[i - 1])) / h: c0 = E (1 + 1 / (2 r)), c1 = -E / (2 r).  Where sn == 0 the step is first order
+ *   whatever came before, (0, 1, 1, 0): the result is the data prediction itself (diffusers' lower_order_final with final_sigmas_type "zero",
+ *   k-diffusion's sigmas[i + 1] == 0 rule).  Refused for flow = 1: lambda is -infinity at sigma = 1, and on the analytic Gaussian problem the
+ *   sampler is worse than Euler on the flow schedule at every step count.
+ * MX_SAMPLER_AB2 (both models): h = sn - s, cx = 1; first order c0 = h (the Euler step); second order with w = h / (2 (s - sigmas[i - 1])):
+ *   c0 = h (1 + w), c1 = -h w.  The final step stays second order.
+ * Returns 0; non-zero, with the reason in the last error, for a null table, n_steps < 1, sigmas not strictly decreasing, a negative sigma, an
+ * unknown sampler or MX_SAMPLER_EULER (which has no coefficients). */
+int mx_sampler_coeffs(int sampler, int flow, const float* sigmas, int n_steps, float* out);
+
+/* ------------------------------------------------------------------------------------------
  * Resize of a client's 8-bit image or mask to the request's resolution (sduss_amd/csrc/image_resize.hip, resize_coeffs.cpp), bit-equal to
  * Pillow's Image.resize for modes "RGB" and "L" -- what diffusers' VaeImageProcessor.preprocess does in front of the VAE, and its mask
  * processor in front of the binarisation.  Pillow's 8-bit resampler (ImagingResample) is integer arithmetic on integer coefficient tables:

@@ -1,7 +1,8 @@
-// The per-element arithmetic of the scheduler steps, one definition for every translation unit that steps latents (elementwise.hip, inpaint.hip):
-// the io-dtype loads and stores, the CFG combine, the two Euler updates and the re-noising of clean latents.  Every function is a chain of separately
-// rounded IEEE fp32 operations that torch evaluates identically op by op, so an including file must not contract mul + add into FMA: it is built with
-// -ffp-contract=off (Makefile) and the pragma below covers everything that follows the include.
+// The per-element arithmetic of the scheduler steps, one definition for every translation unit that steps latents (elementwise.hip, inpaint.hip,
+// sampler_step.hip): the io-dtype loads and stores, the CFG combine, the two Euler updates, the re-noising of clean latents and the linear multistep
+// update.  Every function is a chain of separately rounded IEEE fp32 operations that torch evaluates identically op by op, so an including file
+// must not contract mul + add into FMA: it is built with -ffp-contract=off (Makefile) and the pragma below covers everything that follows the
+// include.
 #pragma once
 #include "common.h"
 
@@ -51,6 +52,24 @@ __device__ __forceinline__ float renoise(float init, float noise, float keep, fl
   const float a = keep * init;
   const float n = sigma * noise;
   return a + n;
+}
+
+// The multistep samplers (sampler_step.hip): x_next = cx x + c0 D + c1 D_prev, every product and sum rounded on its own.
+// D of DPM-Solver++ 2M, the data prediction of the epsilon model: x - sigma * eps
+__device__ __forceinline__ float multistep_data(float x, float eps, float s) {
+  const float n = s * eps;
+  return x - n;
+}
+// a first-order row: the history is not an operand (on a request's first step it is uninitialised memory)
+__device__ __forceinline__ float multistep_update1(float x, float d, float cx, float c0) {
+  const float a = cx * x;
+  const float b = c0 * d;
+  return a + b;
+}
+__device__ __forceinline__ float multistep_update2(float x, float d, float prev, float cx, float c0, float c1) {
+  const float acc = multistep_update1(x, d, cx, c0);
+  const float c = c1 * prev;
+  return acc + c;
 }
 
 }  // namespace mx

@@ -174,6 +174,15 @@ class InpaintRows(C.Structure):
     _fields_ = [("k", C.c_int), ("slot", C.c_void_p), ("init", C.c_void_p), ("noise", C.c_void_p), ("mask", C.c_void_p)]
 
 
+MX_SAMPLER_EULER, MX_SAMPLER_DPMPP_2M, MX_SAMPLER_AB2 = 0, 1, 2
+SAMPLERS = {"euler": MX_SAMPLER_EULER, "dpmpp_2m": MX_SAMPLER_DPMPP_2M, "ab2": MX_SAMPLER_AB2}     # the kind of a row of mx_cfg_multistep_step
+
+
+class MultistepRows(C.Structure):
+    """mx_multistep_rows: the samplers, coefficients and history of the rows of one multistep launch"""
+    _fields_ = [("kind", C.c_void_p), ("coef", C.c_void_p), ("hist", C.c_void_p)]
+
+
 class WeightEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -299,6 +308,8 @@ SYMBOLS = {
     "mx_cfg_flow_step_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
     "mx_cfg_euler_step_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, C.POINTER(InpaintRows)]),
     "mx_cfg_flow_step_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, C.POINTER(InpaintRows)]),
+    "mx_cfg_multistep_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, C.POINTER(MultistepRows), C.POINTER(InpaintRows)]),
+    "mx_sampler_coeffs": (_i, [_i, _i, _vp, _i, _vp]),
     "mx_inpaint_renoise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i]),
     "mx_mask_to_latent": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "mx_rgb8_paste": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),

@@ -1,5 +1,5 @@
 """Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
-mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the inpainting entries, the image resize, the mask blur / bounding box / overlay).  They allocate outputs with torch and pass raw pointers + the current
+mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the multistep samplers, the inpainting entries, the image resize, the mask blur / bounding box / overlay).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
 
@@ -491,6 +491,68 @@ def cfg_flow_step_masked_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma
                           mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The flow-match step on the same layout: kept elements become (1 - sigma_next) * init + sigma_next * noise (mx_cfg_flow_step_masked)."""
     return _cfg_step_masked_("mx_cfg_flow_step_masked", noise_pred, latents, sigma, sigma_next, guidance_scale, slot, init, noise, mask)
+
+
+# ---- second-order multistep samplers (csrc/sampler_step.hip, sampler_coeffs.cpp) ----
+
+def cfg_multistep_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float,
+                        kind: torch.Tensor, coef: torch.Tensor, hist: torch.Tensor, flow: bool, slot: Optional[torch.Tensor] = None,
+                        init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: one scheduler step on latents [n, C, h, w] whose rows use different samplers (mx_cfg_multistep_step).  kind int32 [n]: 0 = the
+    model's Euler step (``flow``: the flow-match one), 1 = DPM-Solver++ 2M (D = x - sigma m), 2 = AB2 (D = m); coef fp32 [n, 3] = (cx, c0, c1) of this
+    step per row (``sampler_coeffs``); hist fp32 [n, C, h, w]: D of every multistep row's previous step, read where c1 != 0 and overwritten with
+    this step's.  The new latent of a multistep row is cx x + c0 D + c1 hist.  slot / init / noise / mask: the inpainting rows as for
+    ``cfg_euler_step_masked_``."""
+    fn_name = "mx_cfg_multistep_step"
+    l = _lib.load()
+    _need(latents.ndim == 4 and latents.is_contiguous(), f"{fn_name}: latents must be a contiguous [n, C, h, w] tensor")
+    n_lat, c, h, w = latents.shape
+    rows = (2 if guidance_scale > 0 else 1) * n_lat
+    _need(noise_pred.is_contiguous() and noise_pred.dtype == latents.dtype and noise_pred.device == latents.device
+          and noise_pred.numel() == rows * c * h * w, f"{fn_name}: the prediction must be contiguous [{rows}, {c}, {h}, {w}] of the latents' dtype")
+    for name, t in (("sigma", sigma), ("sigma_next", sigma_next)):
+        _need(t.numel() == n_lat, f"{fn_name}: {name} must hold one value per latent row")
+    _need(kind.dtype == torch.int32 and kind.numel() == n_lat and kind.is_contiguous() and kind.device == latents.device,
+          f"{fn_name}: kind must be a contiguous int32 [{n_lat}] on the latents' device")
+    _need(coef.dtype == torch.float32 and tuple(coef.shape) == (n_lat, 3) and coef.is_contiguous() and coef.device == latents.device,
+          f"{fn_name}: coef must be contiguous fp32 [{n_lat}, 3] on the latents' device, got {coef.dtype} {tuple(coef.shape)}")
+    _need(hist.dtype == torch.float32 and tuple(hist.shape) == (n_lat, c, h, w) and hist.is_contiguous() and hist.device == latents.device,
+          f"{fn_name}: hist must be contiguous fp32 [{n_lat}, {c}, {h}, {w}] on the latents' device, got {hist.dtype} {tuple(hist.shape)}")
+    ms = _lib.MultistepRows()
+    ms.kind, ms.coef, ms.hist = kind.data_ptr(), coef.data_ptr(), hist.data_ptr()
+    r = _lib.InpaintRows()
+    if init is not None:
+        k = init.shape[0]
+        _need(slot is not None and noise is not None and mask is not None, f"{fn_name}: inpainting rows need slot, init, noise and mask")
+        _need(slot.dtype == torch.int32 and slot.numel() == n_lat and slot.is_contiguous() and slot.device == latents.device,
+              f"{fn_name}: slot must be a contiguous int32 [{n_lat}] on the latents' device")
+        for name, t in (("init", init), ("noise", noise)):
+            _need(t.dtype == latents.dtype and tuple(t.shape) == (k, c, h, w) and t.is_contiguous() and t.device == latents.device,
+                  f"{fn_name}: {name} must be contiguous [{k}, {c}, {h}, {w}] of the latents' dtype, got {t.dtype} {tuple(t.shape)}")
+        _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (k, h, w) and mask.is_contiguous() and mask.device == latents.device,
+              f"{fn_name}: mask must be contiguous uint8 [{k}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+        r.k, r.slot, r.init, r.noise, r.mask = k, slot.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr()
+    else:
+        _need(slot is None and noise is None and mask is None, f"{fn_name}: slot, noise and mask come with init")
+    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
+    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+    _lib.check(l.mx_cfg_multistep_step(_lib.current_stream(), noise_pred.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
+                                       float(guidance_scale), n_lat, c, h * w, _lib.torch_dtype_code(latents.dtype), int(bool(flow)), C.byref(ms),
+                                       C.byref(r)), fn_name)
+    return latents
+
+
+def sampler_coeffs(sampler: str, sigmas, flow: bool):
+    """the step coefficients of a multistep sampler ("dpmpp_2m" | "ab2") over a schedule, on the host (mx_sampler_coeffs; no GPU needed):
+    sigmas fp32 [n + 1] -> numpy fp32 [n, 4] = (cx, c0 first order, c0 second order, c1 second order) per step"""
+    import numpy as np
+    l = _lib.load()
+    _need(sampler in _lib.SAMPLERS, f"mx_sampler_coeffs: sampler must be one of {sorted(_lib.SAMPLERS)}, got {sampler!r}")
+    sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float32).reshape(-1))
+    _need(sig.size >= 2, "mx_sampler_coeffs: a schedule holds at least one step (two sigmas)")
+    out = np.empty((sig.size - 1, 4), dtype=np.float32)
+    _lib.check(l.mx_sampler_coeffs(_lib.SAMPLERS[sampler], int(bool(flow)), sig.ctypes.data, sig.size - 1, out.ctypes.data), "mx_sampler_coeffs")
+    return out
 
 
 def inpaint_renoise(init: torch.Tensor, noise: torch.Tensor, keep, sigma) -> torch.Tensor:

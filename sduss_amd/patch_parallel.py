@@ -349,6 +349,8 @@ class PatchParallelDenoiser:
     def step(self, req) -> None:
         if getattr(req, "inpaint", None) is not None:        # the step on the gather buffer has no masked form
             raise _lib.MxError("inpainting is not available under patch parallelism")
+        if getattr(req, "sampler", "euler") != "euler":      # nor a multistep form: the history would have to follow the row slabs
+            raise _lib.MxError("multistep samplers are not available under patch parallelism")
         e = self._cache.entry((req.resolution, req.request_id, id(req)), [req], lambda: self.hooks._cond([req], True))
         lat = self._cache.latents(e, [req])
         sig, sig_next, ts = self._cache.step_scalars(e, [req])

@@ -36,6 +36,27 @@ def euler_tables(num_inference_steps: int, num_train_timesteps: int = 1000, beta
     return timesteps, sigmas, float((sigmas.max() ** 2 + 1) ** 0.5)
 
 
+def karras_tables(num_inference_steps: int, rho: float = 7.0):
+    """The Karras et al. (2022) sigma schedule between the first and the last non-zero sigma of ``euler_tables(n)``, as diffusers'
+    ``use_karras_sigmas`` and k-diffusion's ``get_sigmas_karras`` make it: sigma_i = (max^(1/rho) + i / (n - 1) (min^(1/rho) - max^(1/rho)))^rho in
+    fp64, a final 0 appended, rounded to fp32 once; n = 1 gives the single sigma max.  The timesteps are diffusers' ``_sigma_to_t``, the position of
+    log sigma among the 1000 training log sigmas by linear interpolation, left fractional (the UNet entry takes float timesteps).  Returns
+    (timesteps f32[n], sigmas f32[n+1], init_noise_sigma) like ``euler_tables``; init_noise_sigma is the same, since sigma max is."""
+    _ts, base, init_noise_sigma = euler_tables(num_inference_steps)
+    n = num_inference_steps
+    hi, lo = float(base[0]) ** (1.0 / rho), float(base[n - 1]) ** (1.0 / rho)
+    ramp = np.linspace(0.0, 1.0, n) if n > 1 else np.zeros(1)
+    sig = (hi + ramp * (lo - hi)) ** rho
+    betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, 1000, dtype=torch.float32) ** 2       # the training sigmas of euler_tables, ascending
+    alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+    log_train = np.log((((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy().astype(np.float64))
+    log_sig = np.log(sig)
+    low = np.clip(np.searchsorted(log_train, log_sig, side="right") - 1, 0, len(log_train) - 2)   # the last training sigma not above sigma
+    w = np.clip((log_train[low] - log_sig) / (log_train[low] - log_train[low + 1]), 0.0, 1.0)
+    timesteps = ((1.0 - w) * low + w * (low + 1)).astype(np.float32)
+    return timesteps, np.concatenate([sig, [0.0]]).astype(np.float32), init_noise_sigma
+
+
 @dataclass
 class InpaintState:
     """What an inpainting request carries beside its latents (Denoiser.start_inpaint): after every step the kept region of the latents becomes
@@ -72,6 +93,9 @@ class Request:
     start: Optional[float] = None
     finish: Optional[float] = None
     inpaint: Optional[InpaintState] = None
+    sampler: str = "euler"                # "euler" | "dpmpp_2m" | "ab2" (set_timesteps)
+    history: Optional[torch.Tensor] = None   # fp32 [1, C, h, w]: D of the last step of a multistep sampler, a view of its composition's buffer
+    history_step: int = -1                # the step that left ``history``; the next step is second order only if it follows it directly
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -101,14 +125,16 @@ class Denoiser:
     """One ``denoising_step`` over a heterogeneous batch of requests, for either model.  A subclass says which request fields make the
     conditioning (``_cond``), how the model input is made from the latents (``_scale_input``), which scheduler step follows
     (``_scheduler_step``; ``_scheduler_step_rows`` on a patch-parallel gather buffer; ``_scheduler_step_masked`` for a resolution with inpainting
-    requests), how its model slot is called (``_forward``,
+    requests; ``flow`` selects the model's step inside the launch of a resolution with multistep samplers), how its model slot is called (``_forward``,
     ``_forward_mixed``) and whether a batch composition is announced to it (``announces_composition``: MxUNet.set_context_key)."""
     announces_composition = False
+    flow = False                         # the flow-match model: its Euler step and keep factor in mx_cfg_multistep_step
+    samplers = ("euler",)                # what set_timesteps accepts
 
     def __init__(self, model, guidance_scale: float):
         self._model = model
         self.guidance_scale = guidance_scale
-        self._tables: Dict[int, tuple] = {}
+        self._tables: Dict[object, tuple] = {}
         self.concurrent_resolutions = True
         self._streams: List[torch.cuda.Stream] = []
         self._cache = StepCache(model.device)      # per batch composition: conditioning cats, sigma/timestep tables (step_state.py)
@@ -168,6 +194,32 @@ class Denoiser:
         """(keep, sigma) of the start step's noise: latents = keep * clean + sigma * noise"""
         raise NotImplementedError
 
+    def _check_sampler(self, sampler: str) -> None:
+        if sampler not in self.samplers:
+            raise MxError(f"{type(self).__name__}.set_timesteps: sampler must be one of {self.samplers}, got {sampler!r}")
+
+    def _restart(self, req) -> None:
+        """the schedule of a request that starts from an image: the sampler and sigmas its ``set_timesteps`` chose stay (the defaults for a
+        request that never had one), and it forgets its history: its first step, wherever it starts, is first order"""
+        if getattr(req, "sigmas", None) is None or len(req.timesteps) != req.num_inference_steps:
+            self.set_timesteps(req)
+        req.step_index, req.history, req.history_step = 0, None, -1
+
+    def _multistep_rows(self, reqs) -> Optional[tuple]:
+        """(kind per row, coefficient table [n, S, 4]) of one resolution's requests as mx_cfg_multistep_step steps them: kind 0 rows (zeros in the
+        table) are the model's Euler step.  None when every request is an Euler one: the resolution then issues the plain or the masked launch."""
+        from .lib import SAMPLERS
+        names = [getattr(r, "sampler", "euler") for r in reqs]
+        if all(n == "euler" for n in names):
+            return None
+        tab = np.zeros((len(reqs), max(len(r.timesteps) for r in reqs), 4), dtype=np.float32)
+        for i, (r, name) in enumerate(zip(reqs, names)):
+            self._check_sampler(name)
+            if name != "euler":
+                k = len(r.timesteps)
+                tab[i, :k] = ops.sampler_coeffs(name, r.sigmas[:k + 1], self.flow)
+        return [SAMPLERS[n] for n in names], tab
+
     @staticmethod
     def _resize_client_u8(what: str, t: torch.Tensor, size, resample: str, device) -> torch.Tensor:
         """a client's uint8 image [1, H, W, 3] or mask [1, H, W] at the request's (H, W): Pillow's resize on the device (ops.resize_u8)"""
@@ -186,7 +238,7 @@ class Denoiser:
         to the same bytes; None: the image has the request's size already."""
         if size is not None:
             image = self._resize_client_u8("start_from_image", image, size, resample, encoder.device)
-        self.set_timesteps(req)
+        self._restart(req)
         t_start = start_step(req.num_inference_steps, strength)
         keep, sigma = self._start_mix(np.float32(req.sigmas[t_start]))
         f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
@@ -263,7 +315,7 @@ class Denoiser:
         h, w = (image.shape[1], image.shape[2]) if u8 else (image.shape[2], image.shape[3])
         if mask.dtype != torch.uint8 or tuple(mask.shape) != (image.shape[0], h, w):
             raise MxError(f"start_inpaint: expected a uint8 mask {(image.shape[0], h, w)}, got {mask.dtype} {tuple(mask.shape)}")
-        self.set_timesteps(req)
+        self._restart(req)
         t_start = start_step(req.num_inference_steps, strength)
         f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
         init = (encoder.encode_images if u8 else encoder.encode)(image, posterior_noise=posterior_noise)
@@ -296,8 +348,9 @@ class Denoiser:
         here = torch.cuda.current_stream()
         for r in reqs:                                                   # latents may have been produced on another stream
             r.latents.record_stream(here)
-        e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs)), reqs,
-                              lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs))
+        e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs),
+                               tuple(getattr(r, "sampler", "euler") for r in reqs)), reqs,
+                              lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs))
         lat = self._cache.latents(e, reqs)
         sig, sig_next, ts = self._cache.step_scalars(e, reqs)
         return _Part(res, reqs, e, lat, sig, sig_next, torch.cat([ts, ts], dim=0) if do_classifier_free_guidance else ts,
@@ -335,11 +388,18 @@ class Denoiser:
             noise = self._forward_mixed([p.x_in for p in parts], ts, cond, patch_size // 8 if is_sliced else 0)
         g = self.guidance_scale if do_classifier_free_guidance else 0.0
         for p, nz in zip(parts, noise):
-            if p.entry.inpaint is None:
+            ms = p.entry.multistep
+            if ms is not None:                                                     # a request here steps by DPM-Solver++ 2M or AB2: one launch for all samplers
+                hist = self._cache.history(p.entry, p.reqs, p.latents)
+                hist.record_stream(torch.cuda.current_stream())                    # like the latents, it may have been made on another stream
+                ops.cfg_multistep_step_(nz, p.latents, p.sigma, p.sigma_next, g, ms.kind, ms.coef, hist, self.flow, *(p.entry.inpaint or ()))
+            elif p.entry.inpaint is None:
                 self._scheduler_step(nz, p.latents, p.sigma, p.sigma_next, g)      # :382-397
             else:                                                                  # the same step, the kept region of the inpainting rows put back
                 self._scheduler_step_masked(nz, p.latents, p.sigma, p.sigma_next, g, *p.entry.inpaint)
             for i, r in enumerate(p.reqs):                                         # :399-403
+                if ms is not None and ms.host_kind[i]:                             # the history travels on the request, like its latents
+                    r.history, r.history_step = hist[i:i + 1], r.step_index
                 r.step_index += 1
                 r.latents = p.latents[i:i + 1]
 
@@ -349,22 +409,31 @@ class Denoiser:
 
 class SDXLDenoiser(Denoiser):
     announces_composition = True
+    samplers = ("euler", "dpmpp_2m", "ab2")
 
     def __init__(self, unet: MxUNet, guidance_scale: float = 5.0):
         super().__init__(unet, guidance_scale)     # reference default (pipeline_..._esymred.py:265)
         self.unet = unet
 
-    def set_timesteps(self, req: Request) -> None:
-        req.timesteps, req.sigmas = self._table(req.num_inference_steps)[:2]
+    def set_timesteps(self, req: Request, sampler: str = "euler", schedule: str = "default") -> None:
+        """the request's schedule and sampler.  ``sampler``: "euler" (EulerDiscreteScheduler, the default), "dpmpp_2m" (DPM-Solver++ 2M) or "ab2"
+        (second-order Adams-Bashforth); ``schedule``: "default" (``euler_tables``) or "karras" (``karras_tables``) -- "dpmpp_2m" with "karras" is
+        what users call DPM++ 2M Karras, and the sampler gains little without the schedule."""
+        self._check_sampler(sampler)
+        if schedule not in ("default", "karras"):
+            raise MxError(f"SDXLDenoiser.set_timesteps: schedule must be 'default' or 'karras', got {schedule!r}")
+        req.timesteps, req.sigmas = self._table(req.num_inference_steps, schedule)[:2]
         req.step_index = 0
+        req.sampler, req.history, req.history_step = sampler, None, -1
 
     def init_noise_sigma(self, num_inference_steps: int) -> float:
         return self._table(num_inference_steps)[2]
 
-    def _table(self, num_inference_steps: int) -> tuple:
-        if num_inference_steps not in self._tables:
-            self._tables[num_inference_steps] = euler_tables(num_inference_steps)
-        return self._tables[num_inference_steps]
+    def _table(self, num_inference_steps: int, schedule: str = "default") -> tuple:
+        key = num_inference_steps if schedule == "default" else (num_inference_steps, schedule)
+        if key not in self._tables:
+            self._tables[key] = euler_tables(num_inference_steps) if schedule == "default" else karras_tables(num_inference_steps)
+        return self._tables[key]
 
     @staticmethod
     def _cond(reqs, do_classifier_free_guidance: bool) -> tuple:
@@ -412,7 +481,7 @@ def _synthetic_embeds(seed: int, shared: Optional[dict], ctx_len: int, ehs_dim: 
 
 
 def synthetic_request(rid: int, resolution: int, steps: int, cfg, denoiser: SDXLDenoiser, device, dtype=torch.bfloat16,
-                      seed: int = 10086, shared: Optional[dict] = None) -> Request:
+                      seed: int = 10086, shared: Optional[dict] = None, sampler: str = "euler", schedule: str = "default") -> Request:
     """Fixed-prompt synthetic request: embeddings ~N(0,1) from the reference seed, time ids
     (res, res, 0, 0, res, res) (pipeline_..._esymred.py:181-187), latents randn * init_noise_sigma."""
     g = torch.Generator(device="cpu").manual_seed(seed + 17 * rid)
@@ -422,5 +491,5 @@ def synthetic_request(rid: int, resolution: int, steps: int, cfg, denoiser: SDXL
     lat = torch.randn(1, cfg.in_channels, resolution // 8, resolution // 8, generator=g)
     lat = (lat * denoiser.init_noise_sigma(steps)).to(device=device, dtype=dtype)
     req = Request(rid, resolution, steps, lat, pe, ne, pp, npp, tid, tid.clone())
-    denoiser.set_timesteps(req)
+    denoiser.set_timesteps(req, sampler=sampler, schedule=schedule)
     return req

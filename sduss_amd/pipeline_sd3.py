@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .lib import MxError
 from .pipeline import Denoiser, InpaintState, _synthetic_embeds
 from .transformer_sd3 import MxSD3Transformer
 
@@ -45,6 +46,9 @@ class SD3Request:
     start: Optional[float] = None
     finish: Optional[float] = None
     inpaint: Optional[InpaintState] = None
+    sampler: str = "euler"                # "euler" | "ab2" (set_timesteps)
+    history: Optional[torch.Tensor] = None   # fp32 [1, C, h, w]: the model output of the last AB2 step, a view of its composition's buffer
+    history_step: int = -1                # the step that left ``history``
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -57,11 +61,24 @@ class SD3Denoiser(Denoiser):
         super().__init__(transformer, guidance_scale)     # reference default (pipeline_stable_diffusion_3_esymred.py:236)
         self.transformer = transformer
 
-    def set_timesteps(self, req: SD3Request) -> None:
+    flow = True
+    samplers = ("euler", "ab2")
+
+    def set_timesteps(self, req: SD3Request, sampler: str = "euler", schedule: str = "default") -> None:
+        """the request's schedule and sampler: "euler" (the flow-match Euler step, the default) or "ab2" (second-order Adams-Bashforth in sigma).
+        DPM-Solver++ 2M is refused on the flow model: its log-SNR is -infinity at sigma = 1, and on the analytic Gaussian problem it is worse
+        than Euler at every step count.  The Karras schedule is defined for the epsilon model's sigma range only."""
+        if sampler == "dpmpp_2m":
+            raise MxError("SD3Denoiser.set_timesteps: dpmpp_2m is refused on the flow model (log-SNR is -infinity at sigma = 1; worse than Euler "
+                          "on the analytic problem); use 'ab2'")
+        self._check_sampler(sampler)
+        if schedule != "default":
+            raise MxError(f"SD3Denoiser.set_timesteps: the flow model has one schedule; {schedule!r} is for SDXL")
         if req.num_inference_steps not in self._tables:
             self._tables[req.num_inference_steps] = flow_match_tables(req.num_inference_steps)
         req.timesteps, req.sigmas = self._tables[req.num_inference_steps]
         req.step_index = 0
+        req.sampler, req.history, req.history_step = sampler, None, -1
 
     @staticmethod
     def _scale_input(lat: torch.Tensor, sig: torch.Tensor, do_classifier_free_guidance: bool) -> torch.Tensor:
@@ -86,10 +103,11 @@ class SD3Denoiser(Denoiser):
 
 
 def synthetic_sd3_request(rid: int, resolution: int, steps: int, cfg, denoiser: SD3Denoiser, device, dtype=torch.bfloat16,
-                          seed: int = 10086, shared: Optional[dict] = None, ctx_len: int = 333) -> SD3Request:
+                          seed: int = 10086, shared: Optional[dict] = None, ctx_len: int = 333, sampler: str = "euler",
+                          schedule: str = "default") -> SD3Request:
     g = torch.Generator(device="cpu").manual_seed(seed + 17 * rid)
     pe, ne, pp, npp = _synthetic_embeds(seed, shared, ctx_len, cfg.joint_attention_dim, cfg.pooled_projection_dim, device, dtype)
     lat = torch.randn(1, cfg.in_channels, resolution // 8, resolution // 8, generator=g).to(device=device, dtype=dtype)
     req = SD3Request(rid, resolution, steps, lat, pe, ne, pp, npp)
-    denoiser.set_timesteps(req)
+    denoiser.set_timesteps(req, sampler=sampler, schedule=schedule)
     return req

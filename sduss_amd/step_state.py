@@ -7,6 +7,10 @@ tens of steps, so here the concatenated conditioning, a [3, n, S] table (sigma, 
 and a device-resident step index are built ONCE per composition; a step then costs one gather and one increment on the
 device and no host-to-device copy.  The host list of step indices is compared every step, so a caller that rewinds or
 skips a request (bench.py keeps its batch full by resetting step_index) is followed with one small asynchronous upload.
+
+A composition with a multistep sampler (DPM-Solver++ 2M, AB2: csrc/sampler_step.hip) also holds its rows' kinds, their coefficient table of
+every step in both orders and the fp32 history buffer; the step's [n, 3] coefficients are one more gather by the same device index, and the
+order of every row (second only right after a step that left its history) is followed on the host like the step index.
 """
 from __future__ import annotations
 
@@ -25,7 +29,15 @@ def _upload(host: torch.Tensor, device) -> torch.Tensor:
 
 
 class _Entry:
-    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid", "inpaint")
+    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid", "inpaint", "multistep")
+
+
+class _Multistep:
+    """the multistep rows of a composition: ``kind`` int32 [n] on the device (``host_kind`` the same list on the host), ``table`` fp32 [n, S, 2, 3] =
+    (cx, c0, c1) of every step in first and in second order, ``order`` int64 [n] on the device (1 = second order; ``host_order`` what the host
+    last uploaded), ``coef`` fp32 [n, 3] of the current step, ``hist`` the fp32 history buffer [n, C, h, w]"""
+    __slots__ = ("kind", "host_kind", "table", "order", "host_order", "coef", "hist")
+
 
 _next_uid = [0]
 
@@ -42,9 +54,11 @@ class StepCache:
         self.max_entries = max_entries
         self._entries: "OrderedDict[tuple, _Entry]" = OrderedDict()
 
-    def entry(self, key: tuple, reqs: Sequence, build_cond: Callable[[], tuple], build_inpaint: Optional[Callable[[], tuple]] = None) -> _Entry:
+    def entry(self, key: tuple, reqs: Sequence, build_cond: Callable[[], tuple], build_inpaint: Optional[Callable[[], tuple]] = None,
+              build_multistep: Optional[Callable[[], tuple]] = None) -> _Entry:
         """the entry of a batch composition, built on first use.  ``build_inpaint``: the packed rows of its inpainting requests (Denoiser._inpaint_rows;
-        None for a composition without one), fixed for the composition like ``cond``."""
+        None for a composition without one), fixed for the composition like ``cond``.  ``build_multistep``: the kinds and the [n, S, 4] coefficient
+        table of its rows (Denoiser._multistep_rows; None for a composition of Euler requests)."""
         e = self._entries.get(key)
         if e is not None:
             self._entries.move_to_end(key)
@@ -53,6 +67,7 @@ class StepCache:
         e.uid = new_uid()
         e.cond = build_cond()
         e.inpaint = build_inpaint() if build_inpaint is not None else None
+        e.multistep = self._multistep(build_multistep() if build_multistep is not None else None)
         n = len(reqs)
         s_max = max(len(r.timesteps) for r in reqs)
         tab = np.zeros((3, n, s_max), dtype=np.float32)
@@ -72,6 +87,29 @@ class StepCache:
             self._entries.popitem(last=False)
         return e
 
+    def _multistep(self, built: Optional[tuple]) -> Optional[_Multistep]:
+        if built is None:
+            return None
+        kinds, tab4 = built                               # tab4 [n, S, 4] = (cx, c0 first order, c0 second order, c1 second order): mx_sampler_coeffs
+        m = _Multistep()
+        m.host_kind = [k if k in (1, 2) else 0 for k in kinds]
+        m.kind = _upload(torch.tensor(m.host_kind, dtype=torch.int32), self.device)
+        both = np.zeros(tab4.shape[:2] + (2, 3), dtype=np.float32)
+        both[:, :, 0, :2] = tab4[:, :, :2]                # first order: c1 = 0, the history is not read
+        both[:, :, 1, 0] = tab4[:, :, 0]
+        both[:, :, 1, 1:] = tab4[:, :, 2:]
+        m.table = _upload(torch.from_numpy(both), self.device)
+        m.order = torch.zeros(len(kinds), dtype=torch.int64, device=self.device)
+        m.host_order = [0] * len(kinds)
+        m.coef = m.hist = None
+        return m
+
+    @staticmethod
+    def _orders(m: _Multistep, reqs: Sequence) -> List[int]:
+        """1 for the rows that step second order now: a multistep row whose request carries the history of the step right before this one (not the
+        first step of a request wherever it starts, not a rewound one)"""
+        return [int(bool(k) and r.history is not None and r.history_step == r.step_index - 1) for k, r in zip(m.host_kind, reqs)]
+
     def step_scalars(self, e: _Entry, reqs: Sequence) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(sigma, sigma_next, timestep) fp32 [n] of the requests' CURRENT step; advances the device-side index."""
         host = [r.step_index for r in reqs]
@@ -81,6 +119,13 @@ class StepCache:
         if host != e.host_idx:
             e.idx.copy_(_upload(torch.tensor(host, dtype=torch.int64), self.device), non_blocking=True)
         vals = e.table[:, e.rows, e.idx]          # [3, n]
+        m = e.multistep
+        if m is not None:                         # (cx, c0, c1) of this step in each row's order, by the same index
+            order = self._orders(m, reqs)
+            if order != m.host_order:             # a request's first step, its second, a rewind: in between the orders stand
+                m.order.copy_(_upload(torch.tensor(order, dtype=torch.int64), self.device), non_blocking=True)
+                m.host_order = order
+            m.coef = m.table[e.rows, e.idx, m.order]          # [n, 3]
         e.idx += 1
         e.host_idx = [h + 1 for h in host]
         return vals[0], vals[1], vals[2]
@@ -95,3 +140,17 @@ class StepCache:
             return lat
         e.lat = torch.cat([r.latents for r in reqs], dim=0).contiguous()
         return e.lat
+
+    def history(self, e: _Entry, reqs: Sequence, lat: torch.Tensor) -> torch.Tensor:
+        """the composition's fp32 history buffer [n, C, h, w], shaped as the latents ``lat``.  After a step every multistep request holds a view of row
+        i of it, so it is that buffer itself; otherwise (a request arrived from another composition or denoiser) it is rebuilt by concatenation.
+        Only second-order rows are read by the step: the other rows of a rebuilt buffer are uninitialised."""
+        m = e.multistep
+        order = self._orders(m, reqs)
+        h = m.hist
+        if h is not None and h.shape == lat.shape and all(not o or (r.history.data_ptr() == h[i].data_ptr() and r.history.shape[1:] == h.shape[1:])
+                                                          for i, (o, r) in enumerate(zip(order, reqs))):
+            return h
+        blank = torch.empty((1,) + tuple(lat.shape[1:]), dtype=torch.float32, device=lat.device)
+        m.hist = torch.cat([r.history.to(device=lat.device, dtype=torch.float32) if o else blank for o, r in zip(order, reqs)], dim=0).contiguous()
+        return m.hist
