@@ -873,7 +873,7 @@ int mx_cfg_flow_step_rows(void* stream, const void* gathered, void* latents, con
                           float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype);
 
 /* ------------------------------------------------------------------------------------------
- * Inpainting (sduss_amd/csrc/inpaint.hip): repaint the masked part of an image, keep the rest.  diffusers' 4-channel rule of
+ * Inpainting (sduss_amd/csrc/scheduler_step.hip for the masked step, inpaint.hip for the rest): repaint the masked part of an image, keep the rest.  diffusers' 4-channel rule of
  * StableDiffusionXLInpaintPipeline / StableDiffusion3InpaintPipeline, which needs no 9-channel UNet: after every scheduler step
  *     init_proper = add_noise / scale_noise(image_latents, noise, t_next);   latents = (1 - mask) * init_proper + mask * latents.
  * ------------------------------------------------------------------------------------------ */
@@ -919,7 +919,7 @@ int mx_mask_to_latent(void* stream, const uint8_t* mask, uint8_t* out, int B, in
 int mx_rgb8_paste(void* stream, uint8_t* decoded, const uint8_t* original, const uint8_t* mask, int B, int H, int W);
 
 /* ------------------------------------------------------------------------------------------
- * Second-order multistep samplers (sduss_amd/csrc/sampler_step.hip, sampler_coeffs.cpp): DPM-Solver++ 2M for the epsilon model and the second-order
+ * Second-order multistep samplers (sduss_amd/csrc/scheduler_step.hip, sampler_coeffs.cpp): DPM-Solver++ 2M for the epsilon model and the second-order
  * Adams-Bashforth step (AB2) for both models, beside the model's own Euler step in ONE launch over a batch whose requests use different samplers.
  * Both are linear in the latent x, this step's quantity D and the previous step's D:
  *     x_next = cx * x + c0 * D + c1 * D_prev        D = x - sigma * m  (the data prediction, DPM-Solver++)   or   D = m  (the derivative, AB2)

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <string>
 
+#include "../../include/mxdenoise.h"
+
 namespace mx {
 
 typedef unsigned short bf16_t;  // raw bf16 bits
@@ -115,6 +117,17 @@ int cu_count();   // compute units of the current device, whole XCD groups (mult
     }                                                                                    \
   } while (0)
 #define MX_LAUNCH_CHECK() MX_HIP(hipGetLastError())
+
+// f(T{}) with T the element type of an io dtype code (MX_F32, MX_F16, MX_BF16); "<what>: bad dtype" for any other
+template <typename F> static inline int with_io_dtype(int dtype, const char* what, F&& f) {
+  if (dtype == MX_F32) return f(float{});
+  if (dtype == MX_F16) return f(_Float16{});
+  if (dtype == MX_BF16) return f(bf16_t{});
+  MX_CHECK(false, std::string(what) + ": bad dtype");
+  return 1;
+}
+// whether an access of `a` bytes at p is aligned; a null pointer (an absent operand) never stands in the way
+static inline bool aligned_to(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

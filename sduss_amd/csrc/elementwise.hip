@@ -1,15 +1,15 @@
 // Small HBM-bound glue kernels of the step plan (gfx950): layout conversion at the model boundary,
-// sinusoidal embeddings, channel concat, and the fused scheduler / CFG steps either side of the UNet.
+// sinusoidal embeddings, channel concat, and the scheduler's input scaling in front of the UNet (the step behind it: scheduler_step.hip).
 #include <algorithm>
 
 #include "common.h"
 #include "../../include/mxdenoise.h"
 
-// The scheduler kernels reproduce torch's op-by-op IEEE evaluation bit for bit: no mul+add contraction into FMA in this
+// euler_scale_input_kernel and vae_latent_finish_kernel reproduce torch's op-by-op IEEE evaluation bit for bit: no mul+add contraction into FMA in this
 // translation unit (HIP's __fmul_rn/__fadd_rn are plain operators in inlined headers and do get contracted; so plain operators here, plus
 // -ffp-contract=off for this file in the Makefile).
 #pragma clang fp contract(off)
-#include "step_math.h"   // load_as_f32 / store_from_f32, cfg_combine, euler_update, flow_update, renoise: shared with inpaint.hip
+#include "step_math.h"   // load_as_f32 / store_from_f32, rnd, renoise: shared with scheduler_step.hip and inpaint.hip
 
 namespace mx {
 
@@ -111,58 +111,6 @@ __global__ void euler_scale_input_kernel(const T* __restrict__ lat, T* __restric
   store_from_f32<T>(out, idx, load_as_f32<T>(lat, (long)src * elems + e) / denom);
 }
 
-// CFG combine + epsilon Euler step, fp32 math (pipeline_..._esymred.py:382-385; scheduling_euler_discrete.py:210-268)
-template <typename T>
-__global__ void cfg_euler_step_kernel(const T* __restrict__ noise, T* __restrict__ lat, const float* __restrict__ sigma,
-                                      const float* __restrict__ sigma_next, float g, int n_lat, long elems) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)n_lat * elems) return;
-  const int row = (int)(idx / elems);
-  float eps;
-  if (g > 0.f) {
-    const float u = load_as_f32<T>(noise, idx);
-    const float t = load_as_f32<T>(noise, (long)n_lat * elems + idx);
-    eps = cfg_combine<T>(u, t, g);
-  } else {
-    eps = load_as_f32<T>(noise, idx);
-  }
-  const float x = load_as_f32<T>(lat, idx);
-  store_from_f32<T>(lat, idx, euler_update(x, eps, sigma[row], sigma_next[row]));
-}
-
-// The same two steps on the world gather of the split-batch patch parallelism (patch_parallel.py, distri_sdxl_unet_pp.py:163-170), read where it
-// lies: gathered [2 S][n_lat][C][H / S][W], slot k < S the unconditional and slot S + k the conditional prediction of latent rows
-// [k H / S, (k + 1) H / S); lat [n_lat][C][H][W] in place.  A RUN is the R = (H / S) W elements one (latent, channel) plane has in one slot: contiguous
-// in the slot and in the latents, so with R a multiple of V every access is one aligned vector.  One thread per V elements of the latents.
-template <typename T, int V, bool FLOW>
-__global__ void cfg_step_rows_kernel(const T* __restrict__ gathered, T* __restrict__ lat, const float* __restrict__ sigma,
-                                     const float* __restrict__ sigma_next, float g, int n_lat, int C, int S, long R, long n_vec) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_vec) return;
-  const long e0 = idx * V;             // first element, in the latents' order: ((plane * S + slab) * R + e)
-  const long q = e0 / R;
-  const long e = e0 - q * R;
-  const long plane = q / S;            // latent * C + channel
-  const int slab = (int)(q - plane * S);
-  const int row = (int)(plane / C);
-  const long planes = (long)n_lat * C;
-  const T* up = gathered + ((long)slab * planes + plane) * R + e;
-  typedef elem_vec<T, V> vec;
-  const vec u = *reinterpret_cast<const vec*>(up);
-  vec x = *reinterpret_cast<const vec*>(lat + e0);
-  vec t = u;
-  if (g > 0.f) t = *reinterpret_cast<const vec*>(up + (long)S * planes * R);
-  const float s = sigma[row], sn = sigma_next[row];
-#pragma unroll
-  for (int j = 0; j < V; ++j) {
-    const float uj = load_as_f32<T>(u.v, j);
-    const float p = (g > 0.f) ? cfg_combine<T>(uj, load_as_f32<T>(t.v, j), g) : uj;
-    const float xj = load_as_f32<T>(x.v, j);
-    store_from_f32<T>(x.v, j, FLOW ? flow_update(xj, p, s, sn) : euler_update(xj, p, s, sn));
-  }
-  *reinterpret_cast<vec*>(lat + e0) = x;
-}
-
 }  // namespace mx
 
 using namespace mx;
@@ -219,20 +167,6 @@ extern "C" int mx_euler_scale_input(void* stream, const void* latents, void* out
   else if (dtype == MX_F16) hipLaunchKernelGGL((euler_scale_input_kernel<_Float16>), grid, block, 0, s, (const _Float16*)latents, (_Float16*)out, sigma, n_lat, n_rows, (long)elems);
   else if (dtype == MX_BF16) hipLaunchKernelGGL((euler_scale_input_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)latents, (bf16_t*)out, sigma, n_lat, n_rows, (long)elems);
   else MX_CHECK(false, "euler_scale_input: bad dtype");
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mx_cfg_euler_step(void* stream, const void* noise, void* latents, const float* sigma,
-                                 const float* sigma_next, float guidance_scale, int n_lat, int64_t elems, int dtype) {
-  MX_CHECK(noise && latents && sigma && sigma_next && n_lat > 0 && elems > 0, "cfg_euler_step: bad arguments");
-  const long total = (long)n_lat * elems;
-  dim3 grid((unsigned)cdiv64(total, 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MX_F32) hipLaunchKernelGGL((cfg_euler_step_kernel<float>), grid, block, 0, s, (const float*)noise, (float*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else if (dtype == MX_F16) hipLaunchKernelGGL((cfg_euler_step_kernel<_Float16>), grid, block, 0, s, (const _Float16*)noise, (_Float16*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else if (dtype == MX_BF16) hipLaunchKernelGGL((cfg_euler_step_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)noise, (bf16_t*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else MX_CHECK(false, "cfg_euler_step: bad dtype");
   MX_LAUNCH_CHECK();
   return 0;
 }
@@ -299,26 +233,6 @@ __global__ void sinus_embed_kernel(const float* __restrict__ t, bf16_t* __restri
   out[(long)b * dim + i] = f32_to_bf16((i < half) ? cosf(ang) : sinf(ang));
 }
 
-// CFG combine + flow-match Euler step: x <- x + (sigma_next - sigma) * v, fp32 math
-template <typename T>
-__global__ void cfg_flow_step_kernel(const T* __restrict__ noise, T* __restrict__ lat, const float* __restrict__ sigma,
-                                     const float* __restrict__ sigma_next, float g, int n_lat, long elems) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)n_lat * elems) return;
-  const int row = (int)(idx / elems);
-  float v;
-  if (g > 0.f) {
-    const float u = load_as_f32<T>(noise, idx);
-    const float t = load_as_f32<T>(noise, (long)n_lat * elems + idx);
-    v = cfg_combine<T>(u, t, g);   // pipeline_stable_diffusion_3_esymred.py:365-367
-  } else {
-    v = load_as_f32<T>(noise, idx);
-  }
-  const float x = load_as_f32<T>(lat, idx);
-  const float sn = sigma_next[row], s = sigma[row];
-  store_from_f32<T>(lat, idx, flow_update(x, v, s, sn));
-}
-
 int launch_patchify(hipStream_t s, const void* in, int dtype, void* out, int B, int C, int H, int W, int ps) {
   const long total = (long)B * H * W * C;
   dim3 grid((unsigned)cdiv64(total, 256)), block(256);
@@ -352,63 +266,6 @@ int launch_sinus_embed(hipStream_t s, const float* t, void* out, int B, int dim)
   return 0;
 }
 }  // namespace mx
-
-extern "C" int mx_cfg_flow_step(void* stream, const void* noise, void* latents, const float* sigma, const float* sigma_next,
-                                float guidance_scale, int n_lat, int64_t elems, int dtype) {
-  MX_CHECK(noise && latents && sigma && sigma_next && n_lat > 0 && elems > 0, "cfg_flow_step: bad arguments");
-  const long total = (long)n_lat * elems;
-  dim3 grid((unsigned)cdiv64(total, 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MX_F32) hipLaunchKernelGGL((cfg_flow_step_kernel<float>), grid, block, 0, s, (const float*)noise, (float*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else if (dtype == MX_F16) hipLaunchKernelGGL((cfg_flow_step_kernel<_Float16>), grid, block, 0, s, (const _Float16*)noise, (_Float16*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else if (dtype == MX_BF16) hipLaunchKernelGGL((cfg_flow_step_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)noise, (bf16_t*)latents, sigma, sigma_next, guidance_scale, n_lat, (long)elems);
-  else MX_CHECK(false, "cfg_flow_step: bad dtype");
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- the two steps on the world gather of the split-batch patch parallelism (include/mxdenoise.h) ----
-namespace mx {
-template <typename T, bool FLOW>
-static int launch_cfg_step_rows(hipStream_t s, const void* gathered, void* latents, const float* sigma, const float* sigma_next, float g,
-                                int n_lat, int C, int S, long R, long total) {
-  constexpr int V = 16 / (int)sizeof(T);
-  // the vector path needs every run to start on a 16-byte boundary in both buffers: both bases aligned and the run a whole number of vectors
-  const bool vec = R % V == 0 && (uintptr_t)gathered % 16 == 0 && (uintptr_t)latents % 16 == 0;
-  const long n_vec = vec ? total / V : total;
-  const int64_t blocks = cdiv64(n_vec, 256);
-  MX_CHECK(blocks <= 0x7fffffffL, "cfg_step_rows: too many elements for one launch");
-  dim3 grid((unsigned)blocks), block(256);
-  if (vec) hipLaunchKernelGGL((cfg_step_rows_kernel<T, V, FLOW>), grid, block, 0, s, (const T*)gathered, (T*)latents, sigma, sigma_next, g, n_lat, C, S, R, n_vec);
-  else hipLaunchKernelGGL((cfg_step_rows_kernel<T, 1, FLOW>), grid, block, 0, s, (const T*)gathered, (T*)latents, sigma, sigma_next, g, n_lat, C, S, R, n_vec);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-template <bool FLOW>
-static int cfg_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next, float g, int n_lat,
-                         int C, int H, int W, int n_slabs, int dtype) {
-  MX_CHECK(gathered && latents && sigma && sigma_next && n_lat > 0 && C > 0 && H > 0 && W > 0, "cfg_step_rows: bad arguments");
-  MX_CHECK(n_slabs > 0 && H % n_slabs == 0, "cfg_step_rows: the latent height must be a positive multiple of n_slabs");
-  const long R = (long)(H / n_slabs) * W;
-  const long total = (long)n_lat * C * H * W;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MX_F32) return launch_cfg_step_rows<float, FLOW>(s, gathered, latents, sigma, sigma_next, g, n_lat, C, n_slabs, R, total);
-  if (dtype == MX_F16) return launch_cfg_step_rows<_Float16, FLOW>(s, gathered, latents, sigma, sigma_next, g, n_lat, C, n_slabs, R, total);
-  if (dtype == MX_BF16) return launch_cfg_step_rows<bf16_t, FLOW>(s, gathered, latents, sigma, sigma_next, g, n_lat, C, n_slabs, R, total);
-  MX_CHECK(false, "cfg_step_rows: bad dtype");
-  return 1;
-}
-}  // namespace mx
-
-extern "C" int mx_cfg_euler_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next,
-                                      float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype) {
-  return cfg_step_rows<false>(stream, gathered, latents, sigma, sigma_next, guidance_scale, n_lat, C, H, W, n_slabs, dtype);
-}
-
-extern "C" int mx_cfg_flow_step_rows(void* stream, const void* gathered, void* latents, const float* sigma, const float* sigma_next,
-                                     float guidance_scale, int n_lat, int C, int H, int W, int n_slabs, int dtype) {
-  return cfg_step_rows<true>(stream, gathered, latents, sigma, sigma_next, guidance_scale, n_lat, C, H, W, n_slabs, dtype);
-}
 
 // ------------------------------------------------------------------------------------------
 // Row softmax in place on a bf16 [rows, L] score matrix (fp32 math): the VAE decoder's single-head, 512-wide mid-block

@@ -2,10 +2,10 @@
 // StableDiffusion3InpaintPipeline, which works with the base checkpoints of both models.  After every scheduler step the kept region of the latents
 // is put back as the image's own latents re-noised to the step's next sigma:
 //     init_proper = add_noise / scale_noise(image_latents, noise, t_next);   latents = (1 - mask) * init_proper + mask * latents
-// Here that is part of the step launch that reads and writes the latents anyway (cfg_step_masked_kernel), over a batch in which inpainting and plain
-// requests step together.  Beside it the three small kernels a request needs once: its starting latents (inpaint_renoise_kernel), its mask on the
-// latent grid (mask_to_latent_kernel) and the client's own pixels back outside the mask of the decoded image (rgb8_paste_kernel).
-// HBM-bound passes: 16-byte accesses where the layout allows, element accesses otherwise (elementwise.hip's cfg_step_rows_kernel is the pattern).
+// That is part of the step launch that reads and writes the latents anyway (scheduler_step.hip, the MASKED form of cfg_step_kernel), over a batch in
+// which inpainting and plain requests step together.  Here the three small kernels a request needs once: its starting latents
+// (inpaint_renoise_kernel), its mask on the latent grid (mask_to_latent_kernel) and the client's own pixels back outside the mask of the decoded image
+// (rgb8_paste_kernel).  HBM-bound passes: 16-byte accesses where the layout allows, element accesses otherwise.
 #include <algorithm>
 
 #include "common.h"
@@ -16,50 +16,6 @@
 #include "step_math.h"
 
 namespace mx {
-
-// One thread per V elements of the latents [n_lat][C][hw] (in place); pred [2 n_lat | n_lat][C][hw].  Row r with j = slot[r] in [0, k) is an inpainting
-// row: where mask[j][p] == 0 the element becomes renoise(init[j], noise[j], keep, sigma_next[r]) instead of the stepped value.  On the vector path hw is a
-// whole number of vectors and every base is aligned, so a vector lies inside one (row, channel) plane and its V mask bytes are one aligned load.
-template <typename T, int V, bool FLOW>
-__global__ void cfg_step_masked_kernel(const T* __restrict__ pred, T* __restrict__ lat, const float* __restrict__ sigma, const float* __restrict__ sigma_next,
-                                       float g, int n_lat, long elems, int hw, long n_vec, int k, const int* __restrict__ slot,
-                                       const T* __restrict__ init, const T* __restrict__ noise, const unsigned char* __restrict__ mask) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_vec) return;
-  const long e0 = idx * V;
-  const int row = (int)(e0 / elems);
-  typedef elem_vec<T, V> vec;
-  const vec u = *reinterpret_cast<const vec*>(pred + e0);
-  vec t = u;
-  if (g > 0.f) t = *reinterpret_cast<const vec*>(pred + (long)n_lat * elems + e0);
-  vec x = *reinterpret_cast<const vec*>(lat + e0);
-  const float s = sigma[row], sn = sigma_next[row];
-#pragma unroll
-  for (int i = 0; i < V; ++i) {
-    const float ui = load_as_f32<T>(u.v, i);
-    const float p = (g > 0.f) ? cfg_combine<T>(ui, load_as_f32<T>(t.v, i), g) : ui;
-    const float xi = load_as_f32<T>(x.v, i);
-    store_from_f32<T>(x.v, i, FLOW ? flow_update(xi, p, s, sn) : euler_update(xi, p, s, sn));
-  }
-  const int j = k > 0 ? slot[row] : -1;
-  if (j >= 0 && j < k) {                       // (anything else is a plain row: a wrong slot never becomes an address)
-    const long within = e0 - (long)row * elems;
-    const int p0 = (int)(within % hw);
-    const elem_vec<unsigned char, V> m = *reinterpret_cast<const elem_vec<unsigned char, V>*>(mask + (long)j * hw + p0);
-    bool any_kept = false;
-#pragma unroll
-    for (int i = 0; i < V; ++i) any_kept |= m.v[i] == 0;
-    if (any_kept) {
-      const vec a = *reinterpret_cast<const vec*>(init + (long)j * elems + within);
-      const vec n = *reinterpret_cast<const vec*>(noise + (long)j * elems + within);
-      const float keep = FLOW ? 1.0f - sn : 1.0f;
-#pragma unroll
-      for (int i = 0; i < V; ++i)
-        if (m.v[i] == 0) store_from_f32<T>(x.v, i, renoise(load_as_f32<T>(a.v, i), load_as_f32<T>(n.v, i), keep, sn));
-    }
-  }
-  *reinterpret_cast<vec*>(lat + e0) = x;
-}
 
 // out[r] = keep[r] * init[r] + sigma[r] * noise[r] over n rows of `elems`; one thread per V elements (elems % V == 0 on the vector path)
 template <typename T, int V>
@@ -122,43 +78,6 @@ __global__ void rgb8_paste_kernel(unsigned char* __restrict__ dec, const unsigne
   }
 }
 
-static bool aligned_to(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
-
-template <typename T, bool FLOW>
-static int launch_cfg_step_masked(hipStream_t s, const void* pred, void* latents, const float* sigma, const float* sigma_next, float g, int n_lat, int C, int hw,
-                                  const mx_inpaint_rows* r) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const long elems = (long)C * hw, total = (long)n_lat * elems;
-  // the vector path: every plane of hw elements starts on a 16-byte boundary in all four tensors, and on a V-byte boundary in the mask
-  const bool vec = hw % V == 0 && aligned_to(pred, 16) && aligned_to(latents, 16) &&
-                   (r->k == 0 || (aligned_to(r->init, 16) && aligned_to(r->noise, 16) && aligned_to(r->mask, V)));
-  const long n_vec = vec ? total / V : total;
-  const int64_t blocks = cdiv64(n_vec, 256);
-  MX_CHECK(blocks <= 0x7fffffffL, "cfg_step_masked: too many elements for one launch");
-  dim3 grid((unsigned)blocks), block(256);
-  if (vec) hipLaunchKernelGGL((cfg_step_masked_kernel<T, V, FLOW>), grid, block, 0, s, (const T*)pred, (T*)latents, sigma, sigma_next, g, n_lat, elems, hw, n_vec,
-                              r->k, r->slot, (const T*)r->init, (const T*)r->noise, r->mask);
-  else hipLaunchKernelGGL((cfg_step_masked_kernel<T, 1, FLOW>), grid, block, 0, s, (const T*)pred, (T*)latents, sigma, sigma_next, g, n_lat, elems, hw, n_vec,
-                          r->k, r->slot, (const T*)r->init, (const T*)r->noise, r->mask);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-template <bool FLOW>
-static int cfg_step_masked(void* stream, const void* pred, void* latents, const float* sigma, const float* sigma_next, float g, int n_lat, int C, int hw, int dtype,
-                           const mx_inpaint_rows* r) {
-  MX_CHECK(pred && latents && sigma && sigma_next && r, "cfg_step_masked: null operand");
-  MX_CHECK(n_lat > 0 && C > 0 && hw > 0, "cfg_step_masked: sizes must be positive");
-  MX_CHECK(r->k >= 0, "cfg_step_masked: k must not be negative");
-  MX_CHECK(r->k == 0 || (r->slot && r->init && r->noise && r->mask), "cfg_step_masked: inpainting rows need slot, init, noise and mask");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MX_F32) return launch_cfg_step_masked<float, FLOW>(s, pred, latents, sigma, sigma_next, g, n_lat, C, hw, r);
-  if (dtype == MX_F16) return launch_cfg_step_masked<_Float16, FLOW>(s, pred, latents, sigma, sigma_next, g, n_lat, C, hw, r);
-  if (dtype == MX_BF16) return launch_cfg_step_masked<bf16_t, FLOW>(s, pred, latents, sigma, sigma_next, g, n_lat, C, hw, r);
-  MX_CHECK(false, "cfg_step_masked: bad dtype");
-  return 1;
-}
-
 template <typename T>
 static int launch_inpaint_renoise(hipStream_t s, const void* init, const void* noise, void* out, const float* keep, const float* sigma, int n, long elems) {
   constexpr int V = 16 / (int)sizeof(T);
@@ -176,27 +95,14 @@ static int launch_inpaint_renoise(hipStream_t s, const void* init, const void* n
 
 }  // namespace mx
 
-extern "C" int mx_cfg_euler_step_masked(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
-                                        int n_lat, int C, int hw, int dtype, const mx_inpaint_rows* rows) {
-  return mx::cfg_step_masked<false>(stream, noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype, rows);
-}
-
-extern "C" int mx_cfg_flow_step_masked(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
-                                       int n_lat, int C, int hw, int dtype, const mx_inpaint_rows* rows) {
-  return mx::cfg_step_masked<true>(stream, noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype, rows);
-}
-
 extern "C" int mx_inpaint_renoise(void* stream, const void* init, const void* noise, void* out, const float* keep, const float* sigma, int n, int64_t elems,
                                   int dtype) {
   MX_CHECK(init && noise && out && keep && sigma, "inpaint_renoise: null operand");
   MX_CHECK(n > 0 && elems > 0, "inpaint_renoise: sizes must be positive");
   MX_CHECK(out != init && out != noise, "inpaint_renoise: out may alias neither input");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MX_F32) return mx::launch_inpaint_renoise<float>(s, init, noise, out, keep, sigma, n, (long)elems);
-  if (dtype == MX_F16) return mx::launch_inpaint_renoise<_Float16>(s, init, noise, out, keep, sigma, n, (long)elems);
-  if (dtype == MX_BF16) return mx::launch_inpaint_renoise<mx::bf16_t>(s, init, noise, out, keep, sigma, n, (long)elems);
-  MX_CHECK(false, "inpaint_renoise: bad dtype");
-  return 1;
+  return mx::with_io_dtype(dtype, "inpaint_renoise", [&](auto tag) {
+    return mx::launch_inpaint_renoise<decltype(tag)>((hipStream_t)stream, init, noise, out, keep, sigma, n, (long)elems);
+  });
 }
 
 extern "C" int mx_mask_to_latent(void* stream, const uint8_t* mask, uint8_t* out, int B, int H, int W, int f) {

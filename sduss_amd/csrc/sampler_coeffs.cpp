@@ -1,4 +1,4 @@
-// The step coefficients of the multistep samplers (sampler_step.hip), built on the host: DPM-Solver++ 2M in k-diffusion's variance-exploding form
+// The step coefficients of the multistep samplers (scheduler_step.hip), built on the host: DPM-Solver++ 2M in k-diffusion's variance-exploding form
 // (sample_dpmpp_2m) and the second-order Adams-Bashforth step on a non-uniform sigma grid.  Host only and plain C++: nothing of HIP is included, so
 // tests/sampler_coeffs_walk.cpp links this file alone.  Everything is double precision, each coefficient rounded to float once; this file is
 // compiled without FMA contraction (Makefile), so the Python restatement of the tests computes the same doubles.

@@ -1,6 +1,6 @@
-// The per-element arithmetic of the scheduler steps, one definition for every translation unit that steps latents (elementwise.hip, inpaint.hip,
-// sampler_step.hip): the io-dtype loads and stores, the CFG combine, the two Euler updates, the re-noising of clean latents and the linear multistep
-// update.  Every function is a chain of separately rounded IEEE fp32 operations that torch evaluates identically op by op, so an including file
+// The per-element arithmetic of the scheduler step (scheduler_step.hip) and of the kernels beside it that round like it (elementwise.hip's input
+// scaling and vae_latent_finish_kernel, inpaint.hip's start re-noising): the io-dtype loads and stores, the CFG combine, the two Euler updates, the
+// re-noising of clean latents and the linear multistep update.  Every function is a chain of separately rounded IEEE fp32 operations that torch evaluates identically op by op, so an including file
 // must not contract mul + add into FMA: it is built with -ffp-contract=off (Makefile) and the pragma below covers everything that follows the
 // include.
 #pragma once
@@ -29,11 +29,22 @@ template <typename T> __device__ __forceinline__ float rnd(float v) {
 // V elements of T moved as one access (16 bytes on the vector path, one element on the other)
 template <typename T, int V> struct alignas(sizeof(T) * V) elem_vec { T v[V]; };
 
-// The per-element arithmetic of the two CFG steps, shared by the kernels over a [2 n, elems] prediction, the ones that read the world
-// gather of the split-batch patch parallelism where it lies (cfg_step_rows_kernel) and the masked step of inpainting (cfg_step_masked_kernel): the
-// same operations in the same order, so the same bits.
+// The per-element arithmetic of the CFG steps: every form of cfg_step_kernel (scheduler_step.hip) runs these operations in this order, so the same bits.
 // the combine runs in the model dtype (pipeline_..._esymred.py:383-385; pipeline_stable_diffusion_3_esymred.py:365-367): one rounding per op
 template <typename T> __device__ __forceinline__ float cfg_combine(float u, float t, float g) { return rnd<T>(u + rnd<T>(g * rnd<T>(t - u))); }
+// the guided prediction of V elements: u alone without guidance (the conditional half, `cond` elements on, is then not read)
+template <typename T, int V> __device__ __forceinline__ void guided_prediction(const T* up, long cond, float g, float (&p)[V]) {
+  typedef elem_vec<T, V> vec;
+  const vec u = *reinterpret_cast<const vec*>(up);
+  if (g > 0.f) {
+    const vec t = *reinterpret_cast<const vec*>(up + cond);
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = cfg_combine<T>(load_as_f32<T>(u.v, i), load_as_f32<T>(t.v, i), g);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = load_as_f32<T>(u.v, i);
+  }
+}
 // epsilon Euler step (scheduling_euler_discrete.py:210-268): separate IEEE ops (no fma contraction) so the fp32 chain matches torch's op-by-op evaluation
 __device__ __forceinline__ float euler_update(float x, float eps, float s, float sn) {
   const float pred_x0 = (x - (s * eps));
@@ -54,7 +65,7 @@ __device__ __forceinline__ float renoise(float init, float noise, float keep, fl
   return a + n;
 }
 
-// The multistep samplers (sampler_step.hip): x_next = cx x + c0 D + c1 D_prev, every product and sum rounded on its own.
+// The multistep rows (scheduler_step.hip, MULTI): x_next = cx x + c0 D + c1 D_prev, every product and sum rounded on its own.
 // D of DPM-Solver++ 2M, the data prediction of the epsilon model: x - sigma * eps
 __device__ __forceinline__ float multistep_data(float x, float eps, float s) {
   const float n = s * eps;

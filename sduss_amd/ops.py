@@ -361,19 +361,28 @@ def euler_scale_input(latents: torch.Tensor, sigma: torch.Tensor, n_rows: int) -
     return out
 
 
+def _cfg_step_plain_(fn_name: str, noise: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                     guidance_scale: float) -> torch.Tensor:
+    l = _lib.load()
+    assert latents.is_contiguous() and noise.is_contiguous() and noise.dtype == latents.dtype
+    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
+    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+    _lib.check(getattr(l, fn_name)(_lib.current_stream(), noise.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
+                                   float(guidance_scale), latents.shape[0], latents[0].numel(), _lib.torch_dtype_code(latents.dtype)), fn_name)
+    return latents
+
+
 def cfg_euler_step_(noise: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
                     guidance_scale: float) -> torch.Tensor:
     """In place: latents <- Euler step with eps = u + g (t - u); noise = [uncond rows ; cond rows] (g > 0)
     or the plain prediction (g <= 0)."""
-    l = _lib.load()
-    assert latents.is_contiguous() and noise.is_contiguous() and noise.dtype == latents.dtype
-    n_lat = latents.shape[0]
-    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
-    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
-    _lib.check(l.mx_cfg_euler_step(_lib.current_stream(), noise.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
-                                   float(guidance_scale), n_lat, latents[0].numel(), _lib.torch_dtype_code(latents.dtype)),
-               "mx_cfg_euler_step")
-    return latents
+    return _cfg_step_plain_("mx_cfg_euler_step", noise, latents, sigma, sigma_next, guidance_scale)
+
+
+def cfg_flow_step_(noise: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                   guidance_scale: float) -> torch.Tensor:
+    """The flow-match step on the same layout: latents <- latents + (sigma_next - sigma) * (u + g (t - u))."""
+    return _cfg_step_plain_("mx_cfg_flow_step", noise, latents, sigma, sigma_next, guidance_scale)
 
 
 def layernorm_mod(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, rows_per_batch: int, eps: float = 1e-6,
@@ -400,20 +409,11 @@ def rmsnorm_heads_(x: torch.Tensor, nbatch: int, rows_per_batch: int, batch_rows
     return x
 
 
-def cfg_flow_step_(noise: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
-                   guidance_scale: float) -> torch.Tensor:
-    l = _lib.load()
-    assert latents.is_contiguous() and noise.is_contiguous() and noise.dtype == latents.dtype
-    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
-    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
-    _lib.check(l.mx_cfg_flow_step(_lib.current_stream(), noise.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
-                                  float(guidance_scale), latents.shape[0], latents[0].numel(), _lib.torch_dtype_code(latents.dtype)),
-               "mx_cfg_flow_step")
-    return latents
-
-
-def _cfg_step_rows_(fn_name: str, gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
-                    guidance_scale: float, n_slabs: int) -> torch.Tensor:
+def cfg_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                   guidance_scale: float, n_slabs: int, flow: bool) -> torch.Tensor:
+    """In place: the model's step (``flow``: the flow-match one) on the world gather of the split-batch patch parallelism, read where it lies:
+    gathered [2 * n_slabs, n_lat, C, H / n_slabs, W] = [uncond row slabs ; cond row slabs], latents [n_lat, C, H, W]."""
+    fn_name = "mx_cfg_flow_step_rows" if flow else "mx_cfg_euler_step_rows"
     l = _lib.load()
     assert latents.ndim == 4 and latents.is_contiguous() and gathered.is_contiguous() and gathered.dtype == latents.dtype
     n_lat, c, h, w = latents.shape
@@ -427,28 +427,26 @@ def _cfg_step_rows_(fn_name: str, gathered: torch.Tensor, latents: torch.Tensor,
 
 def cfg_euler_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
                          guidance_scale: float, n_slabs: int) -> torch.Tensor:
-    """In place: cfg_euler_step_ on the world gather of the split-batch patch parallelism, read where it lies: gathered
-    [2 * n_slabs, n_lat, C, H / n_slabs, W] = [uncond row slabs ; cond row slabs], latents [n_lat, C, H, W] (mx_cfg_euler_step_rows)."""
-    return _cfg_step_rows_("mx_cfg_euler_step_rows", gathered, latents, sigma, sigma_next, guidance_scale, n_slabs)
+    """cfg_step_rows_ with the Euler step (mx_cfg_euler_step_rows)."""
+    return cfg_step_rows_(gathered, latents, sigma, sigma_next, guidance_scale, n_slabs, False)
 
 
 def cfg_flow_step_rows_(gathered: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
                         guidance_scale: float, n_slabs: int) -> torch.Tensor:
-    """The flow-match step on the same layout (mx_cfg_flow_step_rows)."""
-    return _cfg_step_rows_("mx_cfg_flow_step_rows", gathered, latents, sigma, sigma_next, guidance_scale, n_slabs)
+    """cfg_step_rows_ with the flow-match step (mx_cfg_flow_step_rows)."""
+    return cfg_step_rows_(gathered, latents, sigma, sigma_next, guidance_scale, n_slabs, True)
 
 
-# ---- inpainting (csrc/inpaint.hip) ----
+# ---- the masked and the multistep step (csrc/scheduler_step.hip), inpainting (csrc/inpaint.hip) ----
 
 def _need(cond: bool, what: str) -> None:
     if not cond:
         raise _lib.MxError(what)
 
 
-def _cfg_step_masked_(fn_name: str, noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
-                      guidance_scale: float, slot: Optional[torch.Tensor], init: Optional[torch.Tensor], noise: Optional[torch.Tensor],
-                      mask: Optional[torch.Tensor]) -> torch.Tensor:
-    l = _lib.load()
+def _step_operands(fn_name: str, noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                   guidance_scale: float) -> tuple:
+    """the operands every step on [n, C, h, w] latents shares, checked -> (sigma, sigma_next) as fp32 on the latents' device"""
     _need(latents.ndim == 4 and latents.is_contiguous(), f"{fn_name}: latents must be a contiguous [n, C, h, w] tensor")
     n_lat, c, h, w = latents.shape
     rows = (2 if guidance_scale > 0 else 1) * n_lat
@@ -456,22 +454,37 @@ def _cfg_step_masked_(fn_name: str, noise_pred: torch.Tensor, latents: torch.Ten
           and noise_pred.numel() == rows * c * h * w, f"{fn_name}: the prediction must be contiguous [{rows}, {c}, {h}, {w}] of the latents' dtype")
     for name, t in (("sigma", sigma), ("sigma_next", sigma_next)):
         _need(t.numel() == n_lat, f"{fn_name}: {name} must hold one value per latent row")
+    return tuple(t.to(device=latents.device, dtype=torch.float32).contiguous() for t in (sigma, sigma_next))
+
+
+def _inpaint_rows(fn_name: str, latents: torch.Tensor, slot: Optional[torch.Tensor], init: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                  mask: Optional[torch.Tensor]) -> "_lib.InpaintRows":
+    """the inpainting rows of a step on ``latents``, checked; without init: no rows (k = 0)"""
+    n_lat, c, h, w = latents.shape
     r = _lib.InpaintRows()
-    if init is not None:
-        k = init.shape[0]
-        _need(slot is not None and noise is not None and mask is not None, f"{fn_name}: inpainting rows need slot, init, noise and mask")
-        _need(slot.dtype == torch.int32 and slot.numel() == n_lat and slot.is_contiguous() and slot.device == latents.device,
-              f"{fn_name}: slot must be a contiguous int32 [{n_lat}] on the latents' device")
-        for name, t in (("init", init), ("noise", noise)):
-            _need(t.dtype == latents.dtype and tuple(t.shape) == (k, c, h, w) and t.is_contiguous() and t.device == latents.device,
-                  f"{fn_name}: {name} must be contiguous [{k}, {c}, {h}, {w}] of the latents' dtype, got {t.dtype} {tuple(t.shape)}")
-        _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (k, h, w) and mask.is_contiguous() and mask.device == latents.device,
-              f"{fn_name}: mask must be contiguous uint8 [{k}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
-        r.k, r.slot, r.init, r.noise, r.mask = k, slot.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr()
-    else:
+    if init is None:
         _need(slot is None and noise is None and mask is None, f"{fn_name}: slot, noise and mask come with init")
-    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
-    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+        return r
+    k = init.shape[0]
+    _need(slot is not None and noise is not None and mask is not None, f"{fn_name}: inpainting rows need slot, init, noise and mask")
+    _need(slot.dtype == torch.int32 and slot.numel() == n_lat and slot.is_contiguous() and slot.device == latents.device,
+          f"{fn_name}: slot must be a contiguous int32 [{n_lat}] on the latents' device")
+    for name, t in (("init", init), ("noise", noise)):
+        _need(t.dtype == latents.dtype and tuple(t.shape) == (k, c, h, w) and t.is_contiguous() and t.device == latents.device,
+              f"{fn_name}: {name} must be contiguous [{k}, {c}, {h}, {w}] of the latents' dtype, got {t.dtype} {tuple(t.shape)}")
+    _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (k, h, w) and mask.is_contiguous() and mask.device == latents.device,
+          f"{fn_name}: mask must be contiguous uint8 [{k}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+    r.k, r.slot, r.init, r.noise, r.mask = k, slot.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr()
+    return r
+
+
+def _cfg_step_masked_(fn_name: str, noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                      guidance_scale: float, slot: Optional[torch.Tensor], init: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                      mask: Optional[torch.Tensor]) -> torch.Tensor:
+    l = _lib.load()
+    sg, sn = _step_operands(fn_name, noise_pred, latents, sigma, sigma_next, guidance_scale)
+    r = _inpaint_rows(fn_name, latents, slot, init, noise, mask)
+    n_lat, c, h, w = latents.shape
     _lib.check(getattr(l, fn_name)(_lib.current_stream(), noise_pred.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
                                    float(guidance_scale), n_lat, c, h * w, _lib.torch_dtype_code(latents.dtype), C.byref(r)), fn_name)
     return latents
@@ -493,7 +506,7 @@ def cfg_flow_step_masked_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma
     return _cfg_step_masked_("mx_cfg_flow_step_masked", noise_pred, latents, sigma, sigma_next, guidance_scale, slot, init, noise, mask)
 
 
-# ---- second-order multistep samplers (csrc/sampler_step.hip, sampler_coeffs.cpp) ----
+# ---- second-order multistep samplers (csrc/scheduler_step.hip, sampler_coeffs.cpp) ----
 
 def cfg_multistep_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float,
                         kind: torch.Tensor, coef: torch.Tensor, hist: torch.Tensor, flow: bool, slot: Optional[torch.Tensor] = None,
@@ -505,13 +518,8 @@ def cfg_multistep_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: 
     ``cfg_euler_step_masked_``."""
     fn_name = "mx_cfg_multistep_step"
     l = _lib.load()
-    _need(latents.ndim == 4 and latents.is_contiguous(), f"{fn_name}: latents must be a contiguous [n, C, h, w] tensor")
+    sg, sn = _step_operands(fn_name, noise_pred, latents, sigma, sigma_next, guidance_scale)
     n_lat, c, h, w = latents.shape
-    rows = (2 if guidance_scale > 0 else 1) * n_lat
-    _need(noise_pred.is_contiguous() and noise_pred.dtype == latents.dtype and noise_pred.device == latents.device
-          and noise_pred.numel() == rows * c * h * w, f"{fn_name}: the prediction must be contiguous [{rows}, {c}, {h}, {w}] of the latents' dtype")
-    for name, t in (("sigma", sigma), ("sigma_next", sigma_next)):
-        _need(t.numel() == n_lat, f"{fn_name}: {name} must hold one value per latent row")
     _need(kind.dtype == torch.int32 and kind.numel() == n_lat and kind.is_contiguous() and kind.device == latents.device,
           f"{fn_name}: kind must be a contiguous int32 [{n_lat}] on the latents' device")
     _need(coef.dtype == torch.float32 and tuple(coef.shape) == (n_lat, 3) and coef.is_contiguous() and coef.device == latents.device,
@@ -520,26 +528,24 @@ def cfg_multistep_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: 
           f"{fn_name}: hist must be contiguous fp32 [{n_lat}, {c}, {h}, {w}] on the latents' device, got {hist.dtype} {tuple(hist.shape)}")
     ms = _lib.MultistepRows()
     ms.kind, ms.coef, ms.hist = kind.data_ptr(), coef.data_ptr(), hist.data_ptr()
-    r = _lib.InpaintRows()
-    if init is not None:
-        k = init.shape[0]
-        _need(slot is not None and noise is not None and mask is not None, f"{fn_name}: inpainting rows need slot, init, noise and mask")
-        _need(slot.dtype == torch.int32 and slot.numel() == n_lat and slot.is_contiguous() and slot.device == latents.device,
-              f"{fn_name}: slot must be a contiguous int32 [{n_lat}] on the latents' device")
-        for name, t in (("init", init), ("noise", noise)):
-            _need(t.dtype == latents.dtype and tuple(t.shape) == (k, c, h, w) and t.is_contiguous() and t.device == latents.device,
-                  f"{fn_name}: {name} must be contiguous [{k}, {c}, {h}, {w}] of the latents' dtype, got {t.dtype} {tuple(t.shape)}")
-        _need(mask.dtype == torch.uint8 and tuple(mask.shape) == (k, h, w) and mask.is_contiguous() and mask.device == latents.device,
-              f"{fn_name}: mask must be contiguous uint8 [{k}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
-        r.k, r.slot, r.init, r.noise, r.mask = k, slot.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr()
-    else:
-        _need(slot is None and noise is None and mask is None, f"{fn_name}: slot, noise and mask come with init")
-    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
-    sn = sigma_next.to(device=latents.device, dtype=torch.float32).contiguous()
+    r = _inpaint_rows(fn_name, latents, slot, init, noise, mask)
     _lib.check(l.mx_cfg_multistep_step(_lib.current_stream(), noise_pred.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
                                        float(guidance_scale), n_lat, c, h * w, _lib.torch_dtype_code(latents.dtype), int(bool(flow)), C.byref(ms),
                                        C.byref(r)), fn_name)
     return latents
+
+
+def cfg_step_(pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float, flow: bool,
+              inpaint: Optional[tuple] = None, multistep: Optional[tuple] = None) -> torch.Tensor:
+    """In place: the scheduler step of one resolution's rows, by the entry its requests need.  ``flow``: the flow-match model.  ``inpaint``: (slot,
+    init, noise, mask) of ``cfg_euler_step_masked_`` when a row is an inpainting request; ``multistep``: (kind, coef, hist) of
+    ``cfg_multistep_step_`` when a row steps by DPM-Solver++ 2M or AB2.  With neither it is the plain step, so Euler requests get the launch they
+    always had."""
+    if multistep is not None:
+        return cfg_multistep_step_(pred, latents, sigma, sigma_next, guidance_scale, *multistep, flow, *(inpaint or ()))
+    if inpaint is not None:
+        return (cfg_flow_step_masked_ if flow else cfg_euler_step_masked_)(pred, latents, sigma, sigma_next, guidance_scale, *inpaint)
+    return (cfg_flow_step_ if flow else cfg_euler_step_)(pred, latents, sigma, sigma_next, guidance_scale)
 
 
 def sampler_coeffs(sampler: str, sigmas, flow: bool):

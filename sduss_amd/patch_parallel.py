@@ -26,6 +26,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import lib as _lib
+from . import ops
 from .model_slot import _grow_only
 from .pipeline import SDXLDenoiser
 from .pipeline_sd3 import SD3Denoiser
@@ -285,7 +286,7 @@ class PatchParallelUNet:
     def forward_gathered(self, latents: torch.Tensor, timestep, *cond) -> torch.Tensor:
         """Under a splitting layout: the CFG batch [2n, C, H, W] and its conditioning in (the arguments of ``forward``), the world gather out as it
         lies: [world, n, C, H / n_device_per_batch, W], slot r = the output rows of world rank r (distri_sdxl_unet_pp.py:135-168) -- the
-        ``gathered`` of ops.cfg_euler_step_rows_ / cfg_flow_step_rows_ with n_slabs = n_device_per_batch."""
+        ``gathered`` of ops.cfg_step_rows_ with n_slabs = n_device_per_batch."""
         lay = self.layout
         assert lay is not None, "forward_gathered needs a CfgSplitLayout that splits the CFG batch"
         assert latents.shape[0] % 2 == 0, "the CFG batch is [uncond... ; cond...]"
@@ -337,7 +338,7 @@ class PatchParallelDenoiser:
     Every rank holds the whole latents, as in distrifuser, and applies the same kernel to the same gathered bytes: after a step the latents are
     bit-identical on all ranks."""
 
-    hooks = SDXLDenoiser          # the model's side of a step, shared with the one-GPU denoiser: _cond, _scale_input, _scheduler_step_rows
+    hooks = SDXLDenoiser          # the model's side of a step, shared with the one-GPU denoiser: _cond, _scale_input, flow
 
     def __init__(self, pp: PatchParallelUNet, guidance_scale: float = 5.0):
         assert pp.layout is not None, "the step on the gather buffer needs a CfgSplitLayout that splits the CFG batch"
@@ -355,7 +356,7 @@ class PatchParallelDenoiser:
         lat = self._cache.latents(e, [req])
         sig, sig_next, ts = self._cache.step_scalars(e, [req])
         buf = self.pp.forward_gathered(self.hooks._scale_input(lat, sig, True), torch.cat([ts, ts], dim=0), *e.cond)
-        self.hooks._scheduler_step_rows(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world)
+        ops.cfg_step_rows_(buf, lat, sig, sig_next, self.guidance_scale, self.pp.world, self.hooks.flow)
         req.step_index += 1
         req.latents = lat[0:1]
 

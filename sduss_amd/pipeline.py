@@ -124,11 +124,10 @@ def start_step(num_inference_steps: int, strength: float) -> int:
 class Denoiser:
     """One ``denoising_step`` over a heterogeneous batch of requests, for either model.  A subclass says which request fields make the
     conditioning (``_cond``), how the model input is made from the latents (``_scale_input``), which scheduler step follows
-    (``_scheduler_step``; ``_scheduler_step_rows`` on a patch-parallel gather buffer; ``_scheduler_step_masked`` for a resolution with inpainting
-    requests; ``flow`` selects the model's step inside the launch of a resolution with multistep samplers), how its model slot is called (``_forward``,
+    (``flow``: the flow-match model; ``ops.cfg_step_`` picks the launch a resolution's requests need), how its model slot is called (``_forward``,
     ``_forward_mixed``) and whether a batch composition is announced to it (``announces_composition``: MxUNet.set_context_key)."""
     announces_composition = False
-    flow = False                         # the flow-match model: its Euler step and keep factor in mx_cfg_multistep_step
+    flow = False                         # the flow-match model: its Euler step and the keep factor of its inpainting rows
     samplers = ("euler",)                # what set_timesteps accepts
 
     def __init__(self, model, guidance_scale: float):
@@ -261,7 +260,7 @@ class Denoiser:
         with no start noise: its result, the clean latents in the model dtype, stays on the request (``req.inpaint.init``, diffusers' image_latents)
         beside the fixed ``noise`` (N(0, 1) shaped as the latents; drawn here when None) and the mask on the latent grid.  The request starts at step
         t_start = ``start_step(steps, strength)`` from init noised to that step's sigma; at strength >= 1 from pure noise (is_strength_max).  Every
-        step then puts the kept region back inside its scheduler launch (``_scheduler_step_masked``).  ``paste``: post_inference returns the
+        step then puts the kept region back inside its scheduler launch (``ops.cfg_step_`` with ``inpaint``).  ``paste``: post_inference returns the
         client's own pixels outside the mask, which needs the uint8 image.  ``size`` = (H, W): image and mask come at the client's size and are
         resized to the request's first (``start_from_image``), the mask as a grey image by the same filter -- diffusers' mask processor, whose
         binarisation is then the >= 128 rule on the resized mask; the request keeps the resized pair, so ``paste`` works at the request's size.
@@ -388,15 +387,12 @@ class Denoiser:
             noise = self._forward_mixed([p.x_in for p in parts], ts, cond, patch_size // 8 if is_sliced else 0)
         g = self.guidance_scale if do_classifier_free_guidance else 0.0
         for p, nz in zip(parts, noise):
-            ms = p.entry.multistep
+            ms, hist = p.entry.multistep, None
             if ms is not None:                                                     # a request here steps by DPM-Solver++ 2M or AB2: one launch for all samplers
                 hist = self._cache.history(p.entry, p.reqs, p.latents)
                 hist.record_stream(torch.cuda.current_stream())                    # like the latents, it may have been made on another stream
-                ops.cfg_multistep_step_(nz, p.latents, p.sigma, p.sigma_next, g, ms.kind, ms.coef, hist, self.flow, *(p.entry.inpaint or ()))
-            elif p.entry.inpaint is None:
-                self._scheduler_step(nz, p.latents, p.sigma, p.sigma_next, g)      # :382-397
-            else:                                                                  # the same step, the kept region of the inpainting rows put back
-                self._scheduler_step_masked(nz, p.latents, p.sigma, p.sigma_next, g, *p.entry.inpaint)
+            ops.cfg_step_(nz, p.latents, p.sigma, p.sigma_next, g, self.flow, inpaint=p.entry.inpaint,      # :382-397; the kept region of
+                          multistep=None if ms is None else (ms.kind, ms.coef, hist))                       # inpainting rows put back
             for i, r in enumerate(p.reqs):                                         # :399-403
                 if ms is not None and ms.host_kind[i]:                             # the history travels on the request, like its latents
                     r.history, r.history_step = hist[i:i + 1], r.step_index
@@ -450,10 +446,6 @@ class SDXLDenoiser(Denoiser):
     @staticmethod
     def _start_mix(sigma: np.float32) -> tuple:
         return np.float32(1.0), sigma                        # EulerDiscreteScheduler.add_noise: original + sigma * noise
-
-    _scheduler_step = staticmethod(ops.cfg_euler_step_)
-    _scheduler_step_rows = staticmethod(ops.cfg_euler_step_rows_)
-    _scheduler_step_masked = staticmethod(ops.cfg_euler_step_masked_)
 
     def _inpaint_start_mix(self, req, t_start: int, strength: float) -> tuple:
         if strength >= 1.0:                                  # is_strength_max: pure noise times init_noise_sigma, nothing of the image

@@ -90,9 +90,6 @@ class SD3Denoiser(Denoiser):
     def _start_mix(sigma: np.float32) -> tuple:
         return np.float32(1.0) - sigma, sigma                # FlowMatchEulerDiscreteScheduler.scale_noise: (1 - sigma) * sample + sigma * noise
 
-    _scheduler_step = staticmethod(ops.cfg_flow_step_)                 # :362-372
-    _scheduler_step_rows = staticmethod(ops.cfg_flow_step_rows_)
-    _scheduler_step_masked = staticmethod(ops.cfg_flow_step_masked_)
 
     def _forward(self, x: Dict[str, torch.Tensor], ts, cond, **kwargs) -> Dict[str, torch.Tensor]:
         ehs, pooled = cond

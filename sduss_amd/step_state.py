@@ -8,7 +8,7 @@ and a device-resident step index are built ONCE per composition; a step then cos
 device and no host-to-device copy.  The host list of step indices is compared every step, so a caller that rewinds or
 skips a request (bench.py keeps its batch full by resetting step_index) is followed with one small asynchronous upload.
 
-A composition with a multistep sampler (DPM-Solver++ 2M, AB2: csrc/sampler_step.hip) also holds its rows' kinds, their coefficient table of
+A composition with a multistep sampler (DPM-Solver++ 2M, AB2: csrc/scheduler_step.hip) also holds its rows' kinds, their coefficient table of
 every step in both orders and the fp32 history buffer; the step's [n, 3] coefficients are one more gather by the same device index, and the
 order of every row (second only right after a step that left its history) is followed on the host like the step index.
 """

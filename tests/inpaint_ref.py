@@ -1,4 +1,4 @@
-"""Torch restatements of the inpainting kernels (csrc/inpaint.hip) for tests/test_inpaint_cpu.py and tests/test_inpaint_gpu.py.  Every arithmetic
+"""Torch restatements of the inpainting kernels (csrc/scheduler_step.hip, csrc/inpaint.hip) for tests/test_inpaint_cpu.py and tests/test_inpaint_gpu.py.  Every arithmetic
 chain is fp32, one torch op per operation (torch rounds each on its own and contracts nothing), one cast at the end: the kernels must return
 the same bits.  Everything here runs on the CPU."""
 from __future__ import annotations

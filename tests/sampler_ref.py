@@ -1,4 +1,4 @@
-"""Torch / numpy restatements of the multistep samplers (csrc/sampler_step.hip, sampler_coeffs.cpp, pipeline.karras_tables) for
+"""Torch / numpy restatements of the multistep samplers (csrc/scheduler_step.hip, sampler_coeffs.cpp, pipeline.karras_tables) for
 tests/test_sampler_cpu.py and tests/test_sampler_gpu.py: the coefficient rules in fp64, the Karras schedule, the per-element chain in fp32 (one torch
 op per operation, one cast at the end, as in inpaint_ref.py: the kernel must return the same bits), the fp64 loop of every sampler, diffusers'
 variance-preserving form of DPM-Solver++ 2M, and the analytic Gaussian problem with its closed-form solution.  Everything here runs on the CPU."""

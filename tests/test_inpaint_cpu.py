@@ -1,4 +1,4 @@
-"""Host-side checks of inpainting: the five entries of csrc/inpaint.hip are declared, exported and bound; each refuses bad arguments before any
+"""Host-side checks of inpainting: the five entries of csrc/scheduler_step.hip and csrc/inpaint.hip are declared, exported and bound; each refuses bad arguments before any
 launch; the mask reference is diffusers' mask processor; the start mix of both models; the packed rows of a mixed batch; the request types still
 construct as before.  No GPU: the library loads without a device."""
 import ctypes as C

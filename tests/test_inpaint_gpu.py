@@ -1,4 +1,4 @@
-"""Inpainting on the GPU (csrc/inpaint.hip): the masked scheduler steps, the start re-noising, the mask resize and the pixel paste on their own, then
+"""Inpainting on the GPU (csrc/scheduler_step.hip, csrc/inpaint.hip): the masked scheduler steps, the start re-noising, the mask resize and the pixel paste on their own, then
 Denoiser.start_inpaint / denoising_step / post_inference end to end for both models on the tiny configs of tests/test_vae_encode_gpu.py.
 
 Every comparison is on the raw bits.  The stepped value must be what mx_cfg_euler_step / mx_cfg_flow_step leave (the same device functions); the kept
@@ -11,35 +11,11 @@ import torch
 
 import inpaint_ref as I
 import vae_encode_ref as E
+from step_operands import DTYPES, K, SLOTS, STEP_SHAPES, guards_intact, placed, same_bits
 
 pytestmark = pytest.mark.gpu
 
 from oracle import vae_ref  # noqa: E402  (checker only)
-
-DTYPES = [pytest.param(torch.float32, id="f32"), pytest.param(torch.float16, id="f16"), pytest.param(torch.bfloat16, id="bf16")]
-# (n_lat, C, h, w), element offset of every tensor's base -> the path it takes
-STEP_SHAPES = [pytest.param((3, 4, 5, 3), 0, id="3x4x5x3-elements"),          # hw = 15: no whole vector
-               pytest.param((3, 16, 16, 16), 0, id="3x16x16x16-vectors"),     # 12288 elements: more than one block
-               pytest.param((2, 4, 8, 8), 1, id="2x4x8x8-offset-base")]       # hw a whole number of vectors, every base off by one element
-SLOTS = {3: [-1, 1, 0], 2: [1, -1]}                                           # k = 2, permuted: row != slot
-K = 2
-GUARD = 64
-
-
-def placed(t, offset):
-    """t on the device as a contiguous view ``offset`` elements into a buffer of its dtype with guard elements either side -> (buffer, view)"""
-    fill = 77 if t.dtype in (torch.uint8, torch.int32) else 77.0
-    buf = torch.full((GUARD + offset + t.numel() + GUARD,), fill, dtype=t.dtype, device="cuda")
-    view = buf[GUARD + offset:GUARD + offset + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
-
-
-def guards_intact(buf, view):
-    lo = (view.data_ptr() - buf.data_ptr()) // buf.element_size()
-    ref = torch.full_like(buf, 77 if buf.dtype in (torch.uint8, torch.int32) else 77.0)
-    return torch.equal(I.bits(buf[:lo]), I.bits(ref[:lo])) and torch.equal(I.bits(buf[lo + view.numel():]), I.bits(ref[lo + view.numel():]))
-
 
 def step_operands(shape, dtype, flow, g):
     n, C, h, w = shape
@@ -82,10 +58,6 @@ def plain_step(flow, pred, lat, sigma, sigma_next, g):
     (ops.cfg_flow_step_ if flow else ops.cfg_euler_step_)(pred.cuda(), out, sigma.cuda(), sigma_next.cuda(), g)
     torch.cuda.synchronize()
     return out.cpu()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(I.bits(a), I.bits(b))
 
 
 @pytest.mark.parametrize("g", [5.0, 0.0], ids=["g5", "g0"])

@@ -1,4 +1,4 @@
-"""Host-side checks of the multistep samplers (csrc/sampler_step.hip, sampler_coeffs.cpp; pipeline.karras_tables; the request state): the entries
+"""Host-side checks of the multistep samplers (csrc/scheduler_step.hip, sampler_coeffs.cpp; pipeline.karras_tables; the request state): the entries
 are declared, exported and bound and refuse bad arguments before any launch; mx_sampler_coeffs against the fp64 restatement; the variance-exploding
 form of DPM-Solver++ 2M against diffusers' variance-preserving one; the order of every sampler on the analytic Gaussian problem; the fp32 element
 chain against fp64; the Karras schedule; the request fields and the refusals.  No GPU: the library loads without a device."""

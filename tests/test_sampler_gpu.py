@@ -1,4 +1,4 @@
-"""The multistep samplers on the GPU (csrc/sampler_step.hip): the step launch on its own, then Denoiser.denoising_step over requests of different
+"""The multistep samplers on the GPU (csrc/scheduler_step.hip): the step launch on its own, then Denoiser.denoising_step over requests of different
 samplers -- with a stub in the model slot, so that every step can be replayed on the CPU, and with the tiny models of tests/test_inpaint_gpu.py.
 
 Every comparison of a step is on the raw bits: a multistep row is a chain of separately rounded fp32 operations that torch evaluates identically on
@@ -14,39 +14,13 @@ import torch
 import inpaint_ref as I
 import sampler_ref as S
 import vae_encode_ref as E
+from step_operands import DTYPES, K, SLOTS, STEP_SHAPES, guards_intact, placed, same_bits
 
 pytestmark = pytest.mark.gpu
 
 from oracle import vae_ref  # noqa: E402  (checker only)
 
-DTYPES = [pytest.param(torch.float32, id="f32"), pytest.param(torch.float16, id="f16"), pytest.param(torch.bfloat16, id="bf16")]
-# (n_lat, C, h, w), element offset of every tensor's base -> the path it takes (the shapes of tests/test_inpaint_gpu.py)
-STEP_SHAPES = [pytest.param((3, 4, 5, 3), 0, id="3x4x5x3-elements"),          # hw = 15: no whole vector
-               pytest.param((3, 16, 16, 16), 0, id="3x16x16x16-vectors"),     # 12288 elements: more than one block
-               pytest.param((2, 4, 8, 8), 1, id="2x4x8x8-offset-base")]       # hw a whole number of vectors, every base off by one element
 KINDS = {3: [2, 0, 1], 2: [1, 2]}                                             # permuted: row != kind
-SLOTS = {3: [-1, 1, 0], 2: [1, -1]}
-K = 2
-GUARD = 64
-
-
-def placed(t, offset):
-    """t on the device as a contiguous view ``offset`` elements into a buffer of its dtype with guard elements either side -> (buffer, view)"""
-    fill = 77 if t.dtype in (torch.uint8, torch.int32) else 77.0
-    buf = torch.full((GUARD + offset + t.numel() + GUARD,), fill, dtype=t.dtype, device="cuda")
-    view = buf[GUARD + offset:GUARD + offset + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
-
-
-def guards_intact(buf, view):
-    lo = (view.data_ptr() - buf.data_ptr()) // buf.element_size()
-    ref = torch.full_like(buf, 77 if buf.dtype in (torch.uint8, torch.int32) else 77.0)
-    return torch.equal(I.bits(buf[:lo]), I.bits(ref[:lo])) and torch.equal(I.bits(buf[lo + view.numel():]), I.bits(ref[lo + view.numel():]))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(I.bits(a), I.bits(b))
 
 
 def assert_bits(got, want, what):
