@@ -34,6 +34,14 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {     // one
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
+// a 16-byte chunk of eight bf16 values as floats, and eight floats rounded back into one
+__device__ __forceinline__ void unpack_bf16x8(const u32x4 u, float (&v)[8]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(u[e]); v[2 * e + 1] = bf16hi_to_f32(u[e]); }
+}
+__device__ __forceinline__ u32x4 pack_bf16x8(const float (&v)[8]) {
+  return u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+}
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // exact (erf) GELU, as diffusers' GEGLU uses F.gelu default

@@ -1,4 +1,4 @@
-// NHWC GroupNorm (+SiLU) and LayerNorm for gfx950.  HBM-bound kernels: 16-byte vector accesses,
+// NHWC GroupNorm (+SiLU) and the row norms (LayerNorm, AdaLN modulate, RMSNorm) for gfx950.  HBM-bound kernels: 16-byte vector accesses,
 // fp32 statistics, one read for the moments and one read + one write for the apply pass.
 //
 // GroupNorm serves the reference's PatchGroupNorm.forward (sduss/model_executor/modules/groupnorm.py:42-61):
@@ -14,6 +14,7 @@
 // Pass 2  gn_fold_kernel  : fp64 fold of the partials -> per (image, channel) scale/shift
 // Pass 3  gn_apply_kernel : y = silu?(x*scale + shift)
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "../../include/mxdenoise.h"
@@ -86,13 +87,10 @@ __global__ void gn_stats_kernel(const GnGroup G, const int groups) {
     for (int pi = pl; pi < npix; pi += g.L) {
       const int py = pi / g.tw, px = pi - py * g.tw;
       const long pix = ((long)b * g.H + ty * g.th + py) * g.W + tx * g.tw + px;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(gn_src(x, g, pix, cv * 8));
+      float v[8];
+      unpack_bf16x8(*reinterpret_cast<const u32x4*>(gn_src(x, g, pix, cv * 8)), v);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf16lo_to_f32(v[e]), hi = bf16hi_to_f32(v[e]);
-        s[2 * e] += lo; ss[2 * e] += lo * lo;
-        s[2 * e + 1] += hi; ss[2 * e + 1] += hi * hi;
-      }
+      for (int e = 0; e < 8; ++e) { s[e] += v[e]; ss[e] += v[e] * v[e]; }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -125,6 +123,19 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// The fp64 finish every route shares.  Moments of cnt values from their sum and sum of squares, a negative variance (cancellation) replaced by
+// `negative` (0: the clamp); then y = x * sc + sf with sc = rstd * gamma, sf = beta - sc * mean.
+__device__ __forceinline__ void gn_moments(double s, double q, double cnt, double& mean, double& var, double negative = 0.0) {
+  mean = s / cnt;
+  var = q / cnt - mean * mean;
+  if (var < 0.0) var = negative;
+}
+__device__ __forceinline__ void gn_scale_shift(double mean, double rstd, float gamma, float beta, float& sc, float& sf) {
+  const double rg = rstd * (double)gamma;
+  sc = (float)rg;
+  sf = (float)((double)beta - rg * mean);
 }
 
 // one workgroup (four waves) per (group, image): fp64 fold of tiles x channels-per-group, patch by patch.  Four waves because the fold is a
@@ -181,9 +192,8 @@ __global__ __launch_bounds__(kFoldThreads) void gn_fold_kernel(const GnGroup G, 
     __syncthreads();
     s = (wsum[0][0] + wsum[1][0]) + (wsum[2][0] + wsum[3][0]);   // fixed order: every thread holds the same sums
     q = (wsum[0][1] + wsum[1][1]) + (wsum[2][1] + wsum[3][1]);
-    const double mean = s / cnt;
-    double var = q / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double mean, var;
+    gn_moments(s, q, cnt, mean, var);
     acc_mean += mean;   // mean of patch means      (norm_silu_concat.cu:383)
     acc_var += var;     // mean of patch variances  (norm_silu_concat.cu:384)
   }
@@ -191,10 +201,7 @@ __global__ __launch_bounds__(kFoldThreads) void gn_fold_kernel(const GnGroup G, 
   const double rstd = 1.0 / sqrt(acc_var / npatch + (double)eps);
   for (int c = lane; c < cpg; c += kFoldThreads) {
     const int ch = grp * cpg + c;
-    const float sc = (float)(rstd * (double)gamma[ch]);
-    const float sf = (float)((double)beta[ch] - rstd * (double)gamma[ch] * mean);
-    coef[((long)b * g.C + ch) * 2] = sc;
-    coef[((long)b * g.C + ch) * 2 + 1] = sf;
+    gn_scale_shift(mean, rstd, gamma[ch], beta[ch], coef[((long)b * g.C + ch) * 2], coef[((long)b * g.C + ch) * 2 + 1]);
   }
 }
 
@@ -240,9 +247,8 @@ __global__ void gn_apply_kernel(const GnGroup G, const float* __restrict__ gamma
       double s = 0.0, q = 0.0;
 #pragma unroll
       for (int sub = 0; sub < 8; ++sub) { s += fsub[gi][sub][0]; q += fsub[gi][sub][1]; }
-      const double mean = s / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0.0) var = 0.0;
+      double mean, var;
+      gn_moments(s, q, cnt, mean, var);
       mr[gi][0] = mean;
       mr[gi][1] = 1.0 / sqrt(var + (double)eps);
     }
@@ -252,9 +258,7 @@ __global__ void gn_apply_kernel(const GnGroup G, const float* __restrict__ gamma
     for (int e = 0; e < 8; ++e) {
       const int ch = cv * 8 + e;
       const int gi = ch / cpg;
-      const double rg = mr[gi][1] * (double)gamma[ch];
-      sc[e] = (float)rg;
-      sf[e] = (float)((double)beta[ch] - rg * mr[gi][0]);
+      gn_scale_shift(mr[gi][0], mr[gi][1], gamma[ch], beta[ch], sc[e], sf[e]);
     }
   } else {
     if (pl >= g.L) return;
@@ -266,16 +270,14 @@ __global__ void gn_apply_kernel(const GnGroup G, const float* __restrict__ gamma
   const int p0 = pblk * pix_per_block;
   const int p1 = min(p0 + pix_per_block, hw);
   for (int pi = p0 + pl; pi < p1; pi += g.L) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(gn_src(x, g, (long)b * hw + pi, cv * 8));
-    u32x4 o;
+    float v[8];
+    unpack_bf16x8(*reinterpret_cast<const u32x4*>(gn_src(x, g, (long)b * hw + pi, cv * 8)), v);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float lo = bf16lo_to_f32(v[e]) * sc[2 * e] + sf[2 * e];
-      float hi = bf16hi_to_f32(v[e]) * sc[2 * e + 1] + sf[2 * e + 1];
-      if (SILU) { lo = silu_f(lo); hi = silu_f(hi); }
-      o[e] = pack_bf16x2(lo, hi);
+    for (int e = 0; e < 8; ++e) {
+      v[e] = v[e] * sc[e] + sf[e];
+      if (SILU) v[e] = silu_f(v[e]);
     }
-    *reinterpret_cast<u32x4*>(y + (long)b * y_img + (long)pi * g.C + cv * 8) = o;
+    *reinterpret_cast<u32x4*>(y + (long)b * y_img + (long)pi * g.C + cv * 8) = pack_bf16x8(v);
   }
 }
 
@@ -316,18 +318,15 @@ __global__ __launch_bounds__(64) void gn_pp_coef_kernel(const double* __restrict
     const long o = (((long)own_rank * B + b) * groups + grp) * 2, f = ((long)b * groups + grp) * 2;
     s += (double)world * (fresh_own[f] - all_sums[o]);
     q += (double)world * (fresh_own[f + 1] - all_sums[o + 1]);
-    const double lc = cnt / world, lm = fresh_own[f] / lc;
-    var_fallback = fresh_own[f + 1] / lc - lm * lm;       // "var = torch.where(var < 0, slice_var, var)"
-    if (var_fallback < 0.0) var_fallback = 0.0;
+    double lm;
+    gn_moments(fresh_own[f], fresh_own[f + 1], cnt / world, lm, var_fallback);       // "var = torch.where(var < 0, slice_var, var)"
   }
-  const double mean = s / cnt;
-  double var = q / cnt - mean * mean;
-  if (var < 0.0) var = var_fallback;
+  double mean, var;
+  gn_moments(s, q, cnt, mean, var, var_fallback);
   const double rstd = 1.0 / sqrt(var + (double)eps);
   for (int c = lane; c < cpg; c += 64) {
     const int ch = grp * cpg + c;
-    coef[((long)b * C + ch) * 2] = (float)(rstd * (double)gamma[ch]);
-    coef[((long)b * C + ch) * 2 + 1] = (float)((double)beta[ch] - rstd * (double)gamma[ch] * mean);
+    gn_scale_shift(mean, rstd, gamma[ch], beta[ch], coef[((long)b * C + ch) * 2], coef[((long)b * C + ch) * 2 + 1]);
   }
 }
 
@@ -352,21 +351,26 @@ static int gn_geom(GnGeom& g, int B, int H, int W, int C, int patch) {
   return 0;
 }
 
-}  // namespace mx
+// the scratch of one problem: the statistics pass's partials [B][tiles][C][2], then the coefficients [B][C][2]
+struct GnScratch {
+  size_t part, coef;    // floats
+  size_t bytes() const { return (part + coef) * sizeof(float); }
+  size_t padded() const { return (bytes() + 255) & ~(size_t)255; }     // what a problem of a grouped launch occupies
+};
+static GnScratch gn_scratch(size_t B, size_t tiles, size_t C) { return {B * tiles * C * 2, B * C * 2}; }
+static GnScratch gn_scratch(const GnGeom& g) { return gn_scratch(g.B, (size_t)g.tiles_y * g.tiles_x, g.C); }
 
-namespace mx {
 size_t gn_workspace_exact(int B, int H, int W, int C, int patch) {
   GnGeom g;
   if (patch >= H && patch >= W) patch = 0;
   if (gn_geom(g, B, H, W, C, patch)) return 0;
-  return ((size_t)B * g.tiles_y * g.tiles_x * C * 2 + (size_t)B * C * 2) * sizeof(float);
+  return gn_scratch(g).bytes();
 }
 }  // namespace mx
 
 extern "C" size_t mx_groupnorm_nhwc_workspace_bytes(int B, int H, int W, int C) {
   // loose bound valid for every patch >= 2: the smallest spatial tile then holds >= 4 pixels
-  const size_t tiles = (size_t)H * W / 4 + 1;
-  return ((size_t)B * tiles * C * 2 + (size_t)B * C * 2) * sizeof(float) + 256;
+  return mx::gn_scratch(B, (size_t)H * W / 4 + 1, C).bytes() + 256;
 }
 
 extern "C" int mx_groupnorm_nhwc(void* stream, const void* x, void* y, const float* gamma, const float* beta,
@@ -383,21 +387,23 @@ static size_t gn_fill(GnGroup& G, int i, const void* x, int C1, const void* x2, 
   if (patch != 0 && patch < 2) { set_error("groupnorm: patch must be 0 or >= 2"); return 0; }
   if (gn_geom(P.g, B, H, W, C, patch)) return 0;
   if (x2) { P.g.x2 = (const bf16_t*)x2; P.g.C1 = C1; }
-  const size_t ntiles = (size_t)P.g.tiles_y * P.g.tiles_x;
+  const GnScratch sc = gn_scratch(P.g);
   P.x = (const bf16_t*)x; P.y = (bf16_t*)y; P.y_img = y_img; P.patch = patch;
   P.part = (float*)ws;
   P.gpart = nullptr;
-  P.coef = P.part + (size_t)B * ntiles * C * 2;
+  P.coef = P.part + sc.part;
   const int hw = H * W;
   P.ppb = P.g.L * 8 > hw ? hw : P.g.L * 8;
-  return (((size_t)B * ntiles * C * 2 + (size_t)B * C * 2) * sizeof(float) + 255) & ~(size_t)255;
+  return sc.padded();
 }
-static void gn_prefix(GnGroup& G, int which, int groups) {      // which: 0 stats, 1 fold, 2 apply
+// blk0 of a launch: a workgroup per (image, spatial tile), per (image, group), or per (image, block of ppb pixels)
+enum GnPass { GN_STATS, GN_FOLD, GN_APPLY };
+static void gn_prefix(GnGroup& G, GnPass pass, int groups = 0) {
   long t = 0;
   for (int i = 0; i < G.n; ++i) {
     G.blk0[i] = (int)t;
     const GnGeom& g = G.p[i].g;
-    t += which == 0 ? (long)g.B * g.tiles_y * g.tiles_x : which == 1 ? (long)g.B * groups : (long)g.B * cdiv(g.H * g.W, G.p[i].ppb);
+    t += pass == GN_STATS ? (long)g.B * g.tiles_y * g.tiles_x : pass == GN_FOLD ? (long)g.B * groups : (long)g.B * cdiv(g.H * g.W, G.p[i].ppb);
   }
   for (int i = G.n; i <= MX_MAX_SEGS; ++i) G.blk0[i] = (int)t;
 }
@@ -407,7 +413,7 @@ static int gn_launch_stats(hipStream_t s, GnGroup& G, int C, int groups = 0) {
   const int threads = ((g.tpr * g.L + 63) / 64) * 64;
   const size_t smem = ((size_t)g.L * C * 2 + (groups > 0 ? (size_t)C * 2 : 0)) * sizeof(float);
   MX_CHECK(smem <= 160 * 1024, "groupnorm: LDS budget exceeded");
-  gn_prefix(G, 0, 0);
+  gn_prefix(G, GN_STATS);
   hipLaunchKernelGGL(gn_stats_kernel, dim3(G.blk0[MX_MAX_SEGS]), dim3(threads), smem, s, G, groups);
   MX_LAUNCH_CHECK();
   return 0;
@@ -416,15 +422,12 @@ static int gn_launch_stats(hipStream_t s, GnGroup& G, int C, int groups = 0) {
 static int gn_launch_apply(hipStream_t s, GnGroup& G, int silu, bool fold = false, const float* gamma = nullptr, const float* beta = nullptr, int groups = 0, float eps = 0.f) {
   const GnGeom& g = G.p[0].g;
   const int threads = ((g.tpr * g.L + 63) / 64) * 64;
-  gn_prefix(G, 2, 0);
-  const dim3 grid(G.blk0[MX_MAX_SEGS]), block(threads);
-  if (fold) {
-    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, true>), grid, block, 0, s, G, gamma, beta, groups, eps);
-    else hipLaunchKernelGGL((gn_apply_kernel<false, true>), grid, block, 0, s, G, gamma, beta, groups, eps);
-  } else {
-    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, false>), grid, block, 0, s, G, gamma, beta, groups, eps);
-    else hipLaunchKernelGGL((gn_apply_kernel<false, false>), grid, block, 0, s, G, gamma, beta, groups, eps);
-  }
+  gn_prefix(G, GN_APPLY);
+  auto launch = [&](auto silu_c, auto fold_c) {
+    hipLaunchKernelGGL((gn_apply_kernel<decltype(silu_c)::value, decltype(fold_c)::value>), dim3(G.blk0[MX_MAX_SEGS]), dim3(threads), 0, s, G, gamma, beta, groups, eps);
+  };
+  auto with_fold = [&](auto silu_c) { fold ? launch(silu_c, std::true_type{}) : launch(silu_c, std::false_type{}); };
+  silu ? with_fold(std::true_type{}) : with_fold(std::false_type{});
   MX_LAUNCH_CHECK();
   return 0;
 }
@@ -487,7 +490,7 @@ extern "C" int mx_groupnorm_nhwc_grouped(void* stream, const mx_gn_problem* prob
     return 0;
   }
   if (gn_launch_stats(s, G, C)) return 1;
-  gn_prefix(G, 1, groups);
+  gn_prefix(G, GN_FOLD, groups);
   hipLaunchKernelGGL(gn_fold_kernel, dim3(G.blk0[MX_MAX_SEGS]), dim3(kFoldThreads), 0, s, G, gamma, beta, groups, eps);
   MX_LAUNCH_CHECK();
   if (gn_launch_apply(s, G, silu)) return 1;
@@ -518,7 +521,7 @@ extern "C" int mx_groupnorm_nhwc_from_partials(void* stream, const void* x, void
   F.p[0].g.tiles_y = H * W / chunk; F.p[0].g.tiles_x = 1; F.p[0].g.th = chunk; F.p[0].g.tw = 1;
   hipStream_t s = (hipStream_t)stream;
   prof_begin(s, PROF_NORM, 0.0, 2.0 * 2.0 * B * H * (double)W * C);
-  gn_prefix(F, 1, groups);
+  gn_prefix(F, GN_FOLD, groups);
   MX_CHECK(add_rowbias == nullptr || (add_bias != nullptr && ldrb >= C), "groupnorm: add_rowbias needs add_bias and ldrb >= C");
   hipLaunchKernelGGL(gn_fold_kernel, dim3(F.blk0[MX_MAX_SEGS]), dim3(kFoldThreads), 0, s, F, gamma, beta, groups, eps, add_bias, add_rowbias, ldrb);
   MX_LAUNCH_CHECK();
@@ -552,136 +555,218 @@ int launch_gn_pp_finish(hipStream_t s, const void* x, int C1, const void* x2, vo
 }  // namespace mx
 
 // ------------------------------------------------------------------------------------------
-// LayerNorm over the last dim: one wave per row, values held in registers between the passes.
-// Serves BasicTransformerBlock.norm1/2/3 (modules/transformer.py:191,239,266).
+// Row norms over the last dim (C <= 4096): one wave a row, four rows a workgroup, the row held in registers between the passes.
+// ONE skeleton, row_norm_kernel<VPL, CENTRE, Store>.  CENTRE: the two-pass centred moments (LayerNorm, AdaLN); otherwise the single sum of
+// squares (RMSNorm).  Store (below) turns the eight normalised values of a 16-byte chunk into the output(s): a form holds none of the code
+// and reads none of the operands of another; the struct travels by value.  This file is compiled with FMA contraction on, so the SHAPE of
+// every expression here decides the bits of the outputs.
 // ------------------------------------------------------------------------------------------
 namespace mx {
 
-template <int VPL>  // 16-byte chunks per lane (C <= 64*8*VPL)
-__global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                        const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int M, int C, float eps) {
+template <int VPL, bool CENTRE, typename Store>  // VPL 16-byte chunks per lane (C <= 64*8*VPL)
+__global__ __launch_bounds__(256) void row_norm_kernel(const bf16_t* __restrict__ x, int M, int C, float eps, const Store st) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const int nch = C / 8;
   const bf16_t* xr = x + (long)row * C;
   float v[VPL][8];
-  float sum = 0.f;
+  float sum = 0.f, sq = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int ch = lane + 64 * i;
     if (ch < nch) {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(xr + ch * 8);
+      unpack_bf16x8(*reinterpret_cast<const u32x4*>(xr + ch * 8), v[i]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[i][2 * e] = bf16lo_to_f32(u[e]);
-        v[i][2 * e + 1] = bf16hi_to_f32(u[e]);
-        sum += v[i][2 * e] + v[i][2 * e + 1];
+        if constexpr (CENTRE) sum += v[i][2 * e] + v[i][2 * e + 1];
+        else sq += v[i][2 * e] * v[i][2 * e] + v[i][2 * e + 1] * v[i][2 * e + 1];
       }
-    } else {
+    } else if constexpr (CENTRE) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
     }
   }
-  const float mean = wave_sum(sum) / (float)C;
-  float sq = 0.f;
+  float mean = 0.f;
+  if constexpr (CENTRE) {
+    mean = wave_sum(sum) / (float)C;
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
+    for (int i = 0; i < VPL; ++i) {
+      const int ch = lane + 64 * i;
+      if (ch < nch) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
+        for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
+      }
     }
   }
   const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-  bf16_t* yr = y + (long)row * C;
+  const auto store = st.row(row);
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int ch = lane + 64 * i;
     if (ch < nch) {
-      const f32x4 one4 = {1.f, 1.f, 1.f, 1.f}, zero4 = {0.f, 0.f, 0.f, 0.f};     // gamma == nullptr: plain normalisation (affine folded elsewhere)
-      const f32x4 g0 = gamma ? *reinterpret_cast<const f32x4*>(gamma + ch * 8) : one4;
-      const f32x4 g1 = gamma ? *reinterpret_cast<const f32x4*>(gamma + ch * 8 + 4) : one4;
-      const f32x4 b0 = gamma ? *reinterpret_cast<const f32x4*>(beta + ch * 8) : zero4;
-      const f32x4 b1 = gamma ? *reinterpret_cast<const f32x4*>(beta + ch * 8 + 4) : zero4;
-      float o[8];
+      float n[8];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = (v[i][e] - mean) * rstd * g0[e] + b0[e];
-        o[e + 4] = (v[i][e + 4] - mean) * rstd * g1[e] + b1[e];
-      }
-      u32x4 u = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
-      *reinterpret_cast<u32x4*>(yr + ch * 8) = u;
+      for (int e = 0; e < 8; ++e) n[e] = (CENTRE ? v[i][e] - mean : v[i][e]) * rstd;
+      store(n, ch * 8, (long)row * C + ch * 8);
     }
   }
 }
 
+// f(std::integral_constant<int, VPL>{}) for a row of C values: ceil(C / 8 / 64) chunks a lane -> <1> <2> <3> <4>, above 4 -> <8>
+template <typename F> static inline int with_vpl(int C, F&& f) {
+  const int vpl = cdiv(C / 8, 64);
+  if (vpl <= 1) return f(std::integral_constant<int, 1>{});
+  if (vpl <= 2) return f(std::integral_constant<int, 2>{});
+  if (vpl <= 3) return f(std::integral_constant<int, 3>{});
+  if (vpl <= 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
+
+template <bool CENTRE, typename Store>
+static int launch_row_norm(void* stream, const void* x, int M, int C, float eps, const Store& st) {
+  return with_vpl(C, [&](auto vpl) {
+    hipLaunchKernelGGL((row_norm_kernel<decltype(vpl)::value, CENTRE, Store>), dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, M, C, eps, st);
+    MX_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// The stores.  st.row(row) does what a row needs once and returns store(n, col, at): n = the normalised values of columns [col, col + 8) of
+// that row, at = row * C + col.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load_f32x8(const float* p, float (&f)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { f[e] = a[e]; f[e + 4] = b[e]; }
+}
+
+// LayerNorm, BasicTransformerBlock.norm1/2/3 (modules/transformer.py:191,239,266): y = n * gamma + beta; gamma == nullptr: the plain
+// normalisation (affine folded elsewhere), through the same n * 1 + 0
+struct AffineStore {
+  bf16_t* y; const float* gamma; const float* beta;
+  __device__ __forceinline__ auto row(int) const {
+    return [this](const float (&n)[8], int col, long at) {
+      float g[8], b[8], o[8];
+      if (gamma) { load_f32x8(gamma + col, g); load_f32x8(beta + col, b); }
+      else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { g[e] = 1.f; b[e] = 0.f; }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = n[e] * g[e] + b[e];
+      *reinterpret_cast<u32x4*>(y + at) = pack_bf16x8(o);
+    };
+  }
+};
+
+// rows of a mixed batch: group g holds rows [r0[g], r0[g + 1]) with rpb[g] rows per sample, its first sample is b0[g] (n == 0: one group)
+struct RowGroups { int n; int r0[MX_MAX_SEGS + 1]; int rpb[MX_MAX_SEGS]; int b0[MX_MAX_SEGS]; };
+
+// AdaLN modulate for the MMDiT blocks: y = n * (1 + scale[b]) + shift[b]  (LayerNorm without affine, eps 1e-6), optionally a second output
+// y2 with (scale2, shift2) sharing the normalisation (SD35AdaLayerNormZeroX).  Serves norm1 / norm1_context / norm2 / norm2_context /
+// norm_out of PatchJointTransformerBlock (modules/transformer.py:316-328, 359-360, 377-378; SD3Transformer.py:238).  scale/shift are fp32
+// rows of the one AdaLN projection GEMM of the step (row stride ldmod), one per sample b.
+struct ModStore {
+  bf16_t* y; bf16_t* y2;
+  const float* scale; const float* shift; const float* scale2; const float* shift2;
+  int ldmod, rows_per_batch;
+  RowGroups rg;
+  static __device__ __forceinline__ void modulate(const float (&n)[8], const float* sc, const float* sh, bf16_t* out) {
+    float s[8], h[8], o[8];
+    load_f32x8(sc, s); load_f32x8(sh, h);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = n[e] * (1.f + s[e]) + h[e];
+    *reinterpret_cast<u32x4*>(out) = pack_bf16x8(o);
+  }
+  __device__ __forceinline__ auto row(int row) const {
+    int sample = row / rows_per_batch;
+    if (rg.n > 0) {                              // mixed batch: the row's group, then its sample inside the group
+      int g = 0;
+#pragma unroll
+      for (int k = 1; k < MX_MAX_SEGS; ++k) if (k < rg.n && row >= rg.r0[k]) g = k;
+      sample = rg.b0[g] + (row - rg.r0[g]) / rg.rpb[g];
+    }
+    const long mrow = (long)sample * ldmod;
+    return [this, mrow](const float (&n)[8], int col, long at) {
+      modulate(n, scale + mrow + col, shift + mrow + col, y + at);
+      if (y2) modulate(n, scale2 + mrow + col, shift2 + mrow + col, y2 + at);
+    };
+  }
+};
+
+// T5LayerNorm: y = x * rsqrt(mean(x^2) + eps) * w
+struct RmsStore {
+  bf16_t* y; const float* w;
+  __device__ __forceinline__ auto row(int) const {
+    return [this](const float (&n)[8], int col, long at) {
+      float g[8], o[8];
+      load_f32x8(w + col, g);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = n[e] * g[e];
+      *reinterpret_cast<u32x4*>(y + at) = pack_bf16x8(o);
+    };
+  }
+};
+
+static int layernorm_mod(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift, const float* scale2,
+                         const float* shift2, int ldmod, int M, int C, int rows_per_batch, float eps, const RowGroups& rg) {
+  MX_CHECK(x && y && scale && shift, "layernorm_mod: null operand");
+  MX_CHECK(!y2 || (scale2 && shift2), "layernorm_mod: second output needs scale2/shift2");
+  MX_CHECK(C % 8 == 0 && C <= 64 * 8 * 8, "layernorm_mod: C must be a multiple of 8 and <= 4096");
+  MX_CHECK(rows_per_batch > 0 && (rg.n > 0 || M % rows_per_batch == 0) && ldmod % 4 == 0, "layernorm_mod: bad batch geometry");
+  return launch_row_norm<true>(stream, x, M, C, eps, ModStore{(bf16_t*)y, (bf16_t*)y2, scale, shift, scale2, shift2, ldmod, rows_per_batch, rg});
+}
+
 }  // namespace mx
 
+// ------------------------------------------------------------------------------------------
+// The row-norm entries: the checks, a Store, the one launcher.
+// ------------------------------------------------------------------------------------------
 extern "C" int mx_layernorm(void* stream, const void* x, void* y, const float* gamma, const float* beta,
                             int M, int C, float eps) {
   using namespace mx;
   MX_CHECK(x && y && ((gamma == nullptr) == (beta == nullptr)), "layernorm: null operand (gamma and beta are given together or not at all)");
   MX_CHECK(C % 8 == 0 && C <= 64 * 8 * 8, "layernorm: C must be a multiple of 8 and <= 4096");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(cdiv(M, 4)), block(256);
-  const int vpl = cdiv(C / 8, 64);
-  const bf16_t* xp = (const bf16_t*)x; bf16_t* yp = (bf16_t*)y;
-  if (vpl <= 1) hipLaunchKernelGGL((layernorm_kernel<1>), grid, block, 0, s, xp, yp, gamma, beta, M, C, eps);
-  else if (vpl <= 2) hipLaunchKernelGGL((layernorm_kernel<2>), grid, block, 0, s, xp, yp, gamma, beta, M, C, eps);
-  else if (vpl <= 3) hipLaunchKernelGGL((layernorm_kernel<3>), grid, block, 0, s, xp, yp, gamma, beta, M, C, eps);
-  else if (vpl <= 4) hipLaunchKernelGGL((layernorm_kernel<4>), grid, block, 0, s, xp, yp, gamma, beta, M, C, eps);
-  else hipLaunchKernelGGL((layernorm_kernel<8>), grid, block, 0, s, xp, yp, gamma, beta, M, C, eps);
-  MX_LAUNCH_CHECK();
-  return 0;
+  return launch_row_norm<true>(stream, x, M, C, eps, AffineStore{(bf16_t*)y, gamma, beta});
+}
+
+extern "C" int mx_layernorm_mod(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift,
+                                const float* scale2, const float* shift2, int ldmod, int M, int C, int rows_per_batch, float eps) {
+  mx::RowGroups rg{};
+  return mx::layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, M, C, rows_per_batch, eps, rg);
+}
+
+/* Mixed batch: the rows are n groups one after the other, group g = batches[g] samples of rows_per_batch[g] rows; the modulation rows
+ * (scale / shift, stride ldmod) are per sample in group order. */
+extern "C" int mx_layernorm_mod_grouped(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift,
+                                        const float* scale2, const float* shift2, int ldmod, int C, float eps, const int* batches,
+                                        const int* rows_per_batch, int n) {
+  MX_CHECK(batches && rows_per_batch && n >= 1 && n <= MX_MAX_SEGS, "layernorm_mod: grouped launch needs 1..MX_MAX_SEGS groups");
+  mx::RowGroups rg; rg.n = n;
+  int r = 0, b = 0;
+  for (int g = 0; g < n; ++g) {
+    MX_CHECK(batches[g] > 0 && rows_per_batch[g] > 0, "layernorm_mod: empty group");
+    rg.r0[g] = r; rg.rpb[g] = rows_per_batch[g]; rg.b0[g] = b;
+    r += batches[g] * rows_per_batch[g]; b += batches[g];
+  }
+  for (int g = n; g <= MX_MAX_SEGS; ++g) rg.r0[g] = r;
+  for (int g = n; g < MX_MAX_SEGS; ++g) { rg.rpb[g] = 1; rg.b0[g] = 0; }
+  return mx::layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, r, C, 1, eps, rg);
+}
+
+extern "C" int mx_rmsnorm(void* stream, const void* x, void* y, const float* w, int M, int C, float eps) {
+  using namespace mx;
+  MX_CHECK(x && y && w && M > 0, "rmsnorm: null operand");
+  MX_CHECK(C % 8 == 0 && C <= 64 * 8 * 8 && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) & 15) == 0), "rmsnorm: C must be a multiple of 8 and <= 4096, pointers 16-byte aligned");
+  return launch_row_norm<false>(stream, x, M, C, eps, RmsStore{(bf16_t*)y, w});
 }
 
 // ------------------------------------------------------------------------------------------
-// AdaLN modulate for the MMDiT blocks: y = LN(x) * (1 + scale[b]) + shift[b]  (LayerNorm without affine, eps 1e-6),
-// optionally a second output y2 with (scale2, shift2) sharing the normalisation (SD35AdaLayerNormZeroX).
-// Serves norm1 / norm1_context / norm2 / norm2_context / norm_out of PatchJointTransformerBlock
-// (modules/transformer.py:316-328, 359-360, 377-378; SD3Transformer.py:238).  scale/shift are fp32 rows of the one
-// AdaLN projection GEMM of the step (row stride ldmod).
+// Row kernels outside the skeleton: they keep no row in registers.
 // ------------------------------------------------------------------------------------------
 namespace mx {
-
-// T5LayerNorm: y = x * rsqrt(mean(x^2) + eps) * w; one wave per row, the row stays in registers between the two passes
-template <int VPL>
-__global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const float* __restrict__ w, int M, int C, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const int nch = C / 8;
-  const bf16_t* xr = x + (long)row * C;
-  float v[VPL][8];
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(xr + ch * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[i][2 * e] = bf16lo_to_f32(u[e]); v[i][2 * e + 1] = bf16hi_to_f32(u[e]);
-        sq += v[i][2 * e] * v[i][2 * e] + v[i][2 * e + 1] * v[i][2 * e + 1];
-      }
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-  bf16_t* yr = y + (long)row * C;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
-      const f32x4 g0 = *reinterpret_cast<const f32x4*>(w + ch * 8), g1 = *reinterpret_cast<const f32x4*>(w + ch * 8 + 4);
-      float o[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { o[e] = v[i][e] * rstd * g0[e]; o[e + 4] = v[i][e + 4] * rstd * g1[e]; }
-      *reinterpret_cast<u32x4*>(yr + ch * 8) = u32x4{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
-    }
-  }
-}
 
 // (sum, sum of squares) of every row: the one-slab statistics of the LayerNorm folded into its consumer GEMM (mx_gemm_desc.ln_stats)
 __global__ __launch_bounds__(256) void row_stats_kernel(const bf16_t* __restrict__ x, int ldx, float* __restrict__ stats, int M, int C) {
@@ -692,100 +777,16 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const bf16_t* __restrict
   const bf16_t* xr = x + (long)row * ldx;
   float s1 = 0.f, s2 = 0.f;
   for (int ch = lane; ch < nch; ch += 64) {
-    const u32x4 u = *reinterpret_cast<const u32x4*>(xr + ch * 8);
+    float v[8];
+    unpack_bf16x8(*reinterpret_cast<const u32x4*>(xr + ch * 8), v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float a = bf16lo_to_f32(u[e]), b = bf16hi_to_f32(u[e]);
-      s1 += a + b;
-      s2 += a * a + b * b;
+      s1 += v[2 * e] + v[2 * e + 1];
+      s2 += v[2 * e] * v[2 * e] + v[2 * e + 1] * v[2 * e + 1];
     }
   }
   s1 = wave_sum(s1); s2 = wave_sum(s2);
   if (lane == 0) *reinterpret_cast<f32x2*>(stats + (long)row * 8) = f32x2{s1, s2};     // one slab, row pitch 4 (mxdenoise.h)
-}
-
-// rows of a mixed batch: group g holds rows [r0[g], r0[g + 1]) with rpb[g] rows per sample, its first sample is b0[g] (n == 0: one group)
-struct RowGroups { int n; int r0[MX_MAX_SEGS + 1]; int rpb[MX_MAX_SEGS]; int b0[MX_MAX_SEGS]; };
-
-template <int VPL>
-__global__ __launch_bounds__(256) void layernorm_mod_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                            bf16_t* __restrict__ y2, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, const float* __restrict__ scale2,
-                                                            const float* __restrict__ shift2, int ldmod, int M, int C,
-                                                            int rows_per_batch, float eps, const RowGroups rg) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const int nch = C / 8;
-  const bf16_t* xr = x + (long)row * C;
-  float v[VPL][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(xr + ch * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[i][2 * e] = bf16lo_to_f32(u[e]);
-        v[i][2 * e + 1] = bf16hi_to_f32(u[e]);
-        sum += v[i][2 * e] + v[i][2 * e + 1];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-    }
-  }
-  const float mean = wave_sum(sum) / (float)C;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-  int sample = row / rows_per_batch;
-  if (rg.n > 0) {                              // mixed batch: the row's group, then its sample inside the group
-    int g = 0;
-#pragma unroll
-    for (int k = 1; k < MX_MAX_SEGS; ++k) if (k < rg.n && row >= rg.r0[k]) g = k;
-    sample = rg.b0[g] + (row - rg.r0[g]) / rg.rpb[g];
-  }
-  const long mrow = (long)sample * ldmod;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nch) {
-      float n[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) n[e] = (v[i][e] - mean) * rstd;
-      {
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(scale + mrow + ch * 8);
-        const f32x4 s1 = *reinterpret_cast<const f32x4*>(scale + mrow + ch * 8 + 4);
-        const f32x4 h0 = *reinterpret_cast<const f32x4*>(shift + mrow + ch * 8);
-        const f32x4 h1 = *reinterpret_cast<const f32x4*>(shift + mrow + ch * 8 + 4);
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o[e] = n[e] * (1.f + s0[e]) + h0[e]; o[e + 4] = n[e + 4] * (1.f + s1[e]) + h1[e]; }
-        u32x4 u = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
-        *reinterpret_cast<u32x4*>(y + (long)row * C + ch * 8) = u;
-      }
-      if (y2) {
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(scale2 + mrow + ch * 8);
-        const f32x4 s1 = *reinterpret_cast<const f32x4*>(scale2 + mrow + ch * 8 + 4);
-        const f32x4 h0 = *reinterpret_cast<const f32x4*>(shift2 + mrow + ch * 8);
-        const f32x4 h1 = *reinterpret_cast<const f32x4*>(shift2 + mrow + ch * 8 + 4);
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o[e] = n[e] * (1.f + s0[e]) + h0[e]; o[e + 4] = n[e + 4] * (1.f + s1[e]) + h1[e]; }
-        u32x4 u = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
-        *reinterpret_cast<u32x4*>(y2 + (long)row * C + ch * 8) = u;
-      }
-    }
-  }
 }
 
 // RMSNorm over each 64-wide head of selected rows of a [rows, ld] bf16 matrix, in place:
@@ -809,66 +810,20 @@ __global__ __launch_bounds__(256) void rmsnorm_heads_kernel(bf16_t* __restrict__
   const int head = grp * 8 + hl;
   const bool ok = head < heads_total;
   bf16_t* p = x + row * ld + (ok ? head : 0) * 64 + sub * 8;
-  u32x4 u = *reinterpret_cast<const u32x4*>(p);
   float v[8];
+  unpack_bf16x8(*reinterpret_cast<const u32x4*>(p), v);
   float sq = 0.f;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[2 * e] = bf16lo_to_f32(u[e]); v[2 * e + 1] = bf16hi_to_f32(u[e]);
-    sq += v[2 * e] * v[2 * e] + v[2 * e + 1] * v[2 * e + 1];
-  }
+  for (int e = 0; e < 4; ++e) sq += v[2 * e] * v[2 * e] + v[2 * e + 1] * v[2 * e + 1];
   sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
   const float rs = rsqrtf(sq * (1.0f / 64.0f) + eps) * (head < heads_q ? q_scale : 1.0f);
   const float* w = (head < heads_q ? wq : wk) + sub * 8;
-  u32x4 o;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(v[2 * e] * rs * w[2 * e], v[2 * e + 1] * rs * w[2 * e + 1]);
-  if (ok) *reinterpret_cast<u32x4*>(p) = o;
+  for (int e = 0; e < 8; ++e) v[e] = v[e] * rs * w[e];
+  if (ok) *reinterpret_cast<u32x4*>(p) = pack_bf16x8(v);
 }
 
 }  // namespace mx
-
-static int launch_layernorm_mod(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift, const float* scale2,
-                                const float* shift2, int ldmod, int M, int C, int rows_per_batch, float eps, const mx::RowGroups& rg) {
-  using namespace mx;
-  MX_CHECK(x && y && scale && shift, "layernorm_mod: null operand");
-  MX_CHECK(!y2 || (scale2 && shift2), "layernorm_mod: second output needs scale2/shift2");
-  MX_CHECK(C % 8 == 0 && C <= 64 * 8 * 8, "layernorm_mod: C must be a multiple of 8 and <= 4096");
-  MX_CHECK(rows_per_batch > 0 && (rg.n > 0 || M % rows_per_batch == 0) && ldmod % 4 == 0, "layernorm_mod: bad batch geometry");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(cdiv(M, 4)), block(256);
-  const int vpl = cdiv(C / 8, 64);
-  const bf16_t* xp = (const bf16_t*)x; bf16_t* yp = (bf16_t*)y; bf16_t* y2p = (bf16_t*)y2;
-#define MX_LNMOD(V) hipLaunchKernelGGL((layernorm_mod_kernel<V>), grid, block, 0, s, xp, yp, y2p, scale, shift, scale2, shift2, ldmod, M, C, rows_per_batch, eps, rg)
-  if (vpl <= 1) MX_LNMOD(1); else if (vpl <= 2) MX_LNMOD(2); else if (vpl <= 3) MX_LNMOD(3); else if (vpl <= 4) MX_LNMOD(4); else MX_LNMOD(8);
-#undef MX_LNMOD
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mx_layernorm_mod(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift,
-                                const float* scale2, const float* shift2, int ldmod, int M, int C, int rows_per_batch, float eps) {
-  mx::RowGroups rg; rg.n = 0;
-  return launch_layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, M, C, rows_per_batch, eps, rg);
-}
-
-/* Mixed batch: the rows are n groups one after the other, group g = batches[g] samples of rows_per_batch[g] rows; the modulation rows
- * (scale / shift, stride ldmod) are per sample in group order. */
-extern "C" int mx_layernorm_mod_grouped(void* stream, const void* x, void* y, void* y2, const float* scale, const float* shift,
-                                        const float* scale2, const float* shift2, int ldmod, int C, float eps, const int* batches,
-                                        const int* rows_per_batch, int n) {
-  MX_CHECK(batches && rows_per_batch && n >= 1 && n <= MX_MAX_SEGS, "layernorm_mod: grouped launch needs 1..MX_MAX_SEGS groups");
-  mx::RowGroups rg; rg.n = n;
-  int r = 0, b = 0;
-  for (int g = 0; g < n; ++g) {
-    MX_CHECK(batches[g] > 0 && rows_per_batch[g] > 0, "layernorm_mod: empty group");
-    rg.r0[g] = r; rg.rpb[g] = rows_per_batch[g]; rg.b0[g] = b;
-    r += batches[g] * rows_per_batch[g]; b += batches[g];
-  }
-  for (int g = n; g <= MX_MAX_SEGS; ++g) rg.r0[g] = r;
-  for (int g = n; g < MX_MAX_SEGS; ++g) { rg.rpb[g] = 1; rg.b0[g] = 0; }
-  return launch_layernorm_mod(stream, x, y, y2, scale, shift, scale2, shift2, ldmod, r, C, 1, eps, rg);
-}
 
 extern "C" int mx_rmsnorm_heads(void* stream, void* x, int ld, int nbatch, int rows_per_batch, int batch_rows, int row_off,
                                 int heads_total, int heads_q, const float* wq, const float* wk, float eps, float q_scale) {
@@ -888,22 +843,6 @@ extern "C" int mx_row_stats(void* stream, const void* x, int ldx, float* stats, 
   MX_CHECK(x && stats && M > 0, "row_stats: null operand");
   MX_CHECK(C % 8 == 0 && ldx >= C && ldx % 8 == 0 && (((uintptr_t)x & 15) | ((uintptr_t)stats & 7)) == 0, "row_stats: C and ldx must be multiples of 8, pointers aligned");
   hipLaunchKernelGGL(row_stats_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, stats, M, C);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mx_rmsnorm(void* stream, const void* x, void* y, const float* w, int M, int C, float eps) {
-  using namespace mx;
-  MX_CHECK(x && y && w && M > 0, "rmsnorm: null operand");
-  MX_CHECK(C % 8 == 0 && C <= 64 * 8 * 8 && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) & 15) == 0), "rmsnorm: C must be a multiple of 8 and <= 4096, pointers 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(cdiv(M, 4)), block(256);
-  const int vpl = cdiv(C / 8, 64);
-  const bf16_t* xp = (const bf16_t*)x; bf16_t* yp = (bf16_t*)y;
-  if (vpl <= 1) hipLaunchKernelGGL((rmsnorm_rows_kernel<1>), grid, block, 0, s, xp, yp, w, M, C, eps);
-  else if (vpl <= 2) hipLaunchKernelGGL((rmsnorm_rows_kernel<2>), grid, block, 0, s, xp, yp, w, M, C, eps);
-  else if (vpl <= 4) hipLaunchKernelGGL((rmsnorm_rows_kernel<4>), grid, block, 0, s, xp, yp, w, M, C, eps);
-  else hipLaunchKernelGGL((rmsnorm_rows_kernel<8>), grid, block, 0, s, xp, yp, w, M, C, eps);
   MX_LAUNCH_CHECK();
   return 0;
 }

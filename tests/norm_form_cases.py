@@ -29,7 +29,9 @@ def _k(kind, name, **kw):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
-# mx_layernorm: layernorm_kernel<VPL>, vpl = ceil(C / 8 / 64) -> <1> <2> <3> <4>, above 4 -> <8>; four rows a workgroup (row >= M exits)
+# The row norms share row_norm_kernel<VPL, CENTRE, Store> and ONE ladder (with_vpl): vpl = ceil(C / 8 / 64) -> <1> <2> <3> <4>, above 4 -> <8>;
+# four rows a workgroup (row >= M exits).
+# mx_layernorm: row_norm_kernel<VPL, true, AffineStore>
 # ------------------------------------------------------------------------------------------------------------------------------------------
 LN_CASES = [
     _k("ln", "ln_c8_m1", C=8, M=1, affine=True),                       # <1>, one lane of 64 holds data; M = 1: three waves exit
@@ -47,7 +49,7 @@ LN_CASES = [
 ]
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
-# mx_layernorm_mod: layernorm_mod_kernel<VPL>, the same ladder; sample = row / rows_per_batch; scale / shift (and scale2 / shift2 when y2 is
+# mx_layernorm_mod: row_norm_kernel<VPL, true, ModStore>; sample = row / rows_per_batch; scale / shift (and scale2 / shift2 when y2 is
 # given) are column slices of ONE fp32 matrix [B, 6 C + 4] (ldmod = 6 C + 4 > C), NaN outside the slices
 # ------------------------------------------------------------------------------------------------------------------------------------------
 MOD_CASES = [
@@ -71,15 +73,16 @@ MODG_CASES = [
 ]
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
-# mx_rmsnorm: rmsnorm_rows_kernel<VPL>, ladder <1> <2> <4> <8>: vpl == 3 goes to <4> (unlike LayerNorm's <3>)
+# mx_rmsnorm: row_norm_kernel<VPL, false, RmsStore>.  Its own ladder once had no <3> rung: vpl == 3 ran <4> with an empty fourth chunk, which
+# every loop skipped (ch < nch), so the two cases of that width compute the same bytes on either rung
 # ------------------------------------------------------------------------------------------------------------------------------------------
 RMS_CASES = [
     _k("rms", "rms_c8_m1", C=8, M=1),                        # <1> ragged
     _k("rms", "rms_c512_m301", C=512, M=301),                # <1> full; M = 4k + 1, many workgroups
     _k("rms", "rms_c520_m5_b", C=520, M=5, fam="b"),         # <2> ragged
     _k("rms", "rms_c1024_m5", C=1024, M=5),                  # <2> full
-    _k("rms", "rms_c1032_m5_e", C=1032, M=5, fam="e"),       # vpl == 3 -> <4>, third chunk one lane, fourth empty
-    _k("rms", "rms_c1536_m301", C=1536, M=301),              # vpl == 3 -> <4>, fourth chunk empty
+    _k("rms", "rms_c1032_m5_e", C=1032, M=5, fam="e"),       # <3> ragged: the third chunk holds one lane
+    _k("rms", "rms_c1536_m301", C=1536, M=301),              # <3> full; many workgroups
     _k("rms", "rms_c2048_m1_d", C=2048, M=1, fam="d"),       # <4> full; the one row constant
     _k("rms", "rms_c2056_m5_c", C=2056, M=5, fam="c"),       # <8> (vpl = 5)
     _k("rms", "rms_c4096_m5", C=4096, M=5),                  # <8> full (the T5 width)

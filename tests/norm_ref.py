@@ -4,7 +4,7 @@ guards, NaN padding and comparator.
 Every reference is computed in float64 from the values the kernel actually receives (bf16 / fp16 / fp32 activations, fp32 affine and
 modulation), and every output element gets its OWN bound, the sum of the rounding steps the kernel's arithmetic can take on the way to it.
 
-Row norms (layernorm_kernel, layernorm_mod_kernel, rmsnorm_rows_kernel, rmsnorm_heads_kernel): two passes over registers, C values a row
+Row norms (row_norm_kernel with its three stores -- affine, AdaLN modulate, RMS weight -- and rmsnorm_heads_kernel): two passes over registers, C values a row
   mean           fp32 sum of C terms in any order, one divide:                     d_mean = C 2^-24 mean|x| + 2^-24 |mean|
   variance       fp32 centred sum of squares, likewise (each d = x - mean rounded, each square rounded: 3 2^-24 more), plus the effect of
                  the mean's error on it:                                            d_var = (C + 3) 2^-24 var + 2 mean|x - mean| d_mean + d_mean^2

@@ -1,7 +1,8 @@
 """The normalisation matrix on the GPU: every case of tests/norm_form_cases.py is called through the C ABI (ctypes, not the ops wrappers, which
 size their buffers tightly) on NaN-padded inputs into guarded outputs, twice -- the two results must be equal bit for bit -- and every
 output element is compared with the fp64 reference within that element's own bound (tests/norm_ref.py).  Each case prints its worst
-err / bound; profiles/norm_forms_ratios.txt holds the table of one full run."""
+err / bound; profiles/norm_forms_ratios.txt holds the table of one full run.  The test_row_forms_* tests hold the forms of the one row-norm
+skeleton against each other on the raw bits."""
 import ctypes as C
 
 import pytest
@@ -282,6 +283,91 @@ def test_norm_form(cuda_device, c):
         for n, y in run.separate_launches().items():
             rows, cols = y.shape
             assert torch.equal(_bits(s1[n][:rows, :cols]), _bits(y)), f"{c['name']} {n}: grouped != separate"
+
+
+# ---- the forms of the one row-norm skeleton (row_norm_kernel<VPL, CENTRE, Store>) against each other, on the raw bits ----
+FORM_WIDTHS = [8, 520, 1024, 1032, 1544, 2056, 4096]        # every rung of with_vpl, ragged and full last chunks
+
+
+class _RowForms:
+    """rows [M, C] and one modulation matrix [B, 6 C + 4] (shift | scale | NaN ..., as _Run._mod_ptrs lays it out), both NaN-padded; every launch
+    writes fresh guarded outputs and returns their bits"""
+
+    def __init__(self, Cc, M, B, dev, zero_mod=False):
+        gen = torch.Generator().manual_seed(NC.seed_of(f"row_forms_{Cc}_{M}"))
+        self.lib, self.C, self.dev, self.ldmod = L.load(), Cc, dev, 6 * Cc + 4
+        self.x, _ = R.nan_padded(NC.rows_input("a", M, Cc, gen).to(dev), Cc, extra_rows=2)
+        mod = torch.full((B, self.ldmod), float("nan"))
+        mod[:, :Cc] = 0.0 if zero_mod else torch.randn(B, Cc, generator=gen)
+        mod[:, Cc:2 * Cc] = 0.0 if zero_mod else torch.randn(B, Cc, generator=gen) * 0.3
+        self.mod, _ = R.nan_padded(mod.to(dev), self.ldmod, extra_rows=1)
+
+    def _launch(self, M, n_out, call):
+        outs = [R.guarded(M, self.C, self.C, torch.bfloat16, self.dev) for _ in range(n_out)]
+        L.check(call(*[buf.data_ptr() for buf, _v in outs]), "row form")
+        torch.cuda.synchronize()
+        for buf, _v in outs:
+            assert R.guard_violations(buf, M, self.C) == 0, "the launch wrote outside its output"
+        return [_bits(v).clone() for _buf, v in outs]
+
+    def _x(self, row0):
+        return self.x.data_ptr() + 2 * row0 * self.C
+
+    def _mod_args(self, b0, dual):
+        shift = self.mod.data_ptr() + 4 * b0 * self.ldmod
+        scale = shift + 4 * self.C
+        return (scale, shift) + ((scale, shift) if dual else (None, None)) + (self.ldmod,)
+
+    def ln(self, M, eps, gamma=None, beta=None):
+        return self._launch(M, 1, lambda y: self.lib.mx_layernorm(L.current_stream(), self._x(0), y, _ptr(gamma), _ptr(beta), M, self.C, eps))[0]
+
+    def mod_rows(self, M, rpb, eps, dual=False, row0=0, b0=0):
+        """mx_layernorm_mod on rows [row0, row0 + M), whose first sample is b0; dual: the second output takes the same scale / shift slices"""
+        return self._launch(M, 2 if dual else 1, lambda y, y2=None: self.lib.mx_layernorm_mod(
+            L.current_stream(), self._x(row0), y, y2, *self._mod_args(b0, dual), M, self.C, rpb, eps))
+
+    def grouped(self, batches, rpbs, eps):
+        n, M = len(batches), sum(b * r for b, r in zip(batches, rpbs))
+        bt, rp = (C.c_int * n)(*batches), (C.c_int * n)(*rpbs)
+        return self._launch(M, 1, lambda y: self.lib.mx_layernorm_mod_grouped(
+            L.current_stream(), self._x(0), y, None, *self._mod_args(0, False), self.C, eps,
+            C.cast(bt, C.c_void_p), C.cast(rp, C.c_void_p), n))[0]
+
+
+@pytest.mark.parametrize("Cc", FORM_WIDTHS)
+def test_row_forms_plain_normalisation(cuda_device, Cc):
+    """a zero modulation and the unit affine are the plain LayerNorm: n * (1 + 0) + 0 == n * 1 + 0 == the gamma == nullptr form"""
+    M = 5 + (Cc // 8) % 3
+    f = _RowForms(Cc, M, M, cuda_device, zero_mod=True)
+    plain = f.ln(M, NC.MOD_EPS)
+    assert torch.equal(f.mod_rows(M, 1, NC.MOD_EPS)[0], plain), "zero modulation != plain LayerNorm"
+    ones, zeros = _nan_tail(torch.ones(Cc, device=cuda_device)), _nan_tail(torch.zeros(Cc, device=cuda_device))
+    assert torch.equal(f.ln(M, NC.MOD_EPS, ones, zeros), plain), "gamma = 1, beta = 0 != plain LayerNorm"
+
+
+@pytest.mark.parametrize("Cc", FORM_WIDTHS)
+def test_row_forms_second_output_and_one_group(cuda_device, Cc):
+    """y2 with y's own scale / shift is y, and y does not depend on y2 being asked for; a grouped launch of one group is the ungrouped launch"""
+    B, rpb = 3, 2
+    f = _RowForms(Cc, B * rpb, B, cuda_device)
+    y = f.mod_rows(B * rpb, rpb, NC.MOD_EPS)[0]
+    y_dual, y2 = f.mod_rows(B * rpb, rpb, NC.MOD_EPS, dual=True)
+    assert torch.equal(y_dual, y), "y changes when a second output is written"
+    assert torch.equal(y2, y), "y2 with the same scale / shift != y"
+    assert torch.equal(f.grouped([B], [rpb], NC.MOD_EPS), y), "grouped launch with n = 1 != mx_layernorm_mod"
+
+
+@pytest.mark.parametrize("Cc", FORM_WIDTHS)
+def test_row_forms_groups_equal_their_own_launch(cuda_device, Cc):
+    """every group of a mixed batch equals mx_layernorm_mod on that group's rows alone, its modulation rows starting at b0 * ldmod"""
+    batches, rpbs = [1, 2, 3], [7, 1, 4]
+    f = _RowForms(Cc, sum(b * r for b, r in zip(batches, rpbs)), sum(batches), cuda_device)
+    y = f.grouped(batches, rpbs, NC.MOD_EPS)
+    r0 = b0 = 0
+    for b, r in zip(batches, rpbs):
+        alone = f.mod_rows(b * r, r, NC.MOD_EPS, row0=r0, b0=b0)[0]
+        assert torch.equal(y[r0:r0 + b * r], alone), f"group at row {r0} != its own launch"
+        r0, b0 = r0 + b * r, b0 + b
 
 
 @pytest.mark.parametrize("dn", ["f32", "f16", "bf16"])
