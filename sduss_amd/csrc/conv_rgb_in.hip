@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "../../include/mxdenoise.h"
+#include "conv_tile.h"
 
 // bytes -> value is evaluated operation by operation (t = u / 255; v = 2 t - 1): no contraction into an FMA in this translation unit
 #pragma clang fp contract(off)
@@ -56,8 +57,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_rgb_in_kernel(const RgbInArgs 
   char* patch = smem + kRiStageBytes + wave * (16 * kRiPatch);
   const int n0 = blockIdx.y * (16 * kRiBlocks);
   const int nb = std::min(kRiBlocks, (N - n0) >> 4);                  // 16-feature blocks of this chunk (N % 16 == 0: the launcher)
-  const int tiles_x = (W + 15) >> 4, tiles_y = (H + 3) >> 2;
-  const int tiles = p.B * tiles_x * tiles_y;
+  const int tiles = conv_tiles(p.B, H, W);
   // A operand: lane (j, kq) holds weight row n0 + 16 i + j, columns 8 kq .. 8 kq + 7; columns >= 27 are zero whatever the tensor holds
   bf16x8 wf[kRiBlocks];
   f32x4 bv[kRiBlocks];
@@ -90,14 +90,12 @@ __global__ __launch_bounds__(256, 4) void conv3x3_rgb_in_kernel(const RgbInArgs 
     vx[q] = rem / 3; vc[q] = rem - vx[q] * 3;
   }
   auto fetch = [&](bf16_t (&r)[2], int tile) __attribute__((always_inline)) {
-    const int b = tile / (tiles_x * tiles_y);
-    const int t = tile - b * tiles_x * tiles_y;
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const ConvTile t = conv_tile_at(tile, H, W);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int gy = ty * 4 - 1 + vr[q], gx = tx * 16 - 1 + vx[q];
+      const int gy = t.ty * 4 - 1 + vr[q], gx = t.tx * 16 - 1 + vx[q];
       const bool ok = (tid + 256 * q) < kRiElems && gy >= 0 && gy < H && gx >= 0 && gx < W;      // zero padding is zeros in LDS
-      r[q] = ok ? rgb_in_value(p, b, p.rotate ? H - 1 - gy : gy, p.rotate ? W - 1 - gx : gx, vc[q]) : (bf16_t)0;
+      r[q] = ok ? rgb_in_value(p, t.b, p.rotate ? H - 1 - gy : gy, p.rotate ? W - 1 - gx : gx, vc[q]) : (bf16_t)0;
     }
   };
   int tile = blockIdx.x;
@@ -105,10 +103,9 @@ __global__ __launch_bounds__(256, 4) void conv3x3_rgb_in_kernel(const RgbInArgs 
   bf16_t pre[2];
   fetch(pre, tile);
   while (tile < tiles) {
-    const int b = tile / (tiles_x * tiles_y);
-    const int t = tile - b * tiles_x * tiles_y;
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    const int y = ty * 4 + wave;
+    const ConvTile t = conv_tile_at(tile, H, W);
+    const int b = t.b, tx = t.tx;
+    const int y = t.ty * 4 + wave;
     const int next_tile = tile + gridDim.x;
     sx[tid] = pre[0];
     if (tid + 256 < kRiElems) sx[tid + 256] = pre[1];
@@ -160,10 +157,10 @@ extern "C" int mx_conv3x3_rgb_in(void* stream, const void* image, int image_form
   mx::RgbInArgs a;
   a.image = image; a.w = (const mx::bf16_t*)w; a.bias = bias; a.y = (mx::bf16_t*)y;
   a.B = B; a.H = H; a.W = W; a.N = N; a.format = image_format; a.rotate = rotate;
-  const long tiles = (long)B * ((H + 3) / 4) * ((W + 15) / 16);      // (< 2^31: B H W is)
+  const int tiles = mx::conv_tiles(B, H, W);      // (< 2^31: B H W is)
   const int chunks = (N + 16 * mx::kRiBlocks - 1) / (16 * mx::kRiBlocks);
   MX_CHECK(chunks <= 65535, "conv3x3_rgb_in: N too large");
-  const int grid = (int)std::min<long>(tiles, (long)mx::kRiPerCu * mx::cu_count());
+  const int grid = std::min(tiles, mx::kRiPerCu * mx::cu_count());
   hipLaunchKernelGGL(mx::conv3x3_rgb_in_kernel, dim3(grid, chunks), dim3(256), mx::kRiLds, (hipStream_t)stream, a);
   MX_LAUNCH_CHECK();
   return 0;

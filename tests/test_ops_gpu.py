@@ -191,6 +191,30 @@ def test_conv3x3_small_cin(cuda_device, corner, h, w, cout, b, cv):
     _close(got.permute(0, 3, 1, 2), plain.float().cpu().permute(0, 3, 1, 2), 2.0 ** -7, "small Cin vs the tile kernel")
 
 
+@pytest.mark.parametrize("b,h,w", [(2, 5, 17), (1, 32, 32)])      # ragged tiles over two images; W == P: the right edge crosses a patch boundary
+@pytest.mark.parametrize("form,cin,cout,cv", [("conv3x3_small_n_kernel", 128, 4, 0), ("conv3x3_small_cin_kernel", 64, 80, 8)])
+def test_conv3x3_small_corner_rule_inside_one_patch(cuda_device, form, cin, cout, cv, b, h, w):
+    """the whole image inside one patch (P >= max(H, W)): every tap the corner rule (csrc/conv_tile.h, corner_folds) folds leaves the image both ways and
+    reads zero padding before and after folding, so the launch with the rule must equal the launch without it bit for bit"""
+    from sduss_amd import lib, ops
+    g = torch.Generator().manual_seed(h + w + cin + cout)
+    x = torch.zeros(b, h, w, cin)
+    x[..., :cv or cin] = torch.randn(b, h, w, cv or cin, generator=g)
+    xd = _bf(x).cuda()
+    wd = _bf(torch.randn(cout, 9 * cin, generator=g) * (9 * (cv or cin)) ** -0.5).cuda()
+    bias = torch.randn(cout, generator=g).cuda()
+    outs = []
+    for P in (32, 0):
+        d = lib.GemmDesc()                               # the descriptor ops.conv3x3 fills, to ask which kernel serves it
+        d.a, d.w, d.c, d.bias = xd.data_ptr(), wd.data_ptr(), xd.data_ptr(), bias.data_ptr()
+        d.M, d.N, d.K, d.ldc, d.ldr, d.rows_per_batch = b * h * w, cout, 9 * cin, cout, cout, h * w
+        d.B, d.Hin, d.Win, d.Cin, d.Hout, d.Wout, d.stride, d.up, d.corner_patch, d.cin_valid = b, h, w, cin, h, w, 1, 0, P, cv
+        assert lib.gemm_kernels_of(d, conv=True) == [form]
+        outs.append(ops.conv3x3(xd, wd, bias, corner_patch=P, cin_valid=cv))
+    assert float(outs[1].float().abs().max()) > 0.5
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)), "the corner rule changed an image that lies inside one patch"
+
+
 def test_conv3x3_rowbias_residual(cuda_device):
     from sduss_amd import ops
     g = torch.Generator().manual_seed(9)

@@ -176,6 +176,48 @@ def test_exact_unaligned_output(cuda_device):
     assert torch.equal(run_twice(x, w, bias, offset=1), want)
 
 
+# ---- 1b. the two kernels of the shared staged body (csrc/conv_tile.h) against each other ----
+
+def shared_body_operands(B, H, W, Cin):
+    """integer activations in [-2, 2]; weights in {-1, 0, 1} x 2^-6, about half of them zero: every accumulator is k 2^-6 with a small integer k, exact
+    in fp32 in any order AND a bf16 value, so the small-N kernel's bf16 output with a zero bias IS its accumulator.  The bias: one channel pushed to each
+    clamp, one in the interior, each with a random fp32 offset (no multiple of 2^-6: the levels' rounding is exercised)."""
+    g = torch.Generator().manual_seed(77 + 1000 * H + W + Cin)
+    x = torch.randint(-2, 3, (B, H, W, Cin), generator=g).to(torch.bfloat16)
+    w = torch.randint(-1, 2, (3, 9 * Cin), generator=g).float() / 64.0
+    w = (w * (torch.rand(3, 9 * Cin, generator=g) < 0.75)).to(torch.bfloat16)          # zeros: 1/3 drawn + 1/4 of the rest = one half
+    bias = torch.tensor([0.7, 0.0, -0.7]) + torch.randn(3, generator=g) * 0.05
+    return x, w, bias
+
+
+@pytest.mark.parametrize("B,H,W,Cin,offset", [
+    pytest.param(1, 4, 16, 64, 0, id="B1-H4-W16-Cin64"),               # one tile, one chunk
+    pytest.param(2, 5, 17, 128, 0, id="B2-H5-W17-Cin128"),             # ragged both ways, two chunks, prefetch across chunks, tiles and images, byte stores
+    pytest.param(1, 8, 24, 128, 0, id="B1-H8-W24-Cin128"),             # dword stores with a half-full right tile
+    pytest.param(2, 5, 17, 128, 1, id="B2-H5-W17-Cin128-unaligned"),   # the output one byte past a dword
+])
+def test_rgb8_is_the_small_n_accumulator_quantised(cuda_device, B, H, W, Cin, offset):
+    """conv3x3_rgb8_kernel and conv3x3_small_n_kernel run one body: for the same operands the bytes of the first are the fp32 formula applied, on the CPU,
+    to the accumulator the second returns (N = 4, rows 0..2 the rgb8 weights, row 3 and the bias zero; rgb8's own row 3 and bias[3] are NaN)."""
+    from sduss_amd import ops
+    x, w, bias = shared_body_operands(B, H, W, Cin)
+    ref64, _ = acc_on_device(x, w)
+    k = ref64 * 64
+    assert bool((k == k.round()).all()) and float(k.abs().max()) < 256, float(k.abs().max())        # exact in any order, and a bf16 value
+    assert float((w == 0).float().mean()) > 0.4
+    w4 = torch.zeros((4, 9 * Cin), dtype=torch.bfloat16)
+    w4[:3] = w
+    acc = ops.conv3x3(x.cuda(), w4.cuda(), torch.zeros(4, device="cuda")).float().cpu()
+    assert bool((acc[..., 3] == 0).all())
+    assert torch.equal(acc[..., :3].reshape(-1, 3).double(), ref64), "the small-N kernel did not return the exact accumulator"
+    want = formula_cpu(acc[..., :3].contiguous(), bias)
+    inside = ((want > 0) & (want < 255)).float().mean().item()
+    assert bool((want == 0).any()) and bool((want == 255).any()) and inside >= 0.1 and want.unique().numel() >= 32, (inside, want.unique().numel())
+    got = run_twice(x, w, bias, offset=offset)
+    bad = got != want
+    assert not bool(bad.any()), f"{int(bad.sum())} of {got.numel()} bytes differ from the formula on the small-N accumulator (first at {bad.nonzero()[0].tolist()})"
+
+
 # ---- 2. bounded cases ----
 
 @pytest.mark.parametrize("B,H,W,Cin", SHAPES)
