@@ -31,12 +31,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef MX_AEXP
-#define MX_AEXP 0   // ablation builds of attn_fwd_dma_kernel (tools/exp/build_attn_variants.sh): timing only
-#endif
-
 #include "common.h"
 #include "../../include/mxdenoise.h"
+#include "attn_tile.h"
 #include "attn_cross_body.h"
 
 namespace mx {
@@ -81,9 +78,6 @@ __device__ __forceinline__ const AttnArgs& attn_locate(const AttnGroup& ga, int&
   return p;
 }
 
-constexpr int KT = 64;                 // keys per tile
-constexpr int kBufBytes = 16384;       // one ring buffer: K tile (8 KB) then V^T tile (8 KB)
-
 // EXTRA: the additive-bias and causal-mask forms of the text encoders, a separate instantiation (as run-time branches they cost the
 // 60 cross-attention launches of a UNet step 3.4 us each: profiles r02_f vs r02_g)
 template <bool PRE, bool EXTRA = false>
@@ -95,10 +89,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
   const int wave = tid >> 6;
   const int r = lane & 31;   // query column owned by this lane (and fragment row)
   const int hh = lane >> 5;  // half-wave
-  // workgroup -> (query block, head, batch).  Consecutive workgroup ids are dealt round-robin to the 8 XCDs (one L2 each):
-  // with the plain x-fastest order the query blocks of one head land on all 8 XCDs and each L2 fetches that head's K / V^T
-  // (rocprofv3 FETCH_SIZE: 4.4x the algorithmic bytes at Lk = 4429).  When the number of (batch, head) pairs is a multiple
-  // of 8, XCD x instead owns the pairs == x (mod 8) and walks their query blocks consecutively.
   int qb, bh;
   const AttnArgs& p = attn_locate<128>(ga, qb, bh);      // (problem of a grouped launch, query block, batch * H + head)
   if (qb < 0) return;
@@ -106,15 +96,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
   const int b = bh / p.H;
   const int q0 = qb * 128 + wave * 32;
 
-  // ---- Q fragments (B operand of S^T = K Q^T): Q[q0 + r][16*ks + 8*hh .. +7] ----
   bf16x8 qf[4];
-  {
-    int qi = q0 + r;
-    if (qi > p.Lq - 1) qi = p.Lq - 1;
-    const bf16_t* qp = p.q + ((long)b * p.Lq + qi) * p.ldq + head * 64 + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-  }
+  load_q(p, b, head, q0, lane, qf);
 
   // ---- staging: 512 16-byte chunks per tile per operand, 2 per thread (rows srow, srow+32; chunk sch) ----
   const int srow = tid >> 3;
@@ -179,33 +162,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
     }
   };
 
-  // ---- per-lane LDS read offsets for buffer 0 (loop invariant; the buffer bit is XOR-toggled per tile) ----
-  // row r, chunk 2*step + hh: the K fragment of k-step `step` and (at +8192) the V^T fragment of 16-key step `step`
-  unsigned koff[4];
-  {
-    const int swz = (r >> 1) & 7;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) koff[ks] = (unsigned)(r * 128 + (((2 * ks + hh) ^ swz) * 16));
-  }
+  unsigned koff[4];                            // for buffer 0; the buffer bit is XOR-toggled per tile
+  frag_offsets(r, hh, koff);
 
-  f32x16 oacc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 oacc[2] = {zero16, zero16};
   float m_run = -INFINITY;  // !PRE: running max of s*scale_log2 for query column r (identical in both halves)
   float l_run = 0.f;        // this half-wave's partial row sum
-  // PRE: the reference k-step.  A operand: K column of ones = element k == 0 of the step (held by the hh == 0 lanes);
-  // B operand: -m_ref (bf16-representable) in the same element of query column r.
-  const unsigned one_lo = hh == 0 ? 0x3F80u : 0u;
-  const bf16x8 kone = __builtin_bit_cast(bf16x8, u32x4{one_lo, 0u, 0u, 0u});
+  // PRE: the scores leave their MFMA chain as s - m_ref through the reference k-step
+  const bf16x8 kone = ref_step_ones(hh);
   u32x4 qm = {0u, 0u, 0u, 0u};
   float m_ref = 0.f;
 
   const int ntiles = (p.Lk + KT - 1) / KT;
   const bool ragged = (p.Lk % KT) != 0;
-  const float c = p.scale_log2;
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   if (ntiles == 1 && ragged) load_tile_tail(0); else load_tile(0);
   store_tile(st_off);
@@ -217,31 +187,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
       if (ragged && kt + 2 == ntiles) load_tile_tail(kt + 1); else load_tile(kt + 1);
     }
 
-    // ---- S^T = K Q^T : two 32-key blocks.  All eight K fragments are requested before the first MFMA and the two
-    //      accumulator chains alternate, so neither LDS latency nor the MFMA dependency sits between issues. ----
+    // All eight K fragments are requested before the first MFMA, so that no LDS latency sits between the issues.
     bf16x8 fr[8];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) fr[kb * 4 + ks] = *reinterpret_cast<const bf16x8*>(smem + koff[ks] + kb * 4096);
+    read_k(fr, smem, koff);
     __builtin_amdgcn_sched_barrier(0);
     f32x16 s[2];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[kb * 4 + ks], qf[ks], ks == 0 ? zero16 : s[kb], 0, 0, 0);
-    }
-    if constexpr (PRE) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kone, __builtin_bit_cast(bf16x8, qm), s[kb], 0, 0, 0);
-    }
-    // V^T fragments (same registers): in flight while the softmax runs on the vector ALU
-#pragma unroll
-    for (int sidx = 0; sidx < 4; ++sidx)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) fr[sidx * 2 + db] = *reinterpret_cast<const bf16x8*>(smem + koff[sidx] + 8192 + db * 4096);
+    qk(s, fr, qf, zero16);
+    if constexpr (PRE) ref_step(s, kone, qm);
+    read_v(fr, smem, koff);                    // V^T fragments (same registers): in flight while the softmax runs on the vector ALU
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (EXTRA) if (p.bias != nullptr) {   // additive bias, four consecutive keys per load; BEFORE the masks (the pad of a bias row may hold anything) (key = 32 kb + 8 g + 4 hh + {0..3})
       int qi = q0 + r;
@@ -276,82 +229,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
         }
     }
     // ---- online softmax (log2 domain) ----
-    float mx_ = s[0][0];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) mx_ = fmaxf(mx_, s[kb][e]);
-    mx_ = max_across_halves(mx_);
-    float psum = 0.f;
     if constexpr (PRE) {
-      // s already holds s*c - m_ref.  Move the reference only on the first tile or when a row ran more than 8 above it.
+      // s already holds s*c - m_ref.  The row maximum first: the reference moves only on the first tile or when a row ran more than 8 above it.
+      const float mx_ = col_max(s);
       const bool first = kt == 0;
-      if (first || __any(mx_ > 8.0f)) {
-        float delta = 0.f;
-        if (first || mx_ > 8.0f) {
-          const float nr = bf16lo_to_f32(pack2(m_ref + mx_, 0.f));        // new reference, bf16-representable
-          delta = nr - m_ref;
-          m_ref = nr;
-        }
-        qm[0] = hh == 0 ? (pack2(-m_ref, 0.f) & 0xffffu) : 0u;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) s[kb][e] -= delta;
-        if (!first) {
-          const float alpha = __builtin_amdgcn_exp2f(-delta);
-          l_run *= alpha;
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
-        }
-      }
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(s[kb][e]);
-          s[kb][e] = pe;
-          psum += pe;
-        }
-      l_run += psum;
+      if (first || __any(mx_ > 8.0f))
+        move_reference(s, mx_, first, m_ref, l_run, oacc, [&](float m) __attribute__((always_inline)) { qm[0] = ref_step_word(m, hh); });
+      l_run += exp_sum(s);
     } else {
-      const float m_new = fmaxf(m_run, mx_ * c);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      m_run = m_new;
-      // (packed v_pk_fma_f32 / v_pk_add_f32 forms of this loop measured 0-3 % SLOWER in same-run A/B: scalar kept)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(s[kb][e] * c - m_new);
-          s[kb][e] = pe;
-          psum += pe;
-        }
-      l_run = l_run * alpha + psum;
-      if (!__all(alpha == 1.0f)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
-      }
+      softmax_running_max(s, p.scale_log2, m_run, l_run, oacc);
     }
-    // ---- O^T += V^T P^T : P fragments straight from the S^T accumulators ----
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        u32x4 pw;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pw[e] = pack2(s[kb][8 * s2 + 2 * e], s[kb][8 * s2 + 2 * e + 1]);
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
-        const int sidx = 2 * kb + s2;  // 16-key step inside the tile
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[sidx * 2 + db], pf, oacc[db], 0, 0, 0);
-      }
-    }
+    pv(oacc, s, fr);
     // the next tile lives in the other buffer: toggle the buffer bit of every offset
     st_off ^= kBufBytes;
     if (has_next) store_tile(st_off);
@@ -360,52 +248,26 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnGroup ga) {
     __syncthreads();
   }
 
-  // ---- normalise and store O[q][d] ----
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
-  const int qi = q0 + r;
-  if (qi < p.Lq) {
-    bf16_t* op = p.o + ((long)b * p.Lq + qi) * p.ldo + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = db * 32 + 8 * g + 4 * hh;
-        u32x2 o = {pack2(oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv),
-                   pack2(oacc[db][4 * g + 2] * inv, oacc[db][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2*>(op + d) = o;
-      }
-  }
+  store_o(p, b, head, q0 + r, hh, l_run, oacc);
 }
 
 
 // ----------------------------------------------------------------------------------------------------------------------
-// The same kernel with K / V^T tiles staged by LDS-DMA two tiles ahead (round 2), for key counts that are whole tiles.
-// attn_fwd_kernel fetches tile kt + 1 into registers while it computes tile kt and writes it to LDS at the end of the iteration:
-// one tile of compute (~1.2k cycles per wave) has to cover an L2 / Infinity-Cache round trip under load, and 16 VGPRs hold the
-// staged tile.  Here the tile goes L2 -> LDS directly (global_load_lds_dwordx4, swizzle on the source address) into a ring of
-// three 16-KB buffers, issued right after the barrier of tile kt for tile kt + 2; one counted s_waitcnt vmcnt(4) + one raw
-// s_barrier per tile.  The compute body is attn_fwd_kernel's.
+// The same kernel with K / V^T tiles staged by LDS-DMA two tiles ahead (round 2), for key counts that are whole tiles (the launcher sends ragged
+// ones to attn_fwd_kernel).  attn_fwd_kernel fetches tile kt + 1 into registers while it computes tile kt and writes it to LDS at the end of the
+// iteration: one tile of compute (~1.2k cycles per wave) has to cover an L2 / Infinity-Cache round trip under load, and 16 VGPRs hold the staged
+// tile.  Here the tile goes L2 -> LDS directly (AttnRing, attn_tile.h), issued right after the barrier of tile kt for tile kt + 2; one counted
+// s_waitcnt vmcnt(4) + one raw s_barrier per tile.
 // ----------------------------------------------------------------------------------------------------------------------
 template <bool PRE>
 __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnGroup ga) {
-  #if (MX_AEXP & 32)
-  __shared__ __attribute__((aligned(16))) char smem[3 * kBufBytes + 40 * 1024];
-#elif (MX_AEXP & 64)
-  __shared__ __attribute__((aligned(16))) char smem[3 * kBufBytes + 12 * 1024];
-#else
   __shared__ __attribute__((aligned(16))) char smem[3 * kBufBytes];
-#endif
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int r = lane & 31;   // query column owned by this lane (and fragment row)
   const int hh = lane >> 5;  // half-wave
-  // workgroup -> (query block, head, batch).  Consecutive workgroup ids are dealt round-robin to the 8 XCDs (one L2 each):
-  // with the plain x-fastest order the query blocks of one head land on all 8 XCDs and each L2 fetches that head's K / V^T
-  // (rocprofv3 FETCH_SIZE: 4.4x the algorithmic bytes at Lk = 4429).  When the number of (batch, head) pairs is a multiple
-  // of 8, XCD x instead owns the pairs == x (mod 8) and walks their query blocks consecutively.
   int qb, bh;
   const AttnArgs& p = attn_locate<128>(ga, qb, bh);      // (problem of a grouped launch, query block, batch * H + head)
   if (qb < 0) return;
@@ -413,285 +275,87 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnGroup ga
   const int b = bh / p.H;
   const int q0 = qb * 128 + wave * 32;
 
-  // ---- Q fragments (B operand of S^T = K Q^T): Q[q0 + r][16*ks + 8*hh .. +7] ----
   bf16x8 qf[4];
-  {
-    int qi = q0 + r;
-    if (qi > p.Lq - 1) qi = p.Lq - 1;
-    const bf16_t* qp = p.q + ((long)b * p.Lq + qi) * p.ldq + head * 64 + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-  }
-
-  // ---- staging by LDS-DMA into a three-buffer ring, two tiles ahead: 512 16-byte chunks per tile per operand, 2 per thread.
-  //      Chunk c = i * 256 + tid lands at byte 16 c of the image (an LDS-DMA writes base + 16 * lane); it is row c >> 3, slot c & 7,
-  //      and holds logical chunk slot ^ ((row >> 1) & 7) of that row: the swizzle is applied on the SOURCE address. ----
-  // Addresses: a wave-uniform base that moves with the tile plus a per-lane 32-bit offset fixed for the whole kernel (as in attn_fwd64_kernel:
-  // the per-tile 64-bit address arithmetic cost 6 % of the launch there).
-  const char* kbase = (const char*)(p.k + (long)b * p.k_bstride + head * 64);
-  const char* vbase = (const char*)(p.vt + (long)b * p.vt_bstride + ((long)head * 64) * p.ldvt);
-  unsigned voffk[2], voffv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = i * 256 + tid;
-    const int row = c >> 3, ch = (c & 7) ^ ((row >> 1) & 7);
-    voffk[i] = (unsigned)(row * p.ldk * 2 + ch * 16);
-    voffv[i] = (unsigned)(row * p.ldvt * 2 + ch * 16);
-  }
-  const char* knext = kbase;
-  const char* vnext = vbase;
-  int chunk_left = p.key_chunk > 0 ? p.key_chunk : 0x7fffffff;
-  int chunk_id = 0;
-  const unsigned wave_img = (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-  auto issue_tile = [&](int /*kt: tiles are issued in order*/, int buf) __attribute__((always_inline)) {
-    char* img = smem + buf * kBufBytes + wave_img;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(knext + voffk[i]),
-                                       (__attribute__((address_space(3))) void*)(img + i * 4096), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vnext + voffv[i]),
-                                       (__attribute__((address_space(3))) void*)(img + 8192 + i * 4096), 16, 0, 0);
-    }
-    knext += (long)KT * p.ldk * 2;
-    vnext += KT * 2;
-    chunk_left -= KT;
-    if (chunk_left == 0) {                     // tiles never straddle a chunk (key_chunk % 64 == 0)
-      ++chunk_id;
-      chunk_left = p.key_chunk;
-      knext = kbase + (long)chunk_id * p.k_cstride * 2;
-      vnext = vbase + (long)chunk_id * p.vt_cstride * 2;
-    }
-  };
-
-  // ---- per-lane LDS read offsets for buffer 0 (loop invariant; the buffer bit is XOR-toggled per tile) ----
-  // row r, chunk 2*step + hh: the K fragment of k-step `step` and (at +8192) the V^T fragment of 16-key step `step`
+  load_q(p, b, head, q0, lane, qf);
+  AttnRing<false> ring(p, b, head, tid, wave, smem);
   unsigned koff[4];
-  {
-    const int swz = (r >> 1) & 7;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) koff[ks] = (unsigned)(r * 128 + (((2 * ks + hh) ^ swz) * 16));
-  }
+  frag_offsets(r, hh, koff);
 
-  f32x16 oacc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 oacc[2] = {zero16, zero16};
   float m_run = -INFINITY;  // !PRE: running max of s*scale_log2 for query column r (identical in both halves)
   float l_run = 0.f;        // this half-wave's partial row sum
   // PRE: the scores leave their MFMA chain as s - m_ref: the chain STARTS from the accumulator negm = (-m_ref, ... 16 times) of the lane's query column
   // (round 5; the guide's "row constants as the initial accumulator").  It was a fifth k-step (a K column of ones times -m_ref): two MFMAs per tile on the
   // scores' dependency chain; the splat costs 16 registers and is rewritten only when the reference moves.
-  f32x16 negm = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 negm = zero16;
   float m_ref = 0.f;
+  auto move = [&](f32x16 (&s)[2], bool first) __attribute__((always_inline)) {       // on exact scores in s
+    move_reference(s, col_max(s), first, m_ref, l_run, oacc, [&](float m) __attribute__((always_inline)) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) negm[e] = -m;
+    });
+  };
 
   const int ntiles = (p.Lk + KT - 1) / KT;
-  const bool ragged = false;                   // the launcher sends ragged key counts to attn_fwd_kernel
-  const float c = p.scale_log2;
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-  issue_tile(0, 0);
-  if (ntiles > 1) issue_tile(1, 1);
+  ring.issue(0);
+  if (ntiles > 1) ring.issue(1);
   int buf = 0;                                 // ring buffer of the tile being computed
   unsigned bofs = 0;                           // its byte offset
 
   for (int kt = 0; kt < ntiles; ++kt) {
-    const bool has_next = kt + 1 < ntiles;
     // tile kt has landed (this thread's part; the next tile's four DMAs may stay in flight) ...
-#if !(MX_AEXP & 2)
-    if (has_next) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#if !(MX_AEXP & 4)
+    if (kt + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();              // ... for every thread, and every wave has left the buffer of tile kt - 1
-#endif
     asm volatile("" ::: "memory");
-#if !(MX_AEXP & 2)
-    if (kt + 2 < ntiles) issue_tile(kt + 2, buf == 0 ? 2 : buf - 1);   // (kt + 2) % 3
-#endif
+    if (kt + 2 < ntiles) ring.issue(buf == 0 ? 2 : buf - 1);   // (kt + 2) % 3
 
-    // ---- S^T = K Q^T : two 32-key blocks.  All eight K fragments are requested before the first MFMA and the two
-    //      accumulator chains alternate, so neither LDS latency nor the MFMA dependency sits between issues. ----
+    // All eight K fragments are requested before the first MFMA, so that no LDS latency sits between the issues.
     bf16x8 fr[8];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) fr[kb * 4 + ks] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[ks] + kb * 4096);
+    read_k(fr, smem + bofs, koff);
     __builtin_amdgcn_sched_barrier(0);
     f32x16 s[2];
-#if (MX_AEXP & 8)
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[kb][e] = __builtin_bit_cast(float, __builtin_bit_cast(u32x4, fr[kb * 4 + (e & 3)])[e & 3] << 16) + oacc[kb][e];
-#else
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[kb * 4 + ks], qf[ks], ks == 0 ? (PRE ? negm : zero16) : s[kb], 0, 0, 0);
-    }
-#endif
-    // V^T fragments (same registers): in flight while the softmax runs on the vector ALU
-#pragma unroll
-    for (int sidx = 0; sidx < 4; ++sidx)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) fr[sidx * 2 + db] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[sidx] + 8192 + db * 4096);
+    qk(s, fr, qf, PRE ? negm : zero16);
+    read_v(fr, smem + bofs, koff);             // V^T fragments (same registers): in flight while the softmax runs on the vector ALU
     __builtin_amdgcn_sched_barrier(0);
-    if (ragged && !has_next) {          // mask keys beyond Lk (tail tile only)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int key = kt * KT + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-          if (key >= p.Lk) s[kb][e] = -INFINITY;
-        }
-    }
     // ---- online softmax (log2 domain) ----
-    auto col_max = [&]() __attribute__((always_inline)) {
-      float mx_ = s[0][0];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx_ = fmaxf(mx_, s[kb][e]);
-      return max_across_halves(mx_);
-    };
-    float psum = 0.f;
     if constexpr (PRE) {
       // s already holds s*c - m_ref, m_ref a lazy reference: set from tile 0, raised only when a row runs more than 8 above it.  After
       // tile 0 the exponentials run SPECULATIVELY and the sums are watched (as in attn_fwd64_kernel): a score > 8 above the reference
       // makes its p, hence the lane's sum, exceed 256; then (rarely) the tile is redone exactly.  The row maximum leaves the hot path.
-      auto exps = [&]() __attribute__((always_inline)) {
-        float ps = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-#if (MX_AEXP & 1)
-            const float pe = s[kb][e];
-#else
-            const float pe = __builtin_amdgcn_exp2f(s[kb][e]);
-#endif
-            s[kb][e] = pe;
-            ps += pe;
-          }
-        return ps;
-      };
-      auto move_reference = [&](bool first) __attribute__((always_inline)) {       // on exact scores in s
-        const float mx_ = col_max();
-        float delta = 0.f;
-        if (first || mx_ > 8.0f) {
-          const float nr = bf16lo_to_f32(pack2(m_ref + mx_, 0.f));        // new reference, bf16-representable
-          delta = nr - m_ref;
-          m_ref = nr;
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) negm[e] = -m_ref;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) s[kb][e] -= delta;
-        if (!first) {
-          const float alpha = __builtin_amdgcn_exp2f(-delta);
-          l_run *= alpha;
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
-        }
-      };
+      float psum;
       if (kt == 0) {
-        move_reference(true);
-        psum = exps();
+        move(s, true);
+        psum = exp_sum(s);
       } else {
-        psum = exps();
+        psum = exp_sum(s);
         if (__any(psum > 256.0f)) {            // redo: scores again from the K fragments (the V^T fragments took their registers)
+          read_k(fr, smem + bofs, koff);
+          qk(s, fr, qf, negm);
+          move(s, false);
+          psum = exp_sum(s);
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fr[kb * 4 + ks] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[ks] + kb * 4096);
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-              s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[kb * 4 + ks], qf[ks], ks == 0 ? negm : s[kb], 0, 0, 0);
-          move_reference(false);
-          psum = exps();
-#pragma unroll
-          for (int sidx = 0; sidx < 4; ++sidx)
+          for (int sidx = 0; sidx < 4; ++sidx)     // (read_v written out: as a call this cold re-read costs the kernel a register, 153 -> 154)
 #pragma unroll
             for (int db = 0; db < 2; ++db) fr[sidx * 2 + db] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[sidx] + 8192 + db * 4096);
         }
       }
       l_run += psum;
     } else {
-      const float mx_ = col_max();
-      const float m_new = fmaxf(m_run, mx_ * c);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      m_run = m_new;
-      // (packed v_pk_fma_f32 / v_pk_add_f32 forms of this loop measured 0-3 % SLOWER in same-run A/B: scalar kept)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(s[kb][e] * c - m_new);
-          s[kb][e] = pe;
-          psum += pe;
-        }
-      l_run = l_run * alpha + psum;
-      if (!__all(alpha == 1.0f)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
-      }
+      softmax_running_max(s, p.scale_log2, m_run, l_run, oacc);
     }
-    // ---- O^T += V^T P^T : P fragments straight from the S^T accumulators ----
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        u32x4 pw;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pw[e] = pack2(s[kb][8 * s2 + 2 * e], s[kb][8 * s2 + 2 * e + 1]);
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
-        const int sidx = 2 * kb + s2;  // 16-key step inside the tile
-#if (MX_AEXP & 16)
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) oacc[db][(4 * sidx + e) & 15] += __builtin_bit_cast(float, pw[e] ^ __builtin_bit_cast(u32x4, fr[sidx * 2 + db])[e]);
-#else
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[sidx * 2 + db], pf, oacc[db], 0, 0, 0);
-#endif
-      }
-    }
+    pv(oacc, s, fr);
     buf = buf == 2 ? 0 : buf + 1;
     bofs = (unsigned)buf * kBufBytes;
   }
 
-  // ---- normalise and store O[q][d] ----
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
-  const int qi = q0 + r;
-  if (qi < p.Lq) {
-    bf16_t* op = p.o + ((long)b * p.Lq + qi) * p.ldo + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = db * 32 + 8 * g + 4 * hh;
-        u32x2 o = {pack2(oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv),
-                   pack2(oacc[db][4 * g + 2] * inv, oacc[db][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2*>(op + d) = o;
-      }
-  }
+  store_o(p, b, head, q0 + r, hh, l_run, oacc);
 }
 
 
 // ----------------------------------------------------------------------------------------------------------------------
-// 64 query rows per wave (round 2).  Ablation builds of attn_fwd_dma_kernel (tools/exp/build_attn_variants.sh, MX_AEXP) priced
+// 64 query rows per wave (round 2).  Ablation builds of attn_fwd_dma_kernel (MX_AEXP: tools/exp/README.md, profiles/r02_d_attention_ablation.txt) priced
 // its parts at Lk = 4096: the four LDS-DMA pieces a wave issues per tile cost 19 % of the launch (an LDS-DMA instruction holds
 // the wave's issue for 60-185 cycles, MI355X_MICROARCH.md), exp2 12 %, the S^T MFMAs 9 %, the barrier 4 %; a lone workgroup per CU
 // runs at 57 % of three, i.e. one wave's tile is a serial chain (fragment reads -> S^T -> softmax -> O^T) that other waves must cover.
@@ -715,66 +379,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
   const int b = bh / p.H;
   const int q0 = qb * 256 + wave * 64;
 
-  // ---- Q fragments of the two blocks (B operand of S^T = K Q^T): Q[q0 + 32 blk + r][16*ks + 8*hh .. +7] ----
-  bf16x8 qf[2][4];
-#pragma unroll
-  for (int blk = 0; blk < 2; ++blk) {
-    int qi = q0 + blk * 32 + r;
-    if (qi > p.Lq - 1) qi = p.Lq - 1;
-    const bf16_t* qp = p.q + ((long)b * p.Lq + qi) * p.ldq + head * 64 + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[blk][ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-  }
-
-  // ---- LDS-DMA staging, three-buffer ring, two tiles ahead (layout of attn_fwd_dma_kernel).  Addresses are a wave-uniform
-  //      base that moves with the tile plus a per-lane 32-bit offset fixed for the whole kernel: no vector work per tile. ----
-  const char* kbase = (const char*)(p.k + (long)b * p.k_bstride + head * 64);
-  const char* vbase = (const char*)(p.vt + (long)b * p.vt_bstride + ((long)head * 64) * p.ldvt);
-  // A ragged last tile (rem = Lk % 64 keys) is fetched whole: its K rows >= Lk and its all-padding V^T chunks are redirected to
-  // addresses inside the operands (row Lk - 1; chunk 0 of the V^T row), and masked after they leave LDS.
-  const int rem = p.Lk % KT;
-  unsigned voffk[2], voffv[2], toffk[2], toffv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = i * 256 + tid;
-    const int row = c >> 3, ch = (c & 7) ^ ((row >> 1) & 7);
-    voffk[i] = (unsigned)(row * p.ldk * 2 + ch * 16);
-    voffv[i] = (unsigned)(row * p.ldvt * 2 + ch * 16);
-    toffk[i] = (unsigned)((row < rem ? row : rem - 1) * p.ldk * 2 + ch * 16);
-    toffv[i] = (unsigned)(row * p.ldvt * 2 + ((ch >> 1) * 16 < rem ? ch * 16 : 0));    // chunk ch = positions 8 ch ..: 16-key group ch >> 1
-  }
-  // the next tile to issue: uniform pointers advanced per tile (a chunk boundary of the patch-parallel layout jumps them)
-  const char* knext = kbase;
-  const char* vnext = vbase;
-  int chunk_left = p.key_chunk > 0 ? p.key_chunk : 0x7fffffff;
-  int chunk_id = 0;
-  const unsigned wave_img = (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-  auto issue_tile = [&](int buf, bool tail) __attribute__((always_inline)) {
-    char* img = smem + buf * kBufBytes + wave_img;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(knext + (tail ? toffk[i] : voffk[i])),
-                                       (__attribute__((address_space(3))) void*)(img + i * 4096), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vnext + (tail ? toffv[i] : voffv[i])),
-                                       (__attribute__((address_space(3))) void*)(img + 8192 + i * 4096), 16, 0, 0);
-    }
-    knext += (long)KT * p.ldk * 2;
-    vnext += KT * 2;
-    chunk_left -= KT;
-    if (chunk_left == 0) {                     // tiles never straddle a chunk (key_chunk % 64 == 0)
-      ++chunk_id;
-      chunk_left = p.key_chunk;
-      knext = kbase + (long)chunk_id * p.k_cstride * 2;
-      vnext = vbase + (long)chunk_id * p.vt_cstride * 2;
-    }
-  };
-
-  unsigned koff[4];                            // per-lane LDS read offsets inside a buffer (see attn_fwd_kernel)
-  {
-    const int swz = (r >> 1) & 7;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) koff[ks] = (unsigned)(r * 128 + (((2 * ks + hh) ^ swz) * 16));
-  }
+  bf16x8 qf[2][4];                             // the two 32-query blocks
+  load_q(p, b, head, q0, lane, qf[0]);
+  load_q(p, b, head, q0 + 32, lane, qf[1]);
+  const int rem = p.Lk % KT;                   // keys of a ragged last tile
+  AttnRing<true> ring(p, b, head, tid, wave, smem, rem);
+  unsigned koff[4];
+  frag_offsets(r, hh, koff);
 
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   f32x16 oacc[2][2] = {{zero16, zero16}, {zero16, zero16}};
@@ -783,8 +394,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
   // Block 1: the reference k-step (A operand = a K column of ones, B operand = -m_ref of query column r, bf16-representable): a splat for both blocks does not
   // fit the 256 registers of two waves per SIMD (measured with 11 spills: 332 -> 381 us at Lk 4096).
   f32x16 negm0 = zero16;
-  const unsigned one_lo = hh == 0 ? 0x3F80u : 0u;
-  const bf16x8 kone = __builtin_bit_cast(bf16x8, u32x4{one_lo, 0u, 0u, 0u});
+  const bf16x8 kone = ref_step_ones(hh);
   u32x4 qm1 = {0u, 0u, 0u, 0u};
   float m_ref[2] = {0.f, 0.f};
   auto set_ref = [&](int blk) __attribute__((always_inline)) {
@@ -792,23 +402,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
 #pragma unroll
       for (int e = 0; e < 16; ++e) negm0[e] = -m_ref[0];
     } else {
-      qm1[0] = hh == 0 ? (pack2(-m_ref[1], 0.f) & 0xffffu) : 0u;
+      qm1[0] = ref_step_word(m_ref[1], hh);
     }
   };
 
   const int ntiles = (p.Lk + KT - 1) / KT;     // >= 3 (launcher)
 
-  auto read_k = [&](bf16x8 (&fr)[8], unsigned bofs) __attribute__((always_inline)) {
+  auto col_max = [&](const f32x16 (&s)[2]) __attribute__((always_inline)) {      // (pairwise, not attn_tile.h's chain: the same value; HISTORY.md)
+    float mx_ = fmaxf(s[0][0], s[1][0]);
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) fr[kb * 4 + ks] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[ks] + kb * 4096);
-  };
-  auto read_v = [&](bf16x8 (&fr)[8], unsigned bofs) __attribute__((always_inline)) {
-#pragma unroll
-    for (int sidx = 0; sidx < 4; ++sidx)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) fr[sidx * 2 + db] = *reinterpret_cast<const bf16x8*>(smem + bofs + koff[sidx] + 8192 + db * 4096);
+    for (int e = 1; e < 16; ++e) mx_ = fmaxf(mx_, fmaxf(s[0][e], s[1][e]));
+    return max_across_halves(mx_);
   };
   auto mask_scores = [&](f32x16 (&s)[2]) __attribute__((always_inline)) {        // ragged last tile: keys >= Lk never count
 #pragma unroll
@@ -832,23 +436,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
         fr[sidx * 2 + db] = __builtin_bit_cast(bf16x8, w);
       }
   };
-  auto qk = [&](f32x16 (&s)[2], const bf16x8 (&fr)[8], int blk) __attribute__((always_inline)) {   // s = (K Q^T) - m_ref
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[kb * 4 + ks], qf[blk][ks], ks == 0 ? (blk == 0 ? negm0 : zero16) : s[kb], 0, 0, 0);
-    if (blk != 0) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kone, __builtin_bit_cast(bf16x8, qm1), s[kb], 0, 0, 0);
-    }
-  };
-  auto col_max = [&](const f32x16 (&s)[2]) __attribute__((always_inline)) {
-    float mx_ = fmaxf(s[0][0], s[1][0]);
-#pragma unroll
-    for (int e = 1; e < 16; ++e) mx_ = fmaxf(mx_, fmaxf(s[0][e], s[1][e]));
-    return max_across_halves(mx_);
+  auto scores = [&](f32x16 (&s)[2], const bf16x8 (&fr)[8], int blk) __attribute__((always_inline)) {   // s = (K Q^T) - m_ref
+    qk(s, fr, qf[blk], blk == 0 ? negm0 : zero16);
+    if (blk != 0) ref_step(s, kone, qm1);
   };
   // p = exp2(s) in place, packed to the four B fragments of O^T += V^T P^T; returns this half-wave's sum
   auto exp_pack = [&](f32x16 (&s)[2], u32x4 (&pw)[4]) __attribute__((always_inline)) {
@@ -871,42 +461,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
   // Then (rarely) this path redoes the block exactly: scores again from the K fragments, reference raised to the new maximum, p,
   // and O / l rescaled.  No false negatives; a false positive (32 scores averaging > 3 above the reference) costs time only.
   auto redo = [&](f32x16 (&s)[2], u32x4 (&pw)[4], const bf16x8 (&fr)[8], int blk, const bool tail) __attribute__((always_inline)) {
-    qk(s, fr, blk);
+    scores(s, fr, blk);
     if (tail) mask_scores(s);
-    const float mx_ = col_max(s);
-    float delta = 0.f;
-    if (mx_ > 8.0f) {
-      const float nr = bf16lo_to_f32(pack2(m_ref[blk] + mx_, 0.f));          // new reference (rounded to bf16, as the former k-step form needed it: same values)
-      delta = nr - m_ref[blk];
-      m_ref[blk] = nr;
-    }
-    set_ref(blk);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[kb][e] -= delta;
-    const float alpha = __builtin_amdgcn_exp2f(-delta);
-    l_run[blk] *= alpha;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) oacc[blk][i][e] *= alpha;
+    move_reference(s, col_max(s), false, m_ref[blk], l_run[blk], oacc[blk], [&](float) __attribute__((always_inline)) { set_ref(blk); });
     return exp_pack(s, pw);
   };
 
-  issue_tile(0, false);
-  issue_tile(1, false);
+  ring.issue(0);
+  ring.issue(1);
   // ---- the reference starts at the maximum of tile 0 (a whole tile; its scores are computed again by the loop) ----
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   {
     bf16x8 fr[8];
-    read_k(fr, 0);
+    read_k(fr, smem, koff);
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
       f32x16 s[2];
-      qk(s, fr, blk);
+      scores(s, fr, blk);
       m_ref[blk] = bf16lo_to_f32(pack2(col_max(s), 0.f));
       set_ref(blk);
     }
@@ -919,11 +492,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
     bf16x8 fr[8];
     f32x16 s0[2], s1[2];
     u32x4 pw0[4], pw1[4];
-    read_k(fr, bofs);
-    qk(s0, fr, 0);                             // S^T of block 0
+    read_k(fr, smem + bofs, koff);
+    scores(s0, fr, 0);                           // S^T of block 0
     if (TAIL) mask_scores(s0);
     __builtin_amdgcn_sched_barrier(0);
-    qk(s1, fr, 1);                             // S^T of block 1 beside the exponentials of block 0
+    scores(s1, fr, 1);                           // S^T of block 1 beside the exponentials of block 0
     float ps = exp_pack(s0, pw0);
     __builtin_amdgcn_sched_barrier(0);
     if (TAIL) mask_scores(s1);
@@ -931,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
       ps = redo(s0, pw0, fr, 0, TAIL);
     }
     l_run[0] += ps;
-    read_v(fr, bofs);                          // V^T fragments (the K fragments are dead: same registers)
+    read_v(fr, smem + bofs, koff);                          // V^T fragments (the K fragments are dead: same registers)
     if (TAIL) mask_v(fr);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -942,9 +515,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
     ps = exp_pack(s1, pw1);
     __builtin_amdgcn_sched_barrier(0);
     if (__any(ps > 256.0f)) {
-      read_k(fr, bofs);
+      read_k(fr, smem + bofs, koff);
       ps = redo(s1, pw1, fr, 1, TAIL);
-      read_v(fr, bofs);
+      read_v(fr, smem + bofs, koff);
       if (TAIL) mask_v(fr);
     }
     l_run[1] += ps;
@@ -962,7 +535,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnGroup ga) 
       __builtin_amdgcn_s_barrier();            // tile kt has landed for every thread; every wave has left the buffer of tile kt - 1
       asm volatile("" ::: "memory");
     }
-    if (kt + 2 < ntiles) issue_tile(buf == 0 ? 2 : buf - 1, rem && kt + 3 == ntiles);   // tile kt + 2 into buffer (kt + 2) % 3
+    if (kt + 2 < ntiles) ring.issue(buf == 0 ? 2 : buf - 1, rem && kt + 3 == ntiles);   // tile kt + 2 into buffer (kt + 2) % 3
     tile(false);
     buf = buf == 2 ? 0 : buf + 1;
     bofs = (unsigned)buf * kBufBytes;
@@ -1098,8 +671,8 @@ static const char* const kAttnKernelNames[AK_COUNT] = {MX_ATTN_FORMS(MX_ATTN_NAM
 
 // The instantiation a launch over ga.n problems (ga.g filled) runs.  The kernel is chosen for the launch as a whole -- by its longest query
 // sequence -- and must be able to serve every problem; otherwise the general register-staged kernel takes them all.  -1: force_cross, and the
-// short-key kernel cannot serve the problems.
-static int attention_kernel_of(const mx::AttnGroup& ga, bool pre, bool force_cross) {
+// short-key kernel cannot serve the problems.  max_lq / any_extra: what the pass over the problems found, for the launcher.
+static int attention_kernel_of(const mx::AttnGroup& ga, bool pre, bool force_cross, int* max_lq = nullptr, bool* any_extra = nullptr) {
   using namespace mx;
   const int n = ga.n;
   int maxLq = 0;
@@ -1117,6 +690,8 @@ static int attention_kernel_of(const mx::AttnGroup& ga, bool pre, bool force_cro
     extra = extra || a.causal || a.bias;
     all77 = all77 && a.Lk == 77;
   }
+  if (max_lq) *max_lq = maxLq;
+  if (any_extra) *any_extra = extra;
   // (at Lq 1024 the general kernel is 7 % faster than the short-key one: both are latency-bound)
   if (force_cross && !(all_short && plain && o8)) return -1;
   if (all_short && (maxLq >= 2048 || force_cross || (all77 && pre)) && plain && o8)      // short key sequence: every wave keeps K / V^T in registers
@@ -1131,18 +706,16 @@ static int attention_kernel_of(const mx::AttnGroup& ga, bool pre, bool force_cro
 static int launch_attention_group(void* stream, mx::AttnGroup& ga, bool pre, bool force_cross = false) {
   using namespace mx;
   const int n = ga.n;
-  int maxLq = 0;
   double flops = 0, bytes = 0;
-  bool extra = false;
   for (int i = 0; i < n; ++i) {
     const AttnArgs& a = ga.g[i];
-    maxLq = std::max(maxLq, a.Lq);
-    extra = extra || a.causal || a.bias;
     flops += 4.0 * a.B * a.H * (double)a.Lq * a.Lk * 64.0;
     bytes += 2.0 * a.B * a.H * 64.0 * (2.0 * a.Lq + 2.0 * a.Lk);
   }
+  int maxLq;
+  bool extra;
+  const int form = attention_kernel_of(ga, pre, force_cross, &maxLq, &extra);
   MX_CHECK(!extra || n == 1, "attention: the causal / bias forms are not grouped");
-  const int form = attention_kernel_of(ga, pre, force_cross);
   MX_CHECK(form >= 0, "attention: the short-key kernel needs Lk <= 96, no mask / bias / key chunks and ldo % 8 == 0");
   const bool cross = form == AK_CROSS_PRE77 || form == AK_CROSS_PRE || form == AK_CROSS;
   const int rows = form == AK_W64 ? 256 : 128;

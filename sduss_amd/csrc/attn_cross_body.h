@@ -3,45 +3,15 @@
 #pragma once
 #include "common.h"
 #include "../../include/mxdenoise.h"
+#include "attn_tile.h"
 
 namespace mx {
-
-struct AttnArgs {
-  const bf16_t* q; const bf16_t* k; const bf16_t* vt; bf16_t* o;
-  int ldq, ldk, ldvt, ldo;
-  long vt_bstride;
-  int B, H, Lq, Lk;
-  float scale_log2;  // scale * log2(e)
-  int xcd_map;       // 1: XCD-aware workgroup order (needs B*H % 8 == 0)
-  // patch-parallel K / V^T (mx_attention_prescaled_chunked): keys come in `key_chunk`-long chunks gathered from the ranks;
-  // chunk c of batch b starts at k + c * k_cstride + b * k_bstride (rows of ldk) and vt + c * vt_cstride + b * vt_bstride
-  int key_chunk;     // 0: one contiguous key range per batch
-  long k_bstride, k_cstride, vt_cstride;
-  int causal;        // 1: key j counts for query i only when j <= i (text encoders; attn_fwd_kernel only)
-  const float* bias; // additive score bias [H][Lq][ldb], already in the kernel's log2 domain (T5 relative position bias; attn_fwd_kernel only)
-  int ldb;
-  int xq_wpb;        // short-key kernel: waves that share the 32-query blocks of one (batch, head) (launch_attention_group deals them so that the launch is ONE round)
-};
-
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {   // one v_cvt_pk_bf16_f32
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-}
-
-// max over the two half-waves (lane l and l^32) without the LDS crossbar: v_permlane32_swap exchanges the upper half
-// of a with the lower half of b.  Inline asm because the builtin folds its two results when both inputs are one value.
-__device__ __forceinline__ float max_across_halves(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return fmaxf(a, b);
-}
 
 constexpr int XK_MAXBLK = 3;                   // 32-key blocks (Lk <= 96)
 constexpr int XK_QPW = 64;                     // queries per wave (two 32-query blocks)
 
-// ---- the pieces: one fragment of the head's K / V^T (global -> register, masked), the queries of a 32-query block, one block's arithmetic.  The kernel's
-//      wave keeps the 24 fragments in registers (attn_cross_wave). ----
+// ---- the pieces: one fragment of the head's K / V^T (global -> register, masked), one block's arithmetic (the queries of a 32-query block: load_q,
+//      attn_tile.h).  The kernel's wave keeps the 24 fragments in registers (attn_cross_wave). ----
 constexpr int XK_KFRAGS = XK_MAXBLK * 4;       // K fragments of a head: [32-key block][16-feature step]
 constexpr int XK_VFRAGS = 2 * XK_MAXBLK * 2;   // V^T fragments: [16-key step][32-feature half]
 
@@ -82,16 +52,6 @@ __device__ __forceinline__ bf16x8 xk_vfrag(const AttnArgs& p, const int b, const
   }
   return __builtin_bit_cast(bf16x8, v);
 }
-// the lane's part of the queries q0 .. q0 + 31 of (b, head): B operand of S^T
-__device__ __forceinline__ void xk_load_q(const AttnArgs& p, const int b, const int head, const int q0, const int lane, bf16x8 (&qf)[4]) {
-  const int r = lane & 31, hh = lane >> 5;
-  int qi = q0 + r;
-  if (qi > p.Lq - 1) qi = p.Lq - 1;
-  const bf16_t* qp = p.q + ((long)b * p.Lq + qi) * p.ldq + head * 64 + hh * 8;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-}
-
 // One 32-query block: S^T = K Q^T, single-pass softmax, O^T = V^T P^T, O through the wave's 4-KB LDS patch as whole rows.  kf(kb, ks) / vf(st, db) hand out
 // the fragments.
 template <bool PRE, int LK = 0, class KF, class VF>
@@ -192,11 +152,11 @@ __device__ __forceinline__ void attn_cross_wave(const AttnArgs& p, const int b, 
 #pragma unroll
     for (int db = 0; db < 2; ++db) vf[st][db] = xk_vfrag<LK>(p, b, head, st, db, lane);
   bf16x8 qf[4], qn[4];
-  xk_load_q(p, b, head, q_wave0, lane, qf);
+  load_q(p, b, head, q_wave0, lane, qf);
   for (int blk = 0; blk < nblocks; ++blk) {
     const int q0 = q_wave0 + blk * 32;
     if (q0 >= p.Lq) break;                     // wave-uniform
-    if (blk + 1 < nblocks) xk_load_q(p, b, head, q0 + 32, lane, qn);
+    if (blk + 1 < nblocks) load_q(p, b, head, q0 + 32, lane, qn);
     xk_block<PRE, LK>(p, b, head, q0, qf, [&](int kb, int ks) __attribute__((always_inline)) { return kf[kb][ks]; },
                          [&](int st, int db) __attribute__((always_inline)) { return vf[st][db]; }, patch, lane);
 #pragma unroll

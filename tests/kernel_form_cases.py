@@ -171,6 +171,9 @@ ATTN_CASES = [
     attn("chunked_4", "attn_fwd_dma_kernel<true>", 1, 3, 65, 256, chunks=4),
     attn("chunked_8", "attn_fwd_dma_kernel<true>", 1, 2, 33, 512, chunks=8),
     attn("bias_lk77", "attn_fwd_kernel<true, true>", 1, 2, 77, 77, bias=True),
+    # key chunks off the LDS-DMA kernel: two whole tiles are fewer than its three (the register-staged kernel's chunk branch), and the 64-row kernel's ring
+    attn("chunked_gen_lk128", "attn_fwd_kernel<true>", 2, 2, 65, 128, chunks=2),
+    attn("w64_chunked_2", "attn_fwd64_kernel", 1, 2, 2048, 256, chunks=2),
 ]
 ATTN_NOT_COVERED = {"attn_fwd_kernel<false, true>"}      # (no entry point runs a non-prescaled masked / biased launch)
 

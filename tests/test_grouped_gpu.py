@@ -186,6 +186,11 @@ def test_grouped_geglu_and_ln_fold_256x256(cuda_device):
         assert torch.equal(out[i], ops.gemm(Ag[i], wg, bg, geglu=True)), f"GEGLU problem {i}: grouped != separate"
 
 
+# ([(batch, tokens) of every problem], the key count of all problems or None: self-attention)
+GROUPED_ATTN_SPECS = (([(2, 256), (1, 576), (3, 1024)], None), ([(1, 1024), (1, 2304), (2, 4096)], None), ([(2, 256), (1, 576), (2, 1024)], 77),
+                      ([(1, 1024), (1, 2304), (1, 4096)], 77))
+
+
 def test_grouped_attention(cuda_device):
     """self-attention of three resolutions in one launch (tokens 256 / 576 / 1024 per image -> the LDS-DMA kernel; with 4096 the 64-row
     kernel serves all) and the 77-key cross-attention, against softmax(q k^T / 8) v and against separate launches"""
@@ -193,8 +198,7 @@ def test_grouped_attention(cuda_device):
     l = lib.load()
     heads = 5
     c = heads * 64
-    for spec, lk_fixed in (([(2, 256), (1, 576), (3, 1024)], None), ([(1, 1024), (1, 2304), (2, 4096)], None), ([(2, 256), (1, 576), (2, 1024)], 77),
-                           ([(1, 1024), (1, 2304), (1, 4096)], 77)):
+    for spec, lk_fixed in GROUPED_ATTN_SPECS:
         g = torch.Generator().manual_seed(sum(b * L for b, L in spec) + (lk_fixed or 0))
         probs = (lib.AttnProblem * len(spec))()
         keep, want, outs = [], [], []

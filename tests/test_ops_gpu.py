@@ -470,6 +470,29 @@ def test_attention_prescaled_reference_moves(cuda_device, case, l):
     _prescaled_case(_rt(q), _rt(k), v, 1, f"attention prescaled {case}")
 
 
+# (Lq, Lk, the kernel, ((query row, key, factor), ...)): the reference moves at a ragged key count.  Register-staged kernel: in tile 2 and in the ragged tile 3.
+# 64-row kernel: a row of block 0 (5) and a row of block 1 (40) -- the redo with the tail's score mask and the masked V^T re-read, in both blocks (row 40 is raised
+# in tile 2 and again, further, in the ragged tile).  The V^T pad is NaN (pack_vt(pad=nan) in _prescaled_case).
+RAGGED_MOVES = [(64, 200, "attn_fwd_kernel<true>", ((5, 130, 4.0), (40, 195, 4.0))),
+                (2048, 200, "attn_fwd64_kernel", ((5, 195, 4.0), (40, 130, 4.0), (40, 196, 6.0)))]
+
+
+def ragged_moves_inputs(lq, lk, spikes):
+    g = torch.Generator().manual_seed(17 + lq + lk)
+    q = _rt(torch.randn(1, lq, 64, generator=g)); k = _rt(torch.randn(1, lk, 64, generator=g)); v = _rt(torch.randn(1, lk, 64, generator=g))
+    for row, key, f in spikes:
+        k[0, key] = q[0, row] * f
+    return q, _rt(k), v
+
+
+@pytest.mark.parametrize("lq,lk,kernel,spikes", RAGGED_MOVES, ids=lambda p: str(p) if isinstance(p, (int, str)) else "spikes")
+def test_attention_prescaled_reference_moves_ragged(cuda_device, lq, lk, kernel, spikes):
+    from sduss_amd import lib
+    assert lib.attention_kernel_of(1, 1, lq, lk, 64) == kernel
+    q, k, v = ragged_moves_inputs(lq, lk, spikes)
+    _prescaled_case(q, k, v, 1, f"attention prescaled, ragged {lq}x{lk}, reference moves")
+
+
 def test_gemm_out_scale(cuda_device):
     from sduss_amd import ops
     g = torch.Generator().manual_seed(91)
