@@ -965,6 +965,50 @@ int mx_cfg_multistep_step(void* stream, const void* noise_pred, void* latents, c
 int mx_sampler_coeffs(int sampler, int flow, const float* sigmas, int n_steps, float* out);
 
 /* ------------------------------------------------------------------------------------------
+ * Seeded requests and stochastic samplers (sduss_amd/csrc/noise.h, noise.hip, scheduler_step.hip, sampler_coeffs.cpp).  A request's noise is a pure
+ * function of (seed, purpose, step, element index within the request): Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53,
+ * 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key = (seed low, seed high), counter = (q low, q high, step, domain) with q = idx >> 2 and idx
+ * the element's index in the request's OWN [C, h, w] tensor -- never the batch's; element idx takes normal idx & 3 of its group.  From the output
+ * words (w0, w1, w2, w3):  u = (2 (w0 >> 9) + 1) 2^-24 in (0, 1),  t2 = (2 (w1 >> 9) + 1) 2^-23 in (0, 2),  r = sqrtf(-2 logf(u)),
+ * z0 = r cospif(t2),  z1 = r sinpif(t2);  (w2, w3) give (z2, z3) the same way.  The image of a seeded request therefore does not depend on its row
+ * in a batch or on who it is batched with, and a rewound request (step index reset) reproduces itself.
+ * ------------------------------------------------------------------------------------------ */
+enum { MX_NOISE_INIT = 0, MX_NOISE_START = 1, MX_NOISE_STEP = 2, MX_NOISE_POSTERIOR = 3 };   /* the domain: what the noise is for */
+/* out [n][elems] of `dtype` = scale[r] * z(seed[r], step[r], domain, i): one fp32 multiply, rounded once to `dtype` at the store (scale NULL: 1).
+ * seed device uint64 [n], step device uint32 [n], scale device fp32 [n] or NULL.  raw = 1: out is uint32 [n][elems] and holds the Philox words
+ * themselves (word idx & 3 of group idx >> 2; dtype and scale ignored), so that the integer half can be held bit for bit.  16-byte stores where out
+ * is 16-byte aligned and elems a whole number of vectors, element stores otherwise; offsets are 64-bit.  Refused: a null out, seed or step, a
+ * non-positive size, a negative domain, a bad dtype, raw other than 0 / 1. */
+int mx_noise_fill(void* stream, void* out, int dtype, int n, int64_t elems, const uint64_t* seed, const uint32_t* step, int domain,
+                  const float* scale, int raw);
+/* The noise rows of one stochastic step launch.  Everything lives in device memory. */
+typedef struct {
+  const float*    cn;     /* device fp32 [n_lat]: the noise coefficient of this step; 0 = no noise for the row */
+  const uint64_t* seed;   /* device [n_lat]: the request's seed (read where cn != 0 on a kind-1 / kind-2 row only) */
+  const uint32_t* step;   /* device [n_lat]: the request's step index, the counter's step word (read like seed) */
+} mx_noise_rows;
+/* mx_cfg_multistep_step with noise: a kind-1 or kind-2 row with cn[r] != 0 takes, behind acc of the multistep update, acc = acc + (cn * z), both
+ * operations rounded on their own, z = the noise function at domain MX_NOISE_STEP and idx = the element's index in its row -- made in registers, no
+ * noise tensor exists.  A row with cn == 0 and every kind-0 row read neither seed nor step, run no generator and leave the bits of
+ * mx_cfg_multistep_step; the put-back of inpainting rows follows as there.  A 16-byte vector of 8 sixteen-bit elements is two Philox calls, one of 4
+ * fp32 elements is one, the element path makes one per element.  nz NULL: mx_cfg_multistep_step itself.  Refused, with nothing launched: everything
+ * mx_cfg_multistep_step refuses, and a non-null nz with a null member. */
+int mx_cfg_stochastic_step(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                           int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms, const mx_inpaint_rows* inpaint,
+                           const mx_noise_rows* nz);
+/* The stochastic samplers' coefficients on the host: both step as kind-1 rows (D = x - sigma m) of mx_cfg_stochastic_step. */
+enum { MX_SAMPLER_EULER_A = 3, MX_SAMPLER_DPMPP_2M_SDE = 4 };
+/* mx_sampler_coeffs with a fifth column: out [n_steps][5] = (cx, c0 first order, c0 second order, c1 second order, cn); double arithmetic, each
+ * rounded to float once.  sampler: any of mx_sampler_coeffs' (cn = 0; eta is not used) or
+ * MX_SAMPLER_EULER_A (k-diffusion's sample_euler_ancestral): su = min(sn, eta sqrt(sn^2 (s^2 - sn^2) / s^2)), sd = sqrt(sn^2 - su^2); cx = sd / s,
+ *   c0 = 1 - sd / s (both orders), c1 = 0, cn = su.
+ * MX_SAMPLER_DPMPP_2M_SDE (sample_dpmpp_2m_sde, midpoint): h as for MX_SAMPLER_DPMPP_2M, E = -expm1(-h - eta h), cx = (sn / s) exp(-eta h); first
+ *   order c0 = E; second order c0 = E (1 + 1 / (2 r)), c1 = -E / (2 r); cn = sn sqrt(-expm1(-2 eta h)).  The code is MX_SAMPLER_DPMPP_2M's: at
+ *   eta = 0 the first four columns are that sampler's bits and cn = 0.
+ * Both: sn == 0 gives (0, 1, 1, 0, 0).  Refused: what mx_sampler_coeffs refuses, eta < 0 (or NaN), and flow = 1 for the two stochastic samplers. */
+int mx_sampler_coeffs_eta(int sampler, int flow, const float* sigmas, int n_steps, double eta, float* out);
+
+/* ------------------------------------------------------------------------------------------
  * Resize of a client's 8-bit image or mask to the request's resolution (sduss_amd/csrc/image_resize.hip, resize_coeffs.cpp), bit-equal to
  * Pillow's Image.resize for modes "RGB" and "L" -- what diffusers' VaeImageProcessor.preprocess does in front of the VAE, and its mask
  * processor in front of the binarisation.  Pillow's 8-bit resampler (ImagingResample) is integer arithmetic on integer coefficient tables:

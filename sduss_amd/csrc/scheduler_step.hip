@@ -3,8 +3,11 @@
 //   GATHERED  the prediction is read where the world gather of the split-batch patch parallelism left it (patch_parallel.py)
 //   MULTI     per-row sampler kind, coefficients and an fp32 history: DPM-Solver++ 2M and AB2 beside the model's own Euler step (sampler_coeffs.cpp)
 //   MASKED    the kept region of inpainting rows put back as the image's own latents re-noised to the step's next sigma (inpaint.hip)
-// A form without a feature holds none of its code and reads none of its operands.  Instantiated: plain, GATHERED, MASKED, MULTI + MASKED; each for both
-// models' steps (FLOW) and three io dtypes.  HBM-bound passes: 16-byte accesses where the layout allows, element accesses otherwise.
+//   NOISY     per-row noise cn z behind the multistep update, z made in registers by the request's own generator (noise.h): Euler ancestral and
+//             DPM-Solver++ 2M SDE rows (sampler_coeffs.cpp)
+// A form without a feature holds none of its code and reads none of its operands.  Instantiated: plain, GATHERED, MASKED, MULTI + MASKED,
+// MULTI + MASKED + NOISY; each for both models' steps (FLOW) and three io dtypes.  HBM-bound passes: 16-byte accesses where the layout allows, element
+// accesses otherwise.
 // The plain form is always launched element-wise: its latency sits at the launch floor either way (profiles/sampler_step.txt) and it ends every step.
 #include "common.h"
 #include "../../include/mxdenoise.h"
@@ -13,6 +16,7 @@
 // are plain operators in inlined headers and do get contracted; so plain operators, plus -ffp-contract=off for this file in the Makefile).
 #pragma clang fp contract(off)
 #include "step_math.h"
+#include "noise.h"
 
 namespace mx {
 
@@ -24,12 +28,14 @@ struct step_args {
   int C, S;                                              // GATHERED: pred [2 S][n_lat][C][run], slot k < S the unconditional, S + k the conditional prediction of rows [k H / S, (k + 1) H / S)
   const int* kind; const float* coef; float* hist;       // MULTI: mx_multistep_rows
   int k; const int* slot; const void* init; const void* noise; const unsigned char* mask;   // MASKED: mx_inpaint_rows
+  const float* cn; const unsigned long long* seed; const unsigned* nstep;                   // NOISY: mx_noise_rows
 };
 
 // A multistep row: x_next = cx x + c0 D + c1 hist, hist <- D, with D = x - sigma m (DPM-Solver++ 2M) or D = m (AB2).  The V fp32 history values of a
-// 16-bit vector are V / 4 accesses of 16 bytes.
+// 16-bit vector are V / 4 accesses of 16 bytes.  cn != 0 (NOISY rows only): + cn z behind the update.
 template <typename T, int V>
-__device__ __forceinline__ void multistep_elems(elem_vec<T, V>& x, const float (&m)[V], float s, int kd, const float* coef, float* hist) {
+__device__ __forceinline__ void multistep_elems(elem_vec<T, V>& x, const float (&m)[V], float s, int kd, const float* coef, float* hist, float cn,
+                                                const float (&z)[V]) {
   constexpr int HV = V < 4 ? V : 4;                      // fp32 history values per access: 16 bytes on the vector path
   typedef elem_vec<float, HV> hvec;
   const float cx = coef[0], c0 = coef[1], c1 = coef[2];
@@ -46,7 +52,8 @@ __device__ __forceinline__ void multistep_elems(elem_vec<T, V>& x, const float (
   for (int i = 0; i < V; ++i) {
     const float xi = load_as_f32<T>(x.v, i);
     d[i] = kd == MX_SAMPLER_DPMPP_2M ? multistep_data(xi, m[i], s) : m[i];
-    store_from_f32<T>(x.v, i, c1 != 0.0f ? multistep_update2(xi, d[i], h[i], cx, c0, c1) : multistep_update1(xi, d[i], cx, c0));
+    const float acc = c1 != 0.0f ? multistep_update2(xi, d[i], h[i], cx, c0, c1) : multistep_update1(xi, d[i], cx, c0);
+    store_from_f32<T>(x.v, i, cn != 0.0f ? noisy_update(acc, cn, z[i]) : acc);
   }
 #pragma unroll
   for (int q = 0; q < V / HV; ++q) {
@@ -82,7 +89,7 @@ __device__ __forceinline__ void put_back_kept(elem_vec<T, V>& x, const step_args
 
 // One thread per V elements of the latents.  On the vector path `run` is a whole number of vectors and every base is aligned, so a vector lies inside
 // one run of every tensor.
-template <typename T, int V, bool FLOW, bool GATHERED, bool MULTI, bool MASKED>
+template <typename T, int V, bool FLOW, bool GATHERED, bool MULTI, bool MASKED, bool NOISY>
 __global__ void cfg_step_kernel(const step_args a) {
   const long e0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
   const long total = (long)a.n_lat * a.elems;
@@ -102,7 +109,12 @@ __global__ void cfg_step_kernel(const step_args a) {
   int kd = MX_SAMPLER_EULER;
   if constexpr (MULTI) kd = a.kind[row];
   if (MULTI && (kd == MX_SAMPLER_DPMPP_2M || kd == MX_SAMPLER_AB2)) {
-    multistep_elems<T, V>(x, p, s, kd, a.coef + 3 * (long)row, a.hist + e0);
+    float cn = 0.0f, z[V] = {};
+    if constexpr (NOISY) {                               // a row without noise reads neither its seed nor its step and runs no generator
+      cn = a.cn[row];
+      if (cn != 0.0f) noise_elems<V>(a.seed[row], a.nstep[row], MX_NOISE_STEP, e0 - (long)row * a.elems, z);
+    }
+    multistep_elems<T, V>(x, p, s, kd, a.coef + 3 * (long)row, a.hist + e0, cn, z);
   } else {                                               // the model's own step; every unknown kind too.  hist is left alone
 #pragma unroll
     for (int i = 0; i < V; ++i) {
@@ -116,7 +128,7 @@ __global__ void cfg_step_kernel(const step_args a) {
 
 // The one launcher: the 16-byte path when every base and run allows it (the null pointers of absent features count as aligned), one thread per element
 // otherwise -- and for the plain form always.
-template <bool GATHERED, bool MULTI, bool MASKED>
+template <bool GATHERED, bool MULTI, bool MASKED, bool NOISY = false>
 static int launch_cfg_step(const char* what, void* stream, int dtype, bool flow, const step_args& a) {
   return with_io_dtype(dtype, what, [&](auto tag) {
     typedef decltype(tag) T;
@@ -128,10 +140,10 @@ static int launch_cfg_step(const char* what, void* stream, int dtype, bool flow,
     MX_CHECK(blocks <= 0x7fffffffL, std::string(what) + ": too many elements for one launch");
     const dim3 grid((unsigned)blocks), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (vec && flow) hipLaunchKernelGGL((cfg_step_kernel<T, V, true, GATHERED, MULTI, MASKED>), grid, block, 0, s, a);
-    else if (vec) hipLaunchKernelGGL((cfg_step_kernel<T, V, false, GATHERED, MULTI, MASKED>), grid, block, 0, s, a);
-    else if (flow) hipLaunchKernelGGL((cfg_step_kernel<T, 1, true, GATHERED, MULTI, MASKED>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((cfg_step_kernel<T, 1, false, GATHERED, MULTI, MASKED>), grid, block, 0, s, a);
+    if (vec && flow) hipLaunchKernelGGL((cfg_step_kernel<T, V, true, GATHERED, MULTI, MASKED, NOISY>), grid, block, 0, s, a);
+    else if (vec) hipLaunchKernelGGL((cfg_step_kernel<T, V, false, GATHERED, MULTI, MASKED, NOISY>), grid, block, 0, s, a);
+    else if (flow) hipLaunchKernelGGL((cfg_step_kernel<T, 1, true, GATHERED, MULTI, MASKED, NOISY>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((cfg_step_kernel<T, 1, false, GATHERED, MULTI, MASKED, NOISY>), grid, block, 0, s, a);
     MX_LAUNCH_CHECK();
     return 0;
   });
@@ -209,20 +221,40 @@ extern "C" int mx_cfg_flow_step_masked(void* stream, const void* noise_pred, voi
   return mx::cfg_step_masked(true, stream, noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype, rows);
 }
 
-extern "C" int mx_cfg_multistep_step(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
-                                     int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms, const mx_inpaint_rows* inpaint) {
-  MX_CHECK(noise_pred && latents && sigma && sigma_next && ms, "cfg_multistep_step: null operand");
-  MX_CHECK(ms->kind && ms->coef && ms->hist, "cfg_multistep_step: null kind, coef or hist");
-  MX_CHECK(n_lat > 0 && C > 0 && hw > 0, "cfg_multistep_step: sizes must be positive");
-  MX_CHECK(dtype == MX_F32 || dtype == MX_F16 || dtype == MX_BF16, "cfg_multistep_step: bad dtype");
+namespace mx {
+// the multistep and the stochastic entry: the same refusals under either name; nz: the noise rows (null: none, the form without NOISY)
+static int cfg_step_multistep(const std::string& what, void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next,
+                              float guidance_scale, int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms,
+                              const mx_inpaint_rows* inpaint, const mx_noise_rows* nz) {
+  MX_CHECK(noise_pred && latents && sigma && sigma_next && ms, what + ": null operand");
+  MX_CHECK(ms->kind && ms->coef && ms->hist, what + ": null kind, coef or hist");
+  MX_CHECK(!nz || (nz->cn && nz->seed && nz->step), what + ": null cn, seed or step of the noise rows");
+  MX_CHECK(n_lat > 0 && C > 0 && hw > 0, what + ": sizes must be positive");
+  MX_CHECK(dtype == MX_F32 || dtype == MX_F16 || dtype == MX_BF16, what + ": bad dtype");
   {                                                      // the history is written while both are read: no byte of it may lie inside either
     const size_t esz = dtype == MX_F32 ? 4 : 2, total = (size_t)n_lat * C * hw;
     const uintptr_t h0 = (uintptr_t)ms->hist, h1 = h0 + total * 4, l0 = (uintptr_t)latents, p0 = (uintptr_t)noise_pred;
     const bool apart = (h1 <= l0 || l0 + total * esz <= h0) && (h1 <= p0 || p0 + (guidance_scale > 0.f ? 2 : 1) * total * esz <= h0);
-    MX_CHECK(apart, "cfg_multistep_step: hist may alias neither the latents nor the prediction");
+    MX_CHECK(apart, what + ": hist may alias neither the latents nor the prediction");
   }
-  mx::step_args a = mx::base_args(noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, (long)C * hw);
+  step_args a = base_args(noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, (long)C * hw);
   a.run = hw; a.kind = ms->kind; a.coef = ms->coef; a.hist = ms->hist;
-  if (mx::set_inpaint_rows("cfg_multistep_step", a, inpaint)) return 1;
-  return mx::launch_cfg_step<false, true, true>("cfg_multistep_step", stream, dtype, flow != 0, a);
+  if (set_inpaint_rows(what, a, inpaint)) return 1;
+  if (!nz) return launch_cfg_step<false, true, true>(what.c_str(), stream, dtype, flow != 0, a);
+  a.cn = nz->cn; a.seed = (const unsigned long long*)nz->seed; a.nstep = nz->step;
+  return launch_cfg_step<false, true, true, true>(what.c_str(), stream, dtype, flow != 0, a);
+}
+}  // namespace mx
+
+extern "C" int mx_cfg_multistep_step(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                                     int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms, const mx_inpaint_rows* inpaint) {
+  return mx::cfg_step_multistep("cfg_multistep_step", stream, noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype, flow, ms, inpaint,
+                                nullptr);
+}
+
+extern "C" int mx_cfg_stochastic_step(void* stream, const void* noise_pred, void* latents, const float* sigma, const float* sigma_next, float guidance_scale,
+                                      int n_lat, int C, int hw, int dtype, int flow, const mx_multistep_rows* ms, const mx_inpaint_rows* inpaint,
+                                      const mx_noise_rows* nz) {
+  return mx::cfg_step_multistep("cfg_stochastic_step", stream, noise_pred, latents, sigma, sigma_next, guidance_scale, n_lat, C, hw, dtype, flow, ms, inpaint,
+                                nz);
 }

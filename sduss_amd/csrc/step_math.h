@@ -82,5 +82,10 @@ __device__ __forceinline__ float multistep_update2(float x, float d, float prev,
   const float c = c1 * prev;
   return acc + c;
 }
+// the noise term of a stochastic row (scheduler_step.hip, NOISY): acc + (cn * z) behind the multistep update, z ~ N(0, 1) (noise.h)
+__device__ __forceinline__ float noisy_update(float acc, float cn, float z) {
+  const float n = cn * z;
+  return acc + n;
+}
 
 }  // namespace mx

@@ -178,6 +178,17 @@ MX_SAMPLER_EULER, MX_SAMPLER_DPMPP_2M, MX_SAMPLER_AB2 = 0, 1, 2
 SAMPLERS = {"euler": MX_SAMPLER_EULER, "dpmpp_2m": MX_SAMPLER_DPMPP_2M, "ab2": MX_SAMPLER_AB2}     # the kind of a row of mx_cfg_multistep_step
 
 
+# the stochastic samplers: coefficients by mx_sampler_coeffs_eta; on the device both step as kind-1 rows (D = x - sigma m) with noise rows
+MX_SAMPLER_EULER_A, MX_SAMPLER_DPMPP_2M_SDE = 3, 4
+STOCHASTIC_SAMPLERS = {"euler_a": MX_SAMPLER_EULER_A, "dpmpp_2m_sde": MX_SAMPLER_DPMPP_2M_SDE}
+MX_NOISE_INIT, MX_NOISE_START, MX_NOISE_STEP, MX_NOISE_POSTERIOR = 0, 1, 2, 3      # the domain of mx_noise_fill: what the noise is for
+
+
+class NoiseRows(C.Structure):
+    """mx_noise_rows: the noise coefficient, seed and step index of the rows of one stochastic launch"""
+    _fields_ = [("cn", C.c_void_p), ("seed", C.c_void_p), ("step", C.c_void_p)]
+
+
 class MultistepRows(C.Structure):
     """mx_multistep_rows: the samplers, coefficients and history of the rows of one multistep launch"""
     _fields_ = [("kind", C.c_void_p), ("coef", C.c_void_p), ("hist", C.c_void_p)]
@@ -310,6 +321,9 @@ SYMBOLS = {
     "mx_cfg_flow_step_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, C.POINTER(InpaintRows)]),
     "mx_cfg_multistep_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, C.POINTER(MultistepRows), C.POINTER(InpaintRows)]),
     "mx_sampler_coeffs": (_i, [_i, _i, _vp, _i, _vp]),
+    "mx_cfg_stochastic_step": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, C.POINTER(MultistepRows), C.POINTER(InpaintRows), C.POINTER(NoiseRows)]),
+    "mx_sampler_coeffs_eta": (_i, [_i, _i, _vp, _i, _d, _vp]),
+    "mx_noise_fill": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _vp, _i]),
     "mx_inpaint_renoise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i]),
     "mx_mask_to_latent": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "mx_rgb8_paste": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),

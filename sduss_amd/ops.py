@@ -535,12 +535,79 @@ def cfg_multistep_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: 
     return latents
 
 
+def _seeds_and_steps(fn_name: str, n: int, seed, step, device) -> tuple:
+    """(seed int64 [n] holding the uint64 bits, step int32 [n] holding the uint32 bits) on ``device``; tensors of those dtypes pass through"""
+    out = []
+    for name, t, dt, bits in (("seed", seed, torch.int64, 64), ("step", step, torch.int32, 32)):
+        if not isinstance(t, torch.Tensor):
+            vals = [int(v) & ((1 << bits) - 1) for v in (t if isinstance(t, (list, tuple)) else [t] * n)]
+            t = torch.tensor([v - (1 << bits) if v >> (bits - 1) else v for v in vals], dtype=dt)
+        _need(t.dtype == dt and t.numel() == n, f"{fn_name}: {name} must hold one {dt} value per row")
+        out.append(t.to(device).contiguous())
+    return tuple(out)
+
+
+def seeded_noise(shape, seed, step, domain: int, dtype=torch.float32, device="cuda", scale=None, raw: bool = False) -> torch.Tensor:
+    """[n, ...] of ``dtype``: row r holds scale[r] * N(0, 1) noise that is a function of (seed[r], step[r], domain, index within the row) alone
+    (mx_noise_fill; csrc/noise.h) -- not of n, of r or of the other rows.  seed / step: an int (every row), a list, or an int64 / int32 tensor of the
+    raw bits; ``scale``: None, a float or fp32 [n]; ``raw``: the generator's uint32 words instead, as an int32 tensor of their bits."""
+    fn_name = "mx_noise_fill"
+    l = _lib.load()
+    shape = tuple(int(v) for v in shape)
+    _need(len(shape) >= 2 and all(v > 0 for v in shape), f"{fn_name}: the shape must be [n, ...] with positive sizes")
+    n = shape[0]
+    sd, st = _seeds_and_steps(fn_name, n, seed, step, device)
+    sc = None
+    if scale is not None and not raw:
+        sc = torch.as_tensor(scale, dtype=torch.float32).reshape(-1)
+        _need(sc.numel() in (1, n), f"{fn_name}: scale must hold one value, or one per row")
+        sc = sc.to(device).expand(n).contiguous()
+    out = torch.empty(shape, dtype=torch.int32 if raw else dtype, device=device)
+    _lib.check(l.mx_noise_fill(_lib.current_stream(), out.data_ptr(), 0 if raw else _lib.torch_dtype_code(dtype), n, out[0].numel(), sd.data_ptr(),
+                               st.data_ptr(), int(domain), _p(sc), int(bool(raw))), fn_name)
+    return out
+
+
+def cfg_stochastic_step_(noise_pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float,
+                         kind: torch.Tensor, coef: torch.Tensor, hist: torch.Tensor, flow: bool, cn: torch.Tensor, seed: torch.Tensor,
+                         step: torch.Tensor, slot: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
+                         noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: ``cfg_multistep_step_`` with noise made inside the launch (mx_cfg_stochastic_step): a kind-1 / kind-2 row with cn[r] != 0 ends as
+    cx x + c0 D + c1 hist + cn z, z the request's own N(0, 1) noise of this step (``seeded_noise`` at domain 2 gives the same values).  cn fp32 [n];
+    seed int64 [n] (the uint64 bits); step int32 [n] (the request's step index)."""
+    fn_name = "mx_cfg_stochastic_step"
+    l = _lib.load()
+    sg, sn = _step_operands(fn_name, noise_pred, latents, sigma, sigma_next, guidance_scale)
+    n_lat, c, h, w = latents.shape
+    _need(kind.dtype == torch.int32 and kind.numel() == n_lat and kind.is_contiguous() and kind.device == latents.device,
+          f"{fn_name}: kind must be a contiguous int32 [{n_lat}] on the latents' device")
+    _need(coef.dtype == torch.float32 and tuple(coef.shape) == (n_lat, 3) and coef.is_contiguous() and coef.device == latents.device,
+          f"{fn_name}: coef must be contiguous fp32 [{n_lat}, 3] on the latents' device, got {coef.dtype} {tuple(coef.shape)}")
+    _need(hist.dtype == torch.float32 and tuple(hist.shape) == (n_lat, c, h, w) and hist.is_contiguous() and hist.device == latents.device,
+          f"{fn_name}: hist must be contiguous fp32 [{n_lat}, {c}, {h}, {w}] on the latents' device, got {hist.dtype} {tuple(hist.shape)}")
+    for name, t, dt in (("cn", cn, torch.float32), ("seed", seed, torch.int64), ("step", step, torch.int32)):
+        _need(t.dtype == dt and t.numel() == n_lat and t.is_contiguous() and t.device == latents.device,
+              f"{fn_name}: {name} must be a contiguous {dt} [{n_lat}] on the latents' device")
+    ms = _lib.MultistepRows()
+    ms.kind, ms.coef, ms.hist = kind.data_ptr(), coef.data_ptr(), hist.data_ptr()
+    nz = _lib.NoiseRows()
+    nz.cn, nz.seed, nz.step = cn.data_ptr(), seed.data_ptr(), step.data_ptr()
+    r = _inpaint_rows(fn_name, latents, slot, init, noise, mask)
+    _lib.check(l.mx_cfg_stochastic_step(_lib.current_stream(), noise_pred.data_ptr(), latents.data_ptr(), sg.data_ptr(), sn.data_ptr(),
+                                        float(guidance_scale), n_lat, c, h * w, _lib.torch_dtype_code(latents.dtype), int(bool(flow)), C.byref(ms),
+                                        C.byref(r), C.byref(nz)), fn_name)
+    return latents
+
+
 def cfg_step_(pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, guidance_scale: float, flow: bool,
-              inpaint: Optional[tuple] = None, multistep: Optional[tuple] = None) -> torch.Tensor:
+              inpaint: Optional[tuple] = None, multistep: Optional[tuple] = None, noise: Optional[tuple] = None) -> torch.Tensor:
     """In place: the scheduler step of one resolution's rows, by the entry its requests need.  ``flow``: the flow-match model.  ``inpaint``: (slot,
     init, noise, mask) of ``cfg_euler_step_masked_`` when a row is an inpainting request; ``multistep``: (kind, coef, hist) of
-    ``cfg_multistep_step_`` when a row steps by DPM-Solver++ 2M or AB2.  With neither it is the plain step, so Euler requests get the launch they
-    always had."""
+    ``cfg_multistep_step_`` when a row steps by DPM-Solver++ 2M or AB2; ``noise``: (cn, seed, step) of ``cfg_stochastic_step_`` beside ``multistep``
+    when a row steps by a stochastic sampler.  With none of them it is the plain step, so Euler requests get the launch they always had."""
+    if noise is not None:
+        _need(multistep is not None, "cfg_step_: noise rows come with multistep rows")
+        return cfg_stochastic_step_(pred, latents, sigma, sigma_next, guidance_scale, *multistep, flow, *noise, *(inpaint or ()))
     if multistep is not None:
         return cfg_multistep_step_(pred, latents, sigma, sigma_next, guidance_scale, *multistep, flow, *(inpaint or ()))
     if inpaint is not None:
@@ -548,14 +615,21 @@ def cfg_step_(pred: torch.Tensor, latents: torch.Tensor, sigma: torch.Tensor, si
     return (cfg_flow_step_ if flow else cfg_euler_step_)(pred, latents, sigma, sigma_next, guidance_scale)
 
 
-def sampler_coeffs(sampler: str, sigmas, flow: bool):
+def sampler_coeffs(sampler: str, sigmas, flow: bool, eta: Optional[float] = None):
     """the step coefficients of a multistep sampler ("dpmpp_2m" | "ab2") over a schedule, on the host (mx_sampler_coeffs; no GPU needed):
-    sigmas fp32 [n + 1] -> numpy fp32 [n, 4] = (cx, c0 first order, c0 second order, c1 second order) per step"""
+    sigmas fp32 [n + 1] -> numpy fp32 [n, 4] = (cx, c0 first order, c0 second order, c1 second order) per step.  With ``eta`` (mx_sampler_coeffs_eta):
+    [n, 5], the noise coefficient cn behind them, and the stochastic samplers "euler_a" | "dpmpp_2m_sde" beside the two."""
     import numpy as np
     l = _lib.load()
-    _need(sampler in _lib.SAMPLERS, f"mx_sampler_coeffs: sampler must be one of {sorted(_lib.SAMPLERS)}, got {sampler!r}")
+    names = dict(_lib.SAMPLERS, **(_lib.STOCHASTIC_SAMPLERS if eta is not None else {}))
+    _need(sampler in names, f"mx_sampler_coeffs: sampler must be one of {sorted(names)}, got {sampler!r}")
     sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float32).reshape(-1))
     _need(sig.size >= 2, "mx_sampler_coeffs: a schedule holds at least one step (two sigmas)")
+    if eta is not None:
+        out = np.empty((sig.size - 1, 5), dtype=np.float32)
+        _lib.check(l.mx_sampler_coeffs_eta(names[sampler], int(bool(flow)), sig.ctypes.data, sig.size - 1, float(eta), out.ctypes.data),
+                   "mx_sampler_coeffs_eta")
+        return out
     out = np.empty((sig.size - 1, 4), dtype=np.float32)
     _lib.check(l.mx_sampler_coeffs(_lib.SAMPLERS[sampler], int(bool(flow)), sig.ctypes.data, sig.size - 1, out.ctypes.data), "mx_sampler_coeffs")
     return out

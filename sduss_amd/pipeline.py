@@ -93,9 +93,11 @@ class Request:
     start: Optional[float] = None
     finish: Optional[float] = None
     inpaint: Optional[InpaintState] = None
-    sampler: str = "euler"                # "euler" | "dpmpp_2m" | "ab2" (set_timesteps)
+    sampler: str = "euler"                # "euler" | "dpmpp_2m" | "ab2" | "euler_a" | "dpmpp_2m_sde" (set_timesteps)
     history: Optional[torch.Tensor] = None   # fp32 [1, C, h, w]: D of the last step of a multistep sampler, a view of its composition's buffer
     history_step: int = -1                # the step that left ``history``; the next step is second order only if it follows it directly
+    seed: Optional[int] = None            # the request's noise is a function of (seed, purpose, step, element) alone (csrc/noise.h); None: unseeded
+    eta: float = 0.0                      # the noise level of a stochastic sampler (set_timesteps)
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -129,6 +131,7 @@ class Denoiser:
     announces_composition = False
     flow = False                         # the flow-match model: its Euler step and the keep factor of its inpainting rows
     samplers = ("euler",)                # what set_timesteps accepts
+    stochastic_samplers = ()             # those of them that draw noise every step: they need a seeded request
 
     def __init__(self, model, guidance_scale: float):
         self._model = model
@@ -204,20 +207,51 @@ class Denoiser:
             self.set_timesteps(req)
         req.step_index, req.history, req.history_step = 0, None, -1
 
+    def init_noise_sigma(self, num_inference_steps: int) -> float:
+        """what N(0, 1) noise is scaled by to make a request's initial latents (the flow model: 1)"""
+        return 1.0
+
+    def seed_request(self, req, seed: int) -> None:
+        """Make ``req`` a seeded request: its initial latents become init_noise_sigma times its own noise (domain 0, step 0; ops.seeded_noise), and
+        every noise drawn for it later -- the start noise of image-to-image and inpainting, the step noise of a stochastic sampler -- comes from
+        ``seed`` too, so its image does not depend on the batches it travels in."""
+        req.seed = int(seed) & (2 ** 64 - 1)
+        lat = req.latents
+        req.latents = ops.seeded_noise(lat.shape, req.seed, 0, 0, dtype=lat.dtype, device=lat.device,
+                                       scale=float(self.init_noise_sigma(req.num_inference_steps)))
+
+    def _start_noise(self, req, shape, encoder) -> torch.Tensor:
+        """the start / kept-region noise of a request that starts from an image: its own (domain 1) when it is seeded, torch's otherwise"""
+        if getattr(req, "seed", None) is not None:
+            return ops.seeded_noise(shape, [req.seed] * shape[0], 0, 1, dtype=encoder.out_dtype, device=encoder.device)
+        return torch.randn(tuple(shape), device=encoder.device, dtype=encoder.out_dtype)
+
     def _multistep_rows(self, reqs) -> Optional[tuple]:
         """(kind per row, coefficient table [n, S, 4]) of one resolution's requests as mx_cfg_multistep_step steps them: kind 0 rows (zeros in the
-        table) are the model's Euler step.  None when every request is an Euler one: the resolution then issues the plain or the masked launch."""
-        from .lib import SAMPLERS
+        table) are the model's Euler step.  None when every request is an Euler one: the resolution then issues the plain or the masked launch.
+        With a stochastic request (a kind-1 row on the device) a third member follows: (cn table [n, S], seed per row) of mx_cfg_stochastic_step,
+        zeros for the rows without noise."""
+        from .lib import SAMPLERS, STOCHASTIC_SAMPLERS
         names = [getattr(r, "sampler", "euler") for r in reqs]
         if all(n == "euler" for n in names):
             return None
-        tab = np.zeros((len(reqs), max(len(r.timesteps) for r in reqs), 4), dtype=np.float32)
+        steps = max(len(r.timesteps) for r in reqs)
+        tab = np.zeros((len(reqs), steps, 4), dtype=np.float32)
+        cn, seeds = np.zeros((len(reqs), steps), dtype=np.float32), [0] * len(reqs)
         for i, (r, name) in enumerate(zip(reqs, names)):
             self._check_sampler(name)
-            if name != "euler":
-                k = len(r.timesteps)
+            k = len(r.timesteps)
+            if name in STOCHASTIC_SAMPLERS:
+                if getattr(r, "seed", None) is None:
+                    raise MxError(f"the stochastic sampler {name!r} needs a seeded request (Denoiser.seed_request)")
+                five = ops.sampler_coeffs(name, r.sigmas[:k + 1], self.flow, eta=r.eta)
+                tab[i, :k], cn[i, :k], seeds[i] = five[:, :4], five[:, 4], r.seed
+            elif name != "euler":
                 tab[i, :k] = ops.sampler_coeffs(name, r.sigmas[:k + 1], self.flow)
-        return [SAMPLERS[n] for n in names], tab
+        kinds = [SAMPLERS["dpmpp_2m"] if n in STOCHASTIC_SAMPLERS else SAMPLERS[n] for n in names]
+        if any(n in STOCHASTIC_SAMPLERS for n in names):
+            return kinds, tab, (cn, seeds)
+        return kinds, tab
 
     @staticmethod
     def _resize_client_u8(what: str, t: torch.Tensor, size, resample: str, device) -> torch.Tensor:
@@ -243,7 +277,7 @@ class Denoiser:
         f = 2 ** (len(encoder.cfg.block_out_channels) - 1)
         h, w = (image.shape[1], image.shape[2]) if image.dtype == torch.uint8 else (image.shape[2], image.shape[3])
         if start_noise is None:
-            start_noise = torch.randn((image.shape[0], encoder.cfg.latent_channels, h // f, w // f), device=encoder.device, dtype=encoder.out_dtype)
+            start_noise = self._start_noise(req, (image.shape[0], encoder.cfg.latent_channels, h // f, w // f), encoder)
         enc = encoder.encode_images if image.dtype == torch.uint8 else encoder.encode
         req.latents = enc(image, posterior_noise=posterior_noise, start_noise=start_noise, keep=float(keep), sigma=float(sigma))
         req.step_index = t_start
@@ -320,7 +354,7 @@ class Denoiser:
         init = (encoder.encode_images if u8 else encoder.encode)(image, posterior_noise=posterior_noise)
         mask_u8 = mask.to(encoder.device).contiguous()
         if noise is None:
-            noise = torch.randn(init.shape, device=encoder.device, dtype=encoder.out_dtype)
+            noise = self._start_noise(req, tuple(init.shape), encoder)
         noise = noise.to(device=encoder.device, dtype=encoder.out_dtype).contiguous()
         req.inpaint = InpaintState(init, noise, ops.mask_to_latent(mask_u8, f), image.to(encoder.device).contiguous() if u8 else None, mask_u8, paste,
                                    full_image, full_mask, region, overlay)
@@ -348,7 +382,8 @@ class Denoiser:
         for r in reqs:                                                   # latents may have been produced on another stream
             r.latents.record_stream(here)
         e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs),
-                               tuple(getattr(r, "sampler", "euler") for r in reqs)), reqs,
+                               tuple(getattr(r, "sampler", "euler") for r in reqs),
+                               tuple((getattr(r, "seed", None), getattr(r, "eta", 0.0)) for r in reqs)), reqs,
                               lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs))
         lat = self._cache.latents(e, reqs)
         sig, sig_next, ts = self._cache.step_scalars(e, reqs)
@@ -392,7 +427,8 @@ class Denoiser:
                 hist = self._cache.history(p.entry, p.reqs, p.latents)
                 hist.record_stream(torch.cuda.current_stream())                    # like the latents, it may have been made on another stream
             ops.cfg_step_(nz, p.latents, p.sigma, p.sigma_next, g, self.flow, inpaint=p.entry.inpaint,      # :382-397; the kept region of
-                          multistep=None if ms is None else (ms.kind, ms.coef, hist))                       # inpainting rows put back
+                          multistep=None if ms is None else (ms.kind, ms.coef, hist),                       # inpainting rows put back
+                          noise=None if ms is None or ms.seed is None else (ms.cn, ms.seed, ms.nstep))      # a stochastic request: still one launch
             for i, r in enumerate(p.reqs):                                         # :399-403
                 if ms is not None and ms.host_kind[i]:                             # the history travels on the request, like its latents
                     r.history, r.history_step = hist[i:i + 1], r.step_index
@@ -405,22 +441,31 @@ class Denoiser:
 
 class SDXLDenoiser(Denoiser):
     announces_composition = True
-    samplers = ("euler", "dpmpp_2m", "ab2")
+    samplers = ("euler", "dpmpp_2m", "ab2", "euler_a", "dpmpp_2m_sde")
+    stochastic_samplers = ("euler_a", "dpmpp_2m_sde")
 
     def __init__(self, unet: MxUNet, guidance_scale: float = 5.0):
         super().__init__(unet, guidance_scale)     # reference default (pipeline_..._esymred.py:265)
         self.unet = unet
 
-    def set_timesteps(self, req: Request, sampler: str = "euler", schedule: str = "default") -> None:
-        """the request's schedule and sampler.  ``sampler``: "euler" (EulerDiscreteScheduler, the default), "dpmpp_2m" (DPM-Solver++ 2M) or "ab2"
-        (second-order Adams-Bashforth); ``schedule``: "default" (``euler_tables``) or "karras" (``karras_tables``) -- "dpmpp_2m" with "karras" is
-        what users call DPM++ 2M Karras, and the sampler gains little without the schedule."""
+    def set_timesteps(self, req: Request, sampler: str = "euler", schedule: str = "default", eta: float = 1.0) -> None:
+        """the request's schedule and sampler.  ``sampler``: "euler" (EulerDiscreteScheduler, the default), "dpmpp_2m" (DPM-Solver++ 2M), "ab2"
+        (second-order Adams-Bashforth), or the stochastic "euler_a" (k-diffusion's Euler ancestral) and "dpmpp_2m_sde" (DPM-Solver++ 2M SDE,
+        midpoint), which add ``eta``-scaled noise of the request's own generator every step and so need a seeded request (``seed_request``);
+        ``schedule``: "default" (``euler_tables``) or "karras" (``karras_tables``) -- "dpmpp_2m" with "karras" is what users call DPM++ 2M Karras,
+        "dpmpp_2m_sde" with it DPM++ 2M SDE Karras, and the sampler gains little without the schedule."""
         self._check_sampler(sampler)
         if schedule not in ("default", "karras"):
             raise MxError(f"SDXLDenoiser.set_timesteps: schedule must be 'default' or 'karras', got {schedule!r}")
+        stochastic = sampler in self.stochastic_samplers
+        if stochastic and getattr(req, "seed", None) is None:
+            raise MxError(f"SDXLDenoiser.set_timesteps: the stochastic sampler {sampler!r} needs a seeded request (seed_request)")
+        if stochastic and not eta >= 0.0:
+            raise MxError(f"SDXLDenoiser.set_timesteps: eta must not be negative, got {eta!r}")
         req.timesteps, req.sigmas = self._table(req.num_inference_steps, schedule)[:2]
         req.step_index = 0
         req.sampler, req.history, req.history_step = sampler, None, -1
+        req.eta = float(eta) if stochastic else 0.0
 
     def init_noise_sigma(self, num_inference_steps: int) -> float:
         return self._table(num_inference_steps)[2]

@@ -10,7 +10,9 @@ skips a request (bench.py keeps its batch full by resetting step_index) is follo
 
 A composition with a multistep sampler (DPM-Solver++ 2M, AB2: csrc/scheduler_step.hip) also holds its rows' kinds, their coefficient table of
 every step in both orders and the fp32 history buffer; the step's [n, 3] coefficients are one more gather by the same device index, and the
-order of every row (second only right after a step that left its history) is followed on the host like the step index.
+order of every row (second only right after a step that left its history) is followed on the host like the step index.  With a stochastic
+sampler (Euler ancestral, DPM-Solver++ 2M SDE) it holds the rows' seeds and noise coefficients of every step as well; the step's [n] noise
+coefficients are a further gather, and the device-side step index itself is the counter word of the rows' generators.
 """
 from __future__ import annotations
 
@@ -35,8 +37,10 @@ class _Entry:
 class _Multistep:
     """the multistep rows of a composition: ``kind`` int32 [n] on the device (``host_kind`` the same list on the host), ``table`` fp32 [n, S, 2, 3] =
     (cx, c0, c1) of every step in first and in second order, ``order`` int64 [n] on the device (1 = second order; ``host_order`` what the host
-    last uploaded), ``coef`` fp32 [n, 3] of the current step, ``hist`` the fp32 history buffer [n, C, h, w]"""
-    __slots__ = ("kind", "host_kind", "table", "order", "host_order", "coef", "hist")
+    last uploaded), ``coef`` fp32 [n, 3] of the current step, ``hist`` the fp32 history buffer [n, C, h, w].  A composition with a stochastic row
+    (mx_cfg_stochastic_step) also: ``cn_table`` fp32 [n, S], ``seed`` int64 [n] (the uint64 bits), and ``cn`` fp32 [n] / ``nstep`` int32 [n] of the
+    current step; ``seed`` is None otherwise"""
+    __slots__ = ("kind", "host_kind", "table", "order", "host_order", "coef", "hist", "cn_table", "seed", "cn", "nstep")
 
 
 _next_uid = [0]
@@ -90,7 +94,7 @@ class StepCache:
     def _multistep(self, built: Optional[tuple]) -> Optional[_Multistep]:
         if built is None:
             return None
-        kinds, tab4 = built                               # tab4 [n, S, 4] = (cx, c0 first order, c0 second order, c1 second order): mx_sampler_coeffs
+        kinds, tab4 = built[:2]                           # tab4 [n, S, 4] = (cx, c0 first order, c0 second order, c1 second order): mx_sampler_coeffs
         m = _Multistep()
         m.host_kind = [k if k in (1, 2) else 0 for k in kinds]
         m.kind = _upload(torch.tensor(m.host_kind, dtype=torch.int32), self.device)
@@ -101,7 +105,11 @@ class StepCache:
         m.table = _upload(torch.from_numpy(both), self.device)
         m.order = torch.zeros(len(kinds), dtype=torch.int64, device=self.device)
         m.host_order = [0] * len(kinds)
-        m.coef = m.hist = None
+        m.coef = m.hist = m.cn_table = m.seed = m.cn = m.nstep = None
+        if len(built) > 2:                                # (cn [n, S], seeds): the noise rows of the stochastic requests
+            cn, seeds = built[2]
+            m.cn_table = _upload(torch.from_numpy(np.ascontiguousarray(cn, dtype=np.float32)), self.device)
+            m.seed = _upload(torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64), self.device)
         return m
 
     @staticmethod
@@ -126,6 +134,8 @@ class StepCache:
                 m.order.copy_(_upload(torch.tensor(order, dtype=torch.int64), self.device), non_blocking=True)
                 m.host_order = order
             m.coef = m.table[e.rows, e.idx, m.order]          # [n, 3]
+            if m.seed is not None:                            # the noise coefficient of this step, and the step index as the generators' counter
+                m.cn, m.nstep = m.cn_table[e.rows, e.idx], e.idx.to(torch.int32)
         e.idx += 1
         e.host_idx = [h + 1 for h in host]
         return vals[0], vals[1], vals[2]
