@@ -226,6 +226,14 @@ int mx_gemm_ln_prefers_pass(const mx_gemm_desc* d);
 /* 1 when mx_gemm(d) with stats_out can also write ln_final_out (the launch takes a 256-row tile of the register-exchange kernels, ungrouped) */
 int mx_gemm_ln_final_supported(const mx_gemm_desc* d);
 int mx_gemm_gn_partials_supported(const mx_gemm_desc* d, int conv);   /* 1 when mx_gemm / mx_conv3x3 (d) can write gn_part_out */
+/* By which route each of the three folded LayerNorms of an SDXL transformer block of width C over M token rows reaches its consuming GEMM in the UNet's
+ * step plan (the plan asks the same function; the rule is the table in sduss_amd/csrc/ln_route.h) -- host only.  routes[0..2] = norm1 (q|k|v), norm2
+ * (attn2.to_q), norm3 (GEGLU projection): 0 = a normalisation pass, 1 = ln_stats slabs from the producing launch, 2 = finalised (mean, rstd), ln_final;
+ * routes[3] = 1 when norm3's finalised statistics come from the patch cache's merge kernel.  layers: transformer blocks of the model; n_groups > 1: a
+ * mixed batch, taken as n_groups equal parts of M of one image each; flags: MX_LN_ROUTES_*, TICKETS = the plan holds panel tickets that cover M rows.
+ * Returns non-zero on bad arguments. */
+enum { MX_LN_ROUTES_PATCH_PARALLEL = 1, MX_LN_ROUTES_PATCH_CACHE = 2, MX_LN_ROUTES_TICKETS = 4 };
+int mx_unet_ln_routes(int M, int C, int layers, int n_groups, int flags, int routes[4]);
 /* Which kernel family serves mx_gemm (conv = 0) / mx_conv3x3 (conv = 1) of d -- host only, the same chooser the launch uses:
  *   MX_FORM_TILE_GENERIC   the 128-row register-prefetch tile kernel (small or odd shapes)
  *   MX_FORM_TILE_256       a 256-row tile of the ping-pong kernels (256 x 160 / 128, one tile per CU)

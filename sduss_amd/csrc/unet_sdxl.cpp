@@ -28,6 +28,7 @@
 #include "../../include/mxdenoise.h"
 #include "common.h"
 #include "graph_cache.h"
+#include "ln_route.h"
 #include "patch_cache.h"
 #include "plan_base.h"
 
@@ -49,6 +50,7 @@ extern "C" int mx_attention_prescaled_chunked(void* stream, const void* q, int l
                                               int64_t k_batch_stride, int64_t k_chunk_stride, int64_t vt_chunk_stride);
 
 using mx::bf16_t;
+using mx::LnVia;
 
 struct mx_unet {
   mx_unet_config cfg;
@@ -108,17 +110,18 @@ struct Linear {
   const bf16_t* a; int lda; std::string stem; void* c; int ldc; int M, N, K;      // c[M, N] = a[M, K] * "<stem>.weight"^T + "<stem>.bias"
   const void* residual = nullptr; int ldr = 0; int flags = 0; float out_scale = 0.f;
   const bf16_t* a2 = nullptr; int lda2 = 0;
-  const RowStats* ln = nullptr; bool ln_final = false;
-  RowStats* stats_out = nullptr; bool finalise = false;
+  const RowStats* ln = nullptr; LnVia ln_via = LnVia::Pass;
+  RowStats* stats_out = nullptr; LnVia stats_via = LnVia::Pass;
   Linear& plus(const void* r, int ld) { residual = r; ldr = ld; return *this; }
   Linear& epilogue(int f) { flags = f; return *this; }
   Linear& scaled(float s) { out_scale = s; return *this; }
   Linear& concat(const bf16_t* x2, int ld2) { a2 = x2; lda2 = ld2; return *this; }                  // A = [a | a2] along K (a2 null: a alone)
-  // the A operand is the UN-normalised hidden state and the LayerNorm in front of this linear is folded into it (weights.py fold_layernorm):
-  // statistics st (null: a is already normalised), column sums "<stem>.colsum"; final: the (mean, rstd) form
-  Linear& folded_ln(const RowStats* st, bool final = false) { ln = st; ln_final = final; return *this; }
-  // also produce the statistics of the output rows (null: not wanted); fin: the producer finalises them
-  Linear& leaves_stats(RowStats* st, bool fin = false) { stats_out = st; finalise = fin; return *this; }
+  // the LayerNorm in front of this linear is folded into it (weights.py fold_layernorm) and reaches it by route via (ln_route.h): Slabs / Final = a is the
+  // UN-normalised hidden state with statistics st and column sums "<stem>.colsum"; Pass = nothing, a is already normalised
+  Linear& folded_ln(const RowStats& st, LnVia via) { ln = &st; ln_via = via; return *this; }
+  // the LayerNorm BEHIND this linear reaches its consumer by route via: Slabs = also leave the statistics of the output rows in st, Final = and
+  // finalise them; Pass = nothing
+  Linear& leaves_stats(RowStats& st, LnVia via) { stats_out = &st; stats_via = via; return *this; }
 };
 // where a 3x3 conv reads: the tensor and, patch-parallel, the base of the padded image it is the interior of (one halo row above and below)
 struct ConvIn { bf16_t* t = nullptr; bf16_t* padded = nullptr; };
@@ -367,10 +370,11 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   unsigned* ln_cnt = nullptr;     // panel tickets of the finalising producers: zeroed once per run, every launch leaves them zero
   static constexpr int kLnCnt = 4096;
   // launch d; the statistics of its output rows go to st (from the epilogue when the chosen kernel can, else a pass over the output)
-  bool gemm_with_stats(mx_gemm_desc& d, RowStats& st, bool finalise = false) {
+  // via: the form their consumer reads, Slabs or Final (the producer side of a route)
+  bool gemm_with_stats(mx_gemm_desc& d, RowStats& st, LnVia via) {
     if (!ok()) return false;
     const int slabs = mx_gemm_stats_slabs(&d);
-    if (finalise) {
+    if (via == LnVia::Final) {
       if (slabs <= 0 || !mx_gemm_ln_final_supported(&d) || (d.M + 255) / 256 > kLnCnt) return fail("finalised row statistics: the producing launch cannot write them");
       d.ln_final_out = st.fin; d.ln_final_cnt = st.cnt; d.ln_eps = u->cfg.layer_norm_eps;
     }
@@ -380,9 +384,19 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (!quiet() && mx_row_stats(stream, d.c, d.ldc, st.buf, d.M, d.N)) return fail(std::string("row_stats: ") + mx_last_error());
     return true;
   }
-  void use_ln(mx_gemm_desc& d, const RowStats& st, const std::string& csname, bool final = false) {
-    if (final) d.ln_final = st.fin; else { d.ln_stats = st.buf; d.ln_slabs = st.slabs; }
-    d.ln_colsum = wf(csname, d.N); d.ln_eps = u->cfg.layer_norm_eps;
+  // the consumer side of a route: d reads the folded LayerNorm's statistics st by route via.  segs / row0: the problems of a grouped d and their first
+  // rows -- every problem reads its own rows of the one slab buffer (ln_final excludes grouped launches: ln_route.h never finalises them)
+  void use_ln(mx_gemm_desc& d, const RowStats& st, const std::string& csname, LnVia via, mx_gemm_seg* segs = nullptr, const long* row0 = nullptr) {
+    const float* colsum = wf(csname, d.N);
+    switch (via) {
+      case LnVia::Pass: return;           // (the weight is resolved all the same, so that a validation walk asks for it at every shape)
+      case LnVia::Final: d.ln_final = st.fin; break;
+      case LnVia::Slabs:
+        d.ln_stats = st.buf; d.ln_slabs = st.slabs;
+        for (int g = 0; g < d.n_segs; ++g) segs[g].ln_stats = st.buf + row0[g] * MX_STATS_PITCH(st.slabs) * 2;
+        break;
+    }
+    d.ln_colsum = colsum; d.ln_eps = u->cfg.layer_norm_eps;
   }
   bool linear(const Linear& l) {
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
@@ -390,8 +404,8 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (l.a2) { d.a2 = l.a2; d.lda2 = l.lda2; d.k_split = l.lda; }      // A = [a | a2] along K, read in place
     d.a = l.a; d.lda = l.lda; d.w = wb(l.stem + ".weight", (size_t)l.N * l.K); d.bias = wf(l.stem + ".bias", l.N);
     d.c = l.c; d.ldc = l.ldc; d.M = l.M; d.N = l.N; d.K = l.K; d.residual = l.residual; d.ldr = l.ldr; d.flags = l.flags;
-    if (l.ln) use_ln(d, *l.ln, l.stem + ".colsum", l.ln_final);
-    if (l.stats_out) return gemm_with_stats(d, *l.stats_out, l.finalise);
+    if (l.ln_via != LnVia::Pass) use_ln(d, *l.ln, l.stem + ".colsum", l.ln_via);
+    if (l.stats_via != LnVia::Pass) return gemm_with_stats(d, *l.stats_out, l.stats_via);
     return gemm(d, false);
   }
   // 3x3 conv over the images of every group at the current level (Hin, Win: the first group's size; the others come from ch / cw).  A mixed
@@ -561,220 +575,219 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     return nullptr;
   }
 
-  // modules/transformer.py:32-128 (Transformer2DModel) and :167-290 (BasicTransformerBlock)
-  bf16_t* transformer(const std::string& p, const bf16_t* x, int h, int wd, int C, int heads, int layers, int level) {
-    const int L = h * wd;                 // tokens per image of the first group (the only one unless the batch is mixed)
-    const int M = (int)rows();
-    // per group: tokens per image, first row, its V^T block (rows of MX_VT_LD(tokens) keys)
-    int gL[MX_MAX_SEGS], gldvt[MX_MAX_SEGS]; long gr0[MX_MAX_SEGS], gvt0[MX_MAX_SEGS], vt_elems = 0;
+  // ---- Transformer2DModel (modules/transformer.py:32-128) over BasicTransformerBlocks (:167-290) ----
+  // per resolution group of the rows (one unless the batch is mixed): tokens per image, first row, its V^T block (rows of MX_VT_LD(tokens) keys)
+  struct TokenGroups { int L[MX_MAX_SEGS], ldvt[MX_MAX_SEGS]; long row0[MX_MAX_SEGS], vt0[MX_MAX_SEGS], vt_elems = 0; };
+  // one transformer's shape, LayerNorm routes and buffers (transformer_buffers allocates them in the order they stand here)
+  struct Xf {
+    int C, heads, level, M, L, ldvt;      // (L, ldvt: the first group's tokens per image)
+    TokenGroups g;
+    // The block's three LayerNorms are folded into the linears they feed (weights.py fold_layernorm); via says by which route each reaches its consumer
+    // (ln_route.h: the table).  The producer of a norm's hidden state and its consumer are handed the same member: norm1 proj_in and the previous layer's
+    // ff.net.2 -> q|k|v; norm2 attn1.to_out or the patch cache's merge -> attn2.to_q; norm3 attn2.to_out or the merge -> the GEGLU projection.
+    mx::LnRoutes via;
+    bf16_t* y = nullptr;                  // the hidden state
+    RowStats st;                          // its row statistics: slabs (Slabs) and, where a norm takes Final, (mean, rstd)
+    bf16_t* ln = nullptr;                 // its normalised copy (Pass): the GroupNorm output, dead after proj_in
+    bf16_t *qk = nullptr, *vt = nullptr, *ao = nullptr, *q2 = nullptr, *ff = nullptr;
+    bf16_t *pqc = nullptr, *paoc = nullptr, *ptc = nullptr;          // patch-unit cache: compact queries / attention output / projection output
+    bf16_t *k_send = nullptr, *k_all = nullptr, *vt_all = nullptr;   // patch-parallel: the ranks' K rows and V^T columns
+    KV* kvp = nullptr;                    // the hoisted cross-attention K / V^T of this width
+    mx_gemm_seg qsegs[MX_MAX_SEGS];       // mixed batch: the fused q|k|v projection as a grouped launch (tokens per image and V^T block per group)
+    std::vector<long> vt_off; std::vector<int> ldvt_s, Lk_s;         // patch-unit cache: per sample, its V^T block and keys
+  };
+  void transformer_buffers(Xf& t, bf16_t* gn_out) {
+    const size_t M = t.M, C = t.C;
+    t.y = alloc<bf16_t>(M * C);
+    t.st.buf = (float*)ar.alloc(M * MX_STATS_PITCH(C / 64) * 2 * sizeof(float));
+    if (!t.st.buf) fail("workspace too small");
+    t.ln = gn_out;
+    t.qk = alloc<bf16_t>(M * 2 * C);
+    t.vt = alloc<bf16_t>((size_t)t.g.vt_elems);
+    t.ao = alloc<bf16_t>(M * C);
+    t.q2 = alloc<bf16_t>(M * C);
+    t.ff = alloc<bf16_t>(M * 4 * C);
+    if (t.via.norm1 == LnVia::Final || t.via.norm3 == LnVia::Final) { t.st.fin = (float*)ar.alloc(M * 2 * sizeof(float)); t.st.cnt = ln_cnt; if (!t.st.fin) fail("workspace too small"); }
+    if (pc) { t.pqc = alloc<bf16_t>(M * C); t.paoc = alloc<bf16_t>(M * C); t.ptc = alloc<bf16_t>(M * C); }
+  }
+  // out = (in - mean) * rstd per row, no affine (it lives in the folded weights)
+  void normalise(const bf16_t* in, bf16_t* out, int rows, int C) {
+    if (ok() && !quiet() && mx_layernorm(stream, in, out, nullptr, nullptr, rows, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
+  }
+  // the A operand of a norm's consumer on route via: Pass runs the pass and gives the normalised copy, the others read the hidden state itself
+  const bf16_t* ln_operand(Xf& t, LnVia via) {
+    if (via != LnVia::Pass) return t.y;
+    normalise(t.y, t.ln, t.M, t.C);
+    return t.ln;
+  }
+  // self-attention's fused q | k | v projection of block b, norm1 folded into it (the hidden state in front of it comes from ordinary GEMMs in every mode)
+  void qkv(Xf& t, const std::string& b) {
+    const int C = t.C;
+    const bf16_t* a = ln_operand(t, t.via.norm1);
+    mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
+    d.a = a; d.w = wb(b + ".attn1.to_qkv.weight", (size_t)3 * C * C); d.bias = wf(b + ".attn1.to_qkv.bias", 3 * C);
+    d.c = t.qk; d.vt = t.vt;
+    mx::ln_qkv_shape(d, t.M, C, t.L);
+    if (ng > 1) {
+      std::memset(t.qsegs, 0, sizeof(t.qsegs));
+      for (int g = 0; g < ng; ++g) {
+        t.qsegs[g].a = a + t.g.row0[g] * C; t.qsegs[g].c = t.qk + t.g.row0[g] * 2 * C; t.qsegs[g].vt = t.vt + t.g.vt0[g];
+        t.qsegs[g].M = gB[g] * t.g.L[g]; t.qsegs[g].rows_per_batch = t.g.L[g]; t.qsegs[g].ldvt = t.g.ldvt[g];
+      }
+      d.segs = t.qsegs; d.n_segs = ng;
+    }
+    use_ln(d, t.st, b + ".attn1.to_qkv.colsum", t.via.norm1, t.qsegs, t.g.row0);
+    gemm(d, false);
+  }
+  // ---- the two attention launches over all rows: one grouped launch over the groups' problems in a mixed batch ----
+  void self_problems(const Xf& t, mx_attn_problem* pr) {
+    const int C = t.C;
     for (int g = 0; g < ng; ++g) {
-      gL[g] = ch[g] * cw[g]; gldvt[g] = MX_VT_LD(gL[g]); gr0[g] = row0(g); gvt0[g] = vt_elems;
-      vt_elems += (long)gB[g] * C * gldvt[g];
+      pr[g].q = t.qk + t.g.row0[g] * 2 * C; pr[g].k = t.qk + t.g.row0[g] * 2 * C + C; pr[g].vt = t.vt + t.g.vt0[g]; pr[g].o = t.ao + t.g.row0[g] * C;
+      pr[g].vt_batch_stride = (int64_t)C * t.g.ldvt[g]; pr[g].B = gB[g]; pr[g].Lq = t.g.L[g]; pr[g].Lk = t.g.L[g]; pr[g].ldvt = t.g.ldvt[g];
+    }
+  }
+  void cross_problems(const Xf& t, mx_attn_problem* pr, int li) {      // the hoisted K / V^T are per sample: group g reads the rows of its samples
+    const int C = t.C; const KV* kvp = t.kvp;
+    for (int g = 0; g < ng; ++g) {
+      pr[g].q = t.q2 + t.g.row0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
+      pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = t.ao + t.g.row0[g] * C;
+      pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = t.g.L[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
+    }
+  }
+  void self_attention(Xf& t) {                  // ao = attention(q, k, v of qk | vt)
+    const int C = t.C;
+    mx_attn_problem pr[MX_MAX_SEGS];
+    if (ng > 1) { self_problems(t, pr); attention_grouped(pr, 2 * C, 2 * C, C, t.heads); }
+    else attention(t.qk, 2 * C, t.qk + C, 2 * C, t.vt, t.ldvt, (long)C * t.ldvt, t.ao, C, t.heads, t.L, t.L);
+  }
+  void cross_attention(Xf& t, int li) {         // ao = attention(q2, layer li of the hoisted K / V^T)
+    if (!ok()) return;
+    const int C = t.C; const KV* kvp = t.kvp;
+    mx_attn_problem pr[MX_MAX_SEGS];
+    if (ng > 1) { cross_problems(t, pr, li); attention_grouped(pr, C, kvp->ldk, C, t.heads); }
+    else attention(t.q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride, t.ao, C, t.heads, t.L, ctx_len);
+  }
+  // ---- between the q | k | v projection and the feed-forward: y += attn1, y += attn2, leaving norm3's input form ----
+  // self-attention -> to_out -> residual, then the cross-attention on layer li of the K / V^T of encoder_hidden_states (norm2 in to_q)
+  void attend(Xf& t, const std::string& b, int li) {
+    const int C = t.C, M = t.M;
+    if (is_pp()) {      // every rank gathers the other ranks' K rows and V^T columns (modules/pp/attn.py:137: all_gather(kv))
+      if (ok() && !dry && hipMemcpy2DAsync(t.k_send, (size_t)C * 2, t.qk + C, (size_t)2 * C * 2, (size_t)C * 2, M, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        fail("patch-parallel: K pack failed");
+      all_gather(t.k_send, t.k_all, (size_t)M * C * 2);
+      all_gather(t.vt, t.vt_all, (size_t)B * C * t.ldvt * 2);
+      if (ok() && !dry &&
+          mx_attention_prescaled_chunked(stream, t.qk, 2 * C, t.k_all, C, t.vt_all, t.ldvt, (int64_t)C * t.ldvt, t.ao, C, B, t.heads, t.L, pp_world * t.L, t.L,
+                                         (int64_t)t.L * C, (int64_t)M * C, (int64_t)B * C * t.ldvt))
+        fail(std::string("attention: ") + mx_last_error());
+    } else self_attention(t);
+    linear(Linear{t.ao, C, b + ".attn1.to_out.0", t.y, C, M, C, C}.plus(t.y, C).leaves_stats(t.st, t.via.norm2));
+    linear(Linear{ln_operand(t, t.via.norm2), C, b + ".attn2.to_q", t.q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(t.st, t.via.norm2));
+    cross_attention(t, li);
+    linear(Linear{t.ao, C, b + ".attn2.to_out.0", t.y, C, M, C, C}.plus(t.y, C).leaves_stats(t.st, t.via.norm3));
+  }
+  // patch-unit cache: y += an op's (fresh or cached) output out of its state; the merge kernel is the producer of the norm behind it and leaves the
+  // statistics in the form route via reads (round 5, pc_load_stats: one slab for the 256 / 128-row GEMMs, (mean, rstd) for the 256 x 256 kernel)
+  void pc_merge(Xf& t, char* reg, LnVia via) {
+    switch (via) {
+      case LnVia::Pass: pc_load(t.y, reg, t.level, t.C, nullptr, 0, t.y); break;
+      case LnVia::Slabs: pc_load_stats(t.y, reg, t.level, t.C, t.y, t.st.buf, nullptr); t.st.slabs = 1; break;
+      case LnVia::Final: pc_load_stats(t.y, reg, t.level, t.C, t.y, nullptr, t.st.fin); break;
+    }
+  }
+  // PatchBasicTransformerBlock under a per-patch mask (transformer.py:167-290): the LayerNorms, the q | k | v projection of attn1 and the
+  // feed-forward run on all rows; the self-attention core + to_out and the whole cross-attention run for the asking patches and the
+  // others take the op's cached output (attention.py:59-110, 121-232); then the residual adds
+  void attend_masked(Xf& t, const std::string& b, int li) {
+    const int C = t.C, M = t.M, level = t.level;
+    const KV* kvp = t.kvp;
+    const int pp2 = (pc_p0 >> level) * (pc_p0 >> level);
+    const int Mc = pc_count() * pp2;
+    char* reg1 = pc_region(level, C);
+    if (!pc_partial) {
+      self_attention(t);
+      linear(Linear{t.ao, C, b + ".attn1.to_out.0", t.ptc, C, M, C, C});
+      pc_store(t.ptc, reg1, level, C);
+    } else {
+      pc_gather_rows(t.qk, 2 * C, C, t.pqc, level);
+      pc_attention(t.pqc, t.qk + C, 2 * C, -1, t.vt, t.vt_off.data(), t.ldvt_s.data(), 0, t.paoc, C, t.heads, level, t.Lk_s.data());
+      linear(Linear{t.paoc, C, b + ".attn1.to_out.0", t.ptc, C, Mc, C, C});
+      pc_scatter_rows(t.ptc, C, reg1, level);
+    }
+    // The one RUN-TIME fact outside the route table: under a partial mask (pc_partial, known per block at run time) to_q runs on the asking rows only, so
+    // norm2 is a pass over those rows alone, whatever the table says (the pass over all M rows in front of the gather cost as much as attn2 saved)
+    const LnVia norm2 = pc_partial ? LnVia::Pass : t.via.norm2;
+    pc_merge(t, reg1, norm2);
+    char* reg2 = pc_region(level, C);
+    if (!pc_partial) {
+      linear(Linear{ln_operand(t, norm2), C, b + ".attn2.to_q", t.q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(t.st, norm2));
+      cross_attention(t, li);
+      linear(Linear{t.ao, C, b + ".attn2.to_out.0", t.ptc, C, M, C, C});
+      pc_store(t.ptc, reg2, level, C);
+    } else {
+      pc_gather_rows(t.y, C, C, t.paoc, level);
+      normalise(t.paoc, t.pqc, Mc, C);
+      linear(Linear{t.pqc, C, b + ".attn2.to_q", t.q2, C, Mc, C, C}.scaled(MX_ATTN_QSCALE(0.125f)));
+      if (ok()) {
+        std::vector<long> cvt_off(B); std::vector<int> cld(B, kvp->ldvt), clk(B, ctx_len);
+        for (int bb = 0; bb < B; ++bb) cvt_off[bb] = (long)bb * kvp->vt_bstride;
+        pc_attention(t.q2, kvp->k + (size_t)li * C, kvp->ldk, (long)ctx_len * kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, cvt_off.data(), cld.data(),
+                     kvp->vt_bstride, t.paoc, C, t.heads, level, clk.data());
+      }
+      linear(Linear{t.paoc, C, b + ".attn2.to_out.0", t.ptc, C, Mc, C, C});
+      pc_scatter_rows(t.ptc, C, reg2, level);
+    }
+    pc_merge(t, reg2, t.via.norm3);
+  }
+  // GEGLU feed-forward of block b (norm3 in the GEGLU projection); next: the route of the norm that reads what ff.net.2 leaves (the next layer's norm1)
+  void feed_forward(Xf& t, const std::string& b, LnVia next) {
+    const int C = t.C, M = t.M;
+    linear(Linear{ln_operand(t, t.via.norm3), C, b + ".ff.net.0.proj", t.ff, 4 * C, M, 8 * C, C}.epilogue(MX_EPI_GEGLU).folded_ln(t.st, t.via.norm3));
+    linear(Linear{t.ff, 4 * C, b + ".ff.net.2", t.y, C, M, C, 4 * C}.plus(t.y, C).leaves_stats(t.st, next));
+  }
+  bf16_t* transformer(const std::string& p, const bf16_t* x, int h, int wd, int C, int heads, int layers, int level) {
+    Xf t;
+    t.C = C; t.heads = heads; t.level = level; t.M = (int)rows();
+    t.L = h * wd;                         // tokens per image of the first group (the only one unless the batch is mixed)
+    t.ldvt = MX_VT_LD(t.L);
+    const int M = t.M, L = t.L;
+    mx::LnRows lr; lr.n_groups = ng;
+    for (int g = 0; g < ng; ++g) {
+      t.g.L[g] = ch[g] * cw[g]; t.g.ldvt[g] = MX_VT_LD(t.g.L[g]); t.g.row0[g] = row0(g); t.g.vt0[g] = t.g.vt_elems;
+      t.g.vt_elems += (long)gB[g] * C * t.g.ldvt[g];
+      lr.rows[g] = gB[g] * t.g.L[g]; lr.per_image[g] = t.g.L[g];
     }
     bf16_t* out = alloc<bf16_t>((size_t)M * C);
     const size_t m0 = ar.mark();
     bf16_t* n = alloc<bf16_t>((size_t)M * C);
     if (is_pp()) groupnorm_pp(x, n, (long)L * C, p + ".norm", h, wd, C, u->cfg.transformer_norm_eps, false, level);
     else groupnorm(x, n, p + ".norm", h, wd, C, u->cfg.transformer_norm_eps, false, level_patch(level));
-    bf16_t* y = alloc<bf16_t>((size_t)M * C);
-    // The BasicTransformerBlock's three LayerNorms are folded into the linears they feed (weights.py fold_layernorm).  Where the consuming
-    // GEMM hides the statistics behind its first operand fetch (the 256 / 128-row kernels) the GEMM that wrote the hidden state y also left
-    // the row statistics and no normalisation pass runs; where it would run on the persistent 256 x 256 kernel (mx_gemm_ln_prefers_pass)
-    // a plain (x - mean) * rstd pass feeds the same folded weights.
-    RowStats st;
-    st.buf = (float*)ar.alloc((size_t)M * MX_STATS_PITCH(C / 64) * 2 * sizeof(float));
-    if (!st.buf) fail("workspace too small");
-    bf16_t* ln = n;  // the GroupNorm output is dead after proj_in
-    const int ldvt = MX_VT_LD(L);
-    bf16_t* qk = alloc<bf16_t>((size_t)M * 2 * C);
-    bf16_t* vt = alloc<bf16_t>((size_t)vt_elems);
-    bf16_t* ao = alloc<bf16_t>((size_t)M * C);
-    bf16_t* q2 = alloc<bf16_t>((size_t)M * C);
-    bf16_t* ff = alloc<bf16_t>((size_t)M * 4 * C);
-    mx_gemm_seg qsegs[MX_MAX_SEGS];       // mixed batch: the fused q|k|v projection as a grouped launch (tokens per image and V^T block per group)
-    auto qkv_desc = [&](const std::string& b, const bf16_t* a) {
-      mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-      d.a = a; d.lda = C; d.w = wb(b + ".attn1.to_qkv.weight", (size_t)3 * C * C); d.bias = wf(b + ".attn1.to_qkv.bias", 3 * C);
-      d.c = qk; d.ldc = 2 * C;
-      d.M = M; d.N = 3 * C; d.K = C; d.flags = MX_EPI_QKV; d.seg = C; d.period = 3; d.vt = vt; d.ldvt = ldvt;
-      d.rows_per_batch = L; d.out_scale = MX_ATTN_QSCALE(0.125f);   // q segment only
-      if (ng > 1) {
-        std::memset(qsegs, 0, sizeof(qsegs));
-        for (int g = 0; g < ng; ++g) {
-          qsegs[g].a = a + gr0[g] * C; qsegs[g].c = qk + gr0[g] * 2 * C; qsegs[g].vt = vt + gvt0[g];
-          qsegs[g].M = gB[g] * gL[g]; qsegs[g].rows_per_batch = gL[g]; qsegs[g].ldvt = gldvt[g];
-        }
-        d.segs = qsegs; d.n_segs = ng;
-      }
-      return d;
-    };
-    // the folded LayerNorm's row statistics of a grouped launch: every problem reads its own rows of the one buffer
-    auto use_ln_grouped = [&](mx_gemm_desc& d, const RowStats& st_) {
-      if (d.n_segs > 0) for (int g = 0; g < ng; ++g) qsegs[g].ln_stats = st_.buf + gr0[g] * MX_STATS_PITCH(st_.slabs) * 2;
-    };
-    auto lin_desc = [&](const bf16_t* a, void* c, int ldc, int N, int flags, float out_scale) {
-      mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
-      d.a = a; d.lda = C; d.w = a; d.c = c; d.ldc = ldc; d.M = M; d.N = N; d.K = C; d.flags = flags; d.out_scale = out_scale;
-      return d;
-    };
-    bool pass1, pass2, pass3;     // LayerNorm as a pass (true) or through the statistics (false), per consumer shape
-    {
-      mx_gemm_desc d1 = qkv_desc(p + ".transformer_blocks.0", y);
-      mx_gemm_desc d2 = lin_desc(y, q2, C, C, 0, MX_ATTN_QSCALE(0.125f));
-      mx_gemm_desc d3 = lin_desc(y, ff, 4 * C, 8 * C, MX_EPI_GEGLU, 0.f);
-      pass1 = mx_gemm_ln_prefers_pass(&d1) != 0; pass2 = mx_gemm_ln_prefers_pass(&d2) != 0; pass3 = mx_gemm_ln_prefers_pass(&d3) != 0;
-    }
-    // Patch-unit cache: the hidden state in front of norm2 / norm3 is produced by the state-merge kernel.  Round 5: that kernel leaves the row statistics
-    // (pc_load_stats), so the folded LayerNorms work as on the exact path; only a PARTIAL mask keeps a pass in front of attn2.to_q -- over the asking rows alone.
-    // Round 4: where the consumer runs on the 256 x 256 kernel (pass1 / pass3) and the launches that write the hidden state in front of it can
-    // FINALISE the row statistics (256-row tiles: mx_gemm_ln_final_supported), the pass disappears as well: the producer's last workgroup per
-    // panel leaves (mean, rstd) per row and the consumer starts its accumulators from those 8 bytes (mx_gemm_desc.ln_final).  No patch cache, not
-    // patch-parallel (their hidden states come from other kernels / are compared bit for bit with the unsplit run).
-    bool fin1 = false, fin3 = false;
-    if (!is_pp() && ln_cnt != nullptr && (M + 255) / 256 <= kLnCnt) {
-      auto can_finalise = [&](int K, bool residual) {
-        mx_gemm_desc d = lin_desc(y, y, C, C, 0, 0.f);
-        d.K = K; d.lda = K; if (residual) { d.residual = y; d.ldr = C; }
-        return mx_gemm_ln_final_supported(&d) != 0;
-      };
-      // (norm1's consumer, the fused q | k | v projection, is a GROUPED launch in a mixed batch -- one problem per resolution -- and keeps the pass there;
-      //  norm3's consumer is a per-token linear over all rows, one ordinary launch whatever the mix)
-      fin1 = ng == 1 && pass1 && can_finalise(C, false) && (layers == 1 || can_finalise(4 * C, true));
-      fin3 = pass3 && can_finalise(C, true);
-      if (pc) fin3 = false;                  // (norm3's statistics come from the merge kernel, not from a finalising GEMM)
-      if (fin1 || fin3 || (pc && pass3)) { st.fin = (float*)ar.alloc((size_t)M * 2 * sizeof(float)); st.cnt = ln_cnt; if (!st.fin) fail("workspace too small"); }
-    }
-    const bool pc_fin3 = pc && pass3 && st.fin != nullptr;      // GEGLU on the 256 x 256 kernel: (mean, rstd) from the merge kernel
-    if (fin1) pass1 = false;
-    if (fin3) pass3 = false;
-    const bool folded3 = !pass3 || pc_fin3, final3 = fin3 || pc_fin3;         // norm3 in the GEGLU projection: through statistics, and those finalised
-    bf16_t* pqc = nullptr; bf16_t* paoc = nullptr; bf16_t* ptc = nullptr;     // patch-unit cache: compact queries / attention output / projection output
-    if (pc) { pqc = alloc<bf16_t>((size_t)M * C); paoc = alloc<bf16_t>((size_t)M * C); ptc = alloc<bf16_t>((size_t)M * C); }
-    auto normalise = [&]() {      // ln = (y - mean) * rstd, no affine (it lives in the folded weights)
-      if (ok() && !quiet() && mx_layernorm(stream, y, ln, nullptr, nullptr, M, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
-    };
-    linear(Linear{n, C, p + ".proj_in", y, C, M, C, C}.leaves_stats(pass1 ? nullptr : &st, fin1));
-    // patch-parallel: every rank gathers the other ranks' K rows and V^T columns (modules/pp/attn.py:137: all_gather(kv))
+    // (tickets: the plan has its panel counters and they cover these rows)
+    t.via = mx::ln_routes(lr, C, layers, is_pp(), pc, ln_cnt != nullptr && (M + 255) / 256 <= kLnCnt);
+    transformer_buffers(t, n);
+    linear(Linear{n, C, p + ".proj_in", t.y, C, M, C, C}.leaves_stats(t.st, t.via.norm1));
     // -- K alone travels: the QKV epilogue writes q|k interleaved, so the K halves are packed into a contiguous send buffer first
-    bf16_t* k_send = nullptr; bf16_t* k_all = nullptr; bf16_t* vt_all = nullptr;
     if (is_pp()) {
       if (L % 64 != 0) fail("patch-parallel: local tokens per image must be a multiple of 64 at every attention level");
-      k_send = alloc<bf16_t>((size_t)M * C);
-      k_all = alloc<bf16_t>((size_t)pp_world * M * C);
-      vt_all = alloc<bf16_t>((size_t)pp_world * B * C * ldvt);
+      t.k_send = alloc<bf16_t>((size_t)M * C);
+      t.k_all = alloc<bf16_t>((size_t)pp_world * M * C);
+      t.vt_all = alloc<bf16_t>((size_t)pp_world * B * C * t.ldvt);
     }
-    KV* kvp = kv_for(C);
-    if (!kvp && ok()) fail("no cross-attention K/V buffer for width " + std::to_string(C));
-    // ---- the two attention launches over all rows: one grouped launch over the groups' problems in a mixed batch ----
-    auto self_problems = [&](mx_attn_problem* pr) {
-      for (int g = 0; g < ng; ++g) {
-        pr[g].q = qk + gr0[g] * 2 * C; pr[g].k = qk + gr0[g] * 2 * C + C; pr[g].vt = vt + gvt0[g]; pr[g].o = ao + gr0[g] * C;
-        pr[g].vt_batch_stride = (int64_t)C * gldvt[g]; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = gL[g]; pr[g].ldvt = gldvt[g];
-      }
-    };
-    auto cross_problems = [&](mx_attn_problem* pr, int li) {      // the hoisted K / V^T are per sample: group g reads the rows of its samples
-      for (int g = 0; g < ng; ++g) {
-        pr[g].q = q2 + gr0[g] * C; pr[g].k = kvp->k + (size_t)li * C + (size_t)gb0[g] * ctx_len * kvp->ldk;
-        pr[g].vt = kvp->vt + (size_t)li * C * kvp->ldvt + (size_t)gb0[g] * kvp->vt_bstride; pr[g].o = ao + gr0[g] * C;
-        pr[g].vt_batch_stride = kvp->vt_bstride; pr[g].B = gB[g]; pr[g].Lq = gL[g]; pr[g].Lk = ctx_len; pr[g].ldvt = kvp->ldvt;
-      }
-    };
-    auto self_attention = [&]() {               // ao = attention(q, k, v of qk | vt)
-      mx_attn_problem pr[MX_MAX_SEGS];
-      if (ng > 1) { self_problems(pr); attention_grouped(pr, 2 * C, 2 * C, C, heads); }
-      else attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, (long)C * ldvt, ao, C, heads, L, L);
-    };
-    auto cross_attention = [&](int li) {        // ao = attention(q2, layer li of the hoisted K / V^T)
-      if (!ok()) return;
-      mx_attn_problem pr[MX_MAX_SEGS];
-      if (ng > 1) { cross_problems(pr, li); attention_grouped(pr, C, kvp->ldk, C, heads); }
-      else attention(q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride, ao, C, heads, L, ctx_len);
-    };
-    // ---- between the q | k | v projection and the feed-forward: y += attn1, y += attn2, leaving norm3's input form ----
-    // self-attention -> to_out -> residual, then the cross-attention on layer li of the K / V^T of encoder_hidden_states (norm2 in to_q)
-    auto attend = [&](const std::string& b, int li) {
-      if (is_pp()) {
-        if (ok() && !dry && hipMemcpy2DAsync(k_send, (size_t)C * 2, qk + C, (size_t)2 * C * 2, (size_t)C * 2, M, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-          fail("patch-parallel: K pack failed");
-        all_gather(k_send, k_all, (size_t)M * C * 2);
-        all_gather(vt, vt_all, (size_t)B * C * ldvt * 2);
-        if (ok() && !dry &&
-            mx_attention_prescaled_chunked(stream, qk, 2 * C, k_all, C, vt_all, ldvt, (int64_t)C * ldvt, ao, C, B, heads, L, pp_world * L, L,
-                                           (int64_t)L * C, (int64_t)M * C, (int64_t)B * C * ldvt))
-          fail(std::string("attention: ") + mx_last_error());
-      } else self_attention();
-      linear(Linear{ao, C, b + ".attn1.to_out.0", y, C, M, C, C}.plus(y, C).leaves_stats(pass2 ? nullptr : &st));
-      if (pass2) normalise();
-      linear(Linear{pass2 ? ln : y, C, b + ".attn2.to_q", q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(pass2 ? nullptr : &st));
-      cross_attention(li);
-      linear(Linear{ao, C, b + ".attn2.to_out.0", y, C, M, C, C}.plus(y, C).leaves_stats(pass3 ? nullptr : &st, fin3));
-    };
-    // PatchBasicTransformerBlock under a per-patch mask (transformer.py:167-290): the LayerNorms, the q | k | v projection of attn1 and the
-    // feed-forward run on all rows; the self-attention core + to_out and the whole cross-attention run for the asking patches and the
-    // others take the op's cached output (attention.py:59-110, 121-232); then the residual adds
-    std::vector<long> vt_off(pc ? B : 0); std::vector<int> ldvt_s(vt_off.size()), Lk_s(vt_off.size());
-    if (pc) for (int g = 0; g < ng; ++g) for (int i = 0; i < gB[g]; ++i) { const int bb = gb0[g] + i; vt_off[bb] = gvt0[g] + (long)i * C * gldvt[g]; ldvt_s[bb] = gldvt[g]; Lk_s[bb] = gL[g]; }
-    auto attend_masked = [&](const std::string& b, int li) {
-      const int pp2 = (pc_p0 >> level) * (pc_p0 >> level);
-      const int Mc = pc_count() * pp2;
-      char* reg1 = pc_region(level, C);
-      if (!pc_partial) {
-        self_attention();
-        linear(Linear{ao, C, b + ".attn1.to_out.0", ptc, C, M, C, C});
-        pc_store(ptc, reg1, level, C);
-      } else {
-        pc_gather_rows(qk, 2 * C, C, pqc, level);
-        pc_attention(pqc, qk + C, 2 * C, -1, vt, vt_off.data(), ldvt_s.data(), 0, paoc, C, heads, level, Lk_s.data());
-        linear(Linear{paoc, C, b + ".attn1.to_out.0", ptc, C, Mc, C, C});
-        pc_scatter_rows(ptc, C, reg1, level);
-      }
-      // y += attn1's (fresh or cached) output; norm2's statistics come with the merge when to_q runs over all rows
-      const bool stats2 = !pc_partial && !pass2;
-      if (stats2) { pc_load_stats(y, reg1, level, C, y, st.buf, nullptr); st.slabs = 1; }
-      else pc_load(y, reg1, level, C, nullptr, 0, y);
-      char* reg2 = pc_region(level, C);
-      if (!pc_partial) {
-        if (!stats2) normalise();
-        linear(Linear{stats2 ? y : ln, C, b + ".attn2.to_q", q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(stats2 ? &st : nullptr));
-        cross_attention(li);
-        linear(Linear{ao, C, b + ".attn2.to_out.0", ptc, C, M, C, C});
-        pc_store(ptc, reg2, level, C);
-      } else {
-        // the asking rows alone are normalised (the pass over all M rows in front of this gather cost as much as attn2 saved)
-        pc_gather_rows(y, C, C, paoc, level);
-        if (ok() && !quiet() && mx_layernorm(stream, paoc, pqc, nullptr, nullptr, Mc, C, u->cfg.layer_norm_eps)) fail(std::string("layernorm: ") + mx_last_error());
-        linear(Linear{pqc, C, b + ".attn2.to_q", q2, C, Mc, C, C}.scaled(MX_ATTN_QSCALE(0.125f)));
-        if (ok()) {
-          std::vector<long> cvt_off(B); std::vector<int> cld(B, kvp->ldvt), clk(B, ctx_len);
-          for (int bb = 0; bb < B; ++bb) cvt_off[bb] = (long)bb * kvp->vt_bstride;
-          pc_attention(q2, kvp->k + (size_t)li * C, kvp->ldk, (long)ctx_len * kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, cvt_off.data(), cld.data(),
-                       kvp->vt_bstride, paoc, C, heads, level, clk.data());
-        }
-        linear(Linear{paoc, C, b + ".attn2.to_out.0", ptc, C, Mc, C, C});
-        pc_scatter_rows(ptc, C, reg2, level);
-      }
-      // y += attn2's output; norm3's statistics with the merge: finalised for the 256 x 256 GEGLU kernel, one slab for the others
-      if (pc_fin3) pc_load_stats(y, reg2, level, C, y, nullptr, st.fin);
-      else if (!pass3) { pc_load_stats(y, reg2, level, C, y, st.buf, nullptr); st.slabs = 1; }
-      else pc_load(y, reg2, level, C, nullptr, 0, y);
-    };
+    t.kvp = kv_for(C);
+    if (!t.kvp && ok()) fail("no cross-attention K/V buffer for width " + std::to_string(C));
+    if (pc) {
+      t.vt_off.resize(B); t.ldvt_s.resize(B); t.Lk_s.resize(B);
+      for (int g = 0; g < ng; ++g) for (int i = 0; i < gB[g]; ++i) { const int bb = gb0[g] + i; t.vt_off[bb] = t.g.vt0[g] + (long)i * C * t.g.ldvt[g]; t.ldvt_s[bb] = t.g.ldvt[g]; t.Lk_s[bb] = t.g.L[g]; }
+    }
     for (int k = 0; k < layers && ok(); ++k) {
       const std::string b = p + ".transformer_blocks." + std::to_string(k);
-      {   // self-attention's fused q | k | v projection, norm1 folded into it (the hidden state in front of it comes from ordinary GEMMs in every mode)
-        if (pass1) normalise();
-        mx_gemm_desc d = qkv_desc(b, pass1 ? ln : y);
-        if (!pass1) { use_ln(d, st, b + ".attn1.to_qkv.colsum", fin1); if (!fin1) use_ln_grouped(d, st); } else wf(b + ".attn1.to_qkv.colsum", 3 * C);
-        gemm(d, false);
-      }
-      const int li = ok() ? kvp->next++ : 0;
-      if (pc) attend_masked(b, li); else attend(b, li);
-      // GEGLU feed-forward (norm3 in the GEGLU projection)
-      if (!folded3) normalise();
-      linear(Linear{folded3 ? y : ln, C, b + ".ff.net.0.proj", ff, 4 * C, M, 8 * C, C}.epilogue(MX_EPI_GEGLU).folded_ln(folded3 ? &st : nullptr, final3));
-      const bool more = k + 1 < layers;        // the next layer's norm1 reads what ff.net.2 leaves
-      linear(Linear{ff, 4 * C, b + ".ff.net.2", y, C, M, C, 4 * C}.plus(y, C).leaves_stats(more && !pass1 ? &st : nullptr, fin1 && more));
+      qkv(t, b);
+      const int li = ok() ? t.kvp->next++ : 0;
+      if (pc) attend_masked(t, b, li); else attend(t, b, li);
+      feed_forward(t, b, k + 1 < layers ? t.via.norm1 : LnVia::Pass);
     }
-    linear(Linear{y, C, p + ".proj_out", out, C, M, C, C}.plus(x, C));
+    linear(Linear{t.y, C, p + ".proj_out", out, C, M, C, C}.plus(x, C));
     ar.release(m0);
     dump(p, out, (size_t)M * C);
     return out;
@@ -1277,6 +1290,14 @@ extern "C" mx_unet* mx_unet_create(const mx_unet_config* cfg) {
 }
 
 extern "C" void mx_unet_destroy(mx_unet* u) { delete u; }
+
+extern "C" int mx_unet_ln_routes(int M, int C, int layers, int n_groups, int flags, int routes[4]) {
+  MX_CHECK(routes != nullptr && C > 0 && C % 64 == 0 && layers > 0 && n_groups >= 1 && n_groups <= MX_MAX_SEGS && M >= n_groups, "unet_ln_routes: bad arguments");
+  const mx::LnRoutes r = mx::ln_routes(mx::LnRows::even(M, n_groups), C, layers, (flags & MX_LN_ROUTES_PATCH_PARALLEL) != 0, (flags & MX_LN_ROUTES_PATCH_CACHE) != 0,
+                                       (flags & MX_LN_ROUTES_TICKETS) != 0);
+  routes[0] = (int)r.norm1; routes[1] = (int)r.norm2; routes[2] = (int)r.norm3; routes[3] = r.norm3_from_merge ? 1 : 0;
+  return 0;
+}
 
 extern "C" int mx_unet_set_context_key(mx_unet* u, uint64_t key) {
   MX_CHECK(u != nullptr, "unet_set_context_key: null handle");

@@ -253,6 +253,7 @@ SYMBOLS = {
     "mx_gemm_ln_final_supported": (_i, [C.POINTER(GemmDesc)]),
     "mx_gemm_launches": (_i, [C.POINTER(GemmDesc)]),
     "mx_gemm_gn_partials_supported": (_i, [C.POINTER(GemmDesc), _i]),
+    "mx_unet_ln_routes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "mx_gemm_form": (_i, [C.POINTER(GemmDesc), _i]),
     "mx_gemm_kernel_name": (_i, [C.POINTER(GemmDesc), _i, _i, C.c_char_p, _i]),
     "mx_gemm_kernel_names": (_i, [C.c_char_p, _i]),

@@ -146,6 +146,23 @@ def test_unet_full_width_sdxl_batch8(full_width_sdxl):
     _check(got, want_orig, "unet full width 32x32 batch 8, original weights", max_rel=0.06, l2_rel=0.035)
 
 
+def test_unet_full_width_sdxl_finalised_statistics(full_width_sdxl):
+    """the same widths at UNet batch 32 on a 64 x 64 latent (M = 32768 tokens at the 640-wide level, 8192 at the 1280-wide one: the token counts of the
+    benchmark's step): the smallest batch at which the step plan takes the FINALISED row statistics -- norm3 at both widths and norm1 at the 1280-wide
+    level reach their consumers on the 256 x 256 kernel as (mean, rstd) per row from the producing launch (tests/test_ln_routes_cpu.py pins the routes
+    of these token counts), which no other forward of the suite does"""
+    ocfg, _P, held, net = full_width_sdxl
+    inputs = ref.make_inputs(ocfg, 32, 64)
+    s = inputs[0] + 0.3 * torch.randn(inputs[0].shape, generator=torch.Generator().manual_seed(32))      # thirty-two different samples
+    inputs = (s,) + tuple(inputs[1:])
+    got = net.forward_one(s.cuda().to(torch.bfloat16), *(x.cuda() for x in inputs[1:]))
+    assert (got[1].float() - got[0].float()).abs().max() > 0.05 * got[0].float().abs().max()       # the rows differ: a row mix-up cannot pass
+    # samples are independent: the oracle answers the first, the middle and the last of the 32 rows (its two evaluations of all 32 take 120 s on the
+    # GPU; over all 32 the ratio to the stock bf16 figure came out at 0.33 .. 0.90)
+    rows = [0, 15, 31]
+    _calibrated_all_rows(got[rows], held, ocfg, tuple(x[rows] for x in inputs), "unet full width 64x64 batch 32, rows 0 / 15 / 31")
+
+
 def _calibrated_all_rows(got, P, ocfg, inputs, what, ratio=1.5):
     """Round 5 (advisor: "the oracle now checks only the first and last rows"; verdict: calibrate the tolerances): EVERY row against the fp32 oracle evaluated on
     the GPU (the oracle's code by stock torch ops: seconds; agrees with the CPU oracle to 1e-5, tests/test_headline_shapes_gpu.py), and the bound is relative to
