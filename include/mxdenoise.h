@@ -1102,6 +1102,49 @@ int mx_crop_region(int x1, int y1, int x2, int y2, int mask_w, int mask_h, int w
 int mx_rgb8_overlay(void* stream, const uint8_t* decoded, const uint8_t* original, const uint8_t* mask, uint8_t* out, int B, int H, int W, int x, int y,
                     int w, int h);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA adapters merged into the packed weights on the device (lora_merge.hip, lora_terms.cpp; sduss_amd/lora.py builds the tables).
+ * Every packing transform of sduss_amd/weights.py is linear in W, so a low-rank update is applied in packed space: ONE launch walks a table of
+ * terms.  A term covers rows row0 .. row0 + rows of one packed bf16 matrix [N, K] at byte offset w_off of the blob:
+ *     out[n][k] = bf16_rn( f32(base[n][k]) + sum_t scale_t * sum_r up_t[n - row0][r] * down_t[k][r] )
+ * over all terms of the table with the same (w_off, row0, rows), in table order: bf16 MFMA products with fp32 accumulation per term, scale_t
+ * applied in fp32, ONE rounding at the end.  base and out are DIFFERENT buffers with the same layout (the pristine blob and the active one): the
+ * kernel never reads what it writes, so merging a set twice, or after another set, cannot accumulate.  Rows outside the range are not touched.
+ *   up      bf16 [rows, R]  in the packed row order (weights._geglu_interleave applied where the matrix has it)
+ *   down_t  bf16 [K, R]     the down factor TRANSPOSED, so that both MFMA operands are 16-byte loads per lane
+ *   R       a multiple of 32 (the packer pads with zeros), at most MX_LORA_MAX_RANK summed over the terms of one row range
+ * Matrices with a folded LayerNorm (attn1.to_qkv, attn2.to_q, ff.net.0.proj: weights.fold_layernorm) carry two derived fp32 vectors, written by the
+ * same launch where colsum_off != MX_LORA_NO_VECTOR:
+ *     colsum[n] = the fp32 sum over k of the ROUNDED out[n][k] just stored (a workgroup owns whole rows: no atomics, the same bits every run)
+ *     bias[n]   = bias_base[n] + sum_t scale_t * dbias_t[n - row0]           (dbias fp32 [rows]; a null dbias adds nothing)
+ * at byte offsets colsum_off / bias_off of the blobs (vectors of N entries, indexed by the row n of the matrix).
+ * The divisibility rule of the tiling: row0 % 16 == 0, rows % 16 == 0, rows > 0, K % 64 == 0, K > 0, R % 32 == 0, R > 0; every linear of SDXL-base
+ * and of UNetConfig.tiny() satisfies it (widths 64 .. 1280 and their multiples, context 128 / 2048).  Offsets: w_off a multiple of 16 bytes,
+ * vector offsets multiples of 4; up / down_t 16-byte aligned, dbias 4-byte aligned.
+ * mx_lora_merge_validate (host only, no GPU) returns 0, or 1 with the reason in the last error: a null table with n > 0, a term outside the blob
+ * (matrix or vectors), a shape outside the rule, a null or misaligned operand, a non-finite scale, row ranges of two terms of one matrix that
+ * overlap without being identical (identical ranges are stacked adapters and must then agree in N, K and the vector offsets), a row range whose ranks
+ * sum to more than MX_LORA_MAX_RANK.  n == 0 is valid and launches nothing.
+ * mx_lora_merge validates, builds the device table in `table_dev` (caller-provided device memory of at least mx_lora_table_bytes(n) bytes; nothing
+ * is allocated inside the call), copies it on `stream` and launches one grid over (row range, row block).  It waits for the stream once, before the
+ * launch, so that the table has left host memory when the call returns. */
+#define MX_LORA_NO_VECTOR (~(uint64_t)0)
+#define MX_LORA_MAX_RANK 512
+typedef struct mx_lora_term {
+  uint64_t w_off;             /* byte offset of the packed matrix [N, K] in the blob */
+  int N, K, row0, rows;
+  const void* up;             /* device, bf16 [rows, R] */
+  const void* down_t;         /* device, bf16 [K, R] */
+  int R;
+  float scale;
+  uint64_t colsum_off, bias_off;   /* MX_LORA_NO_VECTOR (both) where the matrix has no folded LayerNorm */
+  const float* dbias;         /* device, fp32 [rows], or NULL */
+} mx_lora_term;
+int mx_lora_merge_validate(const mx_lora_term* t, int n, uint64_t blob_bytes);   /* host only */
+size_t mx_lora_table_bytes(int n);                                               /* host only; 0 for n < 0 */
+int mx_lora_merge(void* stream, const void* base_blob, void* active_blob, uint64_t blob_bytes, const mx_lora_term* terms, int n, void* table_dev,
+                  size_t table_bytes);
+
 #ifdef __cplusplus
 }
 #endif

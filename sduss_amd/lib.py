@@ -194,6 +194,17 @@ class MultistepRows(C.Structure):
     _fields_ = [("kind", C.c_void_p), ("coef", C.c_void_p), ("hist", C.c_void_p)]
 
 
+LORA_NO_VECTOR = (1 << 64) - 1       # MX_LORA_NO_VECTOR
+LORA_MAX_RANK = 512                  # MX_LORA_MAX_RANK
+
+
+class LoraTerm(C.Structure):
+    """mx_lora_term: one low-rank update of a row range of one packed matrix"""
+    _fields_ = [("w_off", C.c_uint64), ("N", C.c_int), ("K", C.c_int), ("row0", C.c_int), ("rows", C.c_int), ("up", C.c_void_p),
+                ("down_t", C.c_void_p), ("R", C.c_int), ("scale", C.c_float), ("colsum_off", C.c_uint64), ("bias_off", C.c_uint64),
+                ("dbias", C.c_void_p)]
+
+
 class WeightEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -337,6 +348,9 @@ SYMBOLS = {
     "mx_mask_bbox_u8": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "mx_crop_region": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "mx_rgb8_overlay": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "mx_lora_merge_validate": (_i, [C.POINTER(LoraTerm), _i, C.c_uint64]),
+    "mx_lora_table_bytes": (_sz, [_i]),
+    "mx_lora_merge": (_i, [_vp, _vp, _vp, C.c_uint64, C.POINTER(LoraTerm), _i, _vp, _sz]),
 }
 
 _lib: Optional[C.CDLL] = None

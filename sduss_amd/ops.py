@@ -1,5 +1,5 @@
 """Thin torch-tensor wrappers over the per-kernel entry points of the C ABI (mx_gemm, mx_conv3x3, mx_conv3x3_rgb8, mx_conv3x3_rgb_in, mx_attention,
-mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the multistep samplers, the inpainting entries, the image resize, the mask blur / bounding box / overlay).  They allocate outputs with torch and pass raw pointers + the current
+mx_layernorm, mx_groupnorm_nhwc, scheduler steps, the multistep samplers, the inpainting entries, the image resize, the mask blur / bounding box / overlay, the LoRA merge).  They allocate outputs with torch and pass raw pointers + the current
 stream; nothing is computed in Python.  Used by the parity tests and by ``pipeline.py``."""
 from __future__ import annotations
 
@@ -792,3 +792,54 @@ def rgb8_overlay(decoded: torch.Tensor, original: torch.Tensor, mask: torch.Tens
         _lib.check(l.mx_rgb8_overlay(_lib.current_stream(), decoded.data_ptr(), original.data_ptr(), mask.data_ptr(), out.data_ptr(), b, hh, ww,
                                      int(x), int(y), w, h), "mx_rgb8_overlay")
     return out
+
+
+def lora_terms(terms) -> "C.Array":
+    """a list of term dicts -> the mx_lora_term array (the tensors stay referenced by the caller).  Keys: w_off, N, K, up (bf16 [rows, R]),
+    down_t (bf16 [K, R]), scale; optional row0 (0), rows (N), colsum_off / bias_off (byte offsets of the folded matrix's fp32 vectors), dbias
+    (fp32 [rows]).  Tensors may also be given as raw device addresses (ints), then with an explicit R."""
+    arr = (_lib.LoraTerm * max(len(terms), 1))()
+    for i, t in enumerate(terms):
+        a = arr[i]
+        a.w_off, a.N, a.K = int(t["w_off"]), int(t["N"]), int(t["K"])
+        a.row0 = int(t.get("row0", 0))
+        a.rows = int(t.get("rows", a.N - a.row0))
+        up, down_t, dbias = t["up"], t["down_t"], t.get("dbias")
+        if torch.is_tensor(up):
+            _need(up.dtype == torch.bfloat16 and down_t.dtype == torch.bfloat16 and up.is_contiguous() and down_t.is_contiguous()
+                  and up.ndim == 2 and down_t.ndim == 2 and up.shape == (a.rows, down_t.shape[1]) and down_t.shape[0] == a.K,
+                  f"mx_lora_merge: term {i}: up must be bf16 [rows, R] and down_t bf16 [K, R], got {tuple(up.shape)} and {tuple(down_t.shape)}")
+            _need(dbias is None or (dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.shape == (a.rows,)),
+                  f"mx_lora_merge: term {i}: dbias must be fp32 [rows]")
+            a.R = int(t.get("R", up.shape[1]))
+            a.up, a.down_t, a.dbias = up.data_ptr(), down_t.data_ptr(), _p(dbias)
+        else:
+            a.R, a.up, a.down_t, a.dbias = int(t["R"]), up, down_t, dbias
+        a.scale = float(t["scale"])
+        cs, bs = t.get("colsum_off"), t.get("bias_off")
+        a.colsum_off = _lib.LORA_NO_VECTOR if cs is None else int(cs)
+        a.bias_off = _lib.LORA_NO_VECTOR if bs is None else int(bs)
+    return arr
+
+
+def lora_merge_validate(terms, blob_bytes: int) -> None:
+    """mx_lora_merge_validate (host only): raises MxError with the library's reason for a table the merge would refuse"""
+    _lib.check(_lib.load().mx_lora_merge_validate(lora_terms(terms), len(terms), int(blob_bytes)), "mx_lora_merge_validate")
+
+
+def lora_merge(base: torch.Tensor, out: torch.Tensor, terms, table: Optional[torch.Tensor] = None) -> None:
+    """out[rows of every term] = bf16(base + sum scale * up down_t^T) in ONE launch (mx_lora_merge): ``base`` and ``out`` are two blobs of the same
+    size (any dtype, viewed as bytes; every offset of a term counts from their first byte), ``terms`` as lora_terms takes them.  ``table``: a uint8
+    device buffer of at least mx_lora_table_bytes(len(terms)) bytes to reuse; allocated here when None."""
+    l = _lib.load()
+    _need(base.is_cuda and out.is_cuda and base.is_contiguous() and out.is_contiguous() and base.device == out.device,
+          "mx_lora_merge: base and out must be contiguous CUDA tensors on one device")
+    nbytes = base.numel() * base.element_size()
+    _need(out.numel() * out.element_size() == nbytes, "mx_lora_merge: base and out differ in size")
+    arr = lora_terms(terms)
+    with torch.cuda.device(base.device):
+        need = l.mx_lora_table_bytes(len(terms))
+        if table is None:
+            table = torch.empty(max(need, 16), dtype=torch.uint8, device=base.device)
+        _lib.check(l.mx_lora_merge(_lib.current_stream(), base.data_ptr(), out.data_ptr(), nbytes, arr, len(terms), table.data_ptr(), table.numel()),
+                   "mx_lora_merge")

@@ -8,14 +8,26 @@ PyTorch is used for device memory and the current stream only; every FLOP runs i
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import lib as _lib
 from .config import UNetConfig
 from .model_slot import ModelSlot, _Config
+from .lora import LoraAdapter, LoraLayout, norm_params, scaled_terms
 from .weights import pack
+
+
+class _LoraState:
+    """what MxUNet.set_adapters keeps between calls"""
+
+    def __init__(self, norms):
+        self.norms = norms          # gamma / beta of the folded LayerNorms (the blob no longer holds them)
+        self.layout = None          # LoraLayout of this model's blob, built on first use
+        self.active = None          # the active blob: base + the current adapter set
+        self.dirty = {}             # {row range key: byte spans} the active blob differs from the base in
+        self.table = None           # device memory for the merge's term table, grow-only
 
 
 class MxUNet(ModelSlot):
@@ -48,6 +60,7 @@ class MxUNet(ModelSlot):
         cc.norm_num_groups = cfg.norm_num_groups
         cc.norm_eps, cc.transformer_norm_eps, cc.layer_norm_eps = cfg.norm_eps, cfg.transformer_norm_eps, cfg.layer_norm_eps
         super().__init__(cfg, cc, pack(cfg, params), device)
+        self._lora = _LoraState(norm_params(params))
         self._next_ctx_key = 0             # set_context_key: names the batch composition of the NEXT forward only
         self.config = _Config(in_channels=cfg.in_channels, time_cond_proj_dim=None,
                               addition_time_embed_dim=cfg.addition_time_embed_dim,
@@ -118,6 +131,55 @@ class MxUNet(ModelSlot):
         assert added_cond_kwargs is not None, "SDXL needs added_cond_kwargs (text_embeds, time_ids)"
         return self._route(sample, timestep, (encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]),
                            is_sliced, patch_size, input_indices)
+
+    # ---- LoRA adapters (sduss_amd/lora.py; mx_lora_merge) ---------------------------------------------
+    def _point_at(self, blob: torch.Tensor) -> None:
+        _lib.check(self._lib.mx_unet_set_weights(self._handle, blob.data_ptr(), blob.numel(), self.weights.table, len(self.weights.names)),
+                   "mx_unet_set_weights")
+
+    def set_adapters(self, adapters: Sequence[Tuple[LoraAdapter, float]]) -> None:
+        """Serve with ``W + sum scale_i (alpha_i / r_i) B_i A_i`` from now on: ``adapters`` = [(LoraAdapter, scale), ...], an empty list = none.
+        The first call allocates the ACTIVE blob as a copy of the packed weights (the base stays pristine).  Every call brings the active blob to
+        exactly the state a fresh copy of the base plus ONE merge of this set has: row ranges and their derived vectors that the previous set
+        changed and this one does not target are copied back from the base, then one launch (mx_lora_merge) rewrites the targeted ranges from
+        the base, so sets never accumulate.  The handle is then pointed at the active blob (mx_unet_set_weights), which drops the stored
+        cross-attention K / V^T and captured graphs.  Runs on the current stream.
+        The set belongs to the SLOT: change it between batches, never under requests in flight (their remaining steps would run with other
+        weights).  An enabled block-skip cache holds activations made with the old weights: the caller resets it (``disable_block_cache`` /
+        ``enable_block_cache``)."""
+        from . import ops
+        st = self._lora
+        if st.layout is None:
+            st.layout = LoraLayout(self.cfg, self.weights.names, st.norms, self.device)
+        base = self.weights.blob
+        terms = scaled_terms(st.layout, adapters)
+        ops.lora_merge_validate(terms, base.numel())         # refuse before anything is touched
+        if not terms and st.active is None:
+            return
+        with torch.cuda.device(self.device):
+            if st.active is None:
+                st.active = base.clone()
+            new = {}
+            for t in terms:
+                spans = [(t["w_off"] + t["row0"] * t["K"] * 2, t["rows"] * t["K"] * 2)]
+                if "colsum_off" in t:
+                    spans += [(t["colsum_off"] + 4 * t["row0"], 4 * t["rows"]), (t["bias_off"] + 4 * t["row0"], 4 * t["rows"])]
+                new[(t["w_off"], t["row0"], t["rows"])] = spans
+            for key, spans in st.dirty.items():
+                if key not in new:
+                    for off, nb in spans:
+                        st.active[off:off + nb].copy_(base[off:off + nb])
+            need = self._lib.mx_lora_table_bytes(len(terms))
+            if st.table is None or st.table.numel() < need:
+                st.table = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            ops.lora_merge(base, st.active, terms, table=st.table)
+            st.dirty = new
+        self._point_at(st.active if terms else base)
+
+    def clear_adapters(self) -> None:
+        """Serve the base weights again: the handle points back at the base blob (the active blob is kept for the next set)."""
+        if self._lora.active is not None:
+            self._point_at(self.weights.blob)
 
     def enable_block_cache(self, down, up=None, forced_after: Optional[int] = None, observe: bool = False) -> None:
         """Route forward() through the block-skip cache, one state per resolution key: what ESYMRED_USE_CACHE=TRUE does to the
