@@ -260,6 +260,17 @@ int mx_attention_kernel_names(char* buf, int cap);
  * (buffer of M * MX_STATS_PITCH(1) * 2 floats) */
 int mx_row_stats(void* stream, const void* x, int ldx, float* stats, int M, int C);
 int mx_conv3x3(void* stream, const mx_gemm_desc* d);   /* implicit GEMM, pad 1 */
+/* The same conv with the input staged once per 64-channel chunk (csrc/conv_halo.hip; an operator of its own, not a route of mx_conv3x3): a tile is
+ * 256 output pixels = whole image rows x 160 features, K runs chunk-major, and the nine taps of a chunk read one staged (rows + 2) x width tile of
+ * 128-byte pixel lines instead of nine copies of it.  Same products, fp32 accumulation and epilogue (bias, row bias, residual, gn_part_out) as the
+ * 256-row tile of mx_conv3x3; the order in which a pixel's products are added differs, so last bits may.
+ * mx_conv3x3_halo_serves (host only, needs no device): the LDS bytes of the launch when ALL of these hold, else 0 -- one resolution group (n_segs 0);
+ * stride 1, up 0, vhalo 0, corner_patch 0; Cin % 64 == 0, Cin <= 8192, K == 9 Cin, cin_valid 0; N % 160 == 0; image width 32 or 64; Hin Win % 256 == 0;
+ * flags 0, no gate, out_scale 0, splitk <= 1; 16-byte aligned operands with ldc % 8 == 0 (and ldr % 8 == 0 with a residual); and (width, Cin, N) is
+ * not one of the two shapes that did not count as faster in the per-shape A/B (profiles/conv_halo_ab.txt): (32, 640, 1280), (64, 320, 640).
+ * mx_conv3x3_halo fails on a descriptor it does not serve: the caller asks first and runs mx_conv3x3 otherwise. */
+int mx_conv3x3_halo_serves(const mx_gemm_desc* d);
+int mx_conv3x3_halo(void* stream, const mx_gemm_desc* d);
 /* Slices the K range of d is dealt to (1 = no split).  Small launches -- fewer 128-row tiles than CUs and >= 16 K tiles: one request, light mixed
  * batches -- run SPLIT-K: every output tile is computed by up to 4 workgroups over disjoint K ranges; each leaves its fp32 partial tile in a
  * library-owned scratch (96 MB + counters per stream, allocated at a stream's first split launch -- also while that stream is being captured:

@@ -442,6 +442,14 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     }
     if (c.gn_part && c.gn_done && ng == 1 && mx_gemm_gn_partials_supported(&d, 1)) { d.gn_part_out = c.gn_part; *c.gn_done = true; }
     d.cin_valid = conv_cin_valid;             // (conv_in only: the latent's channels inside its zero-padded rows)
+    // whole image rows per tile, the input staged once per channel chunk (conv_halo.hip) -- where the launch would otherwise run the same 256-row tile:
+    // a small launch stays on the 128-row tiles and their split-K, which fill more CUs
+    if (mx_conv3x3_halo_serves(&d) && mx_gemm_form(&d, 1) == MX_FORM_TILE_256) {
+      if (!ok()) return false;
+      if (quiet()) return true;
+      if (mx_conv3x3_halo(stream, &d)) return fail(std::string("conv3x3_halo: ") + mx_last_error());
+      return true;
+    }
     return gemm(d, true);
   }
   bool groupnorm(const bf16_t* x, bf16_t* y, const std::string& prefix, int h, int wd, int C, float eps, bool silu, int patch,
