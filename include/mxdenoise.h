@@ -860,6 +860,55 @@ typedef struct mx_skip_decide_args {
 int mx_skip_decide_device(void* stream, const mx_skip_decide_args* args);
 
 /* ------------------------------------------------------------------------------------------
+ * Block-skip cache kernels, one launch each (tests and tools).  The step plans call the launchers of sduss_amd/csrc/patch_cache.hip and
+ * elementwise.hip directly; these wrappers start exactly one of them on caller-made tables, so that every kernel that moves the cache's
+ * state can be checked alone (tests/test_cache_move_gpu.py).  Every pointer is device memory, activations and state are bf16 with C % 8 == 0
+ * (16-byte vectors).  Nothing is allocated, copied or synchronised inside a call.  Returns 0, or 1 with the reason in the last error (a null
+ * operand, a shape the launcher refuses, a failed launch).
+ *
+ * Geometry: samples are described at LEVEL 0 (latent resolution) and every call takes the level of its tensor: image (h >> level) x
+ * (w >> level), first row row0 >> 2 level, patch edge p0 >> level.  A state tensor holds one row of state_row_elems elements per REQUEST; a
+ * sample's row is its slot.  Batch tensors are NHWC / token-major with the samples' images one after the other.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mx_pc_sample { long long row0; int h, w, slot, npx; } mx_pc_sample;   /* first level-0 row, latent size, state row, patches per image row */
+typedef struct mx_pc_patch { int b, py, px, pad; } mx_pc_patch;                      /* sample, patch row, patch column */
+typedef struct mx_pc_range { long long row0; int rows, slot, srow0; } mx_pc_range;   /* batch rows [row0, row0 + rows) <-> rows [srow0, ...) of state row `slot` */
+/* Every sample's image between the batch tensor and its state row.  to_batch = 0: state <- batch.  to_batch = 1: batch <- state, optionally
+ * (fp32, one rounding to bf16) + vec[i][c] (gate = 0) or * vec[i][c] (gate = 1) with i the sample's POSITION in the table and ldvec floats
+ * between positions, then + residual (a batch tensor).  max_image_elems: elements of the largest image at this level (sizes the grid). */
+int mx_pc_image_copy(void* stream, void* batch, void* state, const mx_pc_sample* samples, int n_samples, int level, int C, int64_t state_row_elems,
+                     int to_batch, const float* vec, int ldvec, const void* residual, int64_t max_image_elems, int gate);
+/* batch <- bf16(state + residual) token row by token row, with the statistics of the stored values: stats1[m][8] floats, of which [0..1] =
+ * (sum, sum of squares) are written, and / or fin[m][2] = (mean, rsqrt(max(var, 0) + eps)); m = the row of the batch tensor. */
+int mx_pc_rows_load_stats(void* stream, void* batch, const void* state, const mx_pc_sample* samples, int n_samples, int level, int C,
+                          int64_t state_row_elems, const void* residual, float* stats1, float* fin, float eps, int64_t max_image_rows);
+/* The listed patches of a whole-image tensor (row stride ld_src >= C) -> dst [n][P][P][C], P = p + halo_lo + halo_hi: the patch, halo rows from
+ * the vertical neighbours, halo columns AND corners from the horizontal neighbour's pixel of the patch's own first / last row, zeros at the
+ * image border; (halo_lo, halo_hi) = (0, 0), (1, 1) or (2, 0), the last with an outer ring of zeros in front; up = 1: src holds the image at
+ * half the size and is read through a nearest 2x upsample (p is the patch edge AFTER it). */
+int mx_pc_gather(void* stream, const void* src, int ld_src, int C, void* dst, const mx_pc_patch* list, int n, const mx_pc_sample* samples, int level,
+                 int p, int halo_lo, int halo_hi, int up);
+/* src [n][Ps][Ps][C]: the p x p pixels from (o0, o0) of every compact patch -> the patch's place in its request's state row */
+int mx_pc_scatter(void* stream, const void* src, int Ps, int o0, int C, void* state, int64_t state_row_elems, const mx_pc_patch* list, int n,
+                  const mx_pc_sample* samples, int level, int p);
+/* the listed patches of a whole-image batch tensor -> their places in the state rows */
+int mx_pc_patch_store(void* stream, const void* batch, void* state, int64_t state_row_elems, int C, const mx_pc_patch* list, int n,
+                      const mx_pc_sample* samples, int level, int p);
+/* partial[patch][row] (n * p doubles) = sum over the patch's pixel row of (x - state)^2 */
+int mx_pc_patch_sq_diff(void* stream, const void* x, const void* state, int64_t state_row_elems, int C, const mx_pc_patch* list, int n,
+                        const mx_pc_sample* samples, int level, int p, double* partial);
+/* token ranges between a batch tensor and state rows (to_batch = 1: batch <- state); max_range_elems sizes the grid */
+int mx_pc_range_copy(void* stream, void* batch, void* state, int64_t state_row_elems, int C, const mx_pc_range* ranges, int n, int to_batch,
+                     int64_t max_range_elems);
+/* partial[range][64]: the range's rows * C / 8 vectors are cut into 64 chunks of ceil(vectors / 64); each gets its sum of (x - state)^2 */
+int mx_pc_range_sq_diff(void* stream, const void* x, const void* state, int64_t state_row_elems, int C, const mx_pc_range* ranges, int n,
+                        double* partial);
+/* The per-request pair (elementwise.hip).  partial[i][64] = the chunk sums of (a[i] - b[slot ? slot[i] : i])^2 over rows of elems_per_sample. */
+int mx_sq_diff_partial(void* stream, const void* a, const void* b, int64_t elems_per_sample, int n_samples, double* partial, const int32_t* slot);
+/* rows of bytes_per_sample (a multiple of 16): scatter = 1: slotted[slot[i]] <- batch[i]; 0: batch[i] <- slotted[slot[i]]; slot[i] < 0: not touched */
+int mx_copy_rows(void* stream, void* batch, void* slotted, size_t bytes_per_sample, int n_samples, const int32_t* slot, int scatter);
+
+/* ------------------------------------------------------------------------------------------
  * The element-wise steps either side of the model call.
  * ------------------------------------------------------------------------------------------ */
 /* out[b] = x[b mod n_lat] / sqrt(sigma[b mod n_lat]^2 + 1) for b in [0, n_rows)   (batch_scale_model_input, CFG

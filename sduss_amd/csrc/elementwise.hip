@@ -428,6 +428,15 @@ int launch_copy_rows(hipStream_t s, void* batch, void* slotted, size_t bytes_per
   return 0;
 }
 }  // namespace mx
+// one launch each on caller-made operands (include/mxdenoise.h: "Block-skip cache kernels, one launch each")
+extern "C" int mx_sq_diff_partial(void* stream, const void* a, const void* b, int64_t elems_per_sample, int n_samples, double* partial, const int32_t* slot) {
+  MX_CHECK(a && b && partial && n_samples > 0 && elems_per_sample > 0, "sq_diff_partial: null operand or empty shape");
+  return mx::launch_sq_diff_partial((hipStream_t)stream, a, b, (long)elems_per_sample, n_samples, partial, slot);
+}
+extern "C" int mx_copy_rows(void* stream, void* batch, void* slotted, size_t bytes_per_sample, int n_samples, const int32_t* slot, int scatter) {
+  MX_CHECK(batch && slotted && n_samples > 0 && bytes_per_sample > 0, "copy_rows: null operand or empty shape");
+  return mx::launch_copy_rows((hipStream_t)stream, batch, slotted, bytes_per_sample, n_samples, slot, scatter);
+}
 
 // ------------------------------------------------------------------------------------------
 // The last launch of the VAE encoder (vae_sdxl.cpp, EncodePlan): moments -> the latents a request starts from.

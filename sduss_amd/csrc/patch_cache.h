@@ -6,9 +6,10 @@
 namespace mx {
 // level-0 description of a sample of the batch: first row of its image in the concatenated level-0 activations, latent size, its row of the state
 // tensors (one per request), patches per image row.  At level l: image (h >> l) x (w >> l), first row row0 >> 2l, patch edge p0 >> l.
-struct PcSample { long long row0; int h, w, slot, npx; };
-struct PcPatch { int b, py, px, pad; };
-struct PcRange { long long row0; int rows, slot, srow0; };     // rows [row0, row0 + rows) of a batch tensor <-> rows [srow0, ...) of state row `slot`
+// The tables are the public ones of include/mxdenoise.h (the one-launch entry points take them as they are).
+using PcSample = mx_pc_sample;   // { long long row0; int h, w, slot, npx; }
+using PcPatch = mx_pc_patch;     // { int b, py, px, pad; }
+using PcRange = mx_pc_range;     // { long long row0; int rows, slot, srow0; }: rows [row0, row0 + rows) of a batch tensor <-> rows [srow0, ...) of state row `slot`
 
 int launch_pc_image_copy(hipStream_t st, void* batch, void* state, const void* samp, int B, int level, int C, long state_row_elems, int to_batch,
                          const float* vec, int ldvec, const void* residual, long max_image_elems, int gate = 0);

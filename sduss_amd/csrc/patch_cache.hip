@@ -367,3 +367,48 @@ extern "C" int mx_skip_decide_device(void* stream, const mx_skip_decide_args* ar
   MX_CHECK(args != nullptr, "skip_decide_device: null arguments");
   return mx::launch_pc_decide((hipStream_t)stream, *args);
 }
+
+// ---- one launch each (include/mxdenoise.h: "Block-skip cache kernels, one launch each"): the launchers above on caller-made tables ----
+extern "C" int mx_pc_image_copy(void* stream, void* batch, void* state, const mx_pc_sample* samples, int n_samples, int level, int C, int64_t state_row_elems,
+                                int to_batch, const float* vec, int ldvec, const void* residual, int64_t max_image_elems, int gate) {
+  MX_CHECK(batch && state && samples && level >= 0, "pc_image_copy: null operand");
+  return mx::launch_pc_image_copy((hipStream_t)stream, batch, state, samples, n_samples, level, C, (long)state_row_elems, to_batch, vec, ldvec, residual,
+                                  (long)max_image_elems, gate);
+}
+extern "C" int mx_pc_rows_load_stats(void* stream, void* batch, const void* state, const mx_pc_sample* samples, int n_samples, int level, int C,
+                                     int64_t state_row_elems, const void* residual, float* stats1, float* fin, float eps, int64_t max_image_rows) {
+  MX_CHECK(batch && state && samples && level >= 0, "pc_rows_load_stats: null operand");
+  return mx::launch_pc_rows_load_stats((hipStream_t)stream, batch, state, samples, n_samples, level, C, (long)state_row_elems, residual, stats1, fin, eps,
+                                       (long)max_image_rows);
+}
+extern "C" int mx_pc_gather(void* stream, const void* src, int ld_src, int C, void* dst, const mx_pc_patch* list, int n, const mx_pc_sample* samples, int level,
+                            int p, int halo_lo, int halo_hi, int up) {
+  MX_CHECK(src && dst && list && samples && level >= 0, "pc_gather: null operand");
+  MX_CHECK(ld_src >= C && halo_lo >= 0 && halo_lo <= 2 && halo_hi >= 0 && halo_hi <= 1 && (up == 0 || up == 1), "pc_gather: bad halo or row stride");
+  return mx::launch_pc_gather((hipStream_t)stream, src, ld_src, C, dst, list, n, samples, level, p, halo_lo, halo_hi, up);
+}
+extern "C" int mx_pc_scatter(void* stream, const void* src, int Ps, int o0, int C, void* state, int64_t state_row_elems, const mx_pc_patch* list, int n,
+                             const mx_pc_sample* samples, int level, int p) {
+  MX_CHECK(src && state && list && samples && level >= 0, "pc_scatter: null operand");
+  return mx::launch_pc_scatter((hipStream_t)stream, src, Ps, o0, C, state, (long)state_row_elems, list, n, samples, level, p);
+}
+extern "C" int mx_pc_patch_store(void* stream, const void* batch, void* state, int64_t state_row_elems, int C, const mx_pc_patch* list, int n,
+                                 const mx_pc_sample* samples, int level, int p) {
+  MX_CHECK(batch && state && list && samples && level >= 0, "pc_patch_store: null operand");
+  return mx::launch_pc_patch_store((hipStream_t)stream, batch, state, (long)state_row_elems, C, list, n, samples, level, p);
+}
+extern "C" int mx_pc_patch_sq_diff(void* stream, const void* x, const void* state, int64_t state_row_elems, int C, const mx_pc_patch* list, int n,
+                                   const mx_pc_sample* samples, int level, int p, double* partial) {
+  MX_CHECK(x && state && list && samples && partial && level >= 0, "pc_patch_sq_diff: null operand");
+  return mx::launch_pc_patch_sq_diff((hipStream_t)stream, x, state, (long)state_row_elems, C, list, n, samples, level, p, partial);
+}
+extern "C" int mx_pc_range_copy(void* stream, void* batch, void* state, int64_t state_row_elems, int C, const mx_pc_range* ranges, int n, int to_batch,
+                                int64_t max_range_elems) {
+  MX_CHECK(batch && state && ranges, "pc_range_copy: null operand");
+  return mx::launch_pc_range_copy((hipStream_t)stream, batch, state, (long)state_row_elems, C, ranges, n, to_batch, (long)max_range_elems);
+}
+extern "C" int mx_pc_range_sq_diff(void* stream, const void* x, const void* state, int64_t state_row_elems, int C, const mx_pc_range* ranges, int n,
+                                   double* partial) {
+  MX_CHECK(x && state && ranges && partial, "pc_range_sq_diff: null operand");
+  return mx::launch_pc_range_sq_diff((hipStream_t)stream, x, state, (long)state_row_elems, C, ranges, n, partial);
+}

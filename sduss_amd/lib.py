@@ -131,6 +131,21 @@ class SkipDecideArgs(C.Structure):
                 ("run", C.c_void_p), ("ask_units", C.c_void_p), ("ask_index", C.c_void_p), ("record", C.c_void_p)]
 
 
+class PcSample(C.Structure):
+    """mx_pc_sample: a sample of the batch at level 0 (first row, latent size, state row, patches per image row)"""
+    _fields_ = [("row0", C.c_longlong), ("h", C.c_int), ("w", C.c_int), ("slot", C.c_int), ("npx", C.c_int)]
+
+
+class PcPatch(C.Structure):
+    """mx_pc_patch: patch (py, px) of sample b"""
+    _fields_ = [("b", C.c_int), ("py", C.c_int), ("px", C.c_int), ("pad", C.c_int)]
+
+
+class PcRange(C.Structure):
+    """mx_pc_range: rows [row0, row0 + rows) of a batch tensor <-> rows [srow0, ...) of state row `slot`"""
+    _fields_ = [("row0", C.c_longlong), ("rows", C.c_int), ("slot", C.c_int), ("srow0", C.c_int)]
+
+
 class BlockCacheC(C.Structure):
     _fields_ = [("predict", SKIP_PREDICT_FN), ("ctx", C.c_void_p), ("state", C.c_void_p), ("state_bytes", C.c_size_t),
                 ("batch_key", C.c_uint64), ("cached_key", C.c_uint64), ("cached_valid", C.c_int), ("cached_batch", C.c_int),
@@ -254,6 +269,17 @@ SYMBOLS = {
     "mx_skip_counters_bytes": (_sz, [_i, _i, _i]),
     "mx_skip_decide_host": (_i, [C.POINTER(DeviceForestC), _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mx_skip_decide_device": (_i, [_vp, C.POINTER(SkipDecideArgs)]),
+    # the block-skip cache's kernels, one launch each (tests and tools): tables as device pointers
+    "mx_pc_image_copy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp, _i, _vp, _i64, _i]),
+    "mx_pc_rows_load_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _f, _i64]),
+    "mx_pc_gather": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
+    "mx_pc_scatter": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _i, _vp, _i, _i]),
+    "mx_pc_patch_store": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _vp, _i, _i]),
+    "mx_pc_patch_sq_diff": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _vp, _i, _i, _vp]),
+    "mx_pc_range_copy": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _i, _i64]),
+    "mx_pc_range_sq_diff": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _vp]),
+    "mx_sq_diff_partial": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "mx_copy_rows": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _i]),
     "mx_mmdit_workspace_bytes_pp": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_pp_state_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_forward_pp": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz]),
