@@ -271,6 +271,14 @@ int mx_conv3x3(void* stream, const mx_gemm_desc* d);   /* implicit GEMM, pad 1 *
  * mx_conv3x3_halo fails on a descriptor it does not serve: the caller asks first and runs mx_conv3x3 otherwise. */
 int mx_conv3x3_halo_serves(const mx_gemm_desc* d);
 int mx_conv3x3_halo(void* stream, const mx_gemm_desc* d);
+/* The same kernel for images 128 pixels wide, where two whole rows do not fit its staged buffers: a tile is HALF a block of rows, 4 output rows x
+ * 64 columns at column 0 or 64, staged like a 64-wide tile from an image whose rows are 128 pixels apart, plus the one neighbouring column of the
+ * other half (6 more lines per staged buffer); the outer column is the image edge (zeros).  Same arithmetic and epilogue as mx_conv3x3_halo.
+ * mx_conv3x3_halfrow_serves (host only, needs no device): the LDS bytes of the launch when the conditions of mx_conv3x3_halo_serves hold with
+ * image width 128 and Hin % 4 == 0 in place of its width and Hin Win % 256 conditions (no shape is excluded by the per-shape A/B,
+ * profiles/conv_halfrow_ab.txt), else 0.  mx_conv3x3_halfrow fails on a descriptor it does not serve: ask first, run mx_conv3x3 otherwise. */
+int mx_conv3x3_halfrow_serves(const mx_gemm_desc* d);
+int mx_conv3x3_halfrow(void* stream, const mx_gemm_desc* d);
 /* Slices the K range of d is dealt to (1 = no split).  Small launches -- fewer 128-row tiles than CUs and >= 16 K tiles: one request, light mixed
  * batches -- run SPLIT-K: every output tile is computed by up to 4 workgroups over disjoint K ranges; each leaves its fp32 partial tile in a
  * library-owned scratch (96 MB + counters per stream, allocated at a stream's first split launch -- also while that stream is being captured:

@@ -19,6 +19,20 @@
 //     gemm_bf16_v5.hip.  Every wave's counted wait in the load phase of tap 8 covers its pieces, one barrier before either group reads them;
 //   * weights keep their packed (kh, kw, cin) order: the K tile of (chunk c, tap t) starts at column t Cin + 64 c.
 //
+//
+// HALF (images 128 pixels wide): two whole rows would stage 4 x 128 lines = 64 KB per buffer, and two such buffers do not fit beside the weight ring.
+// A tile is then a HALF ROW BLOCK: 4 output rows x 64 columns at column origin xo = 0 or 64 -- the staged geometry, tap offsets and swizzle keys of the
+// W = 64 form, read from an image whose row stride is 128 pixels (row tile tm = 2 (block of 4 rows) + half).  One of the two side columns is now a real
+// neighbour (column 63 for the right half, 64 for the left half), the other is still the image edge:
+//   * per staged buffer 8 more lines (1 KB): SIDE line s holds the neighbour column's pixel of staged row s (6 lines; 2 of padding), staged once per
+//     chunk by ONE LDS-DMA instruction of wave 0 in the load phase of tap 3 (no other piece is dealt there), whose spare lanes fetch zero-page bytes;
+//     that wave counts one more outstanding DMA in that phase's wait.  A side line carries the swizzle key of the staged line it stands in for
+//     (7 for tile column -1, 0 for tile column 64), on the DMA's source address and on the read;
+//   * the edge lane on the neighbour side reads side line wm + dy + 1 instead of the zero line; the lane on the image-edge side keeps the zero line.
+//     Which side is which is wave-uniform (the tile's half).  A side line sits at the bank position of the line it replaces when wm + dy has the
+//     right parity, else in the other bank half (a two-way conflict on one of the tap's reads);
+//   * a wave's 64 output pixels are still one contiguous, 64-aligned run of rows of C: the epilogue is handed img H W + (y0 + wm) 128 + xo.
+//
 // Summation order over K differs from the tap-major kernel (chunk-major), so last bits may differ; products and accumulation are the same.
 #include "common.h"
 #include "../../include/mxdenoise.h"
@@ -34,19 +48,34 @@ constexpr int HALO_WSTAGE_BYTES = HALO_BN * DMA_BK * 2;        // one stage of t
 constexpr int HALO_ZERO_BYTES = 256;                           // two zero lines: one per bank half
 __host__ __device__ constexpr int halo_lines(int W) { return (256 / W + 2) * W; }
 __host__ __device__ constexpr int halo_xbuf_bytes(int W) { return halo_lines(W) * DMA_BK * 2; }
-__host__ __device__ constexpr int halo_lds_bytes(int W) { return 2 * halo_xbuf_bytes(W) + 3 * HALO_WSTAGE_BYTES + HALO_ZERO_BYTES; }
+constexpr int HALO_SIDE_BYTES = 1024;                          // HALF: the neighbour column of one staged buffer -- one wave-wide DMA: 6 lines + 2 of padding
+__host__ __device__ constexpr int halo_lds_bytes(int W, bool half) {
+  return 2 * halo_xbuf_bytes(W) + 3 * HALO_WSTAGE_BYTES + HALO_ZERO_BYTES + (half ? 2 * HALO_SIDE_BYTES : 0);
+}
+// pieces of the next chunk's staged tile dealt to the load phase of tap T: pieces 0..XN-1 over taps 0..7 (tap 8's wait covers the last)
+__host__ __device__ constexpr int halo_pieces_in_tap(int XN, int T) {
+  int n = 0;
+  for (int i = 0; i < XN; ++i) n += (i * 7) / (XN - 1) == T ? 1 : 0;
+  return n;
+}
 
-template <int W, bool VEC>
+// W: width of a tile in pixels.  HALF: the image is 2 W wide and the tile is one half of a block of rows (the top of this file)
+template <int W, bool HALF, bool VEC>
 __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   constexpr int BN = HALO_BN, MI = 4, NI = BN / 32;
+  constexpr int IW = HALF ? 2 * W : W;         // pixels per image row
   constexpr int LINES = halo_lines(W);
   constexpr int XBUF = halo_xbuf_bytes(W);
   constexpr int XN = LINES * 8 / 512;          // activation DMA instructions per thread per chunk (5 / 6)
   constexpr int WCH = BN * 8, WI = 3;          // weight DMA instructions per thread per K tile (the last re-fetches rows 0..31: same bytes, same slots)
-  constexpr int WRING = 2 * XBUF, ZERO = WRING + 3 * HALO_WSTAGE_BYTES;
+  constexpr int WRING = 2 * XBUF, ZERO = WRING + 3 * HALO_WSTAGE_BYTES, SIDE = ZERO + HALO_ZERO_BYTES;
+  constexpr int SIDE_TAP = 3, SIDE_WAVE = 0;   // HALF: who issues the side column's DMA, and in which tap's load phase
   static_assert(W == 32 || W == 64, "a tile is whole image rows of 32 or 64 pixels");
+  static_assert(!HALF || W == 64, "half rows: a 128-wide image");
+  static_assert(!HALF || (256 / W + 2) * 8 <= 64, "the side column is one wave-wide DMA");
+  static_assert(halo_lds_bytes(W, HALF) <= 160 * 1024, "LDS of one workgroup");
   static_assert(LINES * 8 % 512 == 0 && XBUF % 256 == 0, "whole DMA instructions; buffers keep the bank half of a line");
-  __shared__ __attribute__((aligned(256))) char smem[halo_lds_bytes(W)];
+  __shared__ __attribute__((aligned(256))) char smem[halo_lds_bytes(W, HALF)];
 
   const GemmArgs& p = pk;
   int tm, tn;
@@ -64,9 +93,12 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   // ---- the operand stream ----
   // activations: piece i of thread tid is 16-byte slot (i * 512 + tid) of the staged buffer: line P = slot >> 3, slot cs of the line
   const int m0 = tm * 256, n0 = tn * BN;
-  const int hw = p.Hin * p.Win;                // (Win == W; hw % 256 == 0: a tile lies inside one image)
-  const int img = m0 / hw;
-  const int y0 = (m0 - img * hw) / W;          // first output row of the tile
+  const int hw = p.Hin * p.Win;                // (Win == IW; hw % 256 == 0, HALF: Hin % 4 == 0 -- a tile lies inside one image)
+  const int half = HALF ? tm & 1 : 0;          // HALF: the two halves of a block of rows are neighbours in tm
+  const int mrows0 = HALF ? (tm >> 1) * 512 : m0;      // first pixel of the tile's image rows
+  const int img = mrows0 / hw;
+  const int y0 = (mrows0 - img * hw) / IW;     // first output row of the tile
+  const int xo = half * W;                     // its first column
   const char* xsrc[XN];
 #pragma unroll
   for (int i = 0; i < XN; ++i) {
@@ -74,8 +106,18 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
     const int sr = P / W, x = P - sr * W;
     const int iy = y0 - 1 + sr;
     const bool ok = iy >= 0 && iy < p.Hin;
-    const long off = (((long)img * p.Hin + iy) * W + x) * (long)p.Cin * 2;
+    const long off = (((long)img * p.Hin + iy) * IW + xo + x) * (long)p.Cin * 2;
     xsrc[i] = (ok ? reinterpret_cast<const char*>(p.a) + off : zero) + swz(P, cs) * 16;
+  }
+  // HALF, the side column: lane l of SIDE_WAVE fetches slot (l & 7) of side line l >> 3 = the pixel (y0 - 1 + line, xo - 1 or xo + W)
+  const char* xside = zero;
+  if constexpr (HALF) {
+    const int sl = lane >> 3;
+    const int iy = y0 - 1 + sl;
+    const bool ok = sl < 256 / W + 2 && iy >= 0 && iy < p.Hin;
+    const int xs = half ? xo - 1 : xo + W;
+    const long off = (((long)img * p.Hin + iy) * IW + xs) * (long)p.Cin * 2;
+    xside = (ok ? reinterpret_cast<const char*>(p.a) + off : zero) + (cs ^ (half ? 7 : 0)) * 16;
   }
   const char* wsrc[WI];
 #pragma unroll
@@ -93,6 +135,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   auto advance_x = [&](int next_chunk) __attribute__((always_inline)) {    // the cursor moves to chunk `next_chunk`; past the last: harmless bytes
 #pragma unroll
     for (int i = 0; i < XN; ++i) xsrc[i] = next_chunk < nchunks ? xsrc[i] + DMA_BK * 2 : zero + lane * 16;
+    if constexpr (HALF) xside = next_chunk < nchunks ? xside + DMA_BK * 2 : zero + lane * 16;
+  };
+  auto issue_side = [&](int buf) __attribute__((always_inline)) {          // (SIDE_WAVE only: one instruction, the whole side column of `buf`)
+    glds16(xside, smem + SIDE + buf * HALO_SIDE_BYTES);
   };
   auto issue_w = [&](int stage) __attribute__((always_inline)) {
 #pragma unroll
@@ -117,7 +163,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   const int fq = lane >> 4;
   unsigned wrd[2];                             // weight fragments: inside a ring stage
   unsigned xrd[3][2];                          // activation fragments per dx: line (64 wm + fr + dx), the lane's chunk under that line's key
-  unsigned zrd[3][2];                          // the same bank position inside the zero lines
+  unsigned zrd[3][2];                          // what the edge lane reads instead: the same bank position inside the zero lines; HALF, on the neighbour's
+                                               // side: the same slot of side line wm (the tap adds the buffer and dy + 1 lines)
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const int wrow = wn * (BN / 2) + fr;
@@ -129,6 +176,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
       const int rel = line * 128 + ((ks * 4 + fq) ^ key) * 16;
       xrd[d][ks] = (unsigned)rel;
       zrd[d][ks] = (unsigned)(ZERO + (rel & 255));
+      if constexpr (HALF) { if (d == (half ? 0 : 2)) zrd[d][ks] = (unsigned)(SIDE + wm * 128 + (rel & 127)); }
     }
   }
   const bool lane_left = fr == 0, lane_right = fr == 15;
@@ -139,6 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   // ---- prologue: chunk 0 and the weights of K tiles 0 and 1 ----
 #pragma unroll
   for (int i = 0; i < XN; ++i) issue_x(0, i);
+  if constexpr (HALF) { if (wave == SIDE_WAVE) issue_side(0); }
   advance_x(1);
   issue_w(0); step_w(w_tap_step);
   issue_w(1); step_w(w_tap_step);          // (the cursor stands on tap 2 of chunk 0)
@@ -164,6 +213,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
     auto phase = [&](auto tc) __attribute__((always_inline)) {
       constexpr int T = decltype(tc)::value;
       constexpr int dy = T / 3 - 1, dx = T % 3 - 1, d = dx + 1;
+      constexpr int NX = halo_pieces_in_tap(XN, T);
+      // HALF: the edge lane on the neighbour's side reads side line wm + dy + 1 of this buffer (wave-uniform)
+      const unsigned side_off = HALF && dx != 0 && (dx < 0) == (half != 0) ? (unsigned)(cur * HALO_SIDE_BYTES + (dy + 1) * 128) : 0u;
       // ---- L: all fragments of this K tile, the DMA share of chunk cc + 1 and of K tile + 2, the cursors ----
       bf16x8 wf[2][NI], xf[2][MI];
 #pragma unroll
@@ -173,20 +225,22 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
 #pragma unroll
         for (int j = 0; j < MI; ++j) {
           unsigned a = xb + xrd[d][ks] + (unsigned)((dy + 1) * W * 128 + j * (16 * 128));
-          if (dx == -1 && (j * 16) % W == 0) a = lane_left ? zrd[d][ks] : a;             // pixel x = -1
-          if (dx == 1 && (j * 16 + 16) % W == 0) a = lane_right ? zrd[d][ks] : a;        // pixel x = W
+          if (dx == -1 && (j * 16) % W == 0) a = lane_left ? zrd[d][ks] + side_off : a;          // pixel xo - 1
+          if (dx == 1 && (j * 16 + 16) % W == 0) a = lane_right ? zrd[d][ks] + side_off : a;     // pixel xo + W
           xf[ks][j] = *reinterpret_cast<const bf16x8*>(smem + a);
         }
       }
-      int nx = 0;
 #pragma unroll
       for (int i = 0; i < XN; ++i)
-        if ((i * 7) / (XN - 1) == T) { issue_x(nxt, i); ++nx; }      // pieces 0..XN-1 over taps 0..7, in front of the tap's weights (tap 8's wait covers the last)
+        if ((i * 7) / (XN - 1) == T) issue_x(nxt, i);                // halo_pieces_in_tap: in front of the tap's weights
+      constexpr bool side_tap = HALF && T == SIDE_TAP;
+      if constexpr (side_tap) { if (wave == SIDE_WAVE) issue_side(nxt); }
       issue_w((T + 2) % 3);                                           // K tile + 2 into the stage of K tile - 1
       if (T == 6) to_next_chunk_w(last);                              // the cursor stood on tap 8
       else step_w(T > 6 && last ? 0 : w_tap_step);
       if (T == 8) advance_x(cc + 2);
-      if (nx == 0) wait_vmcnt<WI>(); else if (nx == 1) wait_vmcnt<WI + 1>(); else wait_vmcnt<WI + 2>();   // own part of K tile + 1 (and every older piece)
+      // own part of K tile + 1 (and every older piece); the wave that issued the side column has one more DMA behind it
+      if (side_tap && wave == SIDE_WAVE) wait_vmcnt<WI + NX + 1>(); else wait_vmcnt<WI + NX>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the fragment reads have returned: their stage / buffer may be restaged one phase from now
       __builtin_amdgcn_sched_barrier(0);
       MX_BAR();
@@ -207,25 +261,36 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(const GemmArgs pk) {
   }
   if (!group_b) MX_BAR();                    // re-align the two groups
 
-  gemm_epilogue_regs<NI, MI, false, VEC, true, true, 0, true, false>(p, acc, m0 + wm * 16 * MI, n0 + wn * (BN / 2), fr, fq, ln_rstd);
-  if (p.gn_part != nullptr) gemm_gn_partials<NI, MI>(p, acc, m0 + wm * 16 * MI, n0 + wn * (BN / 2), fr, fq);
+  const int m_wave0 = HALF ? img * hw + (y0 + wm) * IW + xo : m0 + wm * 16 * MI;      // the wave's 64 output pixels: one tile row, contiguous rows of C
+  gemm_epilogue_regs<NI, MI, false, VEC, true, true, 0, true, false>(p, acc, m_wave0, n0 + wn * (BN / 2), fr, fq, ln_rstd);
+  if (p.gn_part != nullptr) gemm_gn_partials<NI, MI>(p, acc, m_wave0, n0 + wn * (BN / 2), fr, fq);
   wait_vmcnt<0>();                           // the past-the-end DMAs are drained before the workgroup retires
 }
 
-// LDS bytes of the instantiation for images `width` pixels wide; 0: none is built
-int conv_halo_lds_bytes(int width) { return width == 32 ? halo_lds_bytes(32) : width == 64 ? halo_lds_bytes(64) : 0; }
+// LDS bytes of the instantiation for images `width` pixels wide (half_rows: the half-row form); 0: none is built
+int conv_halo_lds_bytes(int width, bool half_rows) {
+  if (half_rows) return width == 128 ? halo_lds_bytes(64, true) : 0;
+  return width == 32 ? halo_lds_bytes(32, false) : width == 64 ? halo_lds_bytes(64, false) : 0;
+}
 
-// a is the argument block of a descriptor mx_conv3x3_halo_serves accepted (gemm_dispatch.cpp); vec: per-sample vectors compiled in
-int launch_conv_halo(hipStream_t s, const GemmArgs& a, bool vec) {
+// a is the argument block of a descriptor mx_conv3x3_halo_serves (half_rows: mx_conv3x3_halfrow_serves) accepted (gemm_dispatch.cpp);
+// vec: per-sample vectors compiled in
+int launch_conv_halo(hipStream_t s, const GemmArgs& a, bool vec, bool half_rows) {
   const dim3 grid((a.M / 256) * (a.N / HALO_BN)), block(512);
+  if (half_rows) {
+    if (a.Win != 128) return 1;
+    if (vec) hipLaunchKernelGGL((conv_halo_kernel<64, true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_halo_kernel<64, true, false>), grid, block, 0, s, a);
+    return 0;
+  }
   if (a.Win == 32) {
-    if (vec) hipLaunchKernelGGL((conv_halo_kernel<32, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_halo_kernel<32, false>), grid, block, 0, s, a);
+    if (vec) hipLaunchKernelGGL((conv_halo_kernel<32, false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_halo_kernel<32, false, false>), grid, block, 0, s, a);
     return 0;
   }
   if (a.Win == 64) {
-    if (vec) hipLaunchKernelGGL((conv_halo_kernel<64, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_halo_kernel<64, false>), grid, block, 0, s, a);
+    if (vec) hipLaunchKernelGGL((conv_halo_kernel<64, false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_halo_kernel<64, false, false>), grid, block, 0, s, a);
     return 0;
   }
   return 1;

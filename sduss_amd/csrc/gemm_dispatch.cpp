@@ -580,32 +580,46 @@ static bool plan_of_variant(const mx_gemm_desc* d, bool stats, GemmPlan& p) {
   return plan_of(&q, false, p);
 }
 
-// ---- mx_conv3x3_halo (conv_halo.hip): an entry of its own beside the routes above -- the plan asks mx_conv3x3_halo_serves and calls it, or mx_conv3x3 ----
-int launch_conv_halo(hipStream_t s, const GemmArgs& a, bool vec);
-int conv_halo_lds_bytes(int width);            // 0: no instantiation for that image width
+// ---- mx_conv3x3_halo / mx_conv3x3_halfrow (conv_halo.hip): entries of their own beside the routes above -- the plan asks mx_conv3x3_halo_serves, then
+//      mx_conv3x3_halfrow_serves, and calls the one that serves, or mx_conv3x3 ----
+int launch_conv_halo(hipStream_t s, const GemmArgs& a, bool vec, bool half_rows);
+int conv_halo_lds_bytes(int width, bool half_rows);      // 0: no instantiation for that image width
 
-// LDS bytes of the launch, 0 when the kernel does not serve d (the conditions: include/mxdenoise.h)
-static int conv_halo_serves(const mx_gemm_desc* d) {
-  if (!d || d->n_segs != 0 || d->stride != 1 || d->up != 0 || d->vhalo != 0 || d->corner_patch != 0) return 0;
-  if (d->Cin <= 0 || d->Cin % 64 != 0 || d->Cin > 8192 || d->K != 9 * d->Cin || d->cin_valid != 0) return 0;
-  if (d->N <= 0 || d->N % 160 != 0) return 0;
-  if (d->B <= 0 || d->Hin <= 0 || d->Hout != d->Hin || d->Wout != d->Win || (long)d->Hin * d->Win % 256 != 0) return 0;
-  if ((long)d->B * d->Hin * d->Win != d->M) return 0;
-  if (d->flags != 0 || d->gate || d->out_scale != 0.f || d->splitk > 1) return 0;
-  if (d->rows_per_batch != 0 && d->rows_per_batch != d->Hin * d->Win) return 0;
+// what both forms ask of d, but for the image's width and height (the conditions: include/mxdenoise.h)
+static bool conv_staged_common(const mx_gemm_desc* d) {
+  if (!d || d->n_segs != 0 || d->stride != 1 || d->up != 0 || d->vhalo != 0 || d->corner_patch != 0) return false;
+  if (d->Cin <= 0 || d->Cin % 64 != 0 || d->Cin > 8192 || d->K != 9 * d->Cin || d->cin_valid != 0) return false;
+  if (d->N <= 0 || d->N % 160 != 0) return false;
+  if (d->B <= 0 || d->Hin <= 0 || d->Win <= 0 || d->Hout != d->Hin || d->Wout != d->Win) return false;
+  if ((long)d->B * d->Hin * d->Win != d->M) return false;
+  if (d->flags != 0 || d->gate || d->out_scale != 0.f || d->splitk > 1) return false;
+  if (d->rows_per_batch != 0 && d->rows_per_batch != d->Hin * d->Win) return false;
   // the register-exchange epilogue moves 16-byte pieces of C and of the residual
-  if (d->ldc % 8 != 0 || ((uintptr_t)d->c & 15) != 0) return 0;
-  if (d->residual && (d->ldr % 8 != 0 || ((uintptr_t)d->residual & 15) != 0)) return 0;
+  if (d->ldc % 8 != 0 || ((uintptr_t)d->c & 15) != 0) return false;
+  if (d->residual && (d->ldr % 8 != 0 || ((uintptr_t)d->residual & 15) != 0)) return false;
+  return true;
+}
+
+// LDS bytes of the launch, 0 when the kernel does not serve d
+static int conv_halo_serves(const mx_gemm_desc* d) {
+  if (!conv_staged_common(d) || (long)d->Hin * d->Win % 256 != 0) return 0;
   // shapes of the SDXL step whose median did not beat the tap-major kernel's by more than that kernel's own p10..p90 width in the per-shape A/B
   // (tools/conv_halo_bench.py, profiles/conv_halo_ab.txt): the two shortest K loops, +20.7 us against a width of 24.6 and +25.9 against 28.7
   static const int kNotFaster[][3] = {{32, 640, 1280}, {64, 320, 640}};      // {width, Cin, N}
   for (const auto& s : kNotFaster) if (d->Win == s[0] && d->Cin == s[1] && d->N == s[2]) return 0;
-  return conv_halo_lds_bytes(d->Win);
+  return conv_halo_lds_bytes(d->Win, false);
 }
 
-static int run_conv_halo(void* stream, const mx_gemm_desc* d) {
+// the half-row form: a 128-wide image in tiles of 4 rows x 64 columns
+static int conv_halfrow_serves(const mx_gemm_desc* d) {
+  if (!conv_staged_common(d) || d->Win != 128 || d->Hin % 4 != 0) return 0;
+  return conv_halo_lds_bytes(d->Win, true);
+}
+
+static int run_conv_halo(void* stream, const mx_gemm_desc* d, bool half_rows) {
   MX_CHECK(d != nullptr, "conv3x3_halo: null descriptor");
-  MX_CHECK(conv_halo_serves(d) > 0, "conv3x3_halo: the descriptor is not served (mx_conv3x3_halo_serves); run mx_conv3x3");
+  if (half_rows) MX_CHECK(conv_halfrow_serves(d) > 0, "conv3x3_halfrow: the descriptor is not served (mx_conv3x3_halfrow_serves); run mx_conv3x3");
+  else MX_CHECK(conv_halo_serves(d) > 0, "conv3x3_halo: the descriptor is not served (mx_conv3x3_halo_serves); run mx_conv3x3");
   if (int rc = validate(d, true)) return rc;
   MX_CHECK(!d->stats_out && !d->ln_final_out, "conv3x3_halo: no row statistics");
   if (d->gn_part_out)      // (gn_part_refusal's conditions on the descriptor; the tile is 256 rows)
@@ -620,7 +634,7 @@ static int run_conv_halo(void* stream, const mx_gemm_desc* d) {
     const double kk = 9.0 * d->Cin, Mt = (double)d->M;
     prof_begin(s, PROF_CONV_V2_160, 2.0 * Mt * (double)d->N * kk, 2.0 * (Mt * d->Cin + (double)d->N * d->K + Mt * d->N), d->M, d->N, (int)kk);
   }
-  MX_CHECK(launch_conv_halo(s, a, d->rowbias != nullptr) == 0, "conv3x3_halo: no instantiation for this image width");
+  MX_CHECK(launch_conv_halo(s, a, d->rowbias != nullptr, half_rows) == 0, "conv3x3_halo: no instantiation for this image width");
   prof_end(s);
   MX_LAUNCH_CHECK();
   return 0;
@@ -629,7 +643,9 @@ static int run_conv_halo(void* stream, const mx_gemm_desc* d) {
 }  // namespace mx
 
 extern "C" int mx_conv3x3_halo_serves(const mx_gemm_desc* d) { return mx::conv_halo_serves(d); }
-extern "C" int mx_conv3x3_halo(void* stream, const mx_gemm_desc* d) { return mx::run_conv_halo(stream, d); }
+extern "C" int mx_conv3x3_halo(void* stream, const mx_gemm_desc* d) { return mx::run_conv_halo(stream, d, false); }
+extern "C" int mx_conv3x3_halfrow_serves(const mx_gemm_desc* d) { return mx::conv_halfrow_serves(d); }
+extern "C" int mx_conv3x3_halfrow(void* stream, const mx_gemm_desc* d) { return mx::run_conv_halo(stream, d, true); }
 extern "C" int mx_gemm(void* stream, const mx_gemm_desc* d) { return mx::run(stream, d, false); }
 extern "C" int mx_conv3x3(void* stream, const mx_gemm_desc* d) { return mx::run(stream, d, true); }
 extern "C" void mx_gemm_release_scratch(void* stream, int all) { mx::splitk_release((hipStream_t)stream, all != 0); }

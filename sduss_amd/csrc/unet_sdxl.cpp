@@ -450,6 +450,13 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       if (mx_conv3x3_halo(stream, &d)) return fail(std::string("conv3x3_halo: ") + mx_last_error());
       return true;
     }
+    // 128-wide images: the same kernel on half-row tiles (4 rows x 64 columns and the neighbouring column)
+    if (mx_conv3x3_halfrow_serves(&d) && mx_gemm_form(&d, 1) == MX_FORM_TILE_256) {
+      if (!ok()) return false;
+      if (quiet()) return true;
+      if (mx_conv3x3_halfrow(stream, &d)) return fail(std::string("conv3x3_halfrow: ") + mx_last_error());
+      return true;
+    }
     return gemm(d, true);
   }
   bool groupnorm(const bf16_t* x, bf16_t* y, const std::string& prefix, int h, int wd, int C, float eps, bool silu, int patch,

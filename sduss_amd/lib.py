@@ -239,6 +239,8 @@ SYMBOLS = {
     "mx_conv3x3": (_i, [_vp, C.POINTER(GemmDesc)]),
     "mx_conv3x3_halo": (_i, [_vp, C.POINTER(GemmDesc)]),
     "mx_conv3x3_halo_serves": (_i, [C.POINTER(GemmDesc)]),
+    "mx_conv3x3_halfrow": (_i, [_vp, C.POINTER(GemmDesc)]),
+    "mx_conv3x3_halfrow_serves": (_i, [C.POINTER(GemmDesc)]),
     "mx_gemm_stats_slabs": (_i, [C.POINTER(GemmDesc)]),
     "mx_gemm_ln_prefers_pass": (_i, [C.POINTER(GemmDesc)]),
     "mx_row_stats": (_i, [_vp, _vp, _i, _vp, _i, _i]),

@@ -1,6 +1,7 @@
-"""Per-shape A/B of the two 3x3 conv entries at the stride-1 shapes of the SDXL headline step (batch 4 with guidance = 8 images): mx_conv3x3
-(tap-major, the 256 x 160 tile of gemm_bf16_v5.hip) against mx_conv3x3_halo (conv_halo.hip) on the same descriptor.
-Usage, on a machine with the GPU: python tools/conv_halo_bench.py [--reps 60] [--out FILE]
+"""Per-shape A/B of the 3x3 conv entries at the stride-1 shapes of the SDXL headline step (batch 4 with guidance = 8 images): mx_conv3x3
+(tap-major, the 256 x 160 tile of gemm_bf16_v5.hip) against the staged entry that serves the descriptor -- mx_conv3x3_halo at the 32 and 64 wide
+levels, mx_conv3x3_halfrow at the 128 wide level (both conv_halo.hip).
+Usage, on a machine with the GPU: python tools/conv_halo_bench.py [--reps 60] [--widths 32,64,128] [--out FILE]
 One process, random data, device events around every launch, the two entries alternating; a launch rotates through NSETS operand sets so that
 neither entry finds its weights warm from its own last launch.  Reports median and p10..p90 per entry and shape.  A shape counts as FASTER only
 when the new median beats the old one by more than the old entry's own p10..p90 width.  Also prints the largest difference between the two
@@ -18,9 +19,11 @@ sys.path.insert(0, ROOT)
 from sduss_amd import lib as L  # noqa: E402
 
 BATCH = 8
-# (H = W, Cin, N, launches per step): the stride-1, not upsampled conv rows of profiles/r04_a_shape_profile_b4.txt at the 32 and 64 wide levels
+# (H = W, Cin, N, launches per step): the stride-1, not upsampled conv rows of profiles/r04_a_shape_profile_b4.txt at the 32, 64 and 128 wide levels
+# (128: 320 -> 320 is down block 0 (4, conv1 and conv2 alike) and conv2 of up block 2 (3); 640 / 960 -> 320 are the conv1 of up block 2)
 SHAPES = ((32, 1280, 1280, 10), (32, 2560, 1280, 2), (32, 1920, 1280, 1), (32, 640, 1280, 1),
-          (64, 640, 640, 6), (64, 1920, 640, 1), (64, 1280, 640, 1), (64, 960, 640, 1), (64, 320, 640, 1))
+          (64, 640, 640, 6), (64, 1920, 640, 1), (64, 1280, 640, 1), (64, 960, 640, 1), (64, 320, 640, 1),
+          (128, 320, 320, 7), (128, 640, 320, 2), (128, 960, 320, 1))
 NSETS = 4
 WARM = 3
 
@@ -60,8 +63,10 @@ def _operands(hw, cin, n, form, g):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=60)
+    ap.add_argument("--widths", default="32,64,128", help="image widths to run, comma separated")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    widths = {int(v) for v in a.widths.split(",")}
     assert a.reps >= 20 and torch.cuda.is_available(), "needs a GPU and at least 20 repetitions"
     lib = L.load()
     s = L.current_stream()
@@ -70,15 +75,21 @@ def main():
              f"{'H=W':>4} {'Cin':>5} {'N':>5} {'form':>6} {'n/step':>6} | {'old med':>8} {'p10':>8} {'p90':>8} | {'new med':>8} {'p10':>8} {'p90':>8} | {'gain':>7} {'old width':>9}  verdict   max|new-old|/max|old|"]
     saved = 0.0
     for hw, cin, n, per_step in SHAPES:
+        if hw not in widths:
+            continue
         for form in ("conv1", "conv2") if cin == n else ("conv1",):
             sets = [_operands(hw, cin, n, form, g) for _ in range(NSETS)]
             d0 = sets[0][0]
             assert L.gemm_kernels_of(d0, True)[0].startswith("gemm_v5_kernel<160"), (hw, cin, n)
-            if lib.mx_conv3x3_halo_serves(C.byref(d0)) == 0:      # a shape an earlier run of this comparison excluded
-                lines.append(f"{hw:>4} {cin:>5} {n:>5} {form:>6} {per_step:>6} | not served by mx_conv3x3_halo (mx_conv3x3_halo_serves)")
+            if lib.mx_conv3x3_halo_serves(C.byref(d0)):
+                entry, entry_name = lib.mx_conv3x3_halo, "mx_conv3x3_halo"
+            elif lib.mx_conv3x3_halfrow_serves(C.byref(d0)):
+                entry, entry_name = lib.mx_conv3x3_halfrow, "mx_conv3x3_halfrow"
+            else:                                                  # a shape an earlier run of this comparison excluded
+                lines.append(f"{hw:>4} {cin:>5} {n:>5} {form:>6} {per_step:>6} | not served by mx_conv3x3_halo / mx_conv3x3_halfrow (their _serves)")
                 continue
             old = lambda k: L.check(lib.mx_conv3x3(s, C.byref(sets[k][0])), "mx_conv3x3")
-            new = lambda k: L.check(lib.mx_conv3x3_halo(s, C.byref(sets[k][0])), "mx_conv3x3_halo")
+            new = lambda k: L.check(entry(s, C.byref(sets[k][0])), entry_name)
             old(0); ref = sets[0][1].float().clone()
             new(0); diff = (sets[0][1].float() - ref).abs().max().item() / ref.abs().max().item()
             for _ in range(WARM):                       # every operand set through both entries: code objects, clocks, allocator
