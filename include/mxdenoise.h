@@ -917,6 +917,42 @@ int mx_sq_diff_partial(void* stream, const void* a, const void* b, int64_t elems
 int mx_copy_rows(void* stream, void* batch, void* slotted, size_t bytes_per_sample, int n_samples, const int32_t* slot, int scatter);
 
 /* ------------------------------------------------------------------------------------------
+ * Glue kernels, one launch each (tests and tools).  The step plans call the launchers of sduss_amd/csrc/elementwise.hip directly; these
+ * wrappers start exactly one of them on caller-made operands, so that every kernel at a model's boundary can be checked alone
+ * (tests/test_glue_gpu.py).  Every pointer is device memory; `dtype` is an io dtype code (MX_F32, MX_F16, MX_BF16), every other activation is
+ * bf16.  Nothing is allocated, copied or synchronised inside a call.  Returns 0, or 1 with the reason in the last error: a null operand
+ * (only `pos` of mx_clip_embed may be null), an empty shape, a shape the launcher refuses, a pointer that is not 16-byte aligned where the
+ * kernel moves 16-byte vectors (mx_prep_latent's out, mx_crop_pos, mx_softmax_rows, mx_clip_embed, mx_clip_pool), a failed launch.
+ * ------------------------------------------------------------------------------------------ */
+/* in NCHW [B][Cin][HW] of `dtype` -> out NHWC bf16 [B * HW][CP], channels Cin..CP written as +0; CP % 8 == 0, Cin <= CP */
+int mx_prep_latent(void* stream, const void* in, int dtype, void* out, int B, int Cin, int HW, int CP);
+/* in NHWC bf16 [B * HW][ld], the first C <= ld columns -> out NCHW [B][C][HW] of `dtype` (one rounding from the bf16 value) */
+int mx_nhwc_to_nchw(void* stream, const void* in, void* out, int dtype, int B, int C, int HW, int ld);
+/* Timesteps(dim, flip_sin_to_cos = True, downscale_freq_shift = 0) = [cos | sin](t exp(-ln(1e4) j / (dim / 2))), rounded once to bf16:
+ * tsin [B][d0] of timesteps [B]; addin [B][text_dim + 6 da] = [text_embeds [B][text_dim] (copied) | the da-wide sinusoid of each of the 6
+ * time_ids [B][6]].  d0 and da even. */
+int mx_time_embed(void* stream, const float* timesteps, const void* text_embeds, const float* time_ids, void* tsin, void* addin, int B, int d0,
+                  int text_dim, int da);
+/* out [B][dim] bf16 = the same sinusoid of t [B]; dim even */
+int mx_sinus_embed(void* stream, const float* t, void* out, int B, int dim);
+/* in NCHW [B][C][H][W] of `dtype` -> out bf16 [B * (H / ps) * (W / ps)][ps * ps * C], column (dy * ps + dx) * C + c; H % ps == W % ps == 0 */
+int mx_patchify(void* stream, const void* in, int dtype, void* out, int B, int C, int H, int W, int ps);
+/* in bf16 [B * (H / ps) * (W / ps)][ld], the first ps * ps * C <= ld columns in (p, q, c) order -> out NCHW [B][C][H][W] of `dtype`
+ * ("nhwpqc->nchpwq") */
+int mx_unpatchify(void* stream, const void* in, void* out, int dtype, int B, int C, int H, int W, int ps, int ld);
+/* table bf16 [m][m][d] -> out [h * w][d]: rows (top + y, left + x), top = (m - h) / 2, left = (m - w) / 2 rounded down; d % 8 == 0, h, w <= m */
+int mx_crop_pos(void* stream, const void* table, void* out, int m, int h, int w, int d);
+/* scores bf16 [rows][ld]: the first L columns of every row <- their softmax (fp32 math, the row maximum subtracted, one rounding), in place;
+ * columns L..ld are neither read nor written; L % 8 == ld % 8 == 0 */
+int mx_softmax_rows(void* stream, void* scores, int64_t rows, int L, int64_t ld);
+/* out bf16 [rows][H] = tok[clamp(ids[r], 0, vocab - 1)] + pos[r % L] (fp32 sum of the two bf16 rows, one rounding); pos == NULL: no position
+ * table (the sum's second operand is +0); H % 8 == 0 */
+int mx_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, void* out, int rows, int L, int H, int vocab);
+/* out bf16 [B][H] = x[b][e(b)], x [B][L][H]; e(b) = the first position of ids [B][L] holding eos_id, 0 where none does; eos_id < 0: the first
+ * position of the largest id; H % 8 == 0 */
+int mx_clip_pool(void* stream, const int32_t* ids, const void* x, void* out, int B, int L, int H, int eos_id);
+
+/* ------------------------------------------------------------------------------------------
  * The element-wise steps either side of the model call.
  * ------------------------------------------------------------------------------------------ */
 /* out[b] = x[b mod n_lat] / sqrt(sigma[b mod n_lat]^2 + 1) for b in [0, n_rows)   (batch_scale_model_input, CFG

@@ -1,5 +1,5 @@
 // Small HBM-bound glue kernels of the step plan (gfx950): layout conversion at the model boundary,
-// sinusoidal embeddings, channel concat, and the scheduler's input scaling in front of the UNet (the step behind it: scheduler_step.hip).
+// sinusoidal embeddings, and the scheduler's input scaling in front of the UNet (the step behind it: scheduler_step.hip).
 #include <algorithm>
 
 #include "common.h"
@@ -81,20 +81,6 @@ __global__ void time_embed_kernel(const float* __restrict__ timesteps, const bf1
   }
 }
 
-// out[m, 0:C1] = a[m, :], out[m, C1:C1+C2] = b[m, :]   (torch.cat([hidden, skip], dim=1) in NHWC)
-__global__ void concat_channels_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b,
-                                       bf16_t* __restrict__ out, long M, int C1, int C2) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int chunks = (C1 + C2) / 8;
-  if (idx >= M * chunks) return;
-  const long m = idx / chunks;
-  const int ch = (int)(idx - m * chunks);
-  const int c1 = C1 / 8;
-  const u32x4 v = (ch < c1) ? *reinterpret_cast<const u32x4*>(a + m * C1 + ch * 8)
-                            : *reinterpret_cast<const u32x4*>(b + m * C2 + (ch - c1) * 8);
-  *reinterpret_cast<u32x4*>(out + idx * 8) = v;
-}
-
 // batch_scale_model_input with the CFG duplication fused (scheduling_euler_discrete.py:161-184)
 template <typename T>
 __global__ void euler_scale_input_kernel(const T* __restrict__ lat, T* __restrict__ out, const float* __restrict__ sigma,
@@ -129,6 +115,7 @@ int launch_prep_latent(hipStream_t s, const void* in, int dtype, void* out, int 
   return 0;
 }
 int launch_nhwc_to_nchw(hipStream_t s, const void* in, void* out, int dtype, int B, int C, int HW, int ld) {
+  MX_CHECK(ld >= C, "nhwc_to_nchw: ld must hold the C columns");
   const long total = (long)B * C * HW;
   dim3 grid((unsigned)cdiv64(total, 256)), block(256);
   if (dtype == MX_F32) hipLaunchKernelGGL((nhwc_to_nchw_kernel<float>), grid, block, 0, s, (const bf16_t*)in, (float*)out, B, C, HW, ld);
@@ -140,18 +127,11 @@ int launch_nhwc_to_nchw(hipStream_t s, const void* in, void* out, int dtype, int
 }
 int launch_time_embed(hipStream_t s, const float* timesteps, const void* text_embeds, const float* time_ids,
                       void* tsin, void* addin, int B, int d0, int text_dim, int da) {
+  MX_CHECK(d0 >= 2 && d0 % 2 == 0 && da >= 2 && da % 2 == 0, "time_embed: d0 and da must be even");
   const int w = (d0 > text_dim + 6 * da) ? d0 : text_dim + 6 * da;
   dim3 grid(cdiv(w, 256), B), block(256);
   hipLaunchKernelGGL(time_embed_kernel, grid, block, 0, s, timesteps, (const bf16_t*)text_embeds, time_ids,
                      (bf16_t*)tsin, (bf16_t*)addin, B, d0, text_dim, da);
-  MX_LAUNCH_CHECK();
-  return 0;
-}
-int launch_concat(hipStream_t s, const void* a, const void* b, void* out, long M, int C1, int C2) {
-  MX_CHECK(C1 % 8 == 0 && C2 % 8 == 0, "concat: channels must be multiples of 8");
-  const long total = M * ((C1 + C2) / 8);
-  dim3 grid((unsigned)cdiv64(total, 256)), block(256);
-  hipLaunchKernelGGL(concat_channels_kernel, grid, block, 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, M, C1, C2);
   MX_LAUNCH_CHECK();
   return 0;
 }
@@ -234,6 +214,7 @@ __global__ void sinus_embed_kernel(const float* __restrict__ t, bf16_t* __restri
 }
 
 int launch_patchify(hipStream_t s, const void* in, int dtype, void* out, int B, int C, int H, int W, int ps) {
+  MX_CHECK(ps > 0 && H % ps == 0 && W % ps == 0, "patchify: H and W must be multiples of the patch size");
   const long total = (long)B * H * W * C;
   dim3 grid((unsigned)cdiv64(total, 256)), block(256);
   if (dtype == MX_F32) hipLaunchKernelGGL((patchify_kernel<float>), grid, block, 0, s, (const float*)in, (bf16_t*)out, B, C, H, W, ps);
@@ -244,6 +225,8 @@ int launch_patchify(hipStream_t s, const void* in, int dtype, void* out, int B, 
   return 0;
 }
 int launch_unpatchify(hipStream_t s, const void* in, void* out, int dtype, int B, int C, int H, int W, int ps, int ld) {
+  MX_CHECK(ps > 0 && H % ps == 0 && W % ps == 0, "unpatchify: H and W must be multiples of the patch size");
+  MX_CHECK((long)ld >= (long)ps * ps * C, "unpatchify: ld must hold the ps*ps*C columns");
   const long total = (long)B * H * W * C;
   dim3 grid((unsigned)cdiv64(total, 256)), block(256);
   if (dtype == MX_F32) hipLaunchKernelGGL((unpatchify_kernel<float>), grid, block, 0, s, (const bf16_t*)in, (float*)out, B, C, H, W, ps, ld);
@@ -261,6 +244,7 @@ int launch_crop_pos(hipStream_t s, const void* table, void* out, int m, int h, i
   return 0;
 }
 int launch_sinus_embed(hipStream_t s, const float* t, void* out, int B, int dim) {
+  MX_CHECK(dim >= 2 && dim % 2 == 0, "sinus_embed: dim must be even");
   hipLaunchKernelGGL(sinus_embed_kernel, dim3(cdiv(dim, 256), B), dim3(256), 0, s, t, (bf16_t*)out, dim);
   MX_LAUNCH_CHECK();
   return 0;
@@ -272,6 +256,15 @@ int launch_sinus_embed(hipStream_t s, const float* t, void* out, int B, int dim)
 // attention (diffusers Attention with heads = 1; AutoencoderKL decoder) is computed as GEMM -> softmax -> GEMM.
 // ------------------------------------------------------------------------------------------
 namespace mx {
+// exp(d), d <= 0, as __expf evaluates it -- exp2(fl(log2(e) d)), one v_exp_f32 -- but with results below 2^-126 kept as fp32 subnormals: the
+// instruction alone returns +0 there, and a probability down to 2^-134 still has a bf16 value.  Below -126 the argument is raised by 64 and the
+// result scaled back (exact but for the one rounding into the subnormal range); above it the bits are __expf's.
+__device__ __forceinline__ float exp_gradual(float d) {
+  const float a = 0x1.715476p+0f * d;
+  const bool low = a < -126.0f;
+  const float e = __builtin_amdgcn_exp2f(low ? a + 64.0f : a);
+  return low ? e * 0x1p-64f : e;
+}
 __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ s, int L, long ld) {
   __shared__ float red[8];
   bf16_t* row = s + (long)blockIdx.x * ld;
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ 
   for (int i = t; i < L / 8; i += 256) {
     const u32x4 v = reinterpret_cast<const u32x4*>(row)[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) sum += __expf(bf16lo_to_f32(v[e]) - mx_) + __expf(bf16hi_to_f32(v[e]) - mx_);
+    for (int e = 0; e < 4; ++e) sum += exp_gradual(bf16lo_to_f32(v[e]) - mx_) + exp_gradual(bf16hi_to_f32(v[e]) - mx_);
   }
   sum = wave_sum(sum);
   if ((t & 63) == 0) red[4 + (t >> 6)] = sum;
@@ -300,7 +293,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ 
     const u32x4 v = reinterpret_cast<const u32x4*>(row)[i];
     u32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(__expf(bf16lo_to_f32(v[e]) - mx_) * inv, __expf(bf16hi_to_f32(v[e]) - mx_) * inv);
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(exp_gradual(bf16lo_to_f32(v[e]) - mx_) * inv, exp_gradual(bf16hi_to_f32(v[e]) - mx_) * inv);
     reinterpret_cast<u32x4*>(row)[i] = o;
   }
 }
@@ -364,11 +357,62 @@ int launch_clip_embed(hipStream_t s, const int* ids, const bf16_t* tok, const bf
   return 0;
 }
 int launch_clip_pool(hipStream_t s, const int* ids, const bf16_t* x, bf16_t* out, int B, int L, int H, int eos_id) {
+  MX_CHECK(H % 8 == 0, "clip_pool: hidden size must be a multiple of 8");
   hipLaunchKernelGGL(clip_pool_kernel, dim3(B), dim3(128), 0, s, ids, x, out, L, H, eos_id);
   MX_LAUNCH_CHECK();
   return 0;
 }
 }  // namespace mx
+
+// ----------------------------------------------------------------------------------------------------------------------
+// one launch each on caller-made operands (include/mxdenoise.h: "Glue kernels, one launch each"): the launchers above behind their host checks
+// ----------------------------------------------------------------------------------------------------------------------
+extern "C" int mx_prep_latent(void* stream, const void* in, int dtype, void* out, int B, int Cin, int HW, int CP) {
+  MX_CHECK(in && out && B > 0 && Cin > 0 && HW > 0 && CP > 0, "prep_latent: null operand or empty shape");
+  MX_CHECK(mx::aligned_to(out, 16), "prep_latent: out must be 16-byte aligned");
+  return mx::launch_prep_latent((hipStream_t)stream, in, dtype, out, B, Cin, HW, CP);
+}
+extern "C" int mx_nhwc_to_nchw(void* stream, const void* in, void* out, int dtype, int B, int C, int HW, int ld) {
+  MX_CHECK(in && out && B > 0 && C > 0 && HW > 0, "nhwc_to_nchw: null operand or empty shape");
+  return mx::launch_nhwc_to_nchw((hipStream_t)stream, in, out, dtype, B, C, HW, ld);
+}
+extern "C" int mx_time_embed(void* stream, const float* timesteps, const void* text_embeds, const float* time_ids, void* tsin, void* addin, int B, int d0,
+                             int text_dim, int da) {
+  MX_CHECK(timesteps && text_embeds && time_ids && tsin && addin && B > 0 && d0 > 0 && text_dim > 0 && da > 0, "time_embed: null operand or empty shape");
+  return mx::launch_time_embed((hipStream_t)stream, timesteps, text_embeds, time_ids, tsin, addin, B, d0, text_dim, da);
+}
+extern "C" int mx_sinus_embed(void* stream, const float* t, void* out, int B, int dim) {
+  MX_CHECK(t && out && B > 0 && dim > 0, "sinus_embed: null operand or empty shape");
+  return mx::launch_sinus_embed((hipStream_t)stream, t, out, B, dim);
+}
+extern "C" int mx_patchify(void* stream, const void* in, int dtype, void* out, int B, int C, int H, int W, int ps) {
+  MX_CHECK(in && out && B > 0 && C > 0 && H > 0 && W > 0 && ps > 0, "patchify: null operand or empty shape");
+  return mx::launch_patchify((hipStream_t)stream, in, dtype, out, B, C, H, W, ps);
+}
+extern "C" int mx_unpatchify(void* stream, const void* in, void* out, int dtype, int B, int C, int H, int W, int ps, int ld) {
+  MX_CHECK(in && out && B > 0 && C > 0 && H > 0 && W > 0 && ps > 0, "unpatchify: null operand or empty shape");
+  return mx::launch_unpatchify((hipStream_t)stream, in, out, dtype, B, C, H, W, ps, ld);
+}
+extern "C" int mx_crop_pos(void* stream, const void* table, void* out, int m, int h, int w, int d) {
+  MX_CHECK(table && out && m > 0 && h > 0 && w > 0 && d > 0, "crop_pos: null operand or empty shape");
+  MX_CHECK(mx::aligned_to(table, 16) && mx::aligned_to(out, 16), "crop_pos: table and out must be 16-byte aligned");
+  return mx::launch_crop_pos((hipStream_t)stream, table, out, m, h, w, d);
+}
+extern "C" int mx_softmax_rows(void* stream, void* scores, int64_t rows, int L, int64_t ld) {
+  MX_CHECK(scores && rows > 0 && L > 0 && ld >= L, "softmax_rows: null operand or empty shape");
+  MX_CHECK(mx::aligned_to(scores, 16), "softmax_rows: scores must be 16-byte aligned");
+  return mx::launch_softmax_rows((hipStream_t)stream, scores, (long)rows, L, (long)ld);
+}
+extern "C" int mx_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, void* out, int rows, int L, int H, int vocab) {
+  MX_CHECK(ids && tok && out && rows > 0 && L > 0 && H > 0 && vocab > 0, "clip_embed: null operand or empty shape");
+  MX_CHECK(mx::aligned_to(tok, 16) && mx::aligned_to(pos, 16) && mx::aligned_to(out, 16), "clip_embed: tables and out must be 16-byte aligned");
+  return mx::launch_clip_embed((hipStream_t)stream, ids, (const mx::bf16_t*)tok, (const mx::bf16_t*)pos, (mx::bf16_t*)out, rows, L, H, vocab);
+}
+extern "C" int mx_clip_pool(void* stream, const int32_t* ids, const void* x, void* out, int B, int L, int H, int eos_id) {
+  MX_CHECK(ids && x && out && B > 0 && L > 0 && H > 0, "clip_pool: null operand or empty shape");
+  MX_CHECK(mx::aligned_to(x, 16) && mx::aligned_to(out, 16), "clip_pool: x and out must be 16-byte aligned");
+  return mx::launch_clip_pool((hipStream_t)stream, ids, (const mx::bf16_t*)x, (mx::bf16_t*)out, B, L, H, eos_id);
+}
 
 // ----------------------------------------------------------------------------------------------------------------------
 // Block-skip cache (unet_sdxl.cpp, mx_unet_forward_cached): per-sample squared difference of a block input against the input the block saw

@@ -37,7 +37,6 @@ int launch_prep_latent(hipStream_t s, const void* in, int dtype, void* out, int 
 int launch_nhwc_to_nchw(hipStream_t s, const void* in, void* out, int dtype, int B, int C, int HW, int ld);
 int launch_time_embed(hipStream_t s, const float* timesteps, const void* text_embeds, const float* time_ids,
                       void* tsin, void* addin, int B, int d0, int text_dim, int da);
-int launch_concat(hipStream_t s, const void* a, const void* b, void* out, long M, int C1, int C2);
 size_t gn_workspace_exact(int B, int H, int W, int C, int patch);
 int launch_sq_diff_partial(hipStream_t s, const void* a, const void* b, long elems_per_sample, int B, double* partial, const int* slot = nullptr);
 int launch_gn_pp_partial(hipStream_t s, const void* x, int C1, const void* x2, int B, int H, int W, int C, int groups, void* workspace, double* sums);

@@ -282,6 +282,17 @@ SYMBOLS = {
     "mx_pc_range_sq_diff": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _vp]),
     "mx_sq_diff_partial": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "mx_copy_rows": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _i]),
+    # the glue kernels at the models' boundaries, one launch each (tests and tools)
+    "mx_prep_latent": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i]),
+    "mx_nhwc_to_nchw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "mx_time_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "mx_sinus_embed": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mx_patchify": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
+    "mx_unpatchify": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "mx_crop_pos": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "mx_softmax_rows": (_i, [_vp, _vp, _i64, _i, _i64]),
+    "mx_clip_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "mx_clip_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "mx_mmdit_workspace_bytes_pp": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_pp_state_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "mx_mmdit_forward_pp": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz]),
