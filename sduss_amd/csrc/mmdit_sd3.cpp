@@ -579,6 +579,13 @@ struct Model {
     MX_CHECK(H / ps <= u->cfg.pos_embed_max_size && W / ps <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
     return 0;
   }
+  // the chunk unit (mx_mmdit_forward_cached_mixed and its sizing walks): whole patches of whole tokens, so a latent's tokens split into equal
+  // chunks; the device decision's joint blocks compare their image stream (one input)
+  int check_units(const mx_mmdit* u, const mx::ForwardCall& c) {
+    const std::string who = c.cached_who(name);
+    MX_CHECK(c.patch > 0 && c.patch % u->cfg.patch_size == 0, who + ": the chunk unit (latent pixels per patch edge) must be a multiple of patch_size");
+    return mx::check_cache_units(who, c, c.patch, "the patch", u->cfg.num_layers, 1, 0);
+  }
   int check(const mx_mmdit* u, const mx::ForwardCall& c) {
     for (int g = 1; c.groups && g < c.n_groups; ++g) if (check_shape(u, c.groups[g].H, c.groups[g].W, "mmdit: bad group shape")) return 1;
     if (check_shape(u, c.H, c.W, "mmdit: H, W must be multiples of patch_size")) return 1;
@@ -587,8 +594,61 @@ struct Model {
   }
   void begin(mx_mmdit*, const mx::ForwardCall&) {}
   void end(mx_mmdit*, const mx::ForwardCall&, bool) {}
-  void setup(Plan& p, mx_mmdit* u, const mx::ForwardCall& c) { p.u = u; p.Lt = c.ctx_len; }
-  bool run(Plan& p, const mx::ForwardCall& c) { return p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.pooled, c.out); }
+  int setup(Plan& p, mx_mmdit* u, const mx::ForwardCall& c) {
+    p.u = u; p.Lt = c.ctx_len;
+    return c.cache ? setup_cache(p, u, c) : 0;
+  }
+  // The cache's mode of the plan.  A sizing walk stops at the host tables; a forward then learns which samples hold state and queues on its stream,
+  // ahead of the first launch and in this order: the slot table, the sample and chunk tables, the device decision's tables, the timestep read-back.
+  int setup_cache(Plan& p, mx_mmdit* u, const mx::ForwardCall& c) {
+    const std::string who = c.cached_who(name);
+    mx_block_cache* cache = c.cache;
+    p.bc = cache;
+    if (!c.units()) {
+      if (c.dry) return 0;
+      return p.bc_begin(who, cache, c.batch, c.H, c.W) || p.bc_send_slots(who, Plan::kBcPartRows, Plan::kBcTables, c.batch) || p.bc_read_timesteps(who, c.timesteps, c.batch);
+    }
+    const int ps = u->cfg.patch_size, patch = c.patch, B = p.B;
+    p.pcm = true; p.pcm_patch = patch; p.pcm_slots = cache->n_slots; p.pcm_maxh = cache->max_h; p.pcm_maxw = cache->max_w;
+    long long row0 = 0;
+    for (int g = 0; g < p.ng; ++g) {
+      const int L = (p.gH[g] / ps) * (p.gW[g] / ps), nc = (p.gH[g] / patch) * (p.gW[g] / patch);
+      for (int k = 0; k < p.gB[g]; ++k) {
+        const int b = p.gb0[g] + k;
+        const int slot = (!c.dry && cache->slots) ? cache->slots[b] : b;
+        p.pcm_img.push_back(mx::PcSample{row0, L, 1, slot, 1});
+        p.pcm_ctx.push_back(mx::PcSample{(long long)b * c.ctx_len, c.ctx_len, 1, slot, 1});
+        for (int j = 0; j < nc; ++j) {
+          p.pcm_chunks.push_back(mx::PcRange{row0 + (long long)j * (L / nc), L / nc, slot, j * (L / nc)});
+          p.pcm_chunk_b.push_back(b); p.pcm_chunk_g.push_back(g);
+        }
+        row0 += L;
+      }
+    }
+    p.pcm_nc = (int)p.pcm_chunks.size();
+    if (c.dry) return 0;
+    if (p.bc_begin_slots(who, cache, B)) return 1;
+    MX_CHECK(p.pcm_head_bytes() <= cache->state_bytes, who + ": state buffer too small");
+    const size_t ncm = p.pcm_ncmax();
+    char* hp = (char*)cache->state;
+    p.pcm_dpart = (double*)hp; hp += ncm * 64 * sizeof(double);
+    p.pcm_dimg = (mx::PcSample*)hp; hp += (size_t)p.pcm_slots * sizeof(mx::PcSample);
+    p.pcm_dctx = (mx::PcSample*)hp; hp += (size_t)p.pcm_slots * sizeof(mx::PcSample);
+    p.pcm_dchunks = (mx::PcRange*)hp; hp += ncm * sizeof(mx::PcRange);
+    p.pcm_dtmp = (mx::PcRange*)hp;
+    MX_CHECK(hipMemcpyAsync(p.pcm_dimg, p.pcm_img.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+             hipMemcpyAsync(p.pcm_dctx, p.pcm_ctx.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+             hipMemcpyAsync(p.pcm_dchunks, p.pcm_chunks.data(), (size_t)p.pcm_nc * sizeof(mx::PcRange), hipMemcpyHostToDevice, p.stream) == hipSuccess,
+             who + ": moving the tables failed");
+    return p.bc_dev_begin(who, u->skip_pin, u->cfg.num_layers, (cache->max_h / patch) * (cache->max_w / patch), c.timesteps, p.pcm_chunk_b, p.group_of(), true) ||
+           p.bc_read_timesteps(who, c.timesteps, B);
+  }
+  bool run(Plan& p, const mx::ForwardCall& c) {
+    const bool okr = p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.pooled, c.out);
+    if (c.units() && !c.dry) { c.cache->patches_asked = p.pcm_asked; c.cache->patches_total = p.pcm_total; }
+    return okr;
+  }
+  size_t cache_bytes(const Plan& p) { return p.bc_bytes; }
   std::vector<uint64_t> key_scalars(const mx::ForwardCall&) { return {}; }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.pooled}; }
 };
@@ -596,13 +656,16 @@ int forward_impl(const mx_mmdit* u, const mx::ForwardCall& c) {
   Model m;
   return mx::run_forward<Plan>(const_cast<mx_mmdit*>(u), c, m);
 }
-// the call of a host-only walk of the plan at one shape
-mx::ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
+using mx::dry_call;
+using mx::sizing_comm;
+// the fields every forward entry point fills alike; the image (latents, out, batch, H, W) or the groups and the mode's own fields follow
+mx::ForwardCall forward_call(void* stream, int io_dtype, const float* timesteps, const void* ehs, const void* pooled, int ctx_len, void* workspace,
+                             size_t workspace_bytes) {
   mx::ForwardCall c;
-  c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
+  c.stream = stream; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled; c.ctx_len = ctx_len;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
   return c;
 }
-mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
 
 }  // namespace
 
@@ -638,9 +701,8 @@ extern "C" int mx_mmdit_validate(const mx_mmdit* u, int batch, int H, int W, int
 extern "C" int mx_mmdit_forward(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
                                 const void* ehs, const void* pooled, void* out, int batch, int H, int W, int ctx_len,
                                 void* workspace, size_t workspace_bytes) {
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
-  c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, pooled, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W;
   return forward_impl(u, c);
 }
 
@@ -657,9 +719,8 @@ extern "C" int mx_mmdit_forward_mixed(mx_mmdit* u, void* stream, const mx_unet_g
                                       const void* encoder_hidden_states, const void* pooled_projections, int ctx_len, void* workspace,
                                       size_t workspace_bytes) {
   MX_CHECK(groups != nullptr, "mmdit_forward_mixed: null groups");
-  mx::ForwardCall c;
-  c.stream = stream; c.groups = groups; c.n_groups = n_groups; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = encoder_hidden_states;
-  c.pooled = pooled_projections; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, encoder_hidden_states, pooled_projections, ctx_len, workspace, workspace_bytes);
+  c.groups = groups; c.n_groups = n_groups;
   return forward_impl(u, c);
 }
 
@@ -692,10 +753,8 @@ extern "C" int mx_mmdit_forward_pp(mx_mmdit* u, void* stream, const void* latent
     MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "mmdit_forward_pp: state must be 256-byte aligned device memory");
     MX_CHECK(stale->mode != MX_PP_STALE || stale->all_gather_async != nullptr, "mmdit_forward_pp: a stale step needs all_gather_async");
   }
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents_local; c.out = out_local; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
-  c.batch = batch; c.H = H_local; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-  c.comm = comm; c.stale = stale;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, pooled, ctx_len, workspace, workspace_bytes);
+  c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm; c.stale = stale;
   return forward_impl(u, c);
 }
 
@@ -707,75 +766,23 @@ extern "C" int mx_mmdit_pp_comm_plan(const mx_mmdit* u, int batch, int H_local, 
 }
 
 /* ---- the cache at the reference's unit (token chunks) over a mixed batch in ONE launch sequence (include/mxdenoise.h) ---- */
-namespace {
-int pcm_setup(Plan& p, mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len, int patch, const mx_block_cache* cache, bool dry) {
-  MX_CHECK(u != nullptr, "mmdit: null handle");
-  MX_CHECK(groups && n_groups >= 1 && n_groups <= MX_MAX_SEGS, "mmdit_forward_cached_mixed: 1..MX_MAX_SEGS resolution groups");
-  MX_CHECK(u->cfg.num_layers <= 64, "mmdit_forward_cached_mixed: at most 64 blocks");
-  const int ps = u->cfg.patch_size;
-  MX_CHECK(patch > 0 && patch % ps == 0, "mmdit_forward_cached_mixed: the chunk unit (latent pixels per patch edge) must be a multiple of patch_size");
-  MX_CHECK(cache && cache->n_slots > 0 && cache->max_h > 0 && cache->max_w > 0 && cache->max_h % patch == 0 && cache->max_w % patch == 0,
-           "mmdit_forward_cached_mixed: cache->n_slots, max_h, max_w (multiples of the patch) are required");
-  MX_CHECK(ctx_len > 0, "mmdit: bad shape");
-  p.u = u; p.Lt = ctx_len;
-  p.set_groups(groups, n_groups);
-  p.pcm = true; p.pcm_patch = patch; p.pcm_slots = cache->n_slots; p.pcm_maxh = cache->max_h; p.pcm_maxw = cache->max_w;
-  p.pcm_img.clear(); p.pcm_ctx.clear(); p.pcm_chunks.clear(); p.pcm_chunk_b.clear(); p.pcm_chunk_g.clear();
-  long long row0 = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    MX_CHECK(groups[g].batch > 0 && groups[g].H > 0 && groups[g].W > 0 && groups[g].H % patch == 0 && groups[g].W % patch == 0,
-             "mmdit_forward_cached_mixed: every group's H, W must be multiples of the patch");
-    MX_CHECK(groups[g].H <= cache->max_h && groups[g].W <= cache->max_w, "mmdit_forward_cached_mixed: a group is larger than the state rows (max_h, max_w)");
-    MX_CHECK(groups[g].H / ps <= u->cfg.pos_embed_max_size && groups[g].W / ps <= u->cfg.pos_embed_max_size, "mmdit: latent larger than the positional table");
-    MX_CHECK(dry || (groups[g].latents && groups[g].out), "mmdit: null group operand");
-    const int L = (groups[g].H / ps) * (groups[g].W / ps), nc = (groups[g].H / patch) * (groups[g].W / patch);
-    MX_CHECK(L % nc == 0, "mmdit_forward_cached_mixed: the tokens of a latent must split into equal chunks");
-    for (int k = 0; k < groups[g].batch; ++k) {
-      const int b = p.gb0[g] + k;
-      const int slot = (!dry && cache->slots) ? cache->slots[b] : b;
-      p.pcm_img.push_back(mx::PcSample{row0, L, 1, slot, 1});
-      p.pcm_ctx.push_back(mx::PcSample{(long long)b * ctx_len, ctx_len, 1, slot, 1});
-      for (int j = 0; j < nc; ++j) {
-        p.pcm_chunks.push_back(mx::PcRange{row0 + (long long)j * (L / nc), L / nc, slot, j * (L / nc)});
-        p.pcm_chunk_b.push_back(b); p.pcm_chunk_g.push_back(g);
-      }
-      row0 += L;
-    }
-  }
-  p.pcm_nc = (int)p.pcm_chunks.size();
-  MX_CHECK(p.B <= cache->n_slots, "mmdit_forward_cached_mixed: more samples than state rows (n_slots)");
-  return 0;
-}
-// a host-only walk of a plan whose cache mode the caller has set up: sizes against `sizing`, no launches
-bool dry_walk(Plan& p, const mx_mmdit* u, mx_block_cache* sizing) {
-  p.u = const_cast<mx_mmdit*>(u);
-  p.begin_dry(u->weights);
-  p.bc = sizing;
-  if (p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr)) return true;
-  mx::set_error(p.err);
-  return false;
-}
-size_t pcm_dry(const mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len, int patch, mx_block_cache* sizing, bool want_state) {
-  Plan p;
-  if (pcm_setup(p, const_cast<mx_mmdit*>(u), groups, n_groups, ctx_len, patch, sizing, true) || !dry_walk(p, u, sizing)) return 0;
-  return want_state ? p.bc_bytes + 256 : p.ar.peak + 256;
-}
-}  // namespace
-
 extern "C" size_t mx_mmdit_patch_cache_bytes(const mx_mmdit* u, int n_slots, int max_h, int max_w, int patch, int ctx_len) {
   if (!u || n_slots <= 0 || max_h <= 0 || max_w <= 0 || patch <= 0 || ctx_len <= 0) { mx::set_error("mmdit_patch_cache_bytes: bad arguments"); return 0; }
-  mx_block_cache sizing{};
-  sizing.n_slots = n_slots; sizing.max_h = max_h; sizing.max_w = max_w;
-  mx_unet_group g{nullptr, nullptr, n_slots, max_h, max_w};
-  return pcm_dry(u, &g, 1, ctx_len, patch, &sizing, true);
+  const mx_unet_group g{nullptr, nullptr, n_slots, max_h, max_w};      // every state row in use by a latent that fills it
+  mx_block_cache sizing = mx::sizing_cache(&g, 1);
+  size_t state = 0;
+  mx::ForwardCall c = dry_call(0, 0, 0, ctx_len);
+  c.groups = &g; c.n_groups = 1; c.patch = patch; c.cache = &sizing; c.state_bytes = &state;
+  return forward_impl(u, c) ? 0 : state + 256;
 }
 
 extern "C" size_t mx_mmdit_workspace_bytes_cached_mixed(const mx_mmdit* u, const mx_unet_group* groups, int n_groups, int ctx_len, int patch) {
-  mx_block_cache sizing{};
-  if (groups) for (int g = 0; g < n_groups && g < MX_MAX_SEGS; ++g) {
-    sizing.n_slots += groups[g].batch; sizing.max_h = std::max(sizing.max_h, groups[g].H); sizing.max_w = std::max(sizing.max_w, groups[g].W);
-  }
-  return pcm_dry(u, groups, n_groups, ctx_len, patch, &sizing, false);
+  if (mx::check_cached_groups("mmdit_forward_cached_mixed", groups, n_groups)) return 0;
+  mx_block_cache sizing = mx::sizing_cache(groups, n_groups);
+  size_t peak = 0;
+  mx::ForwardCall c = dry_call(0, 0, 0, ctx_len);
+  c.groups = groups; c.n_groups = n_groups; c.patch = patch; c.cache = &sizing; c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 256;
 }
 
 extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
@@ -785,69 +792,32 @@ extern "C" int mx_mmdit_forward_cached_mixed(mx_mmdit* u, void* stream, const mx
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
-  Plan p;
-  if (pcm_setup(p, u, groups, n_groups, ctx_len, patch, cache, false)) return 1;
-  // the device decision: every joint block compares its image stream (one input)
-  const int ups = (cache->max_h / patch) * (cache->max_w / patch);
-  if (Plan::bc_dev_check(who, cache, u->cfg.num_layers, ups, 1, 0)) return 1;
-  MX_CHECK(timesteps && ehs && pooled && workspace, "mmdit: null operand");
-  MX_CHECK(u->weights.blob != nullptr, "mmdit: weights not set");
-  MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
-  const int B = p.B;
-  if (p.bc_begin_slots(who, cache, B)) return 1;
-  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
-  MX_CHECK(p.pcm_head_bytes() <= cache->state_bytes, who + ": state buffer too small");
-  const size_t ncm = p.pcm_ncmax();
-  char* hp = (char*)cache->state;
-  p.pcm_dpart = (double*)hp; hp += ncm * 64 * sizeof(double);
-  p.pcm_dimg = (mx::PcSample*)hp; hp += (size_t)p.pcm_slots * sizeof(mx::PcSample);
-  p.pcm_dctx = (mx::PcSample*)hp; hp += (size_t)p.pcm_slots * sizeof(mx::PcSample);
-  p.pcm_dchunks = (mx::PcRange*)hp; hp += ncm * sizeof(mx::PcRange);
-  p.pcm_dtmp = (mx::PcRange*)hp;
-  MX_CHECK(hipMemcpyAsync(p.pcm_dimg, p.pcm_img.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
-           hipMemcpyAsync(p.pcm_dctx, p.pcm_ctx.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
-           hipMemcpyAsync(p.pcm_dchunks, p.pcm_chunks.data(), (size_t)p.pcm_nc * sizeof(mx::PcRange), hipMemcpyHostToDevice, p.stream) == hipSuccess,
-           who + ": moving the tables failed");
-  std::vector<int> group_of(B);
-  for (int g = 0; g < p.ng; ++g) for (int k = 0; k < p.gB[g]; ++k) group_of[p.gb0[g] + k] = g;
-  if (p.bc_dev_begin(who, u->skip_pin, u->cfg.num_layers, ups, timesteps, p.pcm_chunk_b, std::move(group_of), true)) return 1;
-  if (p.bc_read_timesteps(who, timesteps, B)) return 1;
-  const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, pooled, groups[0].out);
-  cache->patches_asked = p.pcm_asked; cache->patches_total = p.pcm_total;
-  return p.bc_finish(okr, p.blocks_run);
+  if (mx::check_cached_groups(who, groups, n_groups)) return 1;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, pooled, ctx_len, workspace, workspace_bytes);
+  c.groups = groups; c.n_groups = n_groups; c.patch = patch; c.cache = cache;
+  return forward_impl(u, c);
 }
 
 /* ---- block-skip cache (include/mxdenoise.h; SD3Transformer.py:151-228 with cache_manager.py:163-191) ---- */
 extern "C" size_t mx_mmdit_block_cache_bytes(const mx_mmdit* u, int batch, int H, int W, int ctx_len) {
   if (!u || batch <= 0 || H <= 0 || W <= 0 || ctx_len <= 0 || H % u->cfg.patch_size || W % u->cfg.patch_size) return 0;
-  Plan p;
   mx_block_cache sizing{};
-  p.set_single(batch, H, W, nullptr, nullptr); p.Lt = ctx_len; p.bc_rows = batch;
-  return dry_walk(p, u, &sizing) ? p.bc_bytes : 0;
+  size_t state = 0;
+  mx::ForwardCall c = dry_call(batch, H, W, ctx_len);
+  c.cache = &sizing; c.state_bytes = &state;
+  return forward_impl(u, c) ? 0 : state;
 }
 
 extern "C" int mx_mmdit_forward_cached(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                        const void* pooled, void* out, int batch, int H, int W, int ctx_len, void* workspace,
                                        size_t workspace_bytes, mx_block_cache* cache) {
   const std::string who = "mmdit_forward_cached";
-  MX_CHECK(u != nullptr, "mmdit: null handle");
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the chunk unit only (mx_mmdit_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
-  MX_CHECK(u->cfg.num_layers <= 64, who + ": at most 64 blocks");
-  MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "mmdit: bad shape");
-  if (Model::check_shape(u, H, W, "mmdit: H, W must be multiples of patch_size")) return 1;
-  MX_CHECK(latents && timesteps && ehs && pooled && out && workspace, "mmdit: null operand");
-  MX_CHECK(u->weights.blob != nullptr, "mmdit: weights not set");
-  MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "mmdit: bad io dtype");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
-  Plan p;
-  if (p.bc_begin(who, cache, batch, H, W)) return 1;
-  p.u = u; p.Lt = ctx_len;
-  p.set_single(batch, H, W, latents, out);
-  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
-  if (p.bc_send_slots(who, Plan::kBcPartRows, Plan::kBcTables, batch) || p.bc_read_timesteps(who, timesteps, batch)) return 1;
-  const bool okr = p.run(latents, io_dtype, timesteps, ehs, pooled, out);
-  return p.bc_finish(okr, p.blocks_run);
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, pooled, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W; c.cache = cache;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_mmdit_forward_trace(mx_mmdit* u, void* stream, const void* latents, int io_dtype, const float* timesteps,
@@ -855,9 +825,8 @@ extern "C" int mx_mmdit_forward_trace(mx_mmdit* u, void* stream, const void* lat
                                       void* workspace, size_t workspace_bytes, const char* stage, void* stage_out,
                                       size_t stage_out_bytes) {
   MX_CHECK(stage && stage_out, "mmdit_forward_trace: stage and stage_out required");
-  mx::ForwardCall c;
-  c.stream = stream; c.latents = latents; c.out = out; c.io_dtype = io_dtype; c.timesteps = timesteps; c.ehs = ehs; c.pooled = pooled;
-  c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, pooled, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W;
   c.stage = stage; c.stage_out = stage_out; c.stage_bytes = stage_out_bytes;
   return forward_impl(u, c);
 }

@@ -10,9 +10,11 @@
 //                     comparison partial sums read back as per-row MSEs);
 //   * ForwardCall  -- one forward of a denoiser as named fields, and run_forward, the driver both denoisers share: generic checks -> the
 //                     model's checks -> plan set-up -> recording walk of a stale patch-parallel layout -> eager run or hipGraph replay.
+//                     Plain, mixed, trace, patch-parallel and block-skip-cached forwards and every sizing walk go through it.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <string>
@@ -133,6 +135,11 @@ struct Groups {
       gB[g] = groups[g].batch; gH[g] = groups[g].H; gW[g] = groups[g].W; gb0[g] = B; g_lat[g] = groups[g].latents; g_out[g] = groups[g].out;
       B += groups[g].batch;
     }
+  }
+  std::vector<int> group_of() const {     // per sample: its group
+    std::vector<int> of(B);
+    for (int g = 0; g < ng; ++g) for (int k = 0; k < gB[g]; ++k) of[gb0[g] + k] = g;
+    return of;
   }
 };
 
@@ -328,20 +335,64 @@ struct ForwardCall {
   size_t* peak = nullptr;                // out: workspace bytes the plan took
   size_t* state_need = nullptr;          // out: bytes of the stale patch-parallel state
   const mx_unet_group* groups = nullptr; int n_groups = 0;               // mixed-resolution batch (then batch, H, W, latents, out are the first group's)
+  // block-skip cache: the caller's descriptor, or the zeroed one with n_slots, max_h, max_w of a sizing walk.  Its unit is the sample, or over
+  // `groups` the patch / chunk of `patch` latent pixels a side (the UNet's is its gn_patch)
+  mx_block_cache* cache = nullptr; int patch = 0;
+  size_t* state_bytes = nullptr;         // out: bytes of the cache's state a dry plan took
   bool pp() const { return comm != nullptr && comm->world > 1; }
+  bool units() const { return cache != nullptr && groups != nullptr; }
+  std::string cached_who(const std::string& model) const { return model + (groups ? "_forward_cached_mixed" : "_forward_cached"); }   // prefix of the cached entries' own messages
 };
+// the call of a host-only walk of the plan at one shape
+inline ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
+  ForwardCall c;
+  c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
+  return c;
+}
+inline mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
+// the descriptor a sizing walk of the patch / chunk unit runs against: one state row per sample, as large as the largest group
+inline mx_block_cache sizing_cache(const mx_unet_group* groups, int n_groups) {
+  mx_block_cache s{};
+  for (int g = 0; g < n_groups; ++g) { s.n_slots += groups[g].batch; s.max_h = std::max(s.max_h, groups[g].H); s.max_w = std::max(s.max_w, groups[g].W); }
+  return s;
+}
+// the group list of a cached entry point (the driver's own check speaks of a mixed batch)
+inline int check_cached_groups(const std::string& who, const mx_unet_group* groups, int n_groups) {
+  MX_CHECK(groups && n_groups >= 1 && n_groups <= MX_MAX_SEGS, who + ": 1..MX_MAX_SEGS resolution groups");
+  return 0;
+}
+// A cached call over groups against its unit of `unit` > 0 latent pixels a side (`word` names it in the messages): state rows of whole units that
+// hold every group, one row per sample; then what the device decision needs (n_blocks, n_in_down, n_in_up: DenoiserPlan::bc_dev_check)
+inline int check_cache_units(const std::string& who, const ForwardCall& c, int unit, const std::string& word, int n_blocks, int n_in_down, int n_in_up) {
+  const mx_block_cache* cache = c.cache;
+  MX_CHECK(cache->n_slots > 0 && cache->max_h > 0 && cache->max_w > 0 && cache->max_h % unit == 0 && cache->max_w % unit == 0,
+           who + ": cache->n_slots, max_h, max_w (multiples of " + word + ") are required");
+  int B = 0;
+  for (int g = 0; g < c.n_groups; ++g) {
+    const mx_unet_group& q = c.groups[g];
+    MX_CHECK(q.batch > 0 && q.H > 0 && q.W > 0 && q.H % unit == 0 && q.W % unit == 0, who + ": every group's H, W must be multiples of " + word);
+    MX_CHECK(q.H <= cache->max_h && q.W <= cache->max_w, who + ": a group is larger than the state rows (max_h, max_w)");
+    B += q.batch;
+  }
+  MX_CHECK(B <= cache->n_slots, who + ": more samples than state rows (n_slots)");
+  return DenoiserPlan::bc_dev_check(who, cache, n_blocks, (cache->max_h / unit) * (cache->max_w / unit), n_in_down, n_in_up);
+}
 
 // The driver of both denoisers.  Handle: weights, graphs, pp_sizes.  Model (one object per call) supplies
 //   name                         -- the prefix of the messages;
+//   check_units(u, c)            -- a cached call over groups: the unit, the state rows and the groups against them, the device decision's arguments;
 //   check(u, c)                  -- the model's own shape and operand checks (0 = fine; c.batch / H / W already describe the first group);
 //   begin(u, c) / end(u, c, ok)  -- around the run (the UNet's stored cross-attention K / V^T);
-//   setup(p, u, c)               -- the model's fields of a fresh plan;
+//   setup(p, u, c)               -- the model's fields of a fresh plan (0 = fine); a cached call: the cache's mode, its tables sent, the timesteps read;
 //   run(p, c)                    -- p.run(...) with the call's operands;
+//   cache_bytes(p)               -- state bytes a dry cached plan took;
 //   key_scalars(c), key_operands(c) -- its extra fields of the graph key (the scalars also key the recorded exchange sizes).
+// A cached call runs eagerly (its decision synchronises the stream or calls back into the host) and is never looked up among the graphs.
 template <class Plan, class Handle, class Model>
 int run_forward(Handle* u, ForwardCall c, Model& m) {
   const std::string name = m.name;
   MX_CHECK(u != nullptr, name + ": null handle");
+  if (c.units() && m.check_units(u, c)) return 1;
   if (c.groups) {
     MX_CHECK(c.n_groups >= 1 && c.n_groups <= MX_MAX_SEGS && c.comm == nullptr, name + ": a mixed batch has 1..MX_MAX_SEGS resolution groups and does not run patch-parallel");
     c.batch = c.groups[0].batch; c.H = c.groups[0].H; c.W = c.groups[0].W; c.latents = c.groups[0].latents; c.out = c.groups[0].out;
@@ -368,7 +419,7 @@ int run_forward(Handle* u, ForwardCall c, Model& m) {
     p.stream = s; p.lookup = c.lookup; p.stage = c.stage; p.stage_out = c.stage_out; p.stage_bytes = c.stage_bytes;
     if (c.groups) p.set_groups(c.groups, c.n_groups); else p.set_single(c.batch, c.H, c.W, c.latents, c.out);
     if (pp) p.px.set(c.comm, c.stale);
-    m.setup(p, u, c);
+    if (m.setup(p, u, c)) { err = mx_last_error(); return false; }
     if (pp && c.stale) {      // the state layout (exchanges dealt into chunks, pp_exchange.h) from a host-only recording walk of the same plan
       std::vector<long> lk = {(long)c.batch, (long)c.H, (long)c.W, (long)c.ctx_len};
       for (uint64_t v : m.key_scalars(c)) lk.push_back((long)v);
@@ -388,11 +439,13 @@ int run_forward(Handle* u, ForwardCall c, Model& m) {
     const bool okr = m.run(p, c);
     plan_peak = p.ar.peak;
     if (c.state_need) *c.state_need = p.px.state_top;
+    if (c.state_bytes) *c.state_bytes = m.cache_bytes(p);
+    if (c.cache && !c.dry) p.bc_finish(okr, p.blocks_run);
     if (!okr) err = p.err;
     return okr;
   };
   bool okr;
-  if (c.dry || c.stage || pp) {     // (the all-gather callbacks of a patch-parallel forward cannot be captured)
+  if (c.dry || c.stage || pp || c.cache) {     // (the all-gather callbacks of a patch-parallel forward cannot be captured)
     okr = enqueue((hipStream_t)c.stream);
   } else {
     auto ptr = [](const void* q) { return (uint64_t)(uintptr_t)q; };

@@ -1230,25 +1230,35 @@ struct Model {
     }
     return 0;
   }
+  // the patch unit (mx_unet_forward_cached_mixed and its sizing walks): patches of >= 2 pixels at the deepest level; the device decision's down
+  // and mid blocks compare their input, an up block its input and the skips it consumes
+  int check_units(const mx_unet* u, const mx::ForwardCall& c) {
+    const std::string who = c.cached_who(name);
+    MX_CHECK(c.gn_patch > 0 && (c.gn_patch >> (u->cfg.n_levels - 1)) >= 2, who + ": the patch unit needs is_sliced (gn_patch > 0, >= 2 pixels at the deepest level)");
+    return mx::check_cache_units(who, c, c.gn_patch, "gn_patch", 2 * u->cfg.n_levels + 1, 1, u->cfg.layers_per_block + 2);
+  }
   int check(const mx_unet* u, const mx::ForwardCall& c) {
     const int div = 1 << (u->cfg.n_levels - 1);
-    for (int g = 0; c.groups && g < c.n_groups; ++g) {
-      const mx_unet_group& q = c.groups[g];
-      MX_CHECK(q.H % div == 0 && q.W % div == 0, "unet: bad group shape");
-      if (c.gn_patch > 0)
-        MX_CHECK((q.H % c.gn_patch == 0 && q.W % c.gn_patch == 0) || (c.gn_patch >= q.H && c.gn_patch >= q.W), "unet: every group's H, W must be multiples of gn_patch");
+    if (!c.units()) {     // (the patch unit has stated its own rule for H, W, whole patches: a call it accepts is not measured against 2^(levels-1) as well)
+      for (int g = 0; c.groups && g < c.n_groups; ++g) {
+        const mx_unet_group& q = c.groups[g];
+        MX_CHECK(q.H % div == 0 && q.W % div == 0, "unet: bad group shape");
+        if (c.gn_patch > 0)
+          MX_CHECK((q.H % c.gn_patch == 0 && q.W % c.gn_patch == 0) || (c.gn_patch >= q.H && c.gn_patch >= q.W), "unet: every group's H, W must be multiples of gn_patch");
+      }
+      if (c.pp()) {
+        MX_CHECK(c.gn_patch == 0, "unet pp: patch-parallel runs the exact (is_sliced=False) arithmetic");
+        MX_CHECK(c.H % div == 0, "unet pp: local rows must be divisible by 2^(levels-1)");
+      }
+      if (check_shape(u, c.H, c.W, c.gn_patch)) return 1;
     }
-    if (c.pp()) {
-      MX_CHECK(c.gn_patch == 0, "unet pp: patch-parallel runs the exact (is_sliced=False) arithmetic");
-      MX_CHECK(c.H % div == 0, "unet pp: local rows must be divisible by 2^(levels-1)");
-    }
-    if (check_shape(u, c.H, c.W, c.gn_patch)) return 1;
     MX_CHECK(c.dry || (c.text_embeds && c.time_ids), "unet: null operand");
     return 0;
   }
-  // the composition's stored cross-attention K / V^T (mx_unet_set_context_key): plain and mixed forwards; not patch-parallel (its ranks hold row bands)
+  // the composition's stored cross-attention K / V^T (mx_unet_set_context_key): plain and mixed forwards; not patch-parallel (its ranks hold row bands).
+  // A cached forward projects into its workspace: it neither consults the store nor uses up the key, which stays for the uncached forward it names.
   void begin(mx_unet* u, const mx::ForwardCall& c) {
-    if (c.dry) return;
+    if (c.dry || c.cache) return;
     if (!c.pp()) {
       int Btot = c.batch;
       if (c.groups) { Btot = 0; for (int g = 0; g < c.n_groups; ++g) Btot += c.groups[g].batch; }
@@ -1263,14 +1273,61 @@ struct Model {
     ctx_e->recorded = hipEventRecord(ctx_e->ev, (hipStream_t)c.stream) == hipSuccess;
     if (!ctx_e->recorded) { (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)c.stream); }
   }
-  void setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
+  int setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
     p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
-    bool patch_covers_all = true;
+    bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
     p.gn_patch = patch_covers_all ? 0 : c.gn_patch;
     if (c.pp()) { p.pp_rank = c.comm->rank; p.pp_world = c.comm->world; p.Htot = c.H * c.comm->world; }
+    return c.cache ? setup_cache(p, u, c) : 0;
   }
-  bool run(Plan& p, const mx::ForwardCall& c) { return p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.text_embeds, c.time_ids, c.out); }
+  // The cache's mode of the plan.  A sizing walk stops at the host tables; a forward then learns which samples hold state and queues on its stream,
+  // ahead of the first launch and in this order: the slot table, the sample and patch tables, the device decision's tables, the timestep read-back.
+  int setup_cache(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
+    const std::string who = c.cached_who(name);
+    mx_block_cache* cache = c.cache;
+    p.bc = cache;
+    if (!c.units()) {
+      if (c.dry) return 0;
+      return p.bc_begin(who, cache, c.batch, c.H, c.W) || p.bc_send_slots(who, Plan::bc_part_rows(u->cfg.layers_per_block), Plan::kBcTables, c.batch) ||
+             p.bc_read_timesteps(who, c.timesteps, c.batch);
+    }
+    const int gp = c.gn_patch, B = p.B;
+    p.pc = true; p.pc_p0 = gp; p.pc_maxh = cache->max_h; p.pc_maxw = cache->max_w; p.pc_slots = cache->n_slots;
+    long long row0 = 0;
+    for (int g = 0; g < p.ng; ++g)
+      for (int i = 0; i < p.gB[g]; ++i) {
+        const int b = p.gb0[g] + i;
+        mx::PcSample s; s.row0 = row0; s.h = p.gH[g]; s.w = p.gW[g]; s.slot = (!c.dry && cache->slots) ? cache->slots[b] : b; s.npx = p.gW[g] / gp;
+        p.pc_samp.push_back(s);
+        for (int py = 0; py < p.gH[g] / gp; ++py)
+          for (int px = 0; px < p.gW[g] / gp; ++px) p.pc_all.push_back(mx::PcPatch{b, py, px, 0});
+        row0 += (long long)p.gH[g] * p.gW[g];
+      }
+    p.pc_np = (int)p.pc_all.size();
+    if (c.dry) return 0;
+    if (p.bc_begin_slots(who, cache, B)) return 1;
+    MX_CHECK(p.pc_head_bytes(p.pc_slots, p.pc_maxh, p.pc_maxw, gp) <= cache->state_bytes, who + ": state buffer too small");
+    const size_t npm = Plan::pc_np_max(p.pc_slots, p.pc_maxh, p.pc_maxw, gp);
+    char* hp = (char*)cache->state;
+    p.pc_dpart = (double*)hp; hp += (size_t)(u->cfg.layers_per_block + 2) * npm * gp * sizeof(double);
+    p.pc_dsamp = (mx::PcSample*)hp; hp += (size_t)p.pc_slots * sizeof(mx::PcSample);
+    p.pc_dall = (mx::PcPatch*)hp; hp += npm * sizeof(mx::PcPatch);
+    p.pc_dask = (mx::PcPatch*)hp;
+    MX_CHECK(hipMemcpyAsync(p.pc_dsamp, p.pc_samp.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
+             hipMemcpyAsync(p.pc_dall, p.pc_all.data(), (size_t)p.pc_np * sizeof(mx::PcPatch), hipMemcpyHostToDevice, p.stream) == hipSuccess,
+             who + ": moving the tables failed");
+    std::vector<int> unit_b(p.pc_np);
+    for (int j = 0; j < p.pc_np; ++j) unit_b[j] = p.pc_all[j].b;
+    return p.bc_dev_begin(who, u->skip_pin, 2 * u->cfg.n_levels + 1, (cache->max_h / gp) * (cache->max_w / gp), c.timesteps, std::move(unit_b), p.group_of(), false) ||
+           p.bc_read_timesteps(who, c.timesteps, B);
+  }
+  bool run(Plan& p, const mx::ForwardCall& c) {
+    const bool okr = p.run(c.latents, c.io_dtype, c.timesteps, c.ehs, c.text_embeds, c.time_ids, c.out);
+    if (c.units() && !c.dry) { c.cache->patches_asked = p.pc_asked; c.cache->patches_total = p.pc_total; }
+    return okr;
+  }
+  size_t cache_bytes(const Plan& p) { return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000); }     // (a dry walk's bump pointer starts at a placeholder base, as the arena does)
   std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) { return {(uint64_t)c.gn_patch}; }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
 };
@@ -1278,12 +1335,8 @@ int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   Model m;
   return mx::run_forward<Plan>(const_cast<mx_unet*>(u), c, m);
 }
-// the call of a host-only walk of the plan at one shape
-mx::ForwardCall dry_call(int batch, int H, int W, int ctx_len) {
-  mx::ForwardCall c;
-  c.dry = true; c.batch = batch; c.H = H; c.W = W; c.ctx_len = ctx_len;
-  return c;
-}
+using mx::dry_call;
+using mx::sizing_comm;
 // the fields every forward entry point fills alike; the image (latents, out, batch, H, W) or the groups, gn_patch and the mode's own fields follow
 mx::ForwardCall forward_call(void* stream, int io_dtype, const float* timesteps, const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len,
                              void* workspace, size_t workspace_bytes) {
@@ -1292,7 +1345,6 @@ mx::ForwardCall forward_call(void* stream, int io_dtype, const float* timesteps,
   c.workspace = workspace; c.workspace_bytes = workspace_bytes;
   return c;
 }
-mx_pp_comm sizing_comm(int world) { mx_pp_comm c; c.rank = 0; c.world = world; c.all_gather = nullptr; c.ctx = nullptr; return c; }
 
 }  // namespace
 
@@ -1402,109 +1454,47 @@ extern "C" int mx_unet_forward_mixed_trace(mx_unet* u, void* stream, const mx_un
 }
 
 /* ---- block-skip cache (include/mxdenoise.h; the reference's CacheManager, modules/cache_manager.py:101-161) ---- */
-namespace {
-// a host-only walk of a plan whose cache mode the caller has set up: sizes against `sizing`, no launches
-bool dry_walk(Plan& p, const mx_unet* u, mx_block_cache* sizing) {
-  p.u = const_cast<mx_unet*>(u);
-  p.begin_dry(u->weights);
-  p.bc = sizing;
-  if (p.run(nullptr, MX_BF16, nullptr, nullptr, nullptr, nullptr, nullptr)) return true;
-  mx::set_error(p.err);
-  return false;
-}
-size_t bc_top_bytes(const Plan& p) { return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000) + 256; }     // (dry walk: the bump pointer starts at a placeholder base, as the arena does)
-}  // namespace
-
 extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, int W) {
   if (!u || batch <= 0 || H <= 0 || W <= 0) return 0;
   const int div = 1 << (u->cfg.n_levels - 1);
   if (H % div || W % div) return 0;
-  Plan p;
   mx_block_cache sizing{};
-  p.set_single(batch, H, W, nullptr, nullptr); p.ctx_len = 64; p.gn_patch = 0; p.bc_rows = batch;
-  return dry_walk(p, u, &sizing) ? bc_top_bytes(p) : 0;
+  size_t state = 0;
+  mx::ForwardCall c = dry_call(batch, H, W, 64);     // (the state holds block inputs and outputs: no tensor of it depends on the context length or on gn_patch)
+  c.cache = &sizing; c.state_bytes = &state;
+  return forward_impl(u, c) ? 0 : state + 256;
 }
 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
   const std::string who = "unet_forward_cached";
-  MX_CHECK(u != nullptr, "unet: null handle");
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
-  MX_CHECK(batch > 0 && H > 0 && W > 0 && ctx_len > 0, "unet: bad shape");
-  if (Model::check_shape(u, H, W, gn_patch)) return 1;
-  MX_CHECK(latents && timesteps && ehs && text_embeds && time_ids && out && workspace, "unet: null operand");
-  MX_CHECK(u->weights.blob != nullptr, "unet: weights not set");
-  MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
-  Plan p;
-  if (p.bc_begin(who, cache, batch, H, W)) return 1;
-  p.u = u; p.ctx_len = ctx_len;
-  p.set_single(batch, H, W, latents, out);
-  p.gn_patch = (gn_patch >= H && gn_patch >= W) ? 0 : gn_patch;
-  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
-  if (p.bc_send_slots(who, Plan::bc_part_rows(u->cfg.layers_per_block), Plan::kBcTables, batch) || p.bc_read_timesteps(who, timesteps, batch)) return 1;
-  const bool okr = p.run(latents, io_dtype, timesteps, ehs, text_embeds, time_ids, out);
-  return p.bc_finish(okr, p.blocks_run);
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.latents = latents; c.out = out; c.batch = batch; c.H = H; c.W = W; c.gn_patch = gn_patch; c.cache = cache;
+  return forward_impl(u, c);
 }
-
 
 /* ---- block-skip cache at the reference's unit, the patch, over a mixed-resolution batch in ONE launch sequence (include/mxdenoise.h) ---- */
-namespace {
-int pc_setup(Plan& p, mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch, const mx_block_cache* cache, bool dry) {
-  MX_CHECK(u != nullptr, "unet: null handle");
-  MX_CHECK(groups && n_groups >= 1 && n_groups <= MX_MAX_SEGS, "unet_forward_cached_mixed: 1..MX_MAX_SEGS resolution groups");
-  MX_CHECK(gn_patch > 0 && (gn_patch >> (u->cfg.n_levels - 1)) >= 2, "unet_forward_cached_mixed: the patch unit needs is_sliced (gn_patch > 0, >= 2 pixels at the deepest level)");
-  MX_CHECK(cache && cache->n_slots > 0 && cache->max_h > 0 && cache->max_w > 0 && cache->max_h % gn_patch == 0 && cache->max_w % gn_patch == 0,
-           "unet_forward_cached_mixed: cache->n_slots, max_h, max_w (multiples of gn_patch) are required");
-  MX_CHECK(ctx_len > 0, "unet: bad shape");
-  for (int g = 0; g < n_groups; ++g) {
-    MX_CHECK(groups[g].batch > 0 && groups[g].H > 0 && groups[g].W > 0 && groups[g].H % gn_patch == 0 && groups[g].W % gn_patch == 0,
-             "unet_forward_cached_mixed: every group's H, W must be multiples of gn_patch");
-    MX_CHECK(groups[g].H <= cache->max_h && groups[g].W <= cache->max_w, "unet_forward_cached_mixed: a group is larger than the state rows (max_h, max_w)");
-    MX_CHECK(dry || (groups[g].latents && groups[g].out), "unet: null group operand");
-  }
-  p.u = u; p.ctx_len = ctx_len; p.gn_patch = gn_patch;
-  p.set_groups(groups, n_groups);
-  MX_CHECK(p.B <= cache->n_slots, "unet_forward_cached_mixed: more samples than state rows (n_slots)");
-  p.pc = true; p.pc_p0 = gn_patch; p.pc_maxh = cache->max_h; p.pc_maxw = cache->max_w; p.pc_slots = cache->n_slots;
-  p.pc_samp.clear(); p.pc_all.clear();
-  long long row0 = 0;
-  for (int g = 0; g < n_groups; ++g)
-    for (int i = 0; i < p.gB[g]; ++i) {
-      const int b = p.gb0[g] + i;
-      mx::PcSample s; s.row0 = row0; s.h = p.gH[g]; s.w = p.gW[g]; s.slot = (!dry && cache->slots) ? cache->slots[b] : b; s.npx = p.gW[g] / gn_patch;
-      p.pc_samp.push_back(s);
-      for (int py = 0; py < p.gH[g] / gn_patch; ++py)
-        for (int px = 0; px < p.gW[g] / gn_patch; ++px) p.pc_all.push_back(mx::PcPatch{b, py, px, 0});
-      row0 += (long long)p.gH[g] * p.gW[g];
-    }
-  p.pc_np = (int)p.pc_all.size();
-  return 0;
-}
-// the patch-unit cache's sizing walk: the plan, walked (nullptr-run: pc_setup or the walk refused)
-bool pc_dry(Plan& p, const mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch, mx_block_cache* sizing) {
-  return !pc_setup(p, const_cast<mx_unet*>(u), groups, n_groups, ctx_len, gn_patch, sizing, true) && dry_walk(p, u, sizing);
-}
-}  // namespace
-
 extern "C" size_t mx_unet_patch_cache_bytes(const mx_unet* u, int n_slots, int max_h, int max_w, int gn_patch) {
   if (!u || n_slots <= 0 || max_h <= 0 || max_w <= 0 || gn_patch <= 0 || max_h % gn_patch || max_w % gn_patch) { mx::set_error("patch_cache_bytes: bad arguments"); return 0; }
-  Plan p;
-  mx_block_cache sizing{};
-  sizing.n_slots = n_slots; sizing.max_h = max_h; sizing.max_w = max_w;
-  mx_unet_group g{nullptr, nullptr, n_slots, max_h, max_w};
-  return pc_dry(p, u, &g, 1, 64, gn_patch, &sizing) ? bc_top_bytes(p) : 0;
+  const mx_unet_group g{nullptr, nullptr, n_slots, max_h, max_w};      // every state row in use by a latent that fills it
+  mx_block_cache sizing = mx::sizing_cache(&g, 1);
+  size_t state = 0;
+  mx::ForwardCall c = dry_call(0, 0, 0, 64);
+  c.groups = &g; c.n_groups = 1; c.gn_patch = gn_patch; c.cache = &sizing; c.state_bytes = &state;
+  return forward_impl(u, c) ? 0 : state + 256;
 }
 
 extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const mx_unet_group* groups, int n_groups, int ctx_len, int gn_patch) {
-  Plan p;
-  mx_block_cache sizing{};
-  if (groups) for (int g = 0; g < n_groups && g < MX_MAX_SEGS; ++g) {
-    sizing.n_slots += groups[g].batch; sizing.max_h = std::max(sizing.max_h, groups[g].H); sizing.max_w = std::max(sizing.max_w, groups[g].W);
-  }
-  return pc_dry(p, u, groups, n_groups, ctx_len, gn_patch, &sizing) ? p.ar.peak + 256 : 0;
+  if (mx::check_cached_groups("unet_forward_cached_mixed", groups, n_groups)) return 0;
+  mx_block_cache sizing = mx::sizing_cache(groups, n_groups);
+  size_t peak = 0;
+  mx::ForwardCall c = dry_call(0, 0, 0, ctx_len);
+  c.groups = groups; c.n_groups = n_groups; c.gn_patch = gn_patch; c.cache = &sizing; c.peak = &peak;
+  return forward_impl(u, c) ? 0 : peak + 256;
 }
 
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
@@ -1514,36 +1504,10 @@ extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_u
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
   MX_CHECK(((uintptr_t)cache->state & 255) == 0, who + ": cache->state must be 256-byte aligned");
-  Plan p;
-  if (pc_setup(p, u, groups, n_groups, ctx_len, gn_patch, cache, false)) return 1;
-  // the device decision: the down and mid blocks compare their input, an up block its input and the skips it consumes
-  const int n_blocks = 2 * u->cfg.n_levels + 1, ups = (cache->max_h / gn_patch) * (cache->max_w / gn_patch);
-  if (Plan::bc_dev_check(who, cache, n_blocks, ups, 1, u->cfg.layers_per_block + 2)) return 1;
-  MX_CHECK(timesteps && ehs && text_embeds && time_ids && workspace, "unet: null operand");
-  MX_CHECK(u->weights.blob != nullptr, "unet: weights not set");
-  MX_CHECK(io_dtype == MX_F32 || io_dtype == MX_F16 || io_dtype == MX_BF16, "unet: bad io dtype");
-  const int B = p.B;
-  if (p.bc_begin_slots(who, cache, B)) return 1;
-  p.begin(u->weights, (hipStream_t)stream, workspace, workspace_bytes);
-  const size_t head = p.pc_head_bytes(p.pc_slots, p.pc_maxh, p.pc_maxw, p.pc_p0);
-  MX_CHECK(head <= cache->state_bytes, who + ": state buffer too small");
-  const size_t npm = Plan::pc_np_max(p.pc_slots, p.pc_maxh, p.pc_maxw, p.pc_p0);
-  char* hp = (char*)cache->state;
-  p.pc_dpart = (double*)hp; hp += (size_t)(u->cfg.layers_per_block + 2) * npm * p.pc_p0 * sizeof(double);
-  p.pc_dsamp = (mx::PcSample*)hp; hp += (size_t)p.pc_slots * sizeof(mx::PcSample);
-  p.pc_dall = (mx::PcPatch*)hp; hp += npm * sizeof(mx::PcPatch);
-  p.pc_dask = (mx::PcPatch*)hp;
-  MX_CHECK(hipMemcpyAsync(p.pc_dsamp, p.pc_samp.data(), (size_t)B * sizeof(mx::PcSample), hipMemcpyHostToDevice, p.stream) == hipSuccess &&
-           hipMemcpyAsync(p.pc_dall, p.pc_all.data(), (size_t)p.pc_np * sizeof(mx::PcPatch), hipMemcpyHostToDevice, p.stream) == hipSuccess,
-           who + ": moving the tables failed");
-  std::vector<int> unit_b(p.pc_np), group_of(B);
-  for (int j = 0; j < p.pc_np; ++j) unit_b[j] = p.pc_all[j].b;
-  for (int g = 0; g < p.ng; ++g) for (int k = 0; k < p.gB[g]; ++k) group_of[p.gb0[g] + k] = g;
-  if (p.bc_dev_begin(who, u->skip_pin, n_blocks, ups, timesteps, std::move(unit_b), std::move(group_of), false)) return 1;
-  if (p.bc_read_timesteps(who, timesteps, B)) return 1;
-  const bool okr = p.run(groups[0].latents, io_dtype, timesteps, ehs, text_embeds, time_ids, groups[0].out);
-  cache->patches_asked = p.pc_asked; cache->patches_total = p.pc_total;
-  return p.bc_finish(okr, p.blocks_run);
+  if (mx::check_cached_groups(who, groups, n_groups)) return 1;
+  mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
+  c.groups = groups; c.n_groups = n_groups; c.gn_patch = gn_patch; c.cache = cache;
+  return forward_impl(u, c);
 }
 
 extern "C" int mx_unet_forward_trace(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps,

@@ -552,6 +552,29 @@ def test_patch_unit_cached_forward_all_asking_equals_the_mixed_forward(tiny):
         assert l2 <= 0.025, f"{k}: rel L2 {l2}"      # two bf16 evaluations with different rounding points (measured 1.6 %)
 
 
+def test_cached_forwards_leave_the_stored_context_projection_alone(tiny):
+    """a cached forward neither reads nor clears the handle's context key (mx_unet_set_context_key): it projects K / V^T into its workspace, so
+    the store's (hits, misses) stand where they stood.  The key is put into the handle itself -- the Python wrapper hands an announced key
+    over only before an uncached forward -- so a cached forward that did consult the store would count a miss."""
+    from sduss_amd.block_cache import BlockSkipCache, PatchSkipCache
+    ocfg, net = tiny
+    announce = lambda k: (net.set_context_key(k), net._lib.mx_unet_set_context_key(net._handle, k))
+    try:
+        before = net.context_stats()
+        announce(41)
+        net.forward_one_cached(BlockSkipCache(Always(1)), *_inputs(ocfg, 2, 32), batch_key=3)
+        assert net.context_stats() == before
+        ins = [ref.make_inputs(ocfg, b, hw, seed=80 + i) for i, (b, hw) in enumerate([(1, 16), (1, 32)])]
+        cat = lambda k: torch.cat([x[k] for x in ins]).cuda()
+        announce(42)
+        net.forward_mixed_cached(PatchSkipCache(Always(1), max_latent=32), [x[0].cuda().to(torch.bfloat16) for x in ins], ["a", "b"],
+                                 cat(1), cat(2), cat(3), cat(4), gn_patch=8)
+        torch.cuda.synchronize()
+        assert net.context_stats() == before
+    finally:
+        announce(0)
+
+
 def test_patch_unit_cached_forward_against_its_oracle(tiny):
     """mx_unet_forward_cached_mixed against oracle/cache_patch_ref.CachedSlicedUNetRef -- the reference's cache at its own unit (is_sliced=True:
     dictionaries keyed per 256-px patch; here 64-px patches of 128 / 256 px latents, i.e. 4 and 16 patches per latent) restated literally on the

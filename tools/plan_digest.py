@@ -85,6 +85,17 @@ def tiny_cases():
     say("forward_mixed_cached 35 of 38 ask (whole-image fallback)", *step(14))
     print(f"forward_mixed_cached blocks run {[hex(h) for h in pc.history]}, {pc.patches_asked} of {pc.patches_total} patch-blocks asked", flush=True)
 
+    # one group whose patch covers it (two 16 x 16 latents, gn_patch 16): the cache's unit stays 16 where a plain forward would run gn_patch 0
+    pred = Script()
+    pc = PatchSkipCache(pred, forced_after=1 << 30, max_latent=16)
+    cond1 = mixed_inputs(ocfg, [(2, 16)], 20)[1]
+    step = lambda seed: net.forward_mixed_cached(pc, mixed_inputs(ocfg, [(2, 16)], seed)[0], ["e", "f"], *cond1, gn_patch=16)
+    say("forward_mixed_cached one covered group, first step (nothing cached: all ask)", *step(20))
+    say("forward_mixed_cached one covered group, all ask", *step(21))
+    pred.mask = lambda n: np.zeros(n)
+    say("forward_mixed_cached one covered group, none asks", *step(22))
+    print(f"forward_mixed_cached one covered group blocks run {[hex(h) for h in pc.history]}, {pc.patches_asked} of {pc.patches_total} patch-blocks asked", flush=True)
+
 
 def pp_unet_outs():
     """tests/test_pp_gpu.py::test_two_ranks_equal_one_rank's shape"""
