@@ -324,6 +324,24 @@ typedef struct mx_attn_problem {
   int B, Lq, Lk, ldvt;
 } mx_attn_problem;
 int mx_attention_prescaled_grouped(void* stream, const mx_attn_problem* probs, int n, int ldq, int ldk, int ldo, int H);
+/* Short-key cross-attention with a second, separately normalised key set (the image prompt of an IP-Adapter), one launch:
+ *   o = softmax(q k^T) v + ip_scale[b] * softmax(q k_ip^T) v_ip          (q prescaled as for mx_attention_prescaled; Lk <= 96)
+ * k_ip: bf16, n_img in 1..16 image keys per sample stored padded to 16 rows: key j of sample b is row b*16 + j (row stride ldk_ip, head h at
+ *     columns [64h, 64h+64)); vt_ip: bf16, element (b, h, d, key) at vt_ip[b*vt_ip_batch_stride + (h*64 + d)*16 + MX_VT_POS(key)] (row length 16:
+ *     what mx_gemm's MX_EPI_QKV writes with rows_per_batch = ldvt = 16).  Rows / positions >= n_img are never used and may hold anything.
+ * ip_scale: fp32 [B] in device memory.  A sample whose scale is exactly 0 is computed by the arithmetic of mx_attention_cross_prescaled, bit for
+ * bit, and its image operands are not read.  Fails (no launch) for Lk > 96, n_img outside 1..16, ldo % 8 != 0, a null or misaligned operand. */
+int mx_attention_cross_ip(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, int64_t vt_batch_stride,
+                          const void* k_ip, int ldk_ip, const void* vt_ip, int64_t vt_ip_batch_stride, int n_img, const float* ip_scale,
+                          void* o, int ldo, int B, int H, int Lq, int Lk);
+/* grouped form (see mx_attention_prescaled_grouped): the problems share the row strides and the head count */
+typedef struct mx_attn_ip_problem {
+  const void* q; const void* k; const void* vt; void* o;
+  const void* k_ip; const void* vt_ip; const float* ip_scale;
+  int64_t vt_batch_stride, vt_ip_batch_stride;
+  int B, Lq, Lk, ldvt, n_img;
+} mx_attn_ip_problem;
+int mx_attention_cross_ip_grouped(void* stream, const mx_attn_ip_problem* probs, int n, int ldq, int ldk, int ldk_ip, int ldo, int H);
 /* softmax(q k^T + bias[h]) v: q and the fp32 bias [H][Lq][ldb] both already multiplied by log2(e) (T5: no 1/sqrt(d) scaling, bucketed relative
  * position bias shared by all layers); ldb % 4 == 0, ldb >= Lk rounded up to 64 */
 int mx_attention_prescaled_bias(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
@@ -425,6 +443,21 @@ int mx_unet_set_weights(mx_unet* u, const void* blob, uint64_t blob_bytes,
  * several streams, from one host thread. */
 int mx_unet_set_context_key(mx_unet* u, uint64_t key);
 int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses);   /* forwards served from / written to the store since creation */
+/* IMAGE-PROMPT ADAPTER (IP-Adapter).  Every cross-attention layer gains a second, separately normalised term on n_img (1..16) image tokens:
+ *   attn2(x) = softmax(q k_text^T / 8) v_text + ip_scale[row] * softmax(q k_img^T / 8) v_img,   k_img | v_img = to_k_ip | to_v_ip (image tokens)
+ * computed in the cross-attention launch itself (mx_attention_cross_ip).  The adapter is a second blob (device memory, owned by the caller like the
+ * weights; the table is copied) with one packed bf16 tensor per cross-attention width, "ip_kv_all.<dim>.weight": the layout of
+ * "attn2_kv_all.<dim>.weight" (k | v rows per layer, layers in execution order, K = cross_attention_dim).  blob == NULL removes the adapter.
+ * mx_unet_set_weights leaves it in place and the reverse. */
+int mx_unet_set_ip_adapter(mx_unet* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n_entries, int n_img);
+/* The image tokens of the NEXT forward of this handle (ONE call: consumed by it, like the context key): tokens bf16 [rows, 16, cross_attention_dim],
+ * tokens >= n_img of a row ignored, rows in the forward's batch order; ip_scale fp32 [rows]; both in device memory, alive until the forward has run.
+ * A row with scale 0 computes what it computes without an adapter, bit for bit; a forward that was not announced runs the plan without the image
+ * term.  Served by mx_unet_forward, mx_unet_forward_mixed and their _trace forms with ctx_len <= 96; the block-cache and patch-parallel entry points
+ * and MX_GRAPH=1 refuse an announced forward, as does a handle without an adapter.  The tokens are projected every forward (one small GEMM per
+ * width; the context store holds the text's K / V^T only).  mx_unet_workspace_bytes / _mixed and mx_unet_validate of a handle with an adapter
+ * count and resolve the adapter's part.  (NULL, NULL) withdraws an announcement. */
+int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const float* ip_scale);
 size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len);
 /* host-only walk of the step plan that resolves every packed tensor by name and size (no launches, no GPU needed) */
 int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len);

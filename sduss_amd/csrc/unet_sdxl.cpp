@@ -74,6 +74,11 @@ struct mx_unet {
   std::vector<CtxEntry> ctx_store;
   uint64_t ctx_clock = 0;
   long ctx_hits = 0, ctx_misses = 0;
+  // ---- image-prompt adapter (mx_unet_set_ip_adapter): a second blob with one packed k | v projection per cross-attention width, and the NEXT
+  // forward's image tokens and per-row scales (mx_unet_set_image_tokens; consumed by that forward like ctx_key) ----
+  mx::WeightTable ip_weights;           // blob == nullptr: no adapter
+  int ip_n_img = 0;
+  const void* ip_tokens = nullptr; const float* ip_scale = nullptr;
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -293,10 +298,22 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   bool is_pp() const { return pp_world > 1; }
   // per-forward tensors
   float* temb_all = nullptr; int temb_total = 0; int temb_off = 0;
-  struct KV { bf16_t* k; bf16_t* vt; int ldk; int ldvt; long vt_bstride; int next; int dim; };
+  struct KV { bf16_t* k; bf16_t* vt; int ldk; int ldvt; long vt_bstride; int next; int dim; bf16_t* k_ip; bf16_t* vt_ip; };   // k_ip / vt_ip: the image tokens' (ip)
   std::vector<KV> kv;       // one per distinct attention width
   mx_unet::CtxEntry* ctx_e = nullptr;   // the composition's stored K / V^T (forward_impl: ctx_prepare); ctx_hit: already computed
   bool ctx_hit = false;
+  // image-prompt adapter: this forward carries image tokens [B, kIpKeys, cross_attention_dim] (n_img valid per sample) and fp32 scales [B]; every attn2 then
+  // runs mx_attention_cross_ip on the tokens' K / V^T (layer li of k_ip / vt_ip, laid out like the text's with kIpKeys keys per sample)
+  static constexpr int kIpKeys = 16;
+  bool ip = false;
+  const bf16_t* ip_tokens = nullptr; const float* ip_scale = nullptr; int ip_n_img = 0;
+  const bf16_t* ip_wb(const std::string& name, size_t elems) {      // a tensor of the adapter's blob: PlanBase::w on u->ip_weights
+    if (dry && !lookup) return (const bf16_t*)(uintptr_t)0x1000;
+    std::string e;
+    const void* q = u->ip_weights.find(name, elems * 2, e);
+    if (!q) fail("ip adapter: " + e);
+    return (const bf16_t*)q;
+  }
 
   // ---- patch-parallel helpers --------------------------------------------------------------
   bool all_gather(const void* send, void* recv, size_t bytes_per_rank, bool keep_stale_own = false) {
@@ -675,8 +692,29 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     if (ng > 1) { self_problems(t, pr); attention_grouped(pr, 2 * C, 2 * C, C, t.heads); }
     else attention(t.qk, 2 * C, t.qk + C, 2 * C, t.vt, t.ldvt, (long)C * t.ldvt, t.ao, C, t.heads, t.L, t.L);
   }
+  void cross_attention_ip(Xf& t, int li) {      // the same plus ip_scale[b] * attention(q2, layer li of the image tokens' K / V^T), in the one launch
+    if (quiet()) return;
+    const int C = t.C; const KV* kvp = t.kvp;
+    const long vib = (long)kvp->ldk * kIpKeys;
+    mx_attn_problem pr[MX_MAX_SEGS];
+    mx_attn_ip_problem pi[MX_MAX_SEGS];
+    if (ng > 1) cross_problems(t, pr, li);
+    else {
+      pr[0].q = t.q2; pr[0].k = kvp->k + (size_t)li * C; pr[0].vt = kvp->vt + (size_t)li * C * kvp->ldvt; pr[0].o = t.ao;
+      pr[0].vt_batch_stride = kvp->vt_bstride; pr[0].B = B; pr[0].Lq = t.L; pr[0].Lk = ctx_len; pr[0].ldvt = kvp->ldvt;
+    }
+    for (int g = 0; g < ng; ++g) {
+      pi[g].q = pr[g].q; pi[g].k = pr[g].k; pi[g].vt = pr[g].vt; pi[g].o = pr[g].o; pi[g].vt_batch_stride = pr[g].vt_batch_stride;
+      pi[g].B = pr[g].B; pi[g].Lq = pr[g].Lq; pi[g].Lk = pr[g].Lk; pi[g].ldvt = pr[g].ldvt; pi[g].n_img = ip_n_img;
+      pi[g].k_ip = kvp->k_ip + (size_t)li * C + (size_t)gb0[g] * kIpKeys * kvp->ldk;
+      pi[g].vt_ip = kvp->vt_ip + (size_t)li * C * kIpKeys + (size_t)gb0[g] * vib; pi[g].vt_ip_batch_stride = vib;
+      pi[g].ip_scale = ip_scale + gb0[g];
+    }
+    if (mx_attention_cross_ip_grouped(stream, pi, ng, C, kvp->ldk, kvp->ldk, C, t.heads)) fail(std::string("attention: ") + mx_last_error());
+  }
   void cross_attention(Xf& t, int li) {         // ao = attention(q2, layer li of the hoisted K / V^T)
     if (!ok()) return;
+    if (ip) return cross_attention_ip(t, li);
     const int C = t.C; const KV* kvp = t.kvp;
     mx_attn_problem pr[MX_MAX_SEGS];
     if (ng > 1) { cross_problems(t, pr, li); attention_grouped(pr, C, kvp->ldk, C, t.heads); }
@@ -850,7 +888,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
       size_t wi = 0;
       for (auto& wv : widths) {
         const int dim = wv.first, nl = wv.second;
-        KV e; e.dim = dim; e.next = 0; e.ldk = nl * dim; e.ldvt = ldvt; e.vt_bstride = (long)nl * dim * ldvt;
+        KV e; e.dim = dim; e.next = 0; e.ldk = nl * dim; e.ldvt = ldvt; e.vt_bstride = (long)nl * dim * ldvt; e.k_ip = nullptr; e.vt_ip = nullptr;
         if (ctx_e && !dry) { e.k = ctx_e->k[wi]; e.vt = ctx_e->vt[wi]; }        // the composition's own buffers (mx_unet_set_context_key)
         else { e.k = alloc<bf16_t>((size_t)B * ctx_len * nl * dim); e.vt = alloc<bf16_t>((size_t)B * nl * dim * ldvt); }
         ++wi;
@@ -859,6 +897,14 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
           d.a = ehs; d.lda = ctx; d.w = wb("attn2_kv_all." + std::to_string(dim) + ".weight", (size_t)nl * 2 * dim * ctx);
           d.c = e.k; d.ldc = nl * dim; d.M = B * ctx_len; d.N = nl * 2 * dim; d.K = ctx; d.flags = MX_EPI_QKV; d.seg = dim; d.period = 2;
           d.vt = e.vt; d.ldvt = ldvt; d.rows_per_batch = ctx_len;
+          gemm(d, false);
+        }
+        if (ip) {      // the image tokens' K / V^T beside the text's, projected afresh every forward: one small GEMM per width, outside the context store
+          e.k_ip = alloc<bf16_t>((size_t)B * kIpKeys * nl * dim); e.vt_ip = alloc<bf16_t>((size_t)B * nl * dim * kIpKeys);
+          mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
+          d.a = ip_tokens; d.lda = ctx; d.w = ip_wb("ip_kv_all." + std::to_string(dim) + ".weight", (size_t)nl * 2 * dim * ctx);
+          d.c = e.k_ip; d.ldc = nl * dim; d.M = B * kIpKeys; d.N = nl * 2 * dim; d.K = ctx; d.flags = MX_EPI_QKV; d.seg = dim; d.period = 2;
+          d.vt = e.vt_ip; d.ldvt = kIpKeys; d.rows_per_batch = kIpKeys;
           gemm(d, false);
         }
         kv.push_back(e);
@@ -1219,6 +1265,8 @@ struct Model {
   const char* name = "unet";
   mx_unet::CtxEntry* ctx_e = nullptr;
   bool ctx_hit = false;
+  // the image tokens this forward was announced with (forward_impl takes them off the handle), or the placeholders of a sizing walk with an adapter set
+  const void* ip_tokens = nullptr; const float* ip_scale = nullptr;
   // H, W against the level count and the GroupNorm patch (is_sliced)
   static int check_shape(const mx_unet* u, int H, int W, int gn_patch) {
     const int div = 1 << (u->cfg.n_levels - 1);
@@ -1253,6 +1301,12 @@ struct Model {
       if (check_shape(u, c.H, c.W, c.gn_patch)) return 1;
     }
     MX_CHECK(c.dry || (c.text_embeds && c.time_ids), "unet: null operand");
+    if (ip_tokens && !c.dry) {      // (the block-cache and patch-parallel entry points have refused an announced call: refuse_image_prompt)
+      MX_CHECK(u->ip_weights.blob != nullptr, "unet: image tokens announced without an image-prompt adapter (mx_unet_set_ip_adapter)");
+      MX_CHECK(ip_scale != nullptr, "unet: image tokens need their ip_scale row");
+      MX_CHECK(!mx::GraphCache::env_on(), "unet: an image prompt does not run under MX_GRAPH=1");
+      MX_CHECK(c.ctx_len <= 96, "unet: an image prompt needs ctx_len <= 96 (the short-key attention kernel)");
+    }
     return 0;
   }
   // the composition's stored cross-attention K / V^T (mx_unet_set_context_key): plain and mixed forwards; not patch-parallel (its ranks hold row bands).
@@ -1275,6 +1329,7 @@ struct Model {
   }
   int setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
     p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
+    p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
     p.gn_patch = patch_covers_all ? 0 : c.gn_patch;
@@ -1333,7 +1388,21 @@ struct Model {
 };
 int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   Model m;
+  if (u && !c.dry) {        // the announcement names ONE forward, served or refused
+    mx_unet* uw = const_cast<mx_unet*>(u);
+    m.ip_tokens = uw->ip_tokens; m.ip_scale = uw->ip_scale;
+    uw->ip_tokens = nullptr; uw->ip_scale = nullptr;
+  } else if (u && u->ip_weights.blob && !c.cache && !c.comm && c.ctx_len <= 96) {      // sizing / validating walk of a handle with an adapter: as if announced
+    m.ip_tokens = (const void*)(uintptr_t)0x1000; m.ip_scale = (const float*)(uintptr_t)0x1000;
+  }
   return mx::run_forward<Plan>(const_cast<mx_unet*>(u), c, m);
+}
+// the entry points that do not serve an image prompt (block-skip cache, patch parallelism): an announced call is refused, and the announcement used up
+int refuse_image_prompt(mx_unet* u, const char* how) {
+  if (!u || !u->ip_tokens) return 0;
+  u->ip_tokens = nullptr; u->ip_scale = nullptr;
+  MX_CHECK(false, std::string("unet: an image prompt does not run ") + how);
+  return 1;
 }
 using mx::dry_call;
 using mx::sizing_comm;
@@ -1368,6 +1437,22 @@ extern "C" int mx_unet_ln_routes(int M, int C, int layers, int n_groups, int fla
 extern "C" int mx_unet_set_context_key(mx_unet* u, uint64_t key) {
   MX_CHECK(u != nullptr, "unet_set_context_key: null handle");
   u->ctx_key = key;
+  return 0;
+}
+extern "C" int mx_unet_set_ip_adapter(mx_unet* u, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n_entries, int n_img) {
+  MX_CHECK(u != nullptr, "unet_set_ip_adapter: null handle");
+  u->ip_tokens = nullptr; u->ip_scale = nullptr;
+  if (!blob) { u->ip_weights = mx::WeightTable(); u->ip_n_img = 0; return 0; }
+  MX_CHECK(n_img >= 1 && n_img <= 16, "unet_set_ip_adapter: n_img must be in 1..16");
+  if (u->ip_weights.set("unet_set_ip_adapter", blob, blob_bytes, table, n_entries)) { u->ip_weights = mx::WeightTable(); return 1; }
+  u->ip_n_img = n_img;
+  return 0;
+}
+extern "C" int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const float* ip_scale) {
+  MX_CHECK(u != nullptr, "unet_set_image_tokens: null handle");
+  MX_CHECK((tokens == nullptr) == (ip_scale == nullptr), "unet_set_image_tokens: tokens and ip_scale come together (both NULL: withdraw)");
+  MX_CHECK(((uintptr_t)tokens & 15) == 0 && ((uintptr_t)ip_scale & 3) == 0, "unet_set_image_tokens: misaligned operand");
+  u->ip_tokens = tokens; u->ip_scale = ip_scale;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1468,6 +1553,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
+  if (refuse_image_prompt(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1500,6 +1586,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
+  if (refuse_image_prompt(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1534,6 +1621,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
+  if (refuse_image_prompt(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1555,6 +1643,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
+  if (refuse_image_prompt(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

@@ -58,6 +58,13 @@ class AttnProblem(C.Structure):
                 ("B", C.c_int), ("Lq", C.c_int), ("Lk", C.c_int), ("ldvt", C.c_int)]
 
 
+class AttnIpProblem(C.Structure):
+    """mx_attn_ip_problem"""
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("o", C.c_void_p), ("k_ip", C.c_void_p), ("vt_ip", C.c_void_p),
+                ("ip_scale", C.c_void_p), ("vt_batch_stride", C.c_int64), ("vt_ip_batch_stride", C.c_int64),
+                ("B", C.c_int), ("Lq", C.c_int), ("Lk", C.c_int), ("ldvt", C.c_int), ("n_img", C.c_int)]
+
+
 class GnProblem(C.Structure):
     """mx_gn_problem"""
     _fields_ = [("x", C.c_void_p), ("x2", C.c_void_p), ("y", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int)]
@@ -247,6 +254,8 @@ SYMBOLS = {
     "mx_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _f]),
     "mx_attention_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_cross_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
+    "mx_attention_cross_ip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+    "mx_attention_cross_ip_grouped": (_i, [_vp, C.POINTER(AttnIpProblem), _i, _i, _i, _i, _i, _i]),
     "mx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "mx_groupnorm_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mx_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
@@ -263,6 +272,8 @@ SYMBOLS = {
     "mx_unet_destroy": (None, [_vp]),
     "mx_unet_set_context_key": (_i, [_vp, C.c_uint64]),
     "mx_unet_context_stats": (_i, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "mx_unet_set_ip_adapter": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i, _i]),
+    "mx_unet_set_image_tokens": (_i, [_vp, _vp, _vp]),
     "mx_unet_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),
     "mx_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "mx_unet_validate": (_i, [_vp, _i, _i, _i, _i]),

@@ -133,8 +133,15 @@ class ModelSlot:
         _lib.check(rc, f"mx_{self.ABI}_{name}")
         cache.after_forward()
 
-    def _before_forward(self) -> None:
-        """right before the launch sequence of an uncached forward (the UNet hands over its context key here)"""
+    def _before_forward(self, rows: int) -> None:
+        """right before the launch sequence of an uncached forward over ``rows`` conditioning rows (the UNet hands over its context key and image tokens here)"""
+
+    def _before_trace(self, rows: int) -> None:
+        """the same for a forward stopped at a stage (the UNet: the image tokens; the context key is not for traces)"""
+
+    def _drop_announcement(self, announced, what: str) -> None:
+        """a call that is not ONE uncached launch sequence (``what`` says which): nothing announced reaches it.  ``announced``: what _route took, or
+        None for whatever is pending.  The UNet refuses here when image tokens were announced, so that no prompt is dropped in silence."""
 
     def _one(self, sample: torch.Tensor, timestep, cond, patch: int = 0, cache=None, batch_key: int = 0, row_ids=None,
              stage: Optional[str] = None, stage_shape=None) -> torch.Tensor:
@@ -152,13 +159,15 @@ class ModelSlot:
                 out.data_ptr(), b, h, w, ctx_len, *((patch,) if self.GN_PATCH else ()), ws.data_ptr(), ws.numel())
         if cache is not None:
             assert stage is None
+            self._drop_announcement(None, "the block-skip cache")
             desc = cache.bind(self, b, h, w, batch_key, ctx_len=ctx_len if self.CACHE_CTX_LEN else None, row_ids=row_ids)
             self._call_cached(cache, "forward_cached", *args, desc)
             return out
         if stage is None:
-            self._before_forward()
+            self._before_forward(b)
             _lib.check(self._fn("forward")(*args), f"mx_{self.ABI}_forward")
             return out
+        self._before_trace(b)
         st = torch.empty(stage_shape, dtype=torch.bfloat16, device=self.device)
         _lib.check(self._fn("forward_trace")(*args, stage.encode(), st.data_ptr(), st.numel() * 2), f"mx_{self.ABI}_forward_trace")
         return st
@@ -176,6 +185,7 @@ class ModelSlot:
         head = (self._handle, stream, groups, n, _lib.torch_dtype_code(samples[0].dtype), ts.data_ptr(), *(c.data_ptr() for c in cond), ctx_len)
         if cache is not None:
             assert patch > 0 and stage is None and cache.mmdit_ctx_len == (ctx_len if self.CACHE_CTX_LEN else None)
+            self._drop_announcement(None, "the block-skip cache")
             ws = self._arena(stream, ("mixed_cached", shapes, ctx_len, patch), "workspace_bytes_cached_mixed", groups, n, ctx_len, patch)
             desc = cache.bind(self, shapes, row_ids, patch)
             self._call_cached(cache, "forward_cached_mixed", *head, patch, ws.data_ptr(), ws.numel(), desc)
@@ -183,9 +193,10 @@ class ModelSlot:
         ws = self._arena(stream, ("mixed", shapes, ctx_len), "workspace_bytes_mixed", groups, n, ctx_len)
         args = (*head, *((patch,) if self.GN_PATCH else ()), ws.data_ptr(), ws.numel())
         if stage is None:
-            self._before_forward()
+            self._before_forward(sum(s[0] for s in shapes))
             _lib.check(self._fn("forward_mixed")(*args), f"mx_{self.ABI}_forward_mixed")
             return outs
+        self._before_trace(sum(s[0] for s in shapes))
         st = torch.empty(64 << 20, dtype=torch.bfloat16, device=self.device)        # large enough for any stage of the test shapes
         _lib.check(self._fn("forward_mixed_trace")(*args, stage.encode(), st.data_ptr(), st.numel() * 2), f"mx_{self.ABI}_forward_mixed_trace")
         return [st]
@@ -218,6 +229,7 @@ class ModelSlot:
             ctx_len = cond[0].shape[1] if self.CACHE_CTX_LEN else None
             if self._patch_cache is None or self._patch_cache.mmdit_ctx_len != ctx_len:
                 self._patch_cache = self._new_patch_cache(ctx_len)
+            self._drop_announcement(announced, "the block-skip cache")
             row_ids = [r for k in keys for r in _row_ids(ids[k], sample[k].shape[0])]
             res = self._mixed([sample[k] for k in keys], timestep, cond, patch_size // 8, cache=self._patch_cache, row_ids=row_ids)
             return (dict(zip(keys, res)),)
@@ -229,6 +241,8 @@ class ModelSlot:
                 patch = patch_size // 8
             self._announce(announced)
             return (dict(zip(keys, self._mixed([sample[k] for k in keys], timestep, cond, patch))),)
+        if caches is not None or len(keys) != 1:
+            self._drop_announcement(announced, "the block-skip cache" if caches is not None else "a loop over several resolutions")
         out: Dict[str, torch.Tensor] = {}
         row = 0
         for key in keys:

@@ -262,6 +262,61 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, lq
     return o
 
 
+def attention_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, lq: int, lk: int) -> torch.Tensor:
+    """attention(prescaled=True) through the short-key kernel whatever lq (mx_attention_cross_prescaled; lk <= 96)."""
+    l = _lib.load()
+    _bf16(q); _bf16(k); _bf16(vt)
+    o = torch.empty_like(q)
+    _lib.check(l.mx_attention_cross_prescaled(_lib.current_stream(), q.data_ptr(), q.shape[1], k.data_ptr(), k.shape[1], vt.data_ptr(), vt.shape[2],
+                                              vt.shape[1] * vt.shape[2], o.data_ptr(), o.shape[1], vt.shape[0], heads, lq, lk), "mx_attention_cross_prescaled")
+    return o
+
+
+IP_KEYS = 16           # image keys per sample as stored (n_img <= IP_KEYS valid)
+
+
+def attention_cross_ip(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_ip: torch.Tensor, vt_ip: torch.Tensor, n_img: int, ip_scale: torch.Tensor,
+                       heads: int, lq: int, lk: int) -> torch.Tensor:
+    """Short-key cross-attention plus the image-prompt term, one launch (mx_attention_cross_ip): softmax(q k^T) v + ip_scale[b] softmax(q k_ip^T) v_ip.
+    q prescaled [B*Lq, H*64], k [B*Lk, H*64], vt [B, H*64, ldvt]; k_ip [B*16, H*64] (rows >= n_img of a sample unused), vt_ip [B, H*64, 16] in MX_VT_POS
+    order, ip_scale fp32 [B] on the device."""
+    l = _lib.load()
+    for t_ in (q, k, vt, k_ip, vt_ip):
+        _bf16(t_)
+    b = vt.shape[0]
+    assert ip_scale.is_cuda and ip_scale.dtype == torch.float32 and ip_scale.numel() == b and ip_scale.is_contiguous()
+    assert k_ip.shape[0] == b * IP_KEYS and vt_ip.shape[0] == b and vt_ip.shape[2] == IP_KEYS
+    o = torch.empty_like(q)
+    _lib.check(l.mx_attention_cross_ip(_lib.current_stream(), q.data_ptr(), q.shape[1], k.data_ptr(), k.shape[1], vt.data_ptr(), vt.shape[2],
+                                       vt.shape[1] * vt.shape[2], k_ip.data_ptr(), k_ip.shape[1], vt_ip.data_ptr(), vt_ip.shape[1] * IP_KEYS, n_img,
+                                       ip_scale.data_ptr(), o.data_ptr(), o.shape[1], b, heads, lq, lk), "mx_attention_cross_ip")
+    return o
+
+
+def attention_cross_ip_grouped(problems, heads: int, n_img: int) -> list:
+    """One launch over up to MAX_SEGS problems (mx_attention_cross_ip_grouped): ``problems`` is a list of (q, k, vt, k_ip, vt_ip, ip_scale, lq, lk) with the
+    operands of attention_cross_ip; returns the outputs."""
+    l = _lib.load()
+    n = len(problems)
+    arr = (_lib.AttnIpProblem * n)()
+    outs = []
+    for i, (q, k, vt, k_ip, vt_ip, ip_scale, lq, lk) in enumerate(problems):
+        for t_ in (q, k, vt, k_ip, vt_ip):
+            _bf16(t_)
+        assert ip_scale.is_cuda and ip_scale.dtype == torch.float32 and ip_scale.numel() == vt.shape[0] and ip_scale.is_contiguous()
+        o = torch.empty_like(q)
+        outs.append(o)
+        a = arr[i]
+        a.q, a.k, a.vt, a.o, a.k_ip, a.vt_ip, a.ip_scale = (q.data_ptr(), k.data_ptr(), vt.data_ptr(), o.data_ptr(), k_ip.data_ptr(), vt_ip.data_ptr(),
+                                                          ip_scale.data_ptr())
+        a.vt_batch_stride, a.vt_ip_batch_stride = vt.shape[1] * vt.shape[2], vt_ip.shape[1] * IP_KEYS
+        a.B, a.Lq, a.Lk, a.ldvt, a.n_img = vt.shape[0], lq, lk, vt.shape[2], n_img
+    q0, k0, kip0 = problems[0][0], problems[0][1], problems[0][3]
+    _lib.check(l.mx_attention_cross_ip_grouped(_lib.current_stream(), arr, n, q0.shape[1], k0.shape[1], kip0.shape[1], q0.shape[1], heads),
+               "mx_attention_cross_ip_grouped")
+    return outs
+
+
 def attn_tail(ao: torch.Tensor, y: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, colsum_q: torch.Tensor,
               k: torch.Tensor, vt: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, heads: int, L: int, ctx_len: int, ln_eps: float = 1e-5,
               finalise: bool = True):

@@ -249,6 +249,7 @@ class PatchParallelUNet:
     def forward_local(self, latents_local: torch.Tensor, timestep: torch.Tensor, *cond: torch.Tensor) -> torch.Tensor:
         """this rank's rows in, this rank's output rows out; ``cond``: the model's conditioning tensors (its COND) for the batch"""
         u = self.unet
+        u._drop_announcement(None, "patch parallelism")
         x = latents_local.contiguous()
         b, _c, hl, w = x.shape
         ctx_len = cond[0].shape[1]

@@ -98,6 +98,8 @@ class Request:
     history_step: int = -1                # the step that left ``history``; the next step is second order only if it follows it directly
     seed: Optional[int] = None            # the request's noise is a function of (seed, purpose, step, element) alone (csrc/noise.h); None: unseeded
     eta: float = 0.0                      # the noise level of a stochastic sampler (set_timesteps)
+    image_tokens: Optional[torch.Tensor] = None   # bf16 [2, 16, cross_dim]: the image prompt's tokens of the (unconditional, conditional) row (set_image_prompt)
+    ip_scale: float = 0.0                 # the image prompt's scale; 0 without one
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -375,6 +377,33 @@ class Denoiser:
         return (_upload(torch.tensor(slot, dtype=torch.int32), dev), torch.cat([s.init for s in rows], dim=0).contiguous(),
                 torch.cat([s.noise for s in rows], dim=0).contiguous(), torch.cat([s.mask for s in rows], dim=0).contiguous())
 
+    def set_image_prompt(self, req, image_embeds: Optional[torch.Tensor], scale: float = 1.0) -> None:
+        """Give ``req`` an image prompt (the model slot's image-prompt adapter, MxUNet.set_ip_adapter): ``image_embeds`` [1, embed_dim] as diffusers'
+        ``ip_adapter_image_embeds``, or tokens [1, n_img, cross_dim] made elsewhere; None takes the prompt away.  Projected here, once: the
+        conditional row carries the embeddings' tokens, the unconditional CFG row those of ZERO embeddings at the same scale, as diffusers does
+        (caller-made tokens: zero tokens).  Requests without a prompt run at scale 0, so one batch may mix both kinds."""
+        ip = getattr(self._model, "_ip", None)
+        if image_embeds is None:
+            req.image_tokens, req.ip_scale = None, 0.0
+            return
+        if ip is None:
+            raise MxError(f"{type(self).__name__}.set_image_prompt: the model slot has no image-prompt adapter (MxUNet.set_ip_adapter)")
+        emb = image_embeds.to(self._model.device)
+        req.image_tokens, req.ip_scale = ip[0].project(torch.cat([torch.zeros_like(emb), emb], dim=0)), float(scale)
+
+    def _image_rows(self, reqs, do_classifier_free_guidance: bool) -> Optional[tuple]:
+        """(tokens bf16 [rows, 16, cross_dim], scales fp32 [rows]) of one resolution's model rows, [uncond..., cond...] under CFG; requests without an
+        image prompt: zero tokens at scale 0.  None when no request has one: the forward is then not announced."""
+        toks = [getattr(r, "image_tokens", None) for r in reqs]
+        have = [t for t in toks if t is not None]
+        if not have:
+            return None
+        blank = torch.zeros_like(have[0])
+        halves = (0, 1) if do_classifier_free_guidance else (1,)
+        rows = torch.cat([(blank if t is None else t)[h:h + 1] for h in halves for t in toks], dim=0).contiguous()
+        scale = [float(getattr(r, "ip_scale", 0.0)) if t is not None else 0.0 for _h in halves for r, t in zip(reqs, toks)]
+        return rows, _upload(torch.tensor(scale, dtype=torch.float32), rows.device)
+
     def _gather(self, res: str, reqs: list, do_classifier_free_guidance: bool) -> _Part:
         """the per-resolution gather of :287-339 through the per-composition cache, and the model's input rows (:357-360 + the cat of :327).
         Embeddings are fixed for a request's lifetime: one cat per batch composition, not per step."""
@@ -383,24 +412,31 @@ class Denoiser:
             r.latents.record_stream(here)
         e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs),
                                tuple(getattr(r, "sampler", "euler") for r in reqs),
-                               tuple((getattr(r, "seed", None), getattr(r, "eta", 0.0)) for r in reqs)), reqs,
-                              lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs))
+                               tuple((getattr(r, "seed", None), getattr(r, "eta", 0.0)) for r in reqs),
+                               tuple((id(getattr(r, "image_tokens", None)), getattr(r, "ip_scale", 0.0)) for r in reqs)), reqs,
+                              lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs),
+                              lambda: self._image_rows(reqs, do_classifier_free_guidance))
         lat = self._cache.latents(e, reqs)
         sig, sig_next, ts = self._cache.step_scalars(e, reqs)
         return _Part(res, reqs, e, lat, sig, sig_next, torch.cat([ts, ts], dim=0) if do_classifier_free_guidance else ts,
                      self._scale_input(lat, sig, do_classifier_free_guidance))
 
     def _mixed_composition(self, parts: List[_Part]) -> tuple:
-        """(conditioning of all resolutions concatenated, uid): rows in ascending resolution.  Lives as long as its per-resolution entries."""
+        """(conditioning of all resolutions concatenated, uid, image rows of all resolutions or None): rows in ascending resolution.  Lives as long
+        as its per-resolution entries."""
         entries = [p.entry for p in parts]
         key = tuple(id(e) for e in entries)
         hit = self._mixed_cond.get(key)
         if hit is None or any(a is not b for a, b in zip(hit[0], entries)):
             cat = tuple(torch.cat([e.cond[k] for e in entries], dim=0) for k in range(len(entries[0].cond)))
+            image = next((e.image for e in entries if e.image is not None), None)
+            if image is not None:          # a resolution without an image prompt: zero tokens at scale 0 for its rows
+                per = [e.image or (image[0].new_zeros((e.cond[0].shape[0],) + tuple(image[0].shape[1:])), image[1].new_zeros(e.cond[0].shape[0])) for e in entries]
+                image = tuple(torch.cat([q[k] for q in per], dim=0) for k in range(2))
             if len(self._mixed_cond) > 32:
                 self._mixed_cond.clear()
-            hit = self._mixed_cond[key] = (entries, cat, new_uid())
-        return hit[1], hit[2]
+            hit = self._mixed_cond[key] = (entries, cat, new_uid(), image)
+        return hit[1], hit[2], hit[3]
 
     def _step(self, res_list: List[str], worker_reqs: Dict[str, list], do_classifier_free_guidance: bool, is_sliced: bool, patch_size: int,
               through_dict: bool) -> None:
@@ -409,11 +445,13 @@ class Denoiser:
         ``forward_mixed``, ONE launch sequence.  Conditioning rows: ascending resolution, [uncond..., cond...] inside each (:275-276, 327-339)."""
         parts = [self._gather(res, worker_reqs[res], do_classifier_free_guidance) for res in res_list]
         if len(parts) == 1:
-            (cond, uid), ts = (parts[0].entry.cond, parts[0].entry.uid), parts[0].timesteps
+            (cond, uid, image), ts = (parts[0].entry.cond, parts[0].entry.uid, parts[0].entry.image), parts[0].timesteps
         else:
-            (cond, uid), ts = self._mixed_composition(parts), torch.cat([p.timesteps for p in parts])
+            (cond, uid, image), ts = self._mixed_composition(parts), torch.cat([p.timesteps for p in parts])
         if self.announces_composition:       # the composition's text embeddings are fixed: K / V^T of all layers once per composition
             self._model.set_context_key(uid)
+        if image is not None:                # a request here has an image prompt: the rows' tokens and scales, built once per composition
+            self._model.set_image_tokens(*image)
         if through_dict:
             out = self._forward({p.res: p.x_in for p in parts}, ts, cond, is_sliced=is_sliced, patch_size=patch_size,
                                 input_indices={p.res: [str(r.request_id) for r in p.reqs] for p in parts})

@@ -31,7 +31,7 @@ def _upload(host: torch.Tensor, device) -> torch.Tensor:
 
 
 class _Entry:
-    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid", "inpaint", "multistep")
+    __slots__ = ("cond", "table", "idx", "rows", "host_idx", "lat", "limit", "uid", "inpaint", "multistep", "image")
 
 
 class _Multistep:
@@ -59,10 +59,11 @@ class StepCache:
         self._entries: "OrderedDict[tuple, _Entry]" = OrderedDict()
 
     def entry(self, key: tuple, reqs: Sequence, build_cond: Callable[[], tuple], build_inpaint: Optional[Callable[[], tuple]] = None,
-              build_multistep: Optional[Callable[[], tuple]] = None) -> _Entry:
+              build_multistep: Optional[Callable[[], tuple]] = None, build_image: Optional[Callable[[], tuple]] = None) -> _Entry:
         """the entry of a batch composition, built on first use.  ``build_inpaint``: the packed rows of its inpainting requests (Denoiser._inpaint_rows;
         None for a composition without one), fixed for the composition like ``cond``.  ``build_multistep``: the kinds and the [n, S, 4] coefficient
-        table of its rows (Denoiser._multistep_rows; None for a composition of Euler requests)."""
+        table of its rows (Denoiser._multistep_rows; None for a composition of Euler requests).  ``build_image``: the image tokens and scales of its
+        model rows (Denoiser._image_rows; None for a composition without an image prompt), fixed for the composition like ``cond``."""
         e = self._entries.get(key)
         if e is not None:
             self._entries.move_to_end(key)
@@ -72,6 +73,7 @@ class StepCache:
         e.cond = build_cond()
         e.inpaint = build_inpaint() if build_inpaint is not None else None
         e.multistep = self._multistep(build_multistep() if build_multistep is not None else None)
+        e.image = build_image() if build_image is not None else None
         n = len(reqs)
         s_max = max(len(r.timesteps) for r in reqs)
         tab = np.zeros((3, n, s_max), dtype=np.float32)

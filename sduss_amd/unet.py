@@ -16,7 +16,26 @@ from . import lib as _lib
 from .config import UNetConfig
 from .model_slot import ModelSlot, _Config
 from .lora import LoraAdapter, LoraLayout, norm_params, scaled_terms
-from .weights import pack
+from .weights import PackedWeights, pack
+
+
+def config_c(cfg: UNetConfig) -> "_lib.UNetConfigC":
+    """mx_unet_config of ``cfg``"""
+    cc = _lib.UNetConfigC()
+    cc.in_channels, cc.out_channels = cfg.in_channels, cfg.out_channels
+    cc.n_levels = len(cfg.block_out_channels)
+    for i, v in enumerate(cfg.block_out_channels):
+        cc.block_out_channels[i] = v
+        cc.down_has_attn[i] = int(cfg.down_has_attn[i])
+        cc.transformer_layers[i] = cfg.transformer_layers_per_block[i]
+        cc.num_heads[i] = cfg.num_heads[i]
+    cc.layers_per_block = cfg.layers_per_block
+    cc.cross_attention_dim = cfg.cross_attention_dim
+    cc.addition_time_embed_dim = cfg.addition_time_embed_dim
+    cc.projection_class_embeddings_input_dim = cfg.projection_class_embeddings_input_dim
+    cc.norm_num_groups = cfg.norm_num_groups
+    cc.norm_eps, cc.transformer_norm_eps, cc.layer_norm_eps = cfg.norm_eps, cfg.transformer_norm_eps, cfg.layer_norm_eps
+    return cc
 
 
 class _LoraState:
@@ -45,23 +64,12 @@ class MxUNet(ModelSlot):
     GN_PATCH = True
 
     def __init__(self, cfg: UNetConfig, params: Dict[str, torch.Tensor], device="cuda:0"):
-        cc = _lib.UNetConfigC()
-        cc.in_channels, cc.out_channels = cfg.in_channels, cfg.out_channels
-        cc.n_levels = len(cfg.block_out_channels)
-        for i, v in enumerate(cfg.block_out_channels):
-            cc.block_out_channels[i] = v
-            cc.down_has_attn[i] = int(cfg.down_has_attn[i])
-            cc.transformer_layers[i] = cfg.transformer_layers_per_block[i]
-            cc.num_heads[i] = cfg.num_heads[i]
-        cc.layers_per_block = cfg.layers_per_block
-        cc.cross_attention_dim = cfg.cross_attention_dim
-        cc.addition_time_embed_dim = cfg.addition_time_embed_dim
-        cc.projection_class_embeddings_input_dim = cfg.projection_class_embeddings_input_dim
-        cc.norm_num_groups = cfg.norm_num_groups
-        cc.norm_eps, cc.transformer_norm_eps, cc.layer_norm_eps = cfg.norm_eps, cfg.transformer_norm_eps, cfg.layer_norm_eps
-        super().__init__(cfg, cc, pack(cfg, params), device)
+        super().__init__(cfg, config_c(cfg), pack(cfg, params), device)
         self._lora = _LoraState(norm_params(params))
         self._next_ctx_key = 0             # set_context_key: names the batch composition of the NEXT forward only
+        self._ip = None                    # set_ip_adapter: (IPAdapter, its PackedWeights on the device)
+        self._ip_next = None               # set_image_tokens: (tokens, scales) of the NEXT forward only, handed over right before its launches
+        self._ip_live = None
         self.config = _Config(in_channels=cfg.in_channels, time_cond_proj_dim=None,
                               addition_time_embed_dim=cfg.addition_time_embed_dim,
                               projection_class_embeddings_input_dim=cfg.projection_class_embeddings_input_dim,
@@ -74,14 +82,37 @@ class MxUNet(ModelSlot):
         One-shot: a forward that is not announced projects as before."""
         self._next_ctx_key = int(key)
 
-    def _take_announcement(self) -> int:
-        key, self._next_ctx_key = self._next_ctx_key, 0
-        return key
+    def _take_announcement(self) -> tuple:
+        """(context key, image tokens) announced for the next forward, both one-shot"""
+        announced, self._next_ctx_key, self._ip_next = (self._next_ctx_key, self._ip_next), 0, None
+        return announced
 
-    _announce = set_context_key        # forward() took the key; where the call is ONE uncached sequence, that sequence gets it back
+    def _announce(self, announced) -> None:      # forward() took them; where the call is ONE uncached sequence, that sequence gets them back
+        self._next_ctx_key, self._ip_next = announced
 
-    def _before_forward(self) -> None:
-        _lib.check(self._lib.mx_unet_set_context_key(self._handle, self._take_announcement()), "mx_unet_set_context_key")
+    def _hand_image_tokens(self, ip, rows: int) -> None:
+        if ip is not None:
+            if ip[0].shape[0] != rows:
+                raise _lib.MxError(f"image tokens of {ip[0].shape[0]} rows announced for a forward of {rows} rows")
+            _lib.check(self._lib.mx_unet_set_image_tokens(self._handle, ip[0].data_ptr(), ip[1].data_ptr()), "mx_unet_set_image_tokens")
+            self._ip_live = ip             # alive until the next announcement: the forward that reads them has been issued by then
+
+    def _before_forward(self, rows: int) -> None:
+        key, ip = self._take_announcement()
+        _lib.check(self._lib.mx_unet_set_context_key(self._handle, key), "mx_unet_set_context_key")
+        self._hand_image_tokens(ip, rows)
+
+    def _before_trace(self, rows: int) -> None:
+        ip, self._ip_next = self._ip_next, None
+        self._hand_image_tokens(ip, rows)
+
+    def _drop_announcement(self, announced, what: str) -> None:
+        if announced is None:
+            ip, self._ip_next = self._ip_next, None
+        else:
+            ip = announced[1]
+        if ip is not None:
+            raise _lib.MxError(f"an image prompt does not run through {what}: it is served by ONE uncached launch sequence")
 
     def context_stats(self):
         """(hits, misses) of the per-composition K / V^T store since the handle was created"""
@@ -129,8 +160,40 @@ class MxUNet(ModelSlot):
                 and mid_block_additional_residual is None and down_intrablock_additional_residuals is None
                 and encoder_attention_mask is None)
         assert added_cond_kwargs is not None, "SDXL needs added_cond_kwargs (text_embeds, time_ids)"
+        if added_cond_kwargs.get("image_embeds") is not None:      # rows of all resolutions in the conditioning's order; "ip_scale": a number or [rows]
+            if self._ip is None:
+                raise _lib.MxError("forward: image_embeds without an image-prompt adapter (set_ip_adapter)")
+            tokens = self._ip[0].project(added_cond_kwargs["image_embeds"].to(self.device))
+            scale = added_cond_kwargs.get("ip_scale", 1.0)
+            scale = scale if torch.is_tensor(scale) else torch.full((tokens.shape[0],), float(scale))
+            self.set_image_tokens(tokens, scale)
         return self._route(sample, timestep, (encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]),
                            is_sliced, patch_size, input_indices)
+
+    # ---- image-prompt adapter (sduss_amd/ip_adapter.py; mx_attention_cross_ip) -------------------------
+    def set_ip_adapter(self, adapter) -> None:
+        """Serve image prompts with ``adapter`` (an ip_adapter.IPAdapter) from now on: its blob goes to the device and the handle
+        (mx_unet_set_ip_adapter).  Independent of the LoRA set -- the two live in different blobs.  Forwards change only where image tokens are
+        announced (set_image_tokens, or forward()'s added_cond_kwargs["image_embeds"])."""
+        packed = PackedWeights(adapter.packed, self.device)
+        _lib.check(self._lib.mx_unet_set_ip_adapter(self._handle, packed.blob.data_ptr(), packed.blob.numel(), packed.table, len(packed.names), adapter.n_img),
+                   "mx_unet_set_ip_adapter")
+        self._ip, self._ip_next = (adapter, packed), None
+        self._ws_need = {}                 # the plan of a handle with an adapter takes the image tokens' K / V^T as well
+
+    def clear_ip_adapter(self) -> None:
+        _lib.check(self._lib.mx_unet_set_ip_adapter(self._handle, None, 0, None, 0, 0), "mx_unet_set_ip_adapter")
+        self._ip, self._ip_next = None, None
+        self._ws_need = {}
+
+    def set_image_tokens(self, tokens: torch.Tensor, ip_scale: torch.Tensor) -> None:
+        """Announce the image tokens [rows, 16, cross_attention_dim] (IPAdapter.project) and scales [rows] of the NEXT forward of this model, rows in
+        that forward's batch order (mx_unet_set_image_tokens; one-shot like set_context_key).  The block-cache and patch-parallel forwards refuse
+        an announced call."""
+        tokens = tokens.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        ip_scale = ip_scale.to(device=self.device, dtype=torch.float32).contiguous()
+        assert tokens.ndim == 3 and tokens.shape[1:] == (16, self.cfg.cross_attention_dim) and ip_scale.shape == (tokens.shape[0],)
+        self._ip_next = (tokens, ip_scale)
 
     # ---- LoRA adapters (sduss_amd/lora.py; mx_lora_merge) ---------------------------------------------
     def _point_at(self, blob: torch.Tensor) -> None:
