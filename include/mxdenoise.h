@@ -400,6 +400,20 @@ size_t mx_groupnorm_nhwc_grouped_workspace_bytes(const mx_gn_problem* probs, int
 int mx_groupnorm_nhwc_grouped(void* stream, const mx_gn_problem* probs, int n, int C1, const float* gamma, const float* beta, int C, int groups,
                               float eps, int silu, int patch, void* workspace);
 
+/* FreeU (diffusers' apply_freeu with fourier_filter(threshold = 1), UNet2DConditionModel.enable_freeu), one application, ONE launch: per problem
+ *   skip_out = the skip [B, H, W, C_skip] bf16 with the four lowest frequency bins of every (sample, channel) plane scaled by s -- the closed form
+ *              of fftn / fftshift / 2 x 2 box / ifftn(...).real in fp32, rounded to bf16 once (freeu.hip);
+ *   hidden[:, :, :, :C_hidden / 2] *= b, in place, the product in fp32 and rounded once (hidden NULL with C_hidden 0: the filter alone).
+ * Up to MX_MAX_SEGS problems (the resolutions of a mixed batch) share the launch; the bits of a sample depend on its own plane only, not on the
+ * batch, the other problems, the slab width or the run.  Requirements: H, W in 2..512, C_skip and C_hidden multiples of 16, 16-byte aligned
+ * operands, and skip, skip_out and hidden of a problem do not overlap (the launch reads and writes them concurrently).
+ * mx_freeu_route (host only): the slab width (64 / 32 / 16 channels per workgroup) the launch of these problems takes, per problem whether the slab
+ * is staged in LDS (1) or read twice (0), and n = the longest sequential addition chain of its sums (pixels of an item + items of a lane + 6 tree
+ * levels): what an error bound of the form n * 2^-24 * sum |x| needs. */
+typedef struct mx_freeu_problem { const void* skip; void* skip_out; void* hidden; int B, H, W; } mx_freeu_problem;
+int mx_freeu(void* stream, const mx_freeu_problem* probs, int n, int C_skip, int C_hidden, float s, float b);
+int mx_freeu_route(const mx_freeu_problem* probs, int n, int C_skip, int* slab, int* staged, int* chain);
+
 /* ------------------------------------------------------------------------------------------
  * Outer boundary: the SDXL UNet in the model slot.
  * ------------------------------------------------------------------------------------------ */
@@ -458,6 +472,13 @@ int mx_unet_set_ip_adapter(mx_unet* u, const void* blob, uint64_t blob_bytes, co
  * width; the context store holds the text's K / V^T only).  mx_unet_workspace_bytes / _mixed and mx_unet_validate of a handle with an adapter
  * count and resolve the adapter's part.  (NULL, NULL) withdraws an announcement. */
 int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const float* ip_scale);
+/* FreeU (diffusers' enable_freeu(s1, s2, b1, b2)): while on, every resnet of up blocks 0 and 1 reads its skip through mx_freeu -- up block 0 with
+ * (s1, b1), up block 1 with (s2, b2); one launch in front of each, the filtered skip in a workspace buffer, the hidden state scaled in place.  As in
+ * diffusers it is on only when all four are non-zero; any zero turns it off, and the launch sequence is then the plain one.  A property of the handle
+ * until changed.  Served by mx_unet_forward, mx_unet_forward_mixed and their _trace forms; the sizing and validating walks count its buffer and it is
+ * part of the graph key.  The block-cache entry points (their state compares unfiltered skips) and the patch-parallel ones (the filter needs whole
+ * planes, which lie across ranks) refuse a forward while it is on. */
+int mx_unet_set_freeu(mx_unet* u, float s1, float s2, float b1, float b2);
 size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len);
 /* host-only walk of the step plan that resolves every packed tensor by name and size (no launches, no GPU needed) */
 int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len);

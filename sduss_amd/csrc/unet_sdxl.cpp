@@ -79,6 +79,9 @@ struct mx_unet {
   mx::WeightTable ip_weights;           // blob == nullptr: no adapter
   int ip_n_img = 0;
   const void* ip_tokens = nullptr; const float* ip_scale = nullptr;
+  // ---- FreeU (mx_unet_set_freeu): (s, b) of up blocks 0 and 1; on only with all four non-zero, as in diffusers ----
+  bool freeu_on = false;
+  float freeu_s[2] = {0.f, 0.f}, freeu_b[2] = {0.f, 0.f};
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -313,6 +316,26 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const void* q = u->ip_weights.find(name, elems * 2, e);
     if (!q) fail("ip adapter: " + e);
     return (const bf16_t*)q;
+  }
+
+  // FreeU (mx_unet_set_freeu; freeu.hip): in front of a resnet of up block i < 2, ONE launch leaves the filtered skip in `out` and scales the first
+  // half of the hidden state x in place.  x is private to the up path at that point: it is the arena buffer the previous resnet / transformer /
+  // upsampler of THIS forward wrote, whose only reader left is the resnet that follows (norm1 and the 1x1 shortcut read [x | skip] in place); no
+  // skip aliases it (skips are outputs of the down path) and the block cache, whose state would, does not run with FreeU on.  The skip itself is
+  // only read: it may be conv_in's output or a tensor a trace has dumped.
+  bool fu = false;
+  bool freeu(int i, bf16_t* x, int Cx, const bf16_t* skip, int Cs, bf16_t* out) {
+    if (!ok()) return false;
+    if (quiet()) return true;
+    mx_freeu_problem pr[MX_MAX_SEGS];
+    long r0 = 0;
+    for (int k = 0; k < ng; ++k) {
+      pr[k].skip = skip + r0 * Cs; pr[k].skip_out = out + r0 * Cs; pr[k].hidden = x + r0 * Cx;
+      pr[k].B = gB[k]; pr[k].H = ch[k]; pr[k].W = cw[k];
+      r0 += (long)gB[k] * ch[k] * cw[k];
+    }
+    if (mx_freeu(stream, pr, ng, Cs, Cx, u->freeu_s[i], u->freeu_b[i])) return fail(std::string("freeu: ") + mx_last_error());
+    return true;
   }
 
   // ---- patch-parallel helpers --------------------------------------------------------------
@@ -972,10 +995,19 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     auto up_block = [&](int i) {                                // unet.py:458-503
       const int level = nlev - 1 - i;
       const int Cout = c.block_out_channels[level];
+      // FreeU: diffusers' resolution_idx 0 and 1 (unet_2d_blocks.py:244-267, 337-352 apply_freeu in front of every torch.cat).  One buffer for the
+      // block's filtered skips, as wide as the widest of them; it stays in the arena behind the block's outputs
+      bf16_t* fskip = nullptr;
+      if (fu && i < 2) {
+        int Cmax = 0;
+        for (int j = 0; j < c.layers_per_block + 1; ++j) Cmax = std::max(Cmax, skips[skips.size() - 1 - j].C);
+        fskip = alloc<bf16_t>((size_t)rows() * Cmax);
+      }
       for (int j = 0; j < c.layers_per_block + 1 && ok(); ++j) {
         const Skip sk = skips.back(); skips.pop_back();
         const std::string rp = "up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j);
-        x = resnet(rp, x, h, wd, Ccur + sk.C, Cout, level, sk.t, sk.C);   // torch.cat([x, skip], dim=1) is never materialised
+        if (fskip) freeu(i, x, Ccur, sk.t, sk.C, fskip);
+        x = resnet(rp, x, h, wd, Ccur + sk.C, Cout, level, fskip ? fskip : sk.t, sk.C);   // torch.cat([x, skip], dim=1) is never materialised
         Ccur = Cout;
         if (c.down_has_attn[level]) {
           const std::string ap = "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j);
@@ -1329,6 +1361,7 @@ struct Model {
   }
   int setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
     p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
+    p.fu = fu;
     p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
@@ -1383,11 +1416,25 @@ struct Model {
     return okr;
   }
   size_t cache_bytes(const Plan& p) { return (size_t)(p.bc_top - (char*)(uintptr_t)0x1000); }     // (a dry walk's bump pointer starts at a placeholder base, as the arena does)
-  std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) { return {(uint64_t)c.gn_patch}; }
+  // FreeU as THIS forward runs it (forward_impl): the handle's state on the plain and mixed entry points; off on the block-cache and patch-parallel
+  // ones, which have refused a forward with FreeU on (refuse_freeu) and whose sizing walks take no buffer for it
+  bool fu = false;
+  float fu_sb[4] = {0.f, 0.f, 0.f, 0.f};
+  // (the FreeU state is part of the key: a captured graph holds its launches and their scalars)
+  std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) {
+    std::vector<uint64_t> k{(uint64_t)c.gn_patch};
+    if (fu)
+      for (float v : fu_sb) { uint32_t w; std::memcpy(&w, &v, 4); k.push_back(0x100000000ull | w); }
+    return k;
+  }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
 };
 int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   Model m;
+  if (u && u->freeu_on && !c.pp() && !c.cache) {
+    m.fu = true;
+    m.fu_sb[0] = u->freeu_s[0]; m.fu_sb[1] = u->freeu_s[1]; m.fu_sb[2] = u->freeu_b[0]; m.fu_sb[3] = u->freeu_b[1];
+  }
   if (u && !c.dry) {        // the announcement names ONE forward, served or refused
     mx_unet* uw = const_cast<mx_unet*>(u);
     m.ip_tokens = uw->ip_tokens; m.ip_scale = uw->ip_scale;
@@ -1403,6 +1450,12 @@ int refuse_image_prompt(mx_unet* u, const char* how) {
   u->ip_tokens = nullptr; u->ip_scale = nullptr;
   MX_CHECK(false, std::string("unet: an image prompt does not run ") + how);
   return 1;
+}
+// the entry points that do not serve FreeU: the block-skip cache (its state compares and stores unfiltered skips and would alias the hidden state that
+// FreeU scales in place) and patch parallelism (the filter needs the whole plane, which lies across ranks)
+int refuse_freeu(const mx_unet* u, const char* how) {
+  MX_CHECK(!(u && u->freeu_on), std::string("unet: FreeU does not run ") + how + " (mx_unet_set_freeu with a zero turns it off)");
+  return 0;
 }
 using mx::dry_call;
 using mx::sizing_comm;
@@ -1453,6 +1506,13 @@ extern "C" int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const fl
   MX_CHECK((tokens == nullptr) == (ip_scale == nullptr), "unet_set_image_tokens: tokens and ip_scale come together (both NULL: withdraw)");
   MX_CHECK(((uintptr_t)tokens & 15) == 0 && ((uintptr_t)ip_scale & 3) == 0, "unet_set_image_tokens: misaligned operand");
   u->ip_tokens = tokens; u->ip_scale = ip_scale;
+  return 0;
+}
+extern "C" int mx_unet_set_freeu(mx_unet* u, float s1, float s2, float b1, float b2) {
+  MX_CHECK(u != nullptr, "unet_set_freeu: null handle");
+  MX_CHECK(s1 == s1 && s2 == s2 && b1 == b1 && b2 == b2, "unet_set_freeu: NaN factor");
+  u->freeu_on = s1 != 0.f && s2 != 0.f && b1 != 0.f && b2 != 0.f;
+  u->freeu_s[0] = s1; u->freeu_s[1] = s2; u->freeu_b[0] = b1; u->freeu_b[1] = b2;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1553,7 +1613,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1586,7 +1646,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1621,7 +1681,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1643,7 +1703,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

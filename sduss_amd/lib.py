@@ -70,6 +70,11 @@ class GnProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x2", C.c_void_p), ("y", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int)]
 
 
+class FreeUProblem(C.Structure):
+    """mx_freeu_problem"""
+    _fields_ = [("skip", C.c_void_p), ("skip_out", C.c_void_p), ("hidden", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int)]
+
+
 class UNetGroup(C.Structure):
     """mx_unet_group: the samples of one resolution of a mixed batch"""
     _fields_ = [("latents", C.c_void_p), ("out", C.c_void_p), ("batch", C.c_int), ("H", C.c_int), ("W", C.c_int)]
@@ -274,6 +279,9 @@ SYMBOLS = {
     "mx_unet_context_stats": (_i, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "mx_unet_set_ip_adapter": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i, _i]),
     "mx_unet_set_image_tokens": (_i, [_vp, _vp, _vp]),
+    "mx_unet_set_freeu": (_i, [_vp, _f, _f, _f, _f]),
+    "mx_freeu": (_i, [_vp, C.POINTER(FreeUProblem), _i, _i, _i, _f, _f]),
+    "mx_freeu_route": (_i, [C.POINTER(FreeUProblem), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mx_unet_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),
     "mx_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "mx_unet_validate": (_i, [_vp, _i, _i, _i, _i]),

@@ -317,6 +317,43 @@ def attention_cross_ip_grouped(problems, heads: int, n_img: int) -> list:
     return outs
 
 
+def freeu_route(shapes, c_skip: int) -> tuple:
+    """(slab, [staged], [chain]) of one FreeU launch over problems of ``shapes`` = [(B, H, W), ...] (mx_freeu_route, host only): the channels per
+    workgroup, per problem whether the slab is staged in LDS, and the longest sequential addition chain of its sums."""
+    n = len(shapes)
+    arr = (_lib.FreeUProblem * n)()
+    for a, (b, h, w) in zip(arr, shapes):
+        a.B, a.H, a.W = b, h, w
+    slab, staged, chain = C.c_int(0), (C.c_int * n)(), (C.c_int * n)()
+    _lib.check(_lib.load().mx_freeu_route(arr, n, c_skip, C.byref(slab), staged, chain), "mx_freeu_route")
+    return slab.value, list(staged), list(chain)
+
+
+def freeu(hidden, skip, s: float, b: float):
+    """One FreeU application (mx_freeu; diffusers' apply_freeu): returns the low-frequency-filtered ``skip`` [B, H, W, C] bf16 and scales
+    ``hidden[..., :C_hidden // 2]`` by b IN PLACE (``hidden`` None: the filter alone).  Lists of tensors (up to MAX_SEGS problems of different
+    B, H, W and the same channel counts) run as ONE launch and return a list."""
+    many = isinstance(skip, (list, tuple))
+    skips = list(skip) if many else [skip]
+    hiddens = list(hidden) if many else [hidden]
+    n = len(skips)
+    arr = (_lib.FreeUProblem * n)()
+    outs = []
+    for a, x, hd in zip(arr, skips, hiddens):
+        _bf16(x)
+        assert x.ndim == 4
+        o = torch.empty_like(x)
+        outs.append(o)
+        a.skip, a.skip_out, a.B, a.H, a.W = x.data_ptr(), o.data_ptr(), x.shape[0], x.shape[1], x.shape[2]
+        if hd is not None:
+            _bf16(hd)
+            assert hd.shape[:3] == x.shape[:3] and hd.shape[3] == hiddens[0].shape[3]
+            a.hidden = hd.data_ptr()
+    c_hidden = 0 if hiddens[0] is None else hiddens[0].shape[3]
+    _lib.check(_lib.load().mx_freeu(_lib.current_stream(), arr, n, skips[0].shape[3], c_hidden, float(s), float(b)), "mx_freeu")
+    return outs if many else outs[0]
+
+
 def attn_tail(ao: torch.Tensor, y: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, colsum_q: torch.Tensor,
               k: torch.Tensor, vt: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, heads: int, L: int, ctx_len: int, ln_eps: float = 1e-5,
               finalise: bool = True):

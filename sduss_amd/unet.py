@@ -70,6 +70,7 @@ class MxUNet(ModelSlot):
         self._ip = None                    # set_ip_adapter: (IPAdapter, its PackedWeights on the device)
         self._ip_next = None               # set_image_tokens: (tokens, scales) of the NEXT forward only, handed over right before its launches
         self._ip_live = None
+        self._freeu_on = False             # enable_freeu
         self.config = _Config(in_channels=cfg.in_channels, time_cond_proj_dim=None,
                               addition_time_embed_dim=cfg.addition_time_embed_dim,
                               projection_class_embeddings_input_dim=cfg.projection_class_embeddings_input_dim,
@@ -194,6 +195,20 @@ class MxUNet(ModelSlot):
         ip_scale = ip_scale.to(device=self.device, dtype=torch.float32).contiguous()
         assert tokens.ndim == 3 and tokens.shape[1:] == (16, self.cfg.cross_attention_dim) and ip_scale.shape == (tokens.shape[0],)
         self._ip_next = (tokens, ip_scale)
+
+    # ---- FreeU (mx_unet_set_freeu; freeu.hip) -----------------------------------------------------------
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """diffusers' ``UNet2DConditionModel.enable_freeu``: from now on every resnet of up blocks 0 and 1 reads its skip low-frequency-filtered (scale
+        s1 / s2) beside a hidden state whose first half of the channels is scaled (b1 / b2).  On only when all four are non-zero, as in diffusers.
+        Served by the plain and mixed forwards; the block-skip cache and patch-parallel forwards refuse while it is on."""
+        _lib.check(self._lib.mx_unet_set_freeu(self._handle, float(s1), float(s2), float(b1), float(b2)), "mx_unet_set_freeu")
+        on = all(float(v) != 0.0 for v in (s1, s2, b1, b2))
+        if on != self._freeu_on:           # the plan takes a buffer for the filtered skips while FreeU is on: the arena sizes are walked again
+            self._freeu_on, self._ws_need = on, {}
+
+    def disable_freeu(self) -> None:
+        """diffusers' ``disable_freeu``: the plain launch sequence again"""
+        self.enable_freeu(0.0, 0.0, 0.0, 0.0)
 
     # ---- LoRA adapters (sduss_amd/lora.py; mx_lora_merge) ---------------------------------------------
     def _point_at(self, blob: torch.Tensor) -> None:
