@@ -350,6 +350,14 @@ int mx_attention_prescaled_bias(void* stream, const void* q, int ldq, const void
 int mx_attention_prescaled_causal(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                                   int64_t vt_batch_stride, void* o, int ldo, int B, int H, int L);
 
+/* softmax(q k^T / sqrt(80)) v per (batch, head) for heads of 80 (csrc/attention_d80.hip: OpenCLIP ViT-H/14, the IP-Adapter's image encoder), non-causal,
+ * Lq = Lk = L.  q, k, v: bf16 rows (b*L + i), head h at columns [80h, 80h + 80), row strides ldq / ldk / ldv -- three column ranges of one [M, 3 hidden]
+ * mx_gemm output serve as they are; v is row-major (no V^T store) and q is NOT prescaled: the scale is applied to the fp32 scores.  o: bf16 [B*L, ldo].
+ * A head's K and V stay resident in LDS: refused without a launch for L > MX_ATTN_D80_MAX_L, a null or misaligned operand (q, k, v 16 bytes, o 8), a
+ * leading dimension that is no multiple of 8 (ldo: 4) or shorter than 80 H. */
+#define MX_ATTN_D80_MAX_L 480
+int mx_attention_d80(void* stream, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B, int H, int L);
+
 /* y = LayerNorm(x) * gamma + beta over the last dim C; x,y bf16 [M, C]; gamma/beta fp32 [C], or both NULL: plain (x - mean) * rstd, the
  * input of a linear whose weights carry the affine (weights folded for mx_gemm_desc.ln_stats work unchanged on it, without ln_stats) */
 int mx_layernorm(void* stream, const void* x, void* y, const float* gamma, const float* beta,
@@ -734,6 +742,40 @@ size_t mx_clip_workspace_bytes(const mx_clip* c, int batch);
 int mx_clip_validate(const mx_clip* c, int batch);
 int mx_clip_encode(mx_clip* c, void* stream, const int32_t* ids, void* hidden_out, void* pooled_out, int batch, void* workspace,
                    size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * CLIP vision encoder (csrc/clip_vision.cpp): transformers' CLIPVisionModelWithProjection, what an IP-Adapter's caller runs on the reference image
+ * before the denoising loop (OpenCLIP ViT-H/14 for the SDXL checkpoints: heads of 80, mx_attention_d80; ViT-L/14: heads of 64, mx_attention_prescaled).
+ * Packed weights keep the transformers names except q_proj / k_proj / v_proj, fused into "<layer>.self_attn.qkv_proj.{weight [3H, H], bias [3H]}", and
+ * "vision_model.embeddings.patch_embedding.weight", flattened to bf16 [H, ldw] in (row, column, channel) order with ldw = 3 P P rounded up to 32
+ * (MX_CLIP_VISION_LDW: 588 -> 608), zero-padded; class_embedding and position_embedding bf16.
+ *   images: uint8 interleaved RGB, image_size x image_size pixels per image, row_stride and image_stride in bytes (a centre crop is an offset);
+ *   image_embeds_out: fp32 [batch, projection_dim] = visual_projection(post_layernorm(last[:, 0])), or NULL;
+ *   hidden_out: bf16 [batch, 1 + patches, H] = hidden_states[-2] (the input of the last layer), or NULL: then neither computed nor copied.
+ * ------------------------------------------------------------------------------------------ */
+/* The patch embedding on its own (csrc/patch_embed.hip), one launch:  x[b, 1 + p, :] = W vec(normalise(patch_p)) + pos[1 + p, :],  x[b, 0, :] = cls + pos[0, :]
+ *   image: uint8 RGB, pixel (y, x) of image b at image[b * image_stride + y * row_stride + 3 x]; the grid is GH x GW patches of P x P pixels from (0, 0);
+ *   normalise(u) = (u / 255 - mean[c]) / std[c], fp32 operation by operation, rounded once to bf16;
+ *   w: bf16 [N, ldw], column (ky P + kx) 3 + c, columns [3 P P, ldw) ZERO (ldw >= 3 P P rounded up to 32, % 8 == 0); cls bf16 [N]; pos bf16 [1 + GH GW, N];
+ *   x: bf16 [B, 1 + GH GW, N], acc + pos in fp32 rounded once; N % 16 == 0; w, pos, x 16-byte aligned; mean, std: three host floats each. */
+int mx_patch_embed_u8(void* stream, const void* image, int64_t row_stride, int64_t image_stride, const void* w, int ldw, const void* cls, const void* pos,
+                      void* x, int B, int GH, int GW, int P, int N, const float* mean, const float* std3);
+typedef struct mx_clip_vision_config {
+  int hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, image_size, patch_size;
+  int hidden_act;                 /* 0 = quick_gelu, 1 = gelu (erf) */
+  int projection_dim;
+  float layer_norm_eps;
+  float image_mean[3], image_std[3];
+} mx_clip_vision_config;
+typedef struct mx_clip_vision mx_clip_vision;
+#define MX_CLIP_VISION_LDW(P) ((3 * (P) * (P) + 31) / 32 * 32)      /* row length of the packed patch weight */
+mx_clip_vision* mx_clip_vision_create(const mx_clip_vision_config* cfg);     /* NULL (mx_last_error) unless hidden = 80 heads or 64 heads */
+void mx_clip_vision_destroy(mx_clip_vision* c);
+int mx_clip_vision_set_weights(mx_clip_vision* c, const void* blob, uint64_t blob_bytes, const mx_weight_entry* table, int n_entries);
+size_t mx_clip_vision_workspace_bytes(const mx_clip_vision* c, int batch);
+int mx_clip_vision_validate(const mx_clip_vision* c, int batch);
+int mx_clip_vision_encode(mx_clip_vision* c, void* stream, const void* images, int64_t row_stride, int64_t image_stride, void* image_embeds_out,
+                          void* hidden_out, int batch, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * T5 v1.1 encoder (csrc/t5_text.cpp): SD3's text_encoder_3 (transformers T5EncoderModel, XXL: 24 blocks x 4096, 64 heads of 64, d_ff 10240,

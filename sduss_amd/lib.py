@@ -175,6 +175,16 @@ class CLIPConfigC(C.Structure):
                 ("eos_token_id", C.c_int), ("hidden_layer", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class CLIPVisionConfigC(C.Structure):
+    """mx_clip_vision_config"""
+    _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int),
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("hidden_act", C.c_int), ("projection_dim", C.c_int),
+                ("layer_norm_eps", C.c_float), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
+ATTN_D80_MAX_L = 480                 # MX_ATTN_D80_MAX_L
+
+
 class T5ConfigC(C.Structure):
     _fields_ = [("vocab_size", C.c_int), ("d_model", C.c_int), ("d_ff", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
                 ("layer_norm_epsilon", C.c_float)]
@@ -375,6 +385,14 @@ SYMBOLS = {
     "mx_clip_workspace_bytes": (_sz, [_vp, _i]),
     "mx_clip_validate": (_i, [_vp, _i]),
     "mx_clip_encode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
+    "mx_attention_d80": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i]),
+    "mx_patch_embed_u8": (_i, [_vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f)]),
+    "mx_clip_vision_create": (_vp, [C.POINTER(CLIPVisionConfigC)]),
+    "mx_clip_vision_destroy": (None, [_vp]),
+    "mx_clip_vision_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),
+    "mx_clip_vision_workspace_bytes": (_sz, [_vp, _i]),
+    "mx_clip_vision_validate": (_i, [_vp, _i]),
+    "mx_clip_vision_encode": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _vp, _sz]),
     "mx_attention_prescaled_causal": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i]),
     "mx_attention_prescaled_bias": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _vp, _i]),
     "mx_rmsnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f]),

@@ -272,6 +272,41 @@ def attention_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: i
     return o
 
 
+def attention_d80(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, batch: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T / sqrt(80)) v for heads of 80 (mx_attention_d80): q, k, v bf16 [batch * L, heads * 80], rows may be strided views (three column
+    ranges of one q | k | v buffer), v row-major, q not prescaled -> o bf16 [batch * L, heads * 80].  L <= lib.ATTN_D80_MAX_L."""
+    l = _lib.load()
+    for t_ in (q, k, v):
+        assert t_.is_cuda and t_.dtype == torch.bfloat16 and t_.ndim == 2 and t_.stride(1) == 1 and t_.shape == (q.shape[0], heads * 80)
+    if out is None:
+        out = torch.empty((q.shape[0], heads * 80), dtype=torch.bfloat16, device=q.device)
+    assert out.is_cuda and out.dtype == torch.bfloat16 and out.stride(1) == 1 and q.shape[0] % batch == 0
+    _lib.check(l.mx_attention_d80(_lib.current_stream(), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(),
+                                  out.stride(0), batch, heads, q.shape[0] // batch), "mx_attention_d80")
+    return out
+
+
+def patch_embed_u8(image: torch.Tensor, w: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, patch: int, mean, std,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The CLIP vision encoder's first launch (mx_patch_embed_u8): image uint8 [B, H, W, 3], possibly a strided view (a crop) with H, W whole numbers of
+    ``patch``; w bf16 [N, ldw] in (row, column, channel) order, zero beyond 3 patch^2; cls bf16 [N]; pos bf16 [1 + patches, N] ->
+    x bf16 [B, 1 + patches, N] = [cls | W normalise(patches)] + pos, normalise(u) = (u / 255 - mean[c]) / std[c]."""
+    l = _lib.load()
+    _bf16(w); _bf16(cls); _bf16(pos)
+    assert image.is_cuda and image.dtype == torch.uint8 and image.ndim == 4 and image.shape[3] == 3 and image.stride(3) == 1 and image.stride(2) == 3
+    b, h, wd = image.shape[:3]
+    assert h % patch == 0 and wd % patch == 0
+    gh, gw, n = h // patch, wd // patch, w.shape[0]
+    assert cls.shape == (n,) and pos.shape == (1 + gh * gw, n)
+    if out is None:
+        out = torch.empty((b, 1 + gh * gw, n), dtype=torch.bfloat16, device=image.device)
+    assert out.dtype == torch.bfloat16 and out.shape == (b, 1 + gh * gw, n) and out.is_contiguous()
+    m3, s3 = (C.c_float * 3)(*[float(x) for x in mean]), (C.c_float * 3)(*[float(x) for x in std])
+    _lib.check(l.mx_patch_embed_u8(_lib.current_stream(), image.data_ptr(), image.stride(1), image.stride(0) if b > 1 else 0, w.data_ptr(), w.shape[1],
+                                   cls.data_ptr(), pos.data_ptr(), out.data_ptr(), b, gh, gw, patch, n, m3, s3), "mx_patch_embed_u8")
+    return out
+
+
 IP_KEYS = 16           # image keys per sample as stored (n_img <= IP_KEYS valid)
 
 

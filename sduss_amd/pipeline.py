@@ -377,11 +377,20 @@ class Denoiser:
         return (_upload(torch.tensor(slot, dtype=torch.int32), dev), torch.cat([s.init for s in rows], dim=0).contiguous(),
                 torch.cat([s.noise for s in rows], dim=0).contiguous(), torch.cat([s.mask for s in rows], dim=0).contiguous())
 
-    def set_image_prompt(self, req, image_embeds: Optional[torch.Tensor], scale: float = 1.0) -> None:
+    def set_image_prompt(self, req, image_embeds: Optional[torch.Tensor] = None, scale: float = 1.0, *, image: Optional[torch.Tensor] = None,
+                         encoder=None) -> None:
         """Give ``req`` an image prompt (the model slot's image-prompt adapter, MxUNet.set_ip_adapter): ``image_embeds`` [1, embed_dim] as diffusers'
         ``ip_adapter_image_embeds``, or tokens [1, n_img, cross_dim] made elsewhere; None takes the prompt away.  Projected here, once: the
         conditional row carries the embeddings' tokens, the unconditional CFG row those of ZERO embeddings at the same scale, as diffusers does
-        (caller-made tokens: zero tokens).  Requests without a prompt run at scale 0, so one batch may mix both kinds."""
+        (caller-made tokens: zero tokens).  Requests without a prompt run at scale 0, so one batch may mix both kinds.
+        ``image``: the client's reference image itself, uint8 [1, H, W, 3], encoded by ``encoder`` (clip_vision.MxCLIPVision.encode_images) in place of
+        ``image_embeds``."""
+        if image is not None:
+            if image_embeds is not None:
+                raise MxError(f"{type(self).__name__}.set_image_prompt: pass image or image_embeds, not both")
+            if encoder is None:
+                raise MxError(f"{type(self).__name__}.set_image_prompt: image needs encoder (an MxCLIPVision)")
+            image_embeds = encoder.encode_images(image)
         ip = getattr(self._model, "_ip", None)
         if image_embeds is None:
             req.image_tokens, req.ip_scale = None, 0.0

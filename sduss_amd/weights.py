@@ -300,3 +300,39 @@ def pack_mmdit(cfg, P: Dict[str, torch.Tensor]) -> List[Tuple[str, torch.Tensor]
             lin(f"{b}.ff_context.net.0.proj", f"{b}.ff_context.net.0.proj"); lin(f"{b}.ff_context.net.2", f"{b}.ff_context.net.2")
     lin("proj_out", "proj_out")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# CLIP vision encoder (csrc/clip_vision.cpp)
+# ------------------------------------------------------------------------------------------------------------------
+def clip_vision_ldw(patch: int) -> int:
+    """row length of the packed patch weight: 3 patch^2 rounded up to the 32 of one matrix-instruction k-step (MX_CLIP_VISION_LDW)"""
+    return (3 * patch * patch + 31) // 32 * 32
+
+
+def pack_clip_vision(cfg, P: Dict[str, torch.Tensor]) -> List[Tuple[str, torch.Tensor]]:
+    """transformers' CLIPVisionModelWithProjection state dict (``vision_model.*``, ``visual_projection.weight``) -> packed tensors of
+    csrc/clip_vision.cpp: matrices, the class and the position embedding bf16, vectors fp32, q / k / v fused, the patch convolution [H, 3, P, P]
+    flattened to [H, ldw] in (row, column, channel) order -- a patch row's bytes of the interleaved image are then consecutive k -- and
+    zero-padded.  Every tensor is converted once, from the values given."""
+    bf, f32 = torch.bfloat16, torch.float32
+    out: List[Tuple[str, torch.Tensor]] = []
+    done = set()
+    pe = "vision_model.embeddings.patch_embedding.weight"
+    w = P[pe]
+    h, k = w.shape[0], 3 * cfg.patch_size * cfg.patch_size
+    flat = torch.zeros((h, clip_vision_ldw(cfg.patch_size)), dtype=bf, device=w.device)
+    flat[:, :k] = w.permute(0, 2, 3, 1).reshape(h, k).to(bf)
+    out.append((pe, flat))
+    out.append(("vision_model.embeddings.class_embedding", P["vision_model.embeddings.class_embedding"].to(bf).contiguous()))
+    done.update((pe, "vision_model.embeddings.class_embedding"))
+    for l in range(cfg.num_hidden_layers):
+        a = f"vision_model.encoder.layers.{l}.self_attn"
+        out.append((f"{a}.qkv_proj.weight", torch.cat([P[f"{a}.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], dim=0).to(bf).contiguous()))
+        out.append((f"{a}.qkv_proj.bias", torch.cat([P[f"{a}.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], dim=0).to(f32).contiguous()))
+        done.update(f"{a}.{n}.{t}" for n in ("q_proj", "k_proj", "v_proj") for t in ("weight", "bias"))
+    for name, t in P.items():
+        if name in done or name.endswith("position_ids"):
+            continue
+        out.append((name, (t.to(bf) if t.ndim == 2 else t.to(f32)).contiguous()))
+    return out
