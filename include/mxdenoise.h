@@ -422,6 +422,33 @@ typedef struct mx_freeu_problem { const void* skip; void* skip_out; void* hidden
 int mx_freeu(void* stream, const mx_freeu_problem* probs, int n, int C_skip, int C_hidden, float s, float b);
 int mx_freeu_route(const mx_freeu_problem* probs, int n, int C_skip, int* slab, int* staged, int* chain);
 
+/* Token merging (ToMe for Stable Diffusion, Bolya & Hoffman; tomesd with use_rand = False) around a self-attention, four launches (tome.hip).
+ * The h x w token grid of an image is cut into cells of sy x sx (sy * sx >= 2, h % sy == 0, w % sx == 0, h * w <= 16384); the top-left token of a
+ * cell is a destination (Ndst of them), every other token a source (Nsrc), both numbered in ascending token order.
+ *   mx_tome_sizes (host only)  out = {Ndst, Nsrc, r, Lm}: r = min(Nsrc, int(h w ratio)), lowered until Lm = h w - r is a multiple of 64.  Non-zero
+ *                    with r = 0 and Lm = h w where the level runs unmerged (the cells do not tile the grid, or nothing is left to merge).
+ *   mx_tome_match    x bf16 [B, h w, ldx], C channels (a multiple of 64, <= 1280).  node_max[B, Nsrc] fp32 = the largest cosine of source i against
+ *                    the destinations, node_idx[B, Nsrc] its destination ordinal (equal scores: the lower ordinal).  Rows are scaled to unit L2 norm
+ *                    in fp32 (a zero row has inverse norm 0); neither the normalised rows nor the scores reach memory.
+ *   mx_tome_select   per sample the r sources with the largest node_max are merged (equal node_max: the lower source ordinal first), 0 <= r <= Nsrc.
+ *                    Tables, int32: row_of[B, h w] token -> row of the merged sequence; unm_src[B, Nsrc - r] the tokens of the unmerged sources,
+ *                    ascending; dst_start[B, Ndst + 1] and dst_src[B, r]: the tokens merged into destination j are dst_src[dst_start[j] ..
+ *                    dst_start[j + 1]), ascending.  The merged sequence of Lm = h w - r rows is the unmerged sources, then all destinations.
+ *   mx_tome_merge    out bf16 [B Lm, ldo]: an unmerged source's row is its own; a destination's row is the mean of itself and the sources merged
+ *                    into it (fp32 sum, self first, then ascending; one rounding).  eps >= 0: every gathered row is LayerNorm-ed without affine in
+ *                    fp32 first; eps < 0: plain rows.  C a multiple of 8, <= 1536.
+ *   mx_tome_unmerge  y[b, t] = residual[b, t] + o[b, row_of[b, t]] (fp32, one rounding); residual NULL: the plain unmerge.  y may be the residual.
+ *   mx_tome_table_bytes  the bytes of the four tables, each rounded up to 256, in the order row_of, unm_src, dst_start, dst_src. */
+int mx_tome_sizes(int h, int w, int sy, int sx, float ratio, int out[4]);
+size_t mx_tome_table_bytes(int B, int h, int w, int sy, int sx, int r);
+int mx_tome_match(void* stream, const void* x, int ldx, int B, int h, int w, int sy, int sx, int C, float* node_max, int* node_idx);
+int mx_tome_select(void* stream, const float* node_max, const int* node_idx, int B, int h, int w, int sy, int sx, int r, int* row_of, int* unm_src,
+                   int* dst_start, int* dst_src);
+int mx_tome_merge(void* stream, const void* x, int ldx, int B, int h, int w, int sy, int sx, int C, int r, const int* unm_src, const int* dst_start,
+                  const int* dst_src, float eps, void* out, int ldo);
+int mx_tome_unmerge(void* stream, const void* o, int ldo, const int* row_of, const void* residual, int ldr, void* y, int ldy, int B, int L, int Lm,
+                    int C);
+
 /* ------------------------------------------------------------------------------------------
  * Outer boundary: the SDXL UNet in the model slot.
  * ------------------------------------------------------------------------------------------ */
@@ -487,6 +514,14 @@ int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const float* ip_sca
  * part of the graph key.  The block-cache entry points (their state compares unfiltered skips) and the patch-parallel ones (the filter needs whole
  * planes, which lie across ranks) refuse a forward while it is on. */
 int mx_unet_set_freeu(mx_unet* u, float s1, float s2, float b1, float b2);
+/* Token merging (tomesd.apply_patch(ratio, sx, sy, max_downsample, use_rand = False) with its defaults merge_attn only): while on, every
+ * BasicTransformerBlock of a level whose downsampling factor is <= max_downsample (2: the first attention level, 4: both) runs its self-attention on
+ * the merged sequence -- mx_tome_match on the block's input, mx_tome_select, mx_tome_merge of norm1's output into the q | k | v projection's operand,
+ * the attention core and attn1.to_out on Lm rows, mx_tome_unmerge into the residual stream.  ratio in [0, 0.75]; 0 turns it off and the launch sequence
+ * is the plain one.  A level mx_tome_sizes answers non-zero for runs unmerged.  Served by mx_unet_forward, mx_unet_forward_mixed with ONE resolution
+ * group and their _trace forms; the sizing walks count its buffers and it is part of the graph key.  The block-cache and patch-parallel entry points
+ * and a mixed batch of more than one resolution group refuse a forward while it is on. */
+int mx_unet_set_tome(mx_unet* u, float ratio, int sx, int sy, int max_downsample);
 size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len);
 /* host-only walk of the step plan that resolves every packed tensor by name and size (no launches, no GPU needed) */
 int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len);

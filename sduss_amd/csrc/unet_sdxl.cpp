@@ -82,6 +82,9 @@ struct mx_unet {
   // ---- FreeU (mx_unet_set_freeu): (s, b) of up blocks 0 and 1; on only with all four non-zero, as in diffusers ----
   bool freeu_on = false;
   float freeu_s[2] = {0.f, 0.f}, freeu_b[2] = {0.f, 0.f};
+  // ---- token merging (mx_unet_set_tome): ratio 0 = off ----
+  float tome_ratio = 0.f;
+  int tome_sx = 2, tome_sy = 2, tome_max_ds = 2;
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -632,6 +635,17 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   // ---- Transformer2DModel (modules/transformer.py:32-128) over BasicTransformerBlocks (:167-290) ----
   // per resolution group of the rows (one unless the batch is mixed): tokens per image, first row, its V^T block (rows of MX_VT_LD(tokens) keys)
   struct TokenGroups { int L[MX_MAX_SEGS], ldvt[MX_MAX_SEGS]; long row0[MX_MAX_SEGS], vt0[MX_MAX_SEGS], vt_elems = 0; };
+  // Token merging (mx_unet_set_tome; tome.hip) at a level: the self-attention of every block runs on Lm = L - r rows an image.  Per block: match on
+  // the hidden state y, select, merge of norm1(y) -> xm (the q | k | v projection's operand), attention and attn1.to_out on Lm rows -> om, unmerge
+  // adds om's rows into y.  The sizes are the host's (mx_tome_sizes): nothing is read back, and a graph captures the sequence.
+  struct Tome {
+    int h = 0, w = 0, r = 0, Lm = 0, Ndst = 0, Nsrc = 0;
+    float* node_max = nullptr; int* node_idx = nullptr;
+    int *row_of = nullptr, *unm_src = nullptr, *dst_start = nullptr, *dst_src = nullptr;
+    bf16_t *xm = nullptr, *om = nullptr;
+  };
+  float tome_ratio = 0.f;               // this forward's (Model::setup); 0: off
+  int tome_sx = 2, tome_sy = 2, tome_max_ds = 2;
   // one transformer's shape, LayerNorm routes and buffers (transformer_buffers allocates them in the order they stand here)
   struct Xf {
     int C, heads, level, M, L, ldvt;      // (L, ldvt: the first group's tokens per image)
@@ -649,6 +663,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     KV* kvp = nullptr;                    // the hoisted cross-attention K / V^T of this width
     mx_gemm_seg qsegs[MX_MAX_SEGS];       // mixed batch: the fused q|k|v projection as a grouped launch (tokens per image and V^T block per group)
     std::vector<long> vt_off; std::vector<int> ldvt_s, Lk_s;         // patch-unit cache: per sample, its V^T block and keys
+    Tome tm;                              // token merging at this level (tm.r > 0: on)
   };
   void transformer_buffers(Xf& t, bf16_t* gn_out) {
     const size_t M = t.M, C = t.C;
@@ -663,6 +678,28 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     t.ff = alloc<bf16_t>(M * 4 * C);
     if (t.via.norm1 == LnVia::Final || t.via.norm3 == LnVia::Final) { t.st.fin = (float*)ar.alloc(M * 2 * sizeof(float)); t.st.cnt = ln_cnt; if (!t.st.fin) fail("workspace too small"); }
     if (pc) { t.pqc = alloc<bf16_t>(M * C); t.paoc = alloc<bf16_t>(M * C); t.ptc = alloc<bf16_t>(M * C); }
+    if (t.tm.r > 0) {
+      Tome& m = t.tm;
+      const size_t Bn = B;
+      m.node_max = alloc<float>(Bn * m.Nsrc); m.node_idx = alloc<int>(Bn * m.Nsrc);
+      m.row_of = alloc<int>(Bn * t.L); m.unm_src = alloc<int>(Bn * (m.Nsrc - m.r) + 1); m.dst_start = alloc<int>(Bn * (m.Ndst + 1)); m.dst_src = alloc<int>(Bn * m.r);
+      m.xm = alloc<bf16_t>(Bn * m.Lm * C); m.om = alloc<bf16_t>(Bn * m.Lm * C);
+    }
+  }
+  // the A operand of the q | k | v projection under token merging: the merged, normalised rows of the hidden state
+  const bf16_t* tome_operand(Xf& t) {
+    const Tome& m = t.tm;
+    if (!ok() || quiet()) return m.xm;
+    if (mx_tome_match(stream, t.y, t.C, B, m.h, m.w, tome_sy, tome_sx, t.C, m.node_max, m.node_idx) ||
+        mx_tome_select(stream, m.node_max, m.node_idx, B, m.h, m.w, tome_sy, tome_sx, m.r, m.row_of, m.unm_src, m.dst_start, m.dst_src) ||
+        mx_tome_merge(stream, t.y, t.C, B, m.h, m.w, tome_sy, tome_sx, t.C, m.r, m.unm_src, m.dst_start, m.dst_src, u->cfg.layer_norm_eps, m.xm, t.C))
+      fail(std::string("ToMe: ") + mx_last_error());
+    return m.xm;
+  }
+  void tome_unmerge(Xf& t) {              // y += om[row_of]
+    const Tome& m = t.tm;
+    if (!ok() || quiet()) return;
+    if (mx_tome_unmerge(stream, m.om, t.C, m.row_of, t.y, t.C, t.y, t.C, B, t.L, m.Lm, t.C)) fail(std::string("ToMe: ") + mx_last_error());
   }
   // out = (in - mean) * rstd per row, no affine (it lives in the folded weights)
   void normalise(const bf16_t* in, bf16_t* out, int rows, int C) {
@@ -677,11 +714,12 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   // self-attention's fused q | k | v projection of block b, norm1 folded into it (the hidden state in front of it comes from ordinary GEMMs in every mode)
   void qkv(Xf& t, const std::string& b) {
     const int C = t.C;
-    const bf16_t* a = ln_operand(t, t.via.norm1);
+    const bool merged = t.tm.r > 0;       // (one group, norm1 by Pass: the merge launch normalises the rows it gathers)
+    const bf16_t* a = merged ? tome_operand(t) : ln_operand(t, t.via.norm1);
     mx_gemm_desc d; std::memset(&d, 0, sizeof(d));
     d.a = a; d.w = wb(b + ".attn1.to_qkv.weight", (size_t)3 * C * C); d.bias = wf(b + ".attn1.to_qkv.bias", 3 * C);
     d.c = t.qk; d.vt = t.vt;
-    mx::ln_qkv_shape(d, t.M, C, t.L);
+    if (merged) mx::ln_qkv_shape(d, B * t.tm.Lm, C, t.tm.Lm); else mx::ln_qkv_shape(d, t.M, C, t.L);
     if (ng > 1) {
       std::memset(t.qsegs, 0, sizeof(t.qsegs));
       for (int g = 0; g < ng; ++g) {
@@ -756,8 +794,13 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
           mx_attention_prescaled_chunked(stream, t.qk, 2 * C, t.k_all, C, t.vt_all, t.ldvt, (int64_t)C * t.ldvt, t.ao, C, B, t.heads, t.L, pp_world * t.L, t.L,
                                          (int64_t)t.L * C, (int64_t)M * C, (int64_t)B * C * t.ldvt))
         fail(std::string("attention: ") + mx_last_error());
+    } else if (t.tm.r > 0) {          // token merging: the core and to_out on Lm rows an image, then y += the rows where each token went
+      const int Lm = t.tm.Lm, ldm = MX_VT_LD(Lm);
+      attention(t.qk, 2 * C, t.qk + C, 2 * C, t.vt, ldm, (long)C * ldm, t.ao, C, t.heads, Lm, Lm);
+      linear(Linear{t.ao, C, b + ".attn1.to_out.0", t.tm.om, C, B * Lm, C, C});
+      tome_unmerge(t);
     } else self_attention(t);
-    linear(Linear{t.ao, C, b + ".attn1.to_out.0", t.y, C, M, C, C}.plus(t.y, C).leaves_stats(t.st, t.via.norm2));
+    if (t.tm.r == 0) linear(Linear{t.ao, C, b + ".attn1.to_out.0", t.y, C, M, C, C}.plus(t.y, C).leaves_stats(t.st, t.via.norm2));
     linear(Linear{ln_operand(t, t.via.norm2), C, b + ".attn2.to_q", t.q2, C, M, C, C}.scaled(MX_ATTN_QSCALE(0.125f)).folded_ln(t.st, t.via.norm2));
     cross_attention(t, li);
     linear(Linear{t.ao, C, b + ".attn2.to_out.0", t.y, C, M, C, C}.plus(t.y, C).leaves_stats(t.st, t.via.norm3));
@@ -840,6 +883,15 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     else groupnorm(x, n, p + ".norm", h, wd, C, u->cfg.transformer_norm_eps, false, level_patch(level));
     // (tickets: the plan has its panel counters and they cover these rows)
     t.via = mx::ln_routes(lr, C, layers, is_pp(), pc, ln_cnt != nullptr && (M + 255) / 256 <= kLnCnt);
+    // Token merging at this level (one group; never patch-parallel or cached: those entry points refuse): norm1 reaches q | k | v through the merge
+    // launch and norm2's producer is the unmerge launch, which leaves no statistics -- both by Pass, whatever the table says
+    if (tome_ratio > 0.f && ng == 1 && !is_pp() && !pc && (1 << level) <= tome_max_ds) {
+      int sz[4];
+      if (mx_tome_sizes(h, wd, tome_sy, tome_sx, tome_ratio, sz) == 0 && L <= 16384 && C <= 1280) {
+        t.tm.h = h; t.tm.w = wd; t.tm.Ndst = sz[0]; t.tm.Nsrc = sz[1]; t.tm.r = sz[2]; t.tm.Lm = sz[3];
+        t.via.norm1 = t.via.norm2 = LnVia::Pass;
+      }
+    }
     transformer_buffers(t, n);
     linear(Linear{n, C, p + ".proj_in", t.y, C, M, C, C}.leaves_stats(t.st, t.via.norm1));
     // -- K alone travels: the QKV epilogue writes q|k interleaved, so the K halves are packed into a contiguous send buffer first
@@ -1362,6 +1414,7 @@ struct Model {
   int setup(Plan& p, mx_unet* u, const mx::ForwardCall& c) {
     p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
     p.fu = fu;
+    p.tome_ratio = tome_ratio; p.tome_sx = tome_cell[0]; p.tome_sy = tome_cell[1]; p.tome_max_ds = tome_cell[2];
     p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
@@ -1421,10 +1474,18 @@ struct Model {
   bool fu = false;
   float fu_sb[4] = {0.f, 0.f, 0.f, 0.f};
   // (the FreeU state is part of the key: a captured graph holds its launches and their scalars)
+  // token merging as THIS forward runs it, by the same rule (refuse_tome); part of the key for the same reason
+  float tome_ratio = 0.f;
+  int tome_cell[3] = {2, 2, 2};          // sx, sy, max_downsample
   std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) {
     std::vector<uint64_t> k{(uint64_t)c.gn_patch};
     if (fu)
       for (float v : fu_sb) { uint32_t w; std::memcpy(&w, &v, 4); k.push_back(0x100000000ull | w); }
+    if (tome_ratio > 0.f) {
+      uint32_t w; std::memcpy(&w, &tome_ratio, 4);
+      k.push_back(0x200000000ull | w);
+      for (int v : tome_cell) k.push_back(0x300000000ull | (uint32_t)v);
+    }
     return k;
   }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
@@ -1434,6 +1495,10 @@ int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   if (u && u->freeu_on && !c.pp() && !c.cache) {
     m.fu = true;
     m.fu_sb[0] = u->freeu_s[0]; m.fu_sb[1] = u->freeu_s[1]; m.fu_sb[2] = u->freeu_b[0]; m.fu_sb[3] = u->freeu_b[1];
+  }
+  if (u && u->tome_ratio > 0.f && !c.pp() && !c.cache) {
+    MX_CHECK(!(c.groups && c.n_groups > 1), "unet: ToMe does not run on a mixed batch of more than one resolution group (mx_unet_set_tome with ratio 0 turns it off)");
+    m.tome_ratio = u->tome_ratio; m.tome_cell[0] = u->tome_sx; m.tome_cell[1] = u->tome_sy; m.tome_cell[2] = u->tome_max_ds;
   }
   if (u && !c.dry) {        // the announcement names ONE forward, served or refused
     mx_unet* uw = const_cast<mx_unet*>(u);
@@ -1455,6 +1520,12 @@ int refuse_image_prompt(mx_unet* u, const char* how) {
 // FreeU scales in place) and patch parallelism (the filter needs the whole plane, which lies across ranks)
 int refuse_freeu(const mx_unet* u, const char* how) {
   MX_CHECK(!(u && u->freeu_on), std::string("unet: FreeU does not run ") + how + " (mx_unet_set_freeu with a zero turns it off)");
+  return 0;
+}
+// the entry points that do not serve token merging: the block-skip cache (its state holds attn1.to_out's output per token and patch) and patch
+// parallelism (a rank holds a band of the tokens; the match would cross ranks)
+int refuse_tome(const mx_unet* u, const char* how) {
+  MX_CHECK(!(u && u->tome_ratio > 0.f), std::string("unet: ToMe does not run ") + how + " (mx_unet_set_tome with ratio 0 turns it off)");
   return 0;
 }
 using mx::dry_call;
@@ -1513,6 +1584,14 @@ extern "C" int mx_unet_set_freeu(mx_unet* u, float s1, float s2, float b1, float
   MX_CHECK(s1 == s1 && s2 == s2 && b1 == b1 && b2 == b2, "unet_set_freeu: NaN factor");
   u->freeu_on = s1 != 0.f && s2 != 0.f && b1 != 0.f && b2 != 0.f;
   u->freeu_s[0] = s1; u->freeu_s[1] = s2; u->freeu_b[0] = b1; u->freeu_b[1] = b2;
+  return 0;
+}
+extern "C" int mx_unet_set_tome(mx_unet* u, float ratio, int sx, int sy, int max_downsample) {
+  MX_CHECK(u != nullptr, "unet_set_tome: null handle");
+  MX_CHECK(ratio >= 0.f && ratio <= 0.75f, "unet_set_tome: ratio must be in [0, 0.75]");
+  MX_CHECK(sx >= 1 && sy >= 1 && sx * sy >= 2 && sx <= 64 && sy <= 64, "unet_set_tome: cells of sy x sx tokens, at least two tokens a cell");
+  MX_CHECK(max_downsample == 2 || max_downsample == 4, "unet_set_tome: max_downsample must be 2 (the first attention level) or 4 (both)");
+  u->tome_ratio = ratio; u->tome_sx = sx; u->tome_sy = sy; u->tome_max_ds = max_downsample;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1613,7 +1692,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1646,7 +1725,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1681,7 +1760,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1703,7 +1782,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

@@ -292,6 +292,13 @@ SYMBOLS = {
     "mx_unet_set_freeu": (_i, [_vp, _f, _f, _f, _f]),
     "mx_freeu": (_i, [_vp, C.POINTER(FreeUProblem), _i, _i, _i, _f, _f]),
     "mx_freeu_route": (_i, [C.POINTER(FreeUProblem), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "mx_unet_set_tome": (_i, [_vp, _f, _i, _i, _i]),
+    "mx_tome_sizes": (_i, [_i, _i, _i, _i, _f, C.POINTER(_i)]),
+    "mx_tome_table_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "mx_tome_match": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mx_tome_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mx_tome_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _i]),
+    "mx_tome_unmerge": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
     "mx_unet_set_weights": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i]),
     "mx_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "mx_unet_validate": (_i, [_vp, _i, _i, _i, _i]),

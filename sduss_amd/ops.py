@@ -389,6 +389,68 @@ def freeu(hidden, skip, s: float, b: float):
     return outs if many else outs[0]
 
 
+TomeTables = collections.namedtuple("TomeTables", "row_of unm_src dst_start dst_src h w sx sy r")
+
+
+def tome_sizes(h: int, w: int, sx: int = 2, sy: int = 2, ratio: float = 0.5) -> tuple:
+    """(Ndst, Nsrc, r, Lm) of token merging on an h x w token grid (mx_tome_sizes, host only); r = 0 and Lm = h w where the level runs unmerged"""
+    out = (C.c_int * 4)()
+    _lib.load().mx_tome_sizes(h, w, sy, sx, float(ratio), out)
+    return tuple(out)
+
+
+def tome_match(x: torch.Tensor, h: int, w: int, sx: int = 2, sy: int = 2) -> tuple:
+    """(node_max [B, Nsrc] fp32, node_idx [B, Nsrc] int32) of x [B, h w, C] bf16 (mx_tome_match): every source's best cosine and its destination"""
+    _bf16(x)
+    B, L, Cc = x.shape
+    assert L == h * w and h % sy == 0 and w % sx == 0
+    nsrc = L - (h // sy) * (w // sx)
+    node_max = torch.empty((B, nsrc), dtype=torch.float32, device=x.device)
+    node_idx = torch.empty((B, nsrc), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.load().mx_tome_match(_lib.current_stream(), x.data_ptr(), Cc, B, h, w, sy, sx, Cc, node_max.data_ptr(), node_idx.data_ptr()),
+               "mx_tome_match")
+    return node_max, node_idx
+
+
+def tome_select(node_max: torch.Tensor, node_idx: torch.Tensor, h: int, w: int, r: int, sx: int = 2, sy: int = 2) -> TomeTables:
+    """The four tables of merging the r best-matched sources of every sample (mx_tome_select)"""
+    assert node_max.is_cuda and node_max.dtype == torch.float32 and node_idx.dtype == torch.int32 and node_max.is_contiguous() and node_idx.is_contiguous()
+    B, nsrc = node_max.shape
+    ndst = h * w - nsrc
+    new = lambda n: torch.empty((B, n), dtype=torch.int32, device=node_max.device)      # noqa: E731
+    t = TomeTables(new(h * w), new(nsrc - r), new(ndst + 1), new(r), h, w, sx, sy, r)
+    _lib.check(_lib.load().mx_tome_select(_lib.current_stream(), node_max.data_ptr(), node_idx.data_ptr(), B, h, w, sy, sx, r, t.row_of.data_ptr(),
+                                          t.unm_src.data_ptr(), t.dst_start.data_ptr(), t.dst_src.data_ptr()), "mx_tome_select")
+    return t
+
+
+def tome_merge(x: torch.Tensor, tables: TomeTables, eps: Optional[float] = None) -> torch.Tensor:
+    """The merged sequence [B, Lm, C] of x [B, h w, C] bf16 (mx_tome_merge); ``eps``: LayerNorm every gathered row without affine first"""
+    _bf16(x)
+    t = tables
+    B, L, Cc = x.shape
+    assert L == t.h * t.w and all(v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.shape[0] == B for v in t[:4])
+    out = torch.empty((B, L - t.r, Cc), dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().mx_tome_merge(_lib.current_stream(), x.data_ptr(), Cc, B, t.h, t.w, t.sy, t.sx, Cc, t.r, t.unm_src.data_ptr(),
+                                         t.dst_start.data_ptr(), t.dst_src.data_ptr(), -1.0 if eps is None else float(eps), out.data_ptr(), Cc),
+               "mx_tome_merge")
+    return out
+
+
+def tome_unmerge(o: torch.Tensor, tables: TomeTables, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, h w, C]: every token takes row row_of[token] of o [B, Lm, C] bf16, added to ``residual`` when given (mx_tome_unmerge)"""
+    _bf16(o)
+    B, Lm, Cc = o.shape
+    L = tables.h * tables.w
+    assert Lm == L - tables.r and tables.row_of.shape == (B, L)
+    if residual is not None:
+        assert _bf16(residual).shape == (B, L, Cc)
+    y = torch.empty((B, L, Cc), dtype=torch.bfloat16, device=o.device)
+    _lib.check(_lib.load().mx_tome_unmerge(_lib.current_stream(), o.data_ptr(), Cc, tables.row_of.data_ptr(), _p(residual), Cc, y.data_ptr(), Cc,
+                                           B, L, Lm, Cc), "mx_tome_unmerge")
+    return y
+
+
 def attn_tail(ao: torch.Tensor, y: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, colsum_q: torch.Tensor,
               k: torch.Tensor, vt: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, heads: int, L: int, ctx_len: int, ln_eps: float = 1e-5,
               finalise: bool = True):

@@ -71,6 +71,7 @@ class MxUNet(ModelSlot):
         self._ip_next = None               # set_image_tokens: (tokens, scales) of the NEXT forward only, handed over right before its launches
         self._ip_live = None
         self._freeu_on = False             # enable_freeu
+        self._tome = None                  # enable_tome: (ratio, sx, sy, max_downsample) while on
         self.config = _Config(in_channels=cfg.in_channels, time_cond_proj_dim=None,
                               addition_time_embed_dim=cfg.addition_time_embed_dim,
                               projection_class_embeddings_input_dim=cfg.projection_class_embeddings_input_dim,
@@ -209,6 +210,21 @@ class MxUNet(ModelSlot):
     def disable_freeu(self) -> None:
         """diffusers' ``disable_freeu``: the plain launch sequence again"""
         self.enable_freeu(0.0, 0.0, 0.0, 0.0)
+
+    # ---- token merging (mx_unet_set_tome; tome.hip) ------------------------------------------------------
+    def enable_tome(self, ratio: float = 0.5, sx: int = 2, sy: int = 2, max_downsample: int = 2) -> None:
+        """``tomesd.apply_patch(pipe, ratio, sx=sx, sy=sy, max_downsample=max_downsample, use_rand=False)``: from now on the self-attention of every
+        transformer block at a level downsampled by at most ``max_downsample`` (2: the first attention level, 4: both) runs on a sequence from which
+        ``ratio`` of the tokens have been merged into their most similar cell corner.  ``ratio`` in [0, 0.75]; 0 is the plain forward.  Served by the
+        plain forward and a mixed batch of one resolution; the block-skip cache and patch-parallel forwards refuse while it is on."""
+        _lib.check(self._lib.mx_unet_set_tome(self._handle, float(ratio), int(sx), int(sy), int(max_downsample)), "mx_unet_set_tome")
+        state = (float(ratio), int(sx), int(sy), int(max_downsample)) if ratio > 0 else None
+        if state != self._tome:            # the plan takes tables and merged buffers while it is on: the arena sizes are walked again
+            self._tome, self._ws_need = state, {}
+
+    def disable_tome(self) -> None:
+        """the plain launch sequence again"""
+        self.enable_tome(0.0)
 
     # ---- LoRA adapters (sduss_amd/lora.py; mx_lora_merge) ---------------------------------------------
     def _point_at(self, blob: torch.Tensor) -> None:
