@@ -315,6 +315,14 @@ int mx_attention_prescaled(void* stream, const void* q, int ldq, const void* k, 
  * mx_attention_prescaled itself takes this kernel from Lq >= 2048 and the general one below (the two differ in bf16 rounding of P) */
 int mx_attention_cross_prescaled(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                                  int64_t vt_batch_stride, void* o, int ldo, int B, int H, int Lq, int Lk);
+/* Windowed self-attention (HyperTile), head_dim 64, q prescaled as for mx_attention_prescaled.
+ * A sample's L = gh*gw tokens are a row-major gh x gw grid cut into (gh/wh) x (gw/ww) windows.
+ * Token (y, x) attends to the wh*ww tokens of its own window only.  Operands exactly as mx_attention_prescaled with Lq = Lk = L:
+ * q, k rows b*L + y*gw + x; vt as written by MX_EPI_QKV with rows_per_batch = L; o rows in the same (unpermuted) order.
+ * Nothing is gathered or copied.  gh % wh == 0, gw % ww == 0, ww % 16 == 0 (MX_VT_POS permutes keys inside groups of 16), ldo % 4 == 0,
+ * ldvt >= MX_VT_LD(L); any wh >= 1.  Windows of up to 256 keys stay resident in LDS for all their queries (attention_window.hip). */
+int mx_attention_window(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, int64_t vt_batch_stride,
+                        void* o, int ldo, int B, int H, int gh, int gw, int wh, int ww);
 /* Grouped form: the attention problems of all resolutions present in a mixed batch in ONE launch (see mx_gemm_seg).  The problems share the row
  * strides and the head count; each has its own batch, sequence lengths and operand bases.  One kernel serves the whole launch (chosen by the
  * longest query sequence); the arithmetic per problem is that of mx_attention_prescaled with the same kernel. */
@@ -522,6 +530,14 @@ int mx_unet_set_freeu(mx_unet* u, float s1, float s2, float b1, float b2);
  * group and their _trace forms; the sizing walks count its buffers and it is part of the graph key.  The block-cache and patch-parallel entry points
  * and a mixed batch of more than one resolution group refuse a forward while it is on. */
 int mx_unet_set_tome(mx_unet* u, float ratio, int sx, int sy, int max_downsample);
+/* HyperTile (tfernd/HyperTile with swap_size = 1, scale_depth = False: the deterministic rule): while on, the self-attention core of every
+ * BasicTransformerBlock at depth d <= max_depth (the token grid is (H >> d) x (W >> d); SDXL attends at d = 1 and 2) runs per window through
+ * mx_attention_window on the buffers the plain launch reads and writes.  Per axis of n tokens the window is the smallest divisor of n that is
+ * >= min(tile_tokens, n).  A level whose window is the whole grid, or whose window width is no multiple of 16, runs the plain launch.  tile_tokens 0
+ * turns it off (otherwise 4 .. 4096; max_depth 0 .. 3) and the launch sequence is the plain one.  No buffer is added; it is part of the graph key.
+ * Served by mx_unet_forward, mx_unet_forward_mixed with ONE resolution group and their _trace forms.  The block-cache and patch-parallel entry
+ * points, a mixed batch of more than one resolution group, and a forward with ToMe on as well refuse while it is on. */
+int mx_unet_set_hypertile(mx_unet* u, int tile_tokens, int max_depth);   /* tile_tokens 0 = off */
 size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len);
 /* host-only walk of the step plan that resolves every packed tensor by name and size (no launches, no GPU needed) */
 int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len);

@@ -85,6 +85,8 @@ struct mx_unet {
   // ---- token merging (mx_unet_set_tome): ratio 0 = off ----
   float tome_ratio = 0.f;
   int tome_sx = 2, tome_sy = 2, tome_max_ds = 2;
+  // ---- HyperTile (mx_unet_set_hypertile): tile_tokens 0 = off ----
+  int ht_tile = 0, ht_depth = 2;
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -646,6 +648,14 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   };
   float tome_ratio = 0.f;               // this forward's (Model::setup); 0: off
   int tome_sx = 2, tome_sy = 2, tome_max_ds = 2;
+  // HyperTile (mx_unet_set_hypertile; attention_window.hip): this forward's tile length in tokens (0: off) and the deepest level it cuts.  A level's
+  // window per axis of n tokens is the smallest divisor of n that is >= min(ht_tile, n) (HyperTile's random_divisor with swap_size = 1)
+  int ht_tile = 0, ht_depth = 2;
+  static int ht_divisor(int n, int tile) {
+    int d = std::min(tile, n);
+    while (n % d != 0) ++d;
+    return d;
+  }
   // one transformer's shape, LayerNorm routes and buffers (transformer_buffers allocates them in the order they stand here)
   struct Xf {
     int C, heads, level, M, L, ldvt;      // (L, ldvt: the first group's tokens per image)
@@ -664,6 +674,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     mx_gemm_seg qsegs[MX_MAX_SEGS];       // mixed batch: the fused q|k|v projection as a grouped launch (tokens per image and V^T block per group)
     std::vector<long> vt_off; std::vector<int> ldvt_s, Lk_s;         // patch-unit cache: per sample, its V^T block and keys
     Tome tm;                              // token merging at this level (tm.r > 0: on)
+    int gh = 0, gw = 0, wh = 0, ww = 0;   // HyperTile at this level (wh > 0: on): the token grid and its window
   };
   void transformer_buffers(Xf& t, bf16_t* gn_out) {
     const size_t M = t.M, C = t.C;
@@ -751,7 +762,11 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     const int C = t.C;
     mx_attn_problem pr[MX_MAX_SEGS];
     if (ng > 1) { self_problems(t, pr); attention_grouped(pr, 2 * C, 2 * C, C, t.heads); }
-    else attention(t.qk, 2 * C, t.qk + C, 2 * C, t.vt, t.ldvt, (long)C * t.ldvt, t.ao, C, t.heads, t.L, t.L);
+    else if (t.wh > 0) {                        // HyperTile: every window attends to itself, on the same rows of qk | vt | ao
+      if (ok() && !quiet() &&
+          mx_attention_window(stream, t.qk, 2 * C, t.qk + C, 2 * C, t.vt, t.ldvt, (int64_t)C * t.ldvt, t.ao, C, B, t.heads, t.gh, t.gw, t.wh, t.ww))
+        fail(std::string("attention: ") + mx_last_error());
+    } else attention(t.qk, 2 * C, t.qk + C, 2 * C, t.vt, t.ldvt, (long)C * t.ldvt, t.ao, C, t.heads, t.L, t.L);
   }
   void cross_attention_ip(Xf& t, int li) {      // the same plus ip_scale[b] * attention(q2, layer li of the image tokens' K / V^T), in the one launch
     if (quiet()) return;
@@ -891,6 +906,10 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
         t.tm.h = h; t.tm.w = wd; t.tm.Ndst = sz[0]; t.tm.Nsrc = sz[1]; t.tm.r = sz[2]; t.tm.Lm = sz[3];
         t.via.norm1 = t.via.norm2 = LnVia::Pass;
       }
+    }
+    if (ht_tile > 0 && ng == 1 && !is_pp() && !pc && level <= ht_depth) {
+      const int wh_ = ht_divisor(h, ht_tile), ww_ = ht_divisor(wd, ht_tile);
+      if ((wh_ < h || ww_ < wd) && ww_ % 16 == 0) { t.gh = h; t.gw = wd; t.wh = wh_; t.ww = ww_; }
     }
     transformer_buffers(t, n);
     linear(Linear{n, C, p + ".proj_in", t.y, C, M, C, C}.leaves_stats(t.st, t.via.norm1));
@@ -1415,6 +1434,7 @@ struct Model {
     p.u = u; p.ctx_len = c.ctx_len; p.ctx_e = ctx_e; p.ctx_hit = ctx_hit;
     p.fu = fu;
     p.tome_ratio = tome_ratio; p.tome_sx = tome_cell[0]; p.tome_sy = tome_cell[1]; p.tome_max_ds = tome_cell[2];
+    p.ht_tile = ht[0]; p.ht_depth = ht[1];
     p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
@@ -1477,6 +1497,7 @@ struct Model {
   // token merging as THIS forward runs it, by the same rule (refuse_tome); part of the key for the same reason
   float tome_ratio = 0.f;
   int tome_cell[3] = {2, 2, 2};          // sx, sy, max_downsample
+  int ht[2] = {0, 2};                    // HyperTile the same way (refuse_hypertile): tile_tokens, max_depth
   std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) {
     std::vector<uint64_t> k{(uint64_t)c.gn_patch};
     if (fu)
@@ -1486,6 +1507,8 @@ struct Model {
       k.push_back(0x200000000ull | w);
       for (int v : tome_cell) k.push_back(0x300000000ull | (uint32_t)v);
     }
+    if (ht[0] > 0)
+      for (int v : ht) k.push_back(0x400000000ull | (uint32_t)v);
     return k;
   }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
@@ -1499,6 +1522,11 @@ int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   if (u && u->tome_ratio > 0.f && !c.pp() && !c.cache) {
     MX_CHECK(!(c.groups && c.n_groups > 1), "unet: ToMe does not run on a mixed batch of more than one resolution group (mx_unet_set_tome with ratio 0 turns it off)");
     m.tome_ratio = u->tome_ratio; m.tome_cell[0] = u->tome_sx; m.tome_cell[1] = u->tome_sy; m.tome_cell[2] = u->tome_max_ds;
+  }
+  if (u && u->ht_tile > 0 && !c.pp() && !c.cache) {
+    MX_CHECK(!(c.groups && c.n_groups > 1), "unet: HyperTile does not run on a mixed batch of more than one resolution group (mx_unet_set_hypertile with tile_tokens 0 turns it off)");
+    MX_CHECK(!(u->tome_ratio > 0.f), "unet: HyperTile does not run with ToMe on as well (mx_unet_set_hypertile with tile_tokens 0, or mx_unet_set_tome with ratio 0, turns one off)");
+    m.ht[0] = u->ht_tile; m.ht[1] = u->ht_depth;
   }
   if (u && !c.dry) {        // the announcement names ONE forward, served or refused
     mx_unet* uw = const_cast<mx_unet*>(u);
@@ -1526,6 +1554,12 @@ int refuse_freeu(const mx_unet* u, const char* how) {
 // parallelism (a rank holds a band of the tokens; the match would cross ranks)
 int refuse_tome(const mx_unet* u, const char* how) {
   MX_CHECK(!(u && u->tome_ratio > 0.f), std::string("unet: ToMe does not run ") + how + " (mx_unet_set_tome with ratio 0 turns it off)");
+  return 0;
+}
+// the entry points that do not serve HyperTile: the block-skip cache (the patch-unit form runs its attention per asking patch, on other kernels) and patch
+// parallelism (a rank holds a band of the token grid; a window would cross ranks)
+int refuse_hypertile(const mx_unet* u, const char* how) {
+  MX_CHECK(!(u && u->ht_tile > 0), std::string("unet: HyperTile does not run ") + how + " (mx_unet_set_hypertile with tile_tokens 0 turns it off)");
   return 0;
 }
 using mx::dry_call;
@@ -1592,6 +1626,13 @@ extern "C" int mx_unet_set_tome(mx_unet* u, float ratio, int sx, int sy, int max
   MX_CHECK(sx >= 1 && sy >= 1 && sx * sy >= 2 && sx <= 64 && sy <= 64, "unet_set_tome: cells of sy x sx tokens, at least two tokens a cell");
   MX_CHECK(max_downsample == 2 || max_downsample == 4, "unet_set_tome: max_downsample must be 2 (the first attention level) or 4 (both)");
   u->tome_ratio = ratio; u->tome_sx = sx; u->tome_sy = sy; u->tome_max_ds = max_downsample;
+  return 0;
+}
+extern "C" int mx_unet_set_hypertile(mx_unet* u, int tile_tokens, int max_depth) {
+  MX_CHECK(u != nullptr, "unet_set_hypertile: null handle");
+  MX_CHECK(tile_tokens == 0 || (tile_tokens >= 4 && tile_tokens <= 4096), "unet_set_hypertile: tile_tokens must be 0 (off) or in 4..4096");
+  MX_CHECK(max_depth >= 0 && max_depth <= 3, "unet_set_hypertile: max_depth must be in 0..3");
+  u->ht_tile = tile_tokens; u->ht_depth = max_depth;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1692,7 +1733,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1725,7 +1766,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1760,7 +1801,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1782,7 +1823,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

@@ -272,6 +272,24 @@ def attention_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: i
     return o
 
 
+def attention_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, batch: int, grid: tuple, window: tuple,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windowed self-attention (HyperTile; mx_attention_window): q prescaled, k bf16 [batch * gh * gw, heads * 64] (row views of a q | k buffer are fine),
+    vt [batch, heads * 64, ldvt] as pack_vt over the whole sample; ``grid`` = (gh, gw) tokens, ``window`` = (wh, ww).  Token (y, x) attends to its own
+    window only; o keeps the tokens' order.  ``out``: a bf16 [rows, >= heads * 64] buffer to write into (its row stride is ldo)."""
+    l = _lib.load()
+    for t_ in (q, k):
+        assert t_.is_cuda and t_.dtype == torch.bfloat16 and t_.ndim == 2 and t_.stride(1) == 1
+    _bf16(vt)
+    (gh, gw), (wh, ww) = grid, window
+    if out is None:
+        out = torch.empty((q.shape[0], heads * 64), dtype=torch.bfloat16, device=q.device)
+    assert out.is_cuda and out.dtype == torch.bfloat16 and out.stride(1) == 1
+    _lib.check(l.mx_attention_window(_lib.current_stream(), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), vt.data_ptr(), vt.shape[2],
+                                     vt.shape[1] * vt.shape[2], out.data_ptr(), out.stride(0), batch, heads, gh, gw, wh, ww), "mx_attention_window")
+    return out
+
+
 def attention_d80(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, batch: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T / sqrt(80)) v for heads of 80 (mx_attention_d80): q, k, v bf16 [batch * L, heads * 80], rows may be strided views (three column
     ranges of one q | k | v buffer), v row-major, q not prescaled -> o bf16 [batch * L, heads * 80].  L <= lib.ATTN_D80_MAX_L."""

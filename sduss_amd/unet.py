@@ -38,6 +38,25 @@ def config_c(cfg: UNetConfig) -> "_lib.UNetConfigC":
     return cc
 
 
+def hypertile_windows(cfg: UNetConfig, state: Optional[Tuple[int, int]], H_lat: int, W_lat: int) -> list:
+    """MxUNet.hypertile_windows for ``state`` = (tile_tokens, max_depth) or None (off): the step plan's rule (mx_unet_set_hypertile), host only"""
+    def divisor(n, tile):                      # HyperTile's random_divisor with swap_size = 1: the smallest divisor of n that is >= min(tile, n)
+        return next(d for d in range(min(tile, n), n + 1) if n % d == 0)
+    out = []
+    last = len(cfg.down_has_attn) - 1
+    for depth, has_attn in enumerate(cfg.down_has_attn):
+        if not has_attn and depth != last:     # (the mid block attends at the last level whatever its down block does)
+            continue
+        gh, gw = H_lat >> depth, W_lat >> depth
+        win = None
+        if state and depth <= state[1]:
+            wh, ww = divisor(gh, state[0]), divisor(gw, state[0])
+            if (wh < gh or ww < gw) and ww % 16 == 0:
+                win = (gh, gw, wh, ww)
+        out.append(win)
+    return out
+
+
 class _LoraState:
     """what MxUNet.set_adapters keeps between calls"""
 
@@ -72,6 +91,7 @@ class MxUNet(ModelSlot):
         self._ip_live = None
         self._freeu_on = False             # enable_freeu
         self._tome = None                  # enable_tome: (ratio, sx, sy, max_downsample) while on
+        self._hypertile = None             # enable_hypertile: (tile_tokens, max_depth) while on
         self.config = _Config(in_channels=cfg.in_channels, time_cond_proj_dim=None,
                               addition_time_embed_dim=cfg.addition_time_embed_dim,
                               projection_class_embeddings_input_dim=cfg.projection_class_embeddings_input_dim,
@@ -225,6 +245,27 @@ class MxUNet(ModelSlot):
     def disable_tome(self) -> None:
         """the plain launch sequence again"""
         self.enable_tome(0.0)
+
+    # ---- HyperTile (mx_unet_set_hypertile; attention_window.hip) -----------------------------------------
+    def enable_hypertile(self, tile_size: int = 128, max_depth: int = 2) -> None:
+        """HyperTile (tfernd/HyperTile, ComfyUI's node) with ``swap_size=1, scale_depth=False``: from now on the self-attention of every transformer
+        block at depth <= ``max_depth`` runs per window of the token grid, every window attending to itself.  ``tile_size`` is in pixels
+        (``max(tile_size // 8, 4)`` tokens); 0 is the plain forward.  ``hypertile_windows`` says what a geometry gets.  Served by the plain forward and
+        a mixed batch of one resolution; the block-skip cache and patch-parallel forwards, and a forward with ToMe on as well, refuse while it is on."""
+        tokens = max(int(tile_size) // 8, 4) if tile_size > 0 else 0
+        _lib.check(self._lib.mx_unet_set_hypertile(self._handle, tokens, int(max_depth)), "mx_unet_set_hypertile")
+        state = (tokens, int(max_depth)) if tokens else None
+        if state != self._hypertile:       # no buffer is added, but a sizing walk refuses HyperTile with ToMe: its answers are asked for again
+            self._hypertile, self._ws_need = state, {}
+
+    def disable_hypertile(self) -> None:
+        """the plain launch sequence again"""
+        self.enable_hypertile(0)
+
+    def hypertile_windows(self, H_lat: int, W_lat: int) -> list:
+        """Per attention level of an H_lat x W_lat latent, ``(gh, gw, wh, ww)`` -- the token grid and the window HyperTile cuts it into -- or None where
+        the level runs the plain launch (off, deeper than max_depth, the window is the whole grid, or its width is no multiple of 16)."""
+        return hypertile_windows(self.cfg, self._hypertile, H_lat, W_lat)
 
     # ---- LoRA adapters (sduss_amd/lora.py; mx_lora_merge) ---------------------------------------------
     def _point_at(self, blob: torch.Tensor) -> None:
