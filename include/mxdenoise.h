@@ -323,6 +323,28 @@ int mx_attention_cross_prescaled(void* stream, const void* q, int ldq, const voi
  * ldvt >= MX_VT_LD(L); any wh >= 1.  Windows of up to 256 keys stay resident in LDS for all their queries (attention_window.hip). */
 int mx_attention_window(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, int64_t vt_batch_stride,
                         void* o, int ldo, int B, int H, int gh, int gw, int wh, int ww);
+/* The column mass of a self-attention (self-attention guidance, sag.hip): mass[b][j] = (1 / H) sum_h sum_i P_h[i][j], P_h = softmax over keys of
+ * q_h k_h^T * scale -- how much attention token j receives -- and mask[b][j] = mass[b][j] > 1.  q, k: bf16 rows b*L + i with head h at columns
+ * [64h, 64h + 64), as mx_attention takes them (a q | k buffer is two views of one allocation); any L >= 1.  prescaled != 0: q already carries
+ * MX_ATTN_QSCALE(scale) and `scale` is not read.  mass fp32 [B, L], mask uint8 [B, L].  The probabilities are never stored: two passes over the keys
+ * per 128-row query block and one reduce launch over a workspace of mx_attention_colmass_workspace_bytes (16-byte aligned).  No atomics and a fixed
+ * summation order: the same bits run after run. */
+size_t mx_attention_colmass_workspace_bytes(int B, int H, int L);
+int mx_attention_colmass(void* stream, const void* q, int ldq, const void* k, int ldk, int B, int H, int L, float scale, int prescaled,
+                         void* workspace, size_t workspace_bytes, float* mass, unsigned char* mask);
+/* Self-attention guidance's degraded latents (diffusers' sag_masking in the sigma parametrisation), ONE launch: per output row i, r = rows[i] (HOST
+ * array of n_out <= 64 indices into the n rows; NULL: 0 .. n_out - 1), x0 = latents[r] - sigma[r] eps[r],
+ * out[i] = (mask[r][y h_m / h][x w_m / w] ? blur(x0) : x0) + sigma[r] eps[r].  blur: the separable 9-tap Gaussian exp(-0.5 (t / blur_sigma)^2), t = -4 .. 4,
+ * normalised (mx_sag_blur_taps: doubles on the host, rounded to fp32), under REFLECT padding of 4, accumulated in fp32.  latents, eps (the
+ * unconditional noise rows), out: [., C, h, w] of io dtype `dtype`; sigma fp32 [n]; mask uint8 [n, h_m, w_m] (mx_attention_colmass); all but rows on
+ * the device.  An unmasked element is (x - n) + n with n = sigma eps, each operation rounded to fp32.  h, w > 4. */
+int mx_sag_blur_taps(float blur_sigma, float taps[9]);
+int mx_sag_degrade(void* stream, const void* latents, const void* eps, const float* sigma, const unsigned char* mask, int h_m, int w_m,
+                   const int* rows, int n_out, int n, int C, int h, int w, float blur_sigma, void* out, int dtype);
+/* Self-attention guidance's term folded into the conditional noise rows in front of the unchanged scheduler step: noise [2n, elems] holds the
+ * unconditional rows then the conditional ones; noise[n + r] += coef[i] (noise[r] - eps_d[i]) for r = rows[i], fp32 operations rounded once.  With
+ * coef = sag_scale / guidance_scale the step's eps_u + g (eps_c - eps_u) gains sag_scale (eps_u - eps_d).  rows (distinct), coef: HOST arrays of n_out <= 64. */
+int mx_sag_fold(void* stream, void* noise, const void* eps_d, const float* coef, const int* rows, int n_out, int n, int64_t elems, int dtype);
 /* Grouped form: the attention problems of all resolutions present in a mixed batch in ONE launch (see mx_gemm_seg).  The problems share the row
  * strides and the head count; each has its own batch, sequence lengths and operand bases.  One kernel serves the whole launch (chosen by the
  * longest query sequence); the arithmetic per problem is that of mx_attention_prescaled with the same kernel. */
@@ -538,6 +560,15 @@ int mx_unet_set_tome(mx_unet* u, float ratio, int sx, int sy, int max_downsample
  * Served by mx_unet_forward, mx_unet_forward_mixed with ONE resolution group and their _trace forms.  The block-cache and patch-parallel entry
  * points, a mixed batch of more than one resolution group, and a forward with ToMe on as well refuse while it is on. */
 int mx_unet_set_hypertile(mx_unet* u, int tile_tokens, int max_depth);   /* tile_tokens 0 = off */
+/* Capture for self-attention guidance: the NEXT forward of this handle (ONE call: consumed by it, like the image tokens) runs mx_attention_colmass
+ * behind the q | k | v projection of mid_block.attentions.0.transformer_blocks.0.attn1 on sample rows [0, rows) -- the unconditional half of a CFG
+ * batch -- and writes mass fp32 [rows, L_mid] and mask uint8 [rows, L_mid] (device memory, alive until the forward has run).  Every other launch is
+ * the plain one and the forward's output keeps its bits; the partial sums come from the plan's arena (counted by every sizing walk) and capture is
+ * part of the graph key.  Served by mx_unet_forward, mx_unet_forward_mixed with ONE resolution group and their _trace forms.  The block-cache and
+ * patch-parallel entry points, a mixed batch of more than one resolution group, ToMe, and HyperTile reaching the mid level refuse an announced
+ * forward.  (NULL, NULL, 0) withdraws an announcement.  The _trace forms expose the q | k rows of every transformer block as stage
+ * "<block>.attn1.to_qkv" (bf16 [rows, 2 C], q prescaled): what the capture reads at the mid block's first block. */
+int mx_unet_set_attn_mass(mx_unet* u, float* mass, unsigned char* mask, int rows);
 size_t mx_unet_workspace_bytes(const mx_unet* u, int batch, int H, int W, int ctx_len);
 /* host-only walk of the step plan that resolves every packed tensor by name and size (no launches, no GPU needed) */
 int mx_unet_validate(const mx_unet* u, int batch, int H, int W, int ctx_len);

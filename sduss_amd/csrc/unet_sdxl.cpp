@@ -87,6 +87,8 @@ struct mx_unet {
   int tome_sx = 2, tome_sy = 2, tome_max_ds = 2;
   // ---- HyperTile (mx_unet_set_hypertile): tile_tokens 0 = off ----
   int ht_tile = 0, ht_depth = 2;
+  // ---- self-attention guidance's capture (mx_unet_set_attn_mass): the NEXT forward's buffers, consumed by it like the image tokens; am_rows 0 = none ----
+  float* am_mass = nullptr; unsigned char* am_mask = nullptr; int am_rows = 0;
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -656,6 +658,11 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     while (n % d != 0) ++d;
     return d;
   }
+  // Self-attention guidance's capture (mx_unet_set_attn_mass; sag.hip): behind the q | k | v projection of the mid block's first transformer block the
+  // column mass of sample rows [0, am_rows) goes to the announced buffers.  am_rows 0: off, and the launch sequence is the plain one.
+  float* am_mass = nullptr; unsigned char* am_mask = nullptr; int am_rows = 0;
+  struct Xf;
+  void capture_mass(Xf& t);
   // one transformer's shape, LayerNorm routes and buffers (transformer_buffers allocates them in the order they stand here)
   struct Xf {
     int C, heads, level, M, L, ldvt;      // (L, ldvt: the first group's tokens per image)
@@ -929,6 +936,8 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     for (int k = 0; k < layers && ok(); ++k) {
       const std::string b = p + ".transformer_blocks." + std::to_string(k);
       qkv(t, b);
+      if (stage) dump(b + ".attn1.to_qkv", t.qk, (size_t)M * 2 * C);      // (trace only) the q | k rows as the attention and the mass capture read them
+      if (k == 0 && p == "mid_block.attentions.0") capture_mass(t);
       const int li = ok() ? t.kvp->next++ : 0;
       if (pc) attend_masked(t, b, li); else attend(t, b, li);
       feed_forward(t, b, k + 1 < layers ? t.via.norm1 : LnVia::Pass);
@@ -1308,6 +1317,18 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     return ok();
   }
 };
+// A sizing walk takes the partial sums of a whole batch, so an announced forward finds room whatever its rows (the mid level lies far below the
+// arena's peak); a forward that was not announced takes and launches nothing.
+void Plan::capture_mass(Xf& t) {
+  const int rows_ = dry ? B : am_rows;
+  if (rows_ <= 0 || !ok()) return;
+  const size_t bytes = mx_attention_colmass_workspace_bytes(rows_, t.heads, t.L);
+  float* part = alloc<float>(bytes / sizeof(float));
+  if (!ok() || quiet() || am_rows <= 0) return;
+  if (t.C != t.heads * 64) { fail("unet: the attention mass needs heads of 64 at the mid block"); return; }
+  if (mx_attention_colmass(stream, t.qk, 2 * t.C, t.qk + t.C, 2 * t.C, am_rows, t.heads, t.L, 0.125f, 1, part, bytes, am_mass, am_mask))
+    fail(std::string("attention mass: ") + mx_last_error());
+}
 
 int check_cfg(const mx_unet_config* c) {
   MX_CHECK(c != nullptr, "unet: null config");
@@ -1435,6 +1456,7 @@ struct Model {
     p.fu = fu;
     p.tome_ratio = tome_ratio; p.tome_sx = tome_cell[0]; p.tome_sy = tome_cell[1]; p.tome_max_ds = tome_cell[2];
     p.ht_tile = ht[0]; p.ht_depth = ht[1];
+    p.am_mass = am_mass; p.am_mask = am_mask; p.am_rows = am_rows;
     p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
@@ -1498,6 +1520,9 @@ struct Model {
   float tome_ratio = 0.f;
   int tome_cell[3] = {2, 2, 2};          // sx, sy, max_downsample
   int ht[2] = {0, 2};                    // HyperTile the same way (refuse_hypertile): tile_tokens, max_depth
+  // the attention-mass capture announced for THIS forward (refuse_attn_mass); whether it is on and its rows are part of the key: a captured graph
+  // holds its two launches (the buffers are operands of the key)
+  float* am_mass = nullptr; unsigned char* am_mask = nullptr; int am_rows = 0;
   std::vector<uint64_t> key_scalars(const mx::ForwardCall& c) {
     std::vector<uint64_t> k{(uint64_t)c.gn_patch};
     if (fu)
@@ -1509,9 +1534,13 @@ struct Model {
     }
     if (ht[0] > 0)
       for (int v : ht) k.push_back(0x400000000ull | (uint32_t)v);
+    if (am_rows > 0) k.push_back(0x500000000ull | (uint32_t)am_rows);
     return k;
   }
-  std::vector<const void*> key_operands(const mx::ForwardCall& c) { return {c.text_embeds, c.time_ids}; }
+  std::vector<const void*> key_operands(const mx::ForwardCall& c) {
+    if (am_rows > 0) return {c.text_embeds, c.time_ids, am_mass, am_mask};
+    return {c.text_embeds, c.time_ids};
+  }
 };
 int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
   Model m;
@@ -1532,6 +1561,20 @@ int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
     mx_unet* uw = const_cast<mx_unet*>(u);
     m.ip_tokens = uw->ip_tokens; m.ip_scale = uw->ip_scale;
     uw->ip_tokens = nullptr; uw->ip_scale = nullptr;
+    m.am_mass = uw->am_mass; m.am_mask = uw->am_mask; m.am_rows = uw->am_rows;
+    uw->am_mass = nullptr; uw->am_mask = nullptr; uw->am_rows = 0;
+    if (m.am_rows > 0) {      // (the block-cache and patch-parallel entry points have refused an announced call: refuse_attn_mass)
+      const bool mixed = c.groups != nullptr;
+      const int nlev = u->cfg.n_levels, Btot = mixed ? c.groups[0].batch : c.batch;
+      MX_CHECK(!(mixed && c.n_groups > 1), "unet: the attention mass is not captured on a mixed batch of more than one resolution group (mx_unet_set_attn_mass with NULLs withdraws it)");
+      MX_CHECK(!(u->tome_ratio > 0.f), "unet: the attention mass is not captured with ToMe on (mx_unet_set_tome with ratio 0 turns it off)");
+      MX_CHECK(m.am_rows <= Btot, "unet: the attention mass was announced for more rows than the forward has");
+      if (m.ht[0] > 0 && nlev - 1 <= m.ht[1]) {
+        const int hm = (mixed ? c.groups[0].H : c.H) >> (nlev - 1), wm = (mixed ? c.groups[0].W : c.W) >> (nlev - 1);
+        const int wh = Plan::ht_divisor(hm, m.ht[0]), ww = Plan::ht_divisor(wm, m.ht[0]);
+        MX_CHECK(!((wh < hm || ww < wm) && ww % 16 == 0), "unet: the attention mass is not captured where HyperTile cuts the mid level into windows (mx_unet_set_hypertile with a max_depth above the mid level, or tile_tokens 0)");
+      }
+    }
   } else if (u && u->ip_weights.blob && !c.cache && !c.comm && c.ctx_len <= 96) {      // sizing / validating walk of a handle with an adapter: as if announced
     m.ip_tokens = (const void*)(uintptr_t)0x1000; m.ip_scale = (const float*)(uintptr_t)0x1000;
   }
@@ -1558,6 +1601,14 @@ int refuse_tome(const mx_unet* u, const char* how) {
 }
 // the entry points that do not serve HyperTile: the block-skip cache (the patch-unit form runs its attention per asking patch, on other kernels) and patch
 // parallelism (a rank holds a band of the token grid; a window would cross ranks)
+// the entry points that do not capture the attention mass (block-skip cache: the patch-unit form runs the mid attention per asking patch and may skip the
+// block; patch parallelism: a rank holds a band of the keys): an announced call is refused, and the announcement used up
+int refuse_attn_mass(mx_unet* u, const char* how) {
+  if (!u || u->am_rows <= 0) return 0;
+  u->am_mass = nullptr; u->am_mask = nullptr; u->am_rows = 0;
+  MX_CHECK(false, std::string("unet: the attention mass is not captured ") + how + " (mx_unet_set_attn_mass with NULLs withdraws it)");
+  return 1;
+}
 int refuse_hypertile(const mx_unet* u, const char* how) {
   MX_CHECK(!(u && u->ht_tile > 0), std::string("unet: HyperTile does not run ") + how + " (mx_unet_set_hypertile with tile_tokens 0 turns it off)");
   return 0;
@@ -1633,6 +1684,14 @@ extern "C" int mx_unet_set_hypertile(mx_unet* u, int tile_tokens, int max_depth)
   MX_CHECK(tile_tokens == 0 || (tile_tokens >= 4 && tile_tokens <= 4096), "unet_set_hypertile: tile_tokens must be 0 (off) or in 4..4096");
   MX_CHECK(max_depth >= 0 && max_depth <= 3, "unet_set_hypertile: max_depth must be in 0..3");
   u->ht_tile = tile_tokens; u->ht_depth = max_depth;
+  return 0;
+}
+extern "C" int mx_unet_set_attn_mass(mx_unet* u, float* mass, unsigned char* mask, int rows) {
+  MX_CHECK(u != nullptr, "unet_set_attn_mass: null handle");
+  MX_CHECK((mass == nullptr) == (mask == nullptr) && (mass == nullptr) == (rows == 0), "unet_set_attn_mass: mass, mask and rows come together (NULL, NULL, 0: withdraw)");
+  MX_CHECK(rows >= 0, "unet_set_attn_mass: rows must not be negative");
+  MX_CHECK(((uintptr_t)mass & 3) == 0, "unet_set_attn_mass: misaligned operand");
+  u->am_mass = mass; u->am_mask = mask; u->am_rows = rows;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1733,7 +1792,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1766,7 +1825,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1801,7 +1860,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1823,7 +1882,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

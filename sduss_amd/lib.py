@@ -270,6 +270,11 @@ SYMBOLS = {
     "mx_attention_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_cross_prescaled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_window": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "mx_attention_colmass_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mx_attention_colmass": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp]),
+    "mx_sag_blur_taps": (_i, [_f, C.POINTER(_f)]),
+    "mx_sag_degrade": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _f, _vp, _i]),
+    "mx_sag_fold": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_i), _i, _i, _i64, _i]),
     "mx_attention_cross_ip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_cross_ip_grouped": (_i, [_vp, C.POINTER(AttnIpProblem), _i, _i, _i, _i, _i, _i]),
     "mx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
@@ -295,6 +300,7 @@ SYMBOLS = {
     "mx_freeu_route": (_i, [C.POINTER(FreeUProblem), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mx_unet_set_tome": (_i, [_vp, _f, _i, _i, _i]),
     "mx_unet_set_hypertile": (_i, [_vp, _i, _i]),
+    "mx_unet_set_attn_mass": (_i, [_vp, _vp, _vp, _i]),
     "mx_tome_sizes": (_i, [_i, _i, _i, _i, _f, C.POINTER(_i)]),
     "mx_tome_table_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "mx_tome_match": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

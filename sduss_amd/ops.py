@@ -290,6 +290,75 @@ def attention_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: 
     return out
 
 
+def attention_colmass(q: torch.Tensor, k: torch.Tensor, heads: int, batch: int, prescaled: bool = False, scale: float = 0.125) -> tuple:
+    """(mass fp32 [batch, L], mask uint8 [batch, L]) of a self-attention (mx_attention_colmass; self-attention guidance): mass[b, j] is the mean over
+    heads of the attention token j receives from all queries, mask = mass > 1.  q, k bf16 [batch * L, heads * 64] (row views of a q | k buffer are
+    fine); ``prescaled``: q already carries ATTN_QSCALE.  The probabilities are never formed in memory; the same bits run after run."""
+    l = _lib.load()
+    for t_ in (q, k):
+        _need(t_.is_cuda and t_.dtype == torch.bfloat16 and t_.ndim == 2 and t_.stride(1) == 1, "mx_attention_colmass: q, k must be CUDA bf16 rows")
+    _need(batch > 0 and q.shape[0] % batch == 0 and q.shape[0] > 0 and k.shape[0] == q.shape[0], "mx_attention_colmass: q, k hold batch * L rows each")
+    L = q.shape[0] // batch
+    ws = torch.empty(max(l.mx_attention_colmass_workspace_bytes(batch, heads, L), 16), dtype=torch.uint8, device=q.device)
+    mass = torch.empty((batch, L), dtype=torch.float32, device=q.device)
+    mask = torch.empty((batch, L), dtype=torch.uint8, device=q.device)
+    _lib.check(l.mx_attention_colmass(_lib.current_stream(), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), batch, heads, L, float(scale),
+                                      int(bool(prescaled)), ws.data_ptr(), ws.numel(), mass.data_ptr(), mask.data_ptr()), "mx_attention_colmass")
+    return mass, mask
+
+
+def sag_blur_taps(blur_sigma: float):
+    """the nine fp32 taps of self-attention guidance's Gaussian blur (mx_sag_blur_taps, host only): exp(-0.5 (t / blur_sigma)^2), t = -4 .. 4, normalised in
+    double precision"""
+    import numpy as np
+    taps = (C.c_float * 9)()
+    _lib.check(_lib.load().mx_sag_blur_taps(float(blur_sigma), taps), "mx_sag_blur_taps")
+    return np.array(taps[:], dtype=np.float32)
+
+
+def _host_rows(what: str, rows, n: int):
+    rows = list(range(n)) if rows is None else [int(r) for r in rows]
+    _need(1 <= len(rows) <= 64 and all(0 <= r < n for r in rows), f"{what}: 1..64 row indices inside [0, {n})")
+    return (C.c_int * len(rows))(*rows), len(rows)
+
+
+def sag_degrade(latents: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, mask: torch.Tensor, blur_sigma: float = 1.0, rows=None) -> torch.Tensor:
+    """Self-attention guidance's degraded latents (mx_sag_degrade, one launch): per row r of ``rows`` (default: all), x0 = latents[r] - sigma[r] eps[r] and
+    (mask ? blur(x0) : x0) + sigma[r] eps[r], blur the 9 x 9 Gaussian under reflect padding, mask uint8 [n, h_m, w_m] stretched to the latents' grid
+    by nearest neighbour.  latents [n, C, h, w]; eps: at least n rows of the same dtype and planes (the unconditional noise rows lead the model's
+    output).  Returns [len(rows), C, h, w] in the latents' dtype."""
+    l = _lib.load()
+    _need(latents.is_cuda and latents.ndim == 4 and latents.is_contiguous(), "mx_sag_degrade: latents must be a contiguous CUDA tensor [n, C, h, w]")
+    n, ch, h, w = latents.shape
+    _need(eps.is_contiguous() and eps.dtype == latents.dtype and eps.device == latents.device and eps.ndim == 4 and eps.shape[0] >= n
+          and eps.shape[1:] == latents.shape[1:], f"mx_sag_degrade: eps must hold at least {n} contiguous rows like the latents'")
+    _need(mask.dtype == torch.uint8 and mask.ndim == 3 and mask.shape[0] == n and mask.is_contiguous() and mask.device == latents.device,
+          f"mx_sag_degrade: mask must be contiguous uint8 [{n}, h_m, w_m]")
+    sg = sigma.to(device=latents.device, dtype=torch.float32).contiguous()
+    _need(sg.shape == (n,), f"mx_sag_degrade: one sigma per latent row, got {tuple(sg.shape)}")
+    arr, n_out = _host_rows("mx_sag_degrade", rows, n)
+    out = torch.empty((n_out, ch, h, w), dtype=latents.dtype, device=latents.device)
+    _lib.check(l.mx_sag_degrade(_lib.current_stream(), latents.data_ptr(), eps.data_ptr(), sg.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2],
+                                arr, n_out, n, ch, h, w, float(blur_sigma), out.data_ptr(), _lib.torch_dtype_code(latents.dtype)), "mx_sag_degrade")
+    return out
+
+
+def sag_fold_(noise: torch.Tensor, eps_d: torch.Tensor, coef, rows=None) -> torch.Tensor:
+    """In place (mx_sag_fold): noise [2n, ...] = [uncond..., cond...]; for r = rows[i], noise[n + r] += coef[i] * (noise[r] - eps_d[i]).  With
+    coef = sag_scale / guidance_scale the scheduler step that follows adds sag_scale (eps_u - eps_d) to its guided prediction."""
+    l = _lib.load()
+    _need(noise.is_cuda and noise.is_contiguous() and noise.shape[0] % 2 == 0 and noise.shape[0] > 0, "mx_sag_fold: noise must be contiguous CUDA [2n, ...]")
+    n = noise.shape[0] // 2
+    arr, n_out = _host_rows("mx_sag_fold", rows, n)
+    _need(eps_d.is_contiguous() and eps_d.dtype == noise.dtype and eps_d.device == noise.device and tuple(eps_d.shape) == (n_out, *noise.shape[1:]),
+          f"mx_sag_fold: eps_d must be contiguous {(n_out, *noise.shape[1:])} like the noise")
+    coef = [float(c) for c in coef]
+    _need(len(coef) == n_out, "mx_sag_fold: one factor per row")
+    _lib.check(l.mx_sag_fold(_lib.current_stream(), noise.data_ptr(), eps_d.data_ptr(), (C.c_float * n_out)(*coef), arr, n_out, n, noise[0].numel(),
+                             _lib.torch_dtype_code(noise.dtype)), "mx_sag_fold")
+    return noise
+
+
 def attention_d80(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, batch: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T / sqrt(80)) v for heads of 80 (mx_attention_d80): q, k, v bf16 [batch * L, heads * 80], rows may be strided views (three column
     ranges of one q | k | v buffer), v row-major, q not prescaled -> o bf16 [batch * L, heads * 80].  L <= lib.ATTN_D80_MAX_L."""

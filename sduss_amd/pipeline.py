@@ -100,6 +100,8 @@ class Request:
     eta: float = 0.0                      # the noise level of a stochastic sampler (set_timesteps)
     image_tokens: Optional[torch.Tensor] = None   # bf16 [2, 16, cross_dim]: the image prompt's tokens of the (unconditional, conditional) row (set_image_prompt)
     ip_scale: float = 0.0                 # the image prompt's scale; 0 without one
+    sag_scale: float = 0.0                # self-attention guidance (SDXLDenoiser.set_sag); 0 without it
+    sag_blur_sigma: float = 1.0           # the sigma of its 9 x 9 Gaussian blur
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -143,6 +145,7 @@ class Denoiser:
         self._streams: List[torch.cuda.Stream] = []
         self._cache = StepCache(model.device)      # per batch composition: conditioning cats, sigma/timestep tables (step_state.py)
         self._mixed_cond: Dict[tuple, tuple] = {}  # per mixed composition: the conditioning of all resolutions concatenated
+        self._sag_comp: Dict[int, tuple] = {}      # per composition with a SAG request: (rows, uid and conditioning of its third forward)
 
     @staticmethod
     def _cond(reqs, do_classifier_free_guidance: bool) -> tuple:
@@ -422,7 +425,8 @@ class Denoiser:
         e = self._cache.entry((res, do_classifier_free_guidance, tuple(r.request_id for r in reqs), tuple(id(r) for r in reqs),
                                tuple(getattr(r, "sampler", "euler") for r in reqs),
                                tuple((getattr(r, "seed", None), getattr(r, "eta", 0.0)) for r in reqs),
-                               tuple((id(getattr(r, "image_tokens", None)), getattr(r, "ip_scale", 0.0)) for r in reqs)), reqs,
+                               tuple((id(getattr(r, "image_tokens", None)), getattr(r, "ip_scale", 0.0)) for r in reqs),
+                               tuple((getattr(r, "sag_scale", 0.0), getattr(r, "sag_blur_sigma", 1.0)) for r in reqs)), reqs,
                               lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs),
                               lambda: self._image_rows(reqs, do_classifier_free_guidance))
         lat = self._cache.latents(e, reqs)
@@ -457,7 +461,8 @@ class Denoiser:
             (cond, uid, image), ts = (parts[0].entry.cond, parts[0].entry.uid, parts[0].entry.image), parts[0].timesteps
         else:
             (cond, uid, image), ts = self._mixed_composition(parts), torch.cat([p.timesteps for p in parts])
-        if self.announces_composition:       # the composition's text embeddings are fixed: K / V^T of all layers once per composition
+        sag = self._sag_begin(parts, do_classifier_free_guidance)      # a request here asks for self-attention guidance: refused here, ahead of every
+        if self.announces_composition:       # announcement, or its capture announced.  The composition's text embeddings are fixed: K / V^T of all layers once
             self._model.set_context_key(uid)
         if image is not None:                # a request here has an image prompt: the rows' tokens and scales, built once per composition
             self._model.set_image_tokens(*image)
@@ -468,6 +473,8 @@ class Denoiser:
         else:
             noise = self._forward_mixed([p.x_in for p in parts], ts, cond, patch_size // 8 if is_sliced else 0)
         g = self.guidance_scale if do_classifier_free_guidance else 0.0
+        if sag is not None:                  # degrade, the third forward on its rows, and its term folded into their conditional noise rows
+            self._sag_finish(parts[0], noise[0], sag, g, is_sliced, patch_size, through_dict)
         for p, nz in zip(parts, noise):
             ms, hist = p.entry.multistep, None
             if ms is not None:                                                     # a request here steps by DPM-Solver++ 2M or AB2: one launch for all samplers
@@ -481,6 +488,12 @@ class Denoiser:
                     r.history, r.history_step = hist[i:i + 1], r.step_index
                 r.step_index += 1
                 r.latents = p.latents[i:i + 1]
+
+    def _sag_begin(self, parts: List[_Part], do_classifier_free_guidance: bool):
+        """None unless a request of this step asks for self-attention guidance (only SDXLDenoiser.set_sag makes one)"""
+        if any(getattr(r, "sag_scale", 0.0) > 0.0 for p in parts for r in p.reqs):
+            raise MxError(f"{type(self).__name__}: self-attention guidance is served by the SDXL model only")
+        return None
 
     def _step_resolution(self, res: str, reqs: list, do_classifier_free_guidance: bool, is_sliced: bool, patch_size: int) -> None:
         self._step([res], {res: reqs}, do_classifier_free_guidance, is_sliced, patch_size, through_dict=True)
@@ -543,6 +556,82 @@ class SDXLDenoiser(Denoiser):
         if strength >= 1.0:                                  # is_strength_max: pure noise times init_noise_sigma, nothing of the image
             return np.float32(0.0), np.float32(self.init_noise_sigma(req.num_inference_steps))
         return super()._inpaint_start_mix(req, t_start, strength)
+
+    # ---- self-attention guidance (diffusers' StableDiffusionSAGPipeline; csrc/sag.hip) -------------------
+    def set_sag(self, req: Request, scale: float = 0.75, blur_sigma: float = 1.0) -> None:
+        """Self-attention guidance for ``req`` from its next step on: every step captures how much attention each token of the mid block's first
+        self-attention receives on the request's unconditional row, blurs the predicted clean latents where that mass exceeds 1, runs the model
+        once more on the degraded latents with the negative prompt, and adds ``scale`` (eps_uncond - eps_degraded) to the guided prediction.
+        ``scale`` 0 takes it away.  Needs classifier-free guidance; one resolution a step; not with the block-skip cache, ToMe, or HyperTile
+        reaching the mid level; and not in a batch composition that carries an image prompt (``set_image_prompt`` on any of its requests): the third
+        forward would have to carry the unconditional image tokens too, and that step refuses rather than drop them.  Other requests of the batch
+        are untouched."""
+        if not (scale >= 0.0 and scale < float("inf")):
+            raise MxError(f"SDXLDenoiser.set_sag: scale must be a non-negative number, got {scale!r}")
+        if not (blur_sigma > 0.0 and blur_sigma < float("inf")):
+            raise MxError(f"SDXLDenoiser.set_sag: blur_sigma must be positive, got {blur_sigma!r}")
+        req.sag_scale, req.sag_blur_sigma = float(scale), float(blur_sigma)
+
+    def _sag_begin(self, parts: List[_Part], do_classifier_free_guidance: bool):
+        """None when no request of the step has SAG; else the composition's (rows, uid, conditioning) after capture has been announced"""
+        if not any(getattr(r, "sag_scale", 0.0) > 0.0 for p in parts for r in p.reqs):
+            return None
+        who, m = "SDXLDenoiser: self-attention guidance", self.unet
+        if not do_classifier_free_guidance or not self.guidance_scale > 0.0:
+            raise MxError(f"{who} needs classifier-free guidance")
+        if len(parts) != 1:
+            raise MxError(f"{who} does not run on a step of several resolutions in one sequence")
+        if getattr(m, "_block_caches", None) is not None:
+            raise MxError(f"{who} does not run through the block-skip cache")
+        if m._tome is not None:
+            raise MxError(f"{who} does not run with ToMe on")
+        p = parts[0]
+        if p.entry.image is not None:
+            raise MxError(f"{who} does not run in a batch that carries an image prompt: its third forward would drop the image tokens")
+        n, (h, w) = len(p.reqs), p.latents.shape[2:]
+        if m.hypertile_windows(h, w)[-1] is not None:
+            raise MxError(f"{who} does not run where HyperTile cuts the mid level into windows")
+        if min(h, w) <= 4:
+            raise MxError(f"{who} needs latents of more than 4 x 4")
+        comp = self._sag_comp.get(p.entry.uid)
+        if comp is None:
+            rows = [i for i, r in enumerate(p.reqs) if r.sag_scale > 0.0]
+            reqs = [p.reqs[i] for i in rows]
+            cond = (torch.cat([r.negative_prompt_embeds for r in reqs], dim=0), torch.cat([r.negative_pooled_prompt_embeds for r in reqs], dim=0),
+                    torch.cat([r.negative_add_time_ids for r in reqs], dim=0))
+            if len(self._sag_comp) > 32:
+                self._sag_comp.clear()
+            comp = self._sag_comp[p.entry.uid] = (rows, new_uid(), cond)
+        hm, wm = m.mid_grid(h, w)
+        mass = torch.empty((n, hm * wm), dtype=torch.float32, device=p.latents.device)
+        mask = torch.empty((n, hm * wm), dtype=torch.uint8, device=p.latents.device)
+        m.set_attention_mass(mass, mask, n)
+        return (*comp, mask.view(n, hm, wm))
+
+    def _sag_finish(self, p: _Part, noise: torch.Tensor, sag: tuple, g: float, is_sliced: bool, patch_size: int, through_dict: bool) -> None:
+        rows, uid, cond, mask = sag
+        idx = torch.tensor(rows, dtype=torch.int64, device=noise.device) if len(rows) != len(p.reqs) else None
+        by_blur: Dict[float, list] = {}
+        for j, i in enumerate(rows):
+            by_blur.setdefault(p.reqs[i].sag_blur_sigma, []).append(j)
+        x_deg = None
+        for blur, js in by_blur.items():     # one launch per blur width among the requests: one, but for a caller who mixes them
+            part = ops.sag_degrade(p.latents, noise, p.sigma, mask, blur, rows=[rows[j] for j in js])
+            if len(by_blur) == 1:
+                x_deg = part
+            else:
+                x_deg = torch.empty((len(rows), *part.shape[1:]), dtype=part.dtype, device=part.device) if x_deg is None else x_deg
+                x_deg[js] = part
+        sig = p.sigma if idx is None else p.sigma[idx]
+        ts = p.timesteps[:len(p.reqs)] if idx is None else p.timesteps[idx]
+        x_in = ops.euler_scale_input(x_deg, sig, len(rows))
+        self._model.set_context_key(uid)     # a composition of its own: the hoisted K / V^T of the negative prompts alone
+        if through_dict:
+            eps_d = self._forward({p.res: x_in}, ts, cond, is_sliced=is_sliced, patch_size=patch_size,
+                                  input_indices={p.res: [str(p.reqs[i].request_id) for i in rows]})[p.res]
+        else:
+            eps_d = self._forward_mixed([x_in], ts, cond, patch_size // 8 if is_sliced else 0)[0]
+        ops.sag_fold_(noise, eps_d.contiguous(), [p.reqs[i].sag_scale / g for i in rows], rows=rows)
 
     def _forward(self, x: Dict[str, torch.Tensor], ts, cond, **kwargs) -> Dict[str, torch.Tensor]:
         ehs, pooled, tids = cond

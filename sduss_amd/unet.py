@@ -89,6 +89,8 @@ class MxUNet(ModelSlot):
         self._ip = None                    # set_ip_adapter: (IPAdapter, its PackedWeights on the device)
         self._ip_next = None               # set_image_tokens: (tokens, scales) of the NEXT forward only, handed over right before its launches
         self._ip_live = None
+        self._mass_next = None             # set_attention_mass: (mass, mask, rows) of the NEXT forward only
+        self._mass_live = None
         self._freeu_on = False             # enable_freeu
         self._tome = None                  # enable_tome: (ratio, sx, sy, max_downsample) while on
         self._hypertile = None             # enable_hypertile: (tile_tokens, max_depth) while on
@@ -105,12 +107,19 @@ class MxUNet(ModelSlot):
         self._next_ctx_key = int(key)
 
     def _take_announcement(self) -> tuple:
-        """(context key, image tokens) announced for the next forward, both one-shot"""
-        announced, self._next_ctx_key, self._ip_next = (self._next_ctx_key, self._ip_next), 0, None
+        """(context key, image tokens, attention-mass buffers) announced for the next forward, all one-shot"""
+        announced, self._next_ctx_key, self._ip_next, self._mass_next = (self._next_ctx_key, self._ip_next, self._mass_next), 0, None, None
         return announced
 
     def _announce(self, announced) -> None:      # forward() took them; where the call is ONE uncached sequence, that sequence gets them back
-        self._next_ctx_key, self._ip_next = announced
+        self._next_ctx_key, self._ip_next, self._mass_next = announced
+
+    def _hand_attention_mass(self, am, rows: int) -> None:
+        if am is not None:
+            if am[2] > rows:
+                raise _lib.MxError(f"the attention mass of {am[2]} rows announced for a forward of {rows} rows")
+            _lib.check(self._lib.mx_unet_set_attn_mass(self._handle, am[0].data_ptr(), am[1].data_ptr(), am[2]), "mx_unet_set_attn_mass")
+            self._mass_live = am           # alive until the next announcement, like the image tokens
 
     def _hand_image_tokens(self, ip, rows: int) -> None:
         if ip is not None:
@@ -120,21 +129,27 @@ class MxUNet(ModelSlot):
             self._ip_live = ip             # alive until the next announcement: the forward that reads them has been issued by then
 
     def _before_forward(self, rows: int) -> None:
-        key, ip = self._take_announcement()
+        key, ip, am = self._take_announcement()
         _lib.check(self._lib.mx_unet_set_context_key(self._handle, key), "mx_unet_set_context_key")
         self._hand_image_tokens(ip, rows)
+        self._hand_attention_mass(am, rows)
 
     def _before_trace(self, rows: int) -> None:
         ip, self._ip_next = self._ip_next, None
+        am, self._mass_next = self._mass_next, None
         self._hand_image_tokens(ip, rows)
+        self._hand_attention_mass(am, rows)
 
     def _drop_announcement(self, announced, what: str) -> None:
         if announced is None:
             ip, self._ip_next = self._ip_next, None
+            am, self._mass_next = self._mass_next, None
         else:
-            ip = announced[1]
+            ip, am = announced[1], announced[2]
         if ip is not None:
             raise _lib.MxError(f"an image prompt does not run through {what}: it is served by ONE uncached launch sequence")
+        if am is not None:
+            raise _lib.MxError(f"the attention mass is not captured through {what}: it is served by ONE uncached launch sequence")
 
     def context_stats(self):
         """(hits, misses) of the per-composition K / V^T store since the handle was created"""
@@ -216,6 +231,21 @@ class MxUNet(ModelSlot):
         ip_scale = ip_scale.to(device=self.device, dtype=torch.float32).contiguous()
         assert tokens.ndim == 3 and tokens.shape[1:] == (16, self.cfg.cross_attention_dim) and ip_scale.shape == (tokens.shape[0],)
         self._ip_next = (tokens, ip_scale)
+
+    # ---- self-attention guidance's capture (mx_unet_set_attn_mass; sag.hip) --------------------------------
+    def mid_grid(self, H_lat: int, W_lat: int) -> Tuple[int, int]:
+        """the token grid of the mid block's attention for an H_lat x W_lat latent"""
+        d = len(self.cfg.block_out_channels) - 1
+        return H_lat >> d, W_lat >> d
+
+    def set_attention_mass(self, mass: torch.Tensor, mask: torch.Tensor, rows: int) -> None:
+        """Announce capture for the NEXT forward of this model (mx_unet_set_attn_mass; one-shot like set_image_tokens): behind the q | k | v projection
+        of ``mid_block.attentions.0.transformer_blocks.0.attn1`` the column mass of sample rows [0, rows) -- the unconditional half of a CFG batch --
+        goes to ``mass`` fp32 [rows, L_mid] and ``mask`` uint8 [rows, L_mid] (``mass > 1``).  The forward's output keeps its bits.  The block-cache and
+        patch-parallel forwards, a batch of several resolutions, ToMe, and HyperTile where it cuts the mid level refuse an announced forward."""
+        assert mass.is_cuda and mass.dtype == torch.float32 and mass.is_contiguous() and mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous()
+        assert rows >= 1 and mass.ndim == 2 and mass.shape[0] == rows and mask.shape == mass.shape
+        self._mass_next = (mass, mask, int(rows))
 
     # ---- FreeU (mx_unet_set_freeu; freeu.hip) -----------------------------------------------------------
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
