@@ -372,6 +372,18 @@ typedef struct mx_attn_ip_problem {
   int B, Lq, Lk, ldvt, n_img;
 } mx_attn_ip_problem;
 int mx_attention_cross_ip_grouped(void* stream, const mx_attn_ip_problem* probs, int n, int ldq, int ldk, int ldk_ip, int ldo, int H);
+/* Regional prompts ("attention couple"): short-key cross-attention over up to MX_REGION_SETS separately normalised key sets, one launch:
+ *   o[b, i] = sum over r < counts[b] of weights[b, r, i] * softmax(q_i k_{b,r}^T) v_{b,r}      (q prescaled as for mx_attention_prescaled)
+ * Set r of sample b is the seg_len (<= 96) rows of k from row (b*n_sets + r) * seg_ld, seg_ld = MX_VT_LD(seg_len); rows seg_len .. seg_ld-1 of a set are
+ * padding and may hold anything.  vt: [B][H*64][ldvt] with set r at positions r*seg_ld + MX_VT_POS(key), ldvt >= n_sets*seg_ld: what mx_gemm's
+ * MX_EPI_QKV writes with rows_per_batch = n_sets*seg_ld.  weights: fp32 [B, n_sets, Lq], any finite values, not normalised across sets; counts: int32
+ * [B], each in 1..n_sets; both in device memory.  Sets r >= counts[b] are never read (K, V^T, weights).  A set whose weights are zero over a 32-query
+ * block costs that block the weight loads only.  A sample with counts[b] == 1 is computed by the arithmetic of mx_attention_cross_prescaled over set 0,
+ * bit for bit, and its weights are not read.  Fails (no launch) for n_sets outside 1..MX_REGION_SETS, seg_len outside 1..96, ldvt < n_sets*seg_ld, a
+ * null or misaligned operand. */
+#define MX_REGION_SETS 4
+int mx_attention_cross_regions(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, int64_t vt_batch_stride,
+                               const float* weights, const int32_t* counts, void* o, int ldo, int B, int H, int Lq, int n_sets, int seg_len);
 /* softmax(q k^T + bias[h]) v: q and the fp32 bias [H][Lq][ldb] both already multiplied by log2(e) (T5: no 1/sqrt(d) scaling, bucketed relative
  * position bias shared by all layers); ldb % 4 == 0, ldb >= Lk rounded up to 64 */
 int mx_attention_prescaled_bias(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
@@ -537,6 +549,17 @@ int mx_unet_set_ip_adapter(mx_unet* u, const void* blob, uint64_t blob_bytes, co
  * width; the context store holds the text's K / V^T only).  mx_unet_workspace_bytes / _mixed and mx_unet_validate of a handle with an adapter
  * count and resolve the adapter's part.  (NULL, NULL) withdraws an announcement. */
 int mx_unet_set_image_tokens(mx_unet* u, const void* tokens, const float* ip_scale);
+/* REGIONAL PROMPTS ("attention couple").  The NEXT forward of this handle (ONE call: consumed by it, like the image tokens) runs every cross-attention
+ * layer as
+ *   attn2(x)[b, i] = sum over r < counts[b] of weights[b, r, i] * softmax(q_i k_{b,r}^T / 8) v_{b,r}
+ * in one launch (mx_attention_cross_regions) in place of the plain one; nothing else of the launch sequence changes.  That forward is called with
+ * ctx_len = n_sets * MX_VT_LD(seg_len) and encoder_hidden_states [B, ctx_len, cross_attention_dim]: prompt r of a row at tokens r * MX_VT_LD(seg_len) ..
+ * + seg_len, padding rows and unused sets zero.  counts: int32 [B], each in 1..n_sets; weights_by_grid: n_grids pointers to fp32 [B, n_sets, L], one per
+ * token grid that has transformers, finest first (SDXL-base at 1024 px: 64x64 and 32x32); device memory, alive until the forward has run; the pointer
+ * array itself is copied.  Rows with counts 1 compute the plain forward's bits on their first prompt.  Part of the graph key.  Served by mx_unet_forward,
+ * mx_unet_forward_mixed (one resolution group) and their _trace forms; the block-cache and patch-parallel entry points, a forward that also carries image
+ * tokens, and a ctx_len other than the one above refuse.  ToMe and HyperTile touch self-attention only and stay allowed.  n_sets 0 withdraws. */
+int mx_unet_set_regions(mx_unet* u, int n_sets, int seg_len, const int32_t* counts, const float* const* weights_by_grid, int n_grids);
 /* FreeU (diffusers' enable_freeu(s1, s2, b1, b2)): while on, every resnet of up blocks 0 and 1 reads its skip through mx_freeu -- up block 0 with
  * (s1, b1), up block 1 with (s2, b2); one launch in front of each, the filtered skip in a workspace buffer, the hidden state scaled in place.  As in
  * diffusers it is on only when all four are non-zero; any zero turns it off, and the launch sequence is then the plain one.  A property of the handle

@@ -43,6 +43,14 @@ int launch_gn_pp_partial(hipStream_t s, const void* x, int C1, const void* x2, i
 int launch_gn_pp_finish(hipStream_t s, const void* x, int C1, const void* x2, void* y, long y_img_elems, const float* gamma, const float* beta, const double* all_sums,
                         int world, int B, int H, int W, int C, int groups, int H_total, float eps, int silu, void* workspace,
                         const double* fresh_own = nullptr, int own_rank = 0);
+// regional prompts as announced (mx_unet_set_regions): `sets` prompts of `seg` tokens a sample, counts int32 [B] and one fp32 [B, sets, L] weight buffer per
+// token grid with transformers, finest first; all in device memory, alive until the forward has run.  sets 0: none
+struct RegionSets {
+  static constexpr int kMaxGrids = 4;
+  int sets = 0, seg = 0, grids = 0;
+  const int* counts = nullptr;
+  const float* weights[kMaxGrids] = {nullptr, nullptr, nullptr, nullptr};
+};
 }  // namespace mx
 extern "C" int mx_attention_prescaled_chunked(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                                               int64_t vt_batch_stride, void* o, int ldo, int B, int H, int Lq, int Lk, int key_chunk,
@@ -89,6 +97,8 @@ struct mx_unet {
   int ht_tile = 0, ht_depth = 2;
   // ---- self-attention guidance's capture (mx_unet_set_attn_mass): the NEXT forward's buffers, consumed by it like the image tokens; am_rows 0 = none ----
   float* am_mass = nullptr; unsigned char* am_mask = nullptr; int am_rows = 0;
+  // ---- regional prompts (mx_unet_set_regions): the NEXT forward's sets, counts and per-grid weights, consumed by it like the image tokens; sets 0 = none ----
+  mx::RegionSets rg;
   void ctx_clear() {
     for (auto& e : ctx_store) {
       if (e.last) (void)hipStreamSynchronize(e.last);
@@ -317,6 +327,7 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
   static constexpr int kIpKeys = 16;
   bool ip = false;
   const bf16_t* ip_tokens = nullptr; const float* ip_scale = nullptr; int ip_n_img = 0;
+  mx::RegionSets rg;        // regional prompts announced for this forward (sets 0: none): every attn2 runs cross_attention_regions
   const bf16_t* ip_wb(const std::string& name, size_t elems) {      // a tensor of the adapter's blob: PlanBase::w on u->ip_weights
     if (dry && !lookup) return (const bf16_t*)(uintptr_t)0x1000;
     std::string e;
@@ -795,9 +806,21 @@ struct Plan : mx::DenoiserPlan {      // (stream, arena, weights, groups, exchan
     }
     if (mx_attention_cross_ip_grouped(stream, pi, ng, C, kvp->ldk, kvp->ldk, C, t.heads)) fail(std::string("attention: ") + mx_last_error());
   }
+  // regional prompts: the context is rg.sets prompts of rg.seg tokens a sample, each padded to MX_VT_LD(rg.seg) rows, so the hoisted K / V^T are already
+  // the operands of mx_attention_cross_regions; the weights are those of this transformer's token grid (finest first among the levels with transformers)
+  void cross_attention_regions(Xf& t, int li) {
+    if (quiet()) return;
+    const int C = t.C; const KV* kvp = t.kvp;
+    int gi = 0;
+    for (int l = 0; l < t.level; ++l) gi += u->cfg.down_has_attn[l] ? 1 : 0;
+    if (mx_attention_cross_regions(stream, t.q2, C, kvp->k + (size_t)li * C, kvp->ldk, kvp->vt + (size_t)li * C * kvp->ldvt, kvp->ldvt, kvp->vt_bstride, rg.weights[gi],
+                                   rg.counts, t.ao, C, B, t.heads, t.L, rg.sets, rg.seg))
+      fail(std::string("attention: ") + mx_last_error());
+  }
   void cross_attention(Xf& t, int li) {         // ao = attention(q2, layer li of the hoisted K / V^T)
     if (!ok()) return;
     if (ip) return cross_attention_ip(t, li);
+    if (rg.sets > 0) return cross_attention_regions(t, li);
     const int C = t.C; const KV* kvp = t.kvp;
     mx_attn_problem pr[MX_MAX_SEGS];
     if (ng > 1) { cross_problems(t, pr, li); attention_grouped(pr, C, kvp->ldk, C, t.heads); }
@@ -1391,6 +1414,7 @@ struct Model {
   bool ctx_hit = false;
   // the image tokens this forward was announced with (forward_impl takes them off the handle), or the placeholders of a sizing walk with an adapter set
   const void* ip_tokens = nullptr; const float* ip_scale = nullptr;
+  mx::RegionSets rg;        // the regional prompts this forward was announced with (forward_impl takes them off the handle); part of the graph key
   // H, W against the level count and the GroupNorm patch (is_sliced)
   static int check_shape(const mx_unet* u, int H, int W, int gn_patch) {
     const int div = 1 << (u->cfg.n_levels - 1);
@@ -1458,6 +1482,7 @@ struct Model {
     p.ht_tile = ht[0]; p.ht_depth = ht[1];
     p.am_mass = am_mass; p.am_mask = am_mask; p.am_rows = am_rows;
     p.ip = ip_tokens != nullptr; p.ip_tokens = (const bf16_t*)ip_tokens; p.ip_scale = ip_scale; p.ip_n_img = u->ip_n_img;
+    p.rg = rg;
     bool patch_covers_all = !c.units();     // (the patch unit keeps its gn_patch even where it covers every group: it is the cache's unit, pc_p0)
     for (int g = 0; g < p.ng; ++g) patch_covers_all = patch_covers_all && c.gn_patch >= p.gH[g] && c.gn_patch >= p.gW[g];
     p.gn_patch = patch_covers_all ? 0 : c.gn_patch;
@@ -1535,11 +1560,14 @@ struct Model {
     if (ht[0] > 0)
       for (int v : ht) k.push_back(0x400000000ull | (uint32_t)v);
     if (am_rows > 0) k.push_back(0x500000000ull | (uint32_t)am_rows);
+    if (rg.sets > 0) k.push_back(0x600000000ull | (uint32_t)(rg.sets << 8 | rg.seg));
     return k;
   }
   std::vector<const void*> key_operands(const mx::ForwardCall& c) {
-    if (am_rows > 0) return {c.text_embeds, c.time_ids, am_mass, am_mask};
-    return {c.text_embeds, c.time_ids};
+    std::vector<const void*> ops{c.text_embeds, c.time_ids};
+    if (am_rows > 0) { ops.push_back(am_mass); ops.push_back(am_mask); }
+    if (rg.sets > 0) { ops.push_back(rg.counts); for (int i = 0; i < rg.grids; ++i) ops.push_back(rg.weights[i]); }
+    return ops;
   }
 };
 int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
@@ -1563,6 +1591,16 @@ int forward_impl(const mx_unet* u, const mx::ForwardCall& c) {
     uw->ip_tokens = nullptr; uw->ip_scale = nullptr;
     m.am_mass = uw->am_mass; m.am_mask = uw->am_mask; m.am_rows = uw->am_rows;
     uw->am_mass = nullptr; uw->am_mask = nullptr; uw->am_rows = 0;
+    m.rg = uw->rg;
+    uw->rg = mx::RegionSets();
+    if (m.rg.sets > 0) {      // (the block-cache and patch-parallel entry points have refused an announced call: refuse_regions)
+      int grids = 0;
+      for (int l = 0; l < u->cfg.n_levels; ++l) grids += (u->cfg.down_has_attn[l] || l == u->cfg.n_levels - 1) ? 1 : 0;
+      MX_CHECK(!(c.groups && c.n_groups > 1), "unet: regional prompts do not run on a mixed batch of more than one resolution group (mx_unet_set_regions with n_sets 0 withdraws them)");
+      MX_CHECK(m.ip_tokens == nullptr, "unet: regional prompts and an image prompt do not run in one forward");
+      MX_CHECK(c.ctx_len == m.rg.sets * MX_VT_LD(m.rg.seg), "unet: a regional forward needs ctx_len == n_sets * MX_VT_LD(seg_len)");
+      MX_CHECK(m.rg.grids == grids, "unet: regional prompts need one weight buffer per token grid with transformers (" + std::to_string(grids) + " here)");
+    }
     if (m.am_rows > 0) {      // (the block-cache and patch-parallel entry points have refused an announced call: refuse_attn_mass)
       const bool mixed = c.groups != nullptr;
       const int nlev = u->cfg.n_levels, Btot = mixed ? c.groups[0].batch : c.batch;
@@ -1607,6 +1645,14 @@ int refuse_attn_mass(mx_unet* u, const char* how) {
   if (!u || u->am_rows <= 0) return 0;
   u->am_mass = nullptr; u->am_mask = nullptr; u->am_rows = 0;
   MX_CHECK(false, std::string("unet: the attention mass is not captured ") + how + " (mx_unet_set_attn_mass with NULLs withdraws it)");
+  return 1;
+}
+// the entry points that do not serve regional prompts (block-skip cache: the patch-unit form runs attn2 per asking patch on other kernels and its state
+// would hold blended outputs; patch parallelism: a rank holds a band of the token grid): an announced call is refused, and the announcement used up
+int refuse_regions(mx_unet* u, const char* how) {
+  if (!u || u->rg.sets <= 0) return 0;
+  u->rg = mx::RegionSets();
+  MX_CHECK(false, std::string("unet: regional prompts do not run ") + how + " (mx_unet_set_regions with n_sets 0 withdraws them)");
   return 1;
 }
 int refuse_hypertile(const mx_unet* u, const char* how) {
@@ -1692,6 +1738,23 @@ extern "C" int mx_unet_set_attn_mass(mx_unet* u, float* mass, unsigned char* mas
   MX_CHECK(rows >= 0, "unet_set_attn_mass: rows must not be negative");
   MX_CHECK(((uintptr_t)mass & 3) == 0, "unet_set_attn_mass: misaligned operand");
   u->am_mass = mass; u->am_mask = mask; u->am_rows = rows;
+  return 0;
+}
+extern "C" int mx_unet_set_regions(mx_unet* u, int n_sets, int seg_len, const int32_t* counts, const float* const* weights_by_grid, int n_grids) {
+  MX_CHECK(u != nullptr, "unet_set_regions: null handle");
+  u->rg = mx::RegionSets();
+  if (n_sets == 0) return 0;
+  MX_CHECK(n_sets >= 1 && n_sets <= MX_REGION_SETS, "unet_set_regions: n_sets must be in 1.." + std::to_string(MX_REGION_SETS) + " (0: withdraw)");
+  MX_CHECK(seg_len >= 1 && seg_len <= 96, "unet_set_regions: seg_len must be in 1..96");
+  MX_CHECK(counts != nullptr && weights_by_grid != nullptr && n_grids >= 1 && n_grids <= mx::RegionSets::kMaxGrids, "unet_set_regions: counts and 1..4 weight buffers are needed");
+  MX_CHECK(((uintptr_t)counts & 3) == 0, "unet_set_regions: misaligned operand");
+  mx::RegionSets r;
+  r.sets = n_sets; r.seg = seg_len; r.counts = counts; r.grids = n_grids;
+  for (int i = 0; i < n_grids; ++i) {
+    MX_CHECK(weights_by_grid[i] != nullptr && ((uintptr_t)weights_by_grid[i] & 3) == 0, "unet_set_regions: null or misaligned weight buffer");
+    r.weights[i] = weights_by_grid[i];
+  }
+  u->rg = r;
   return 0;
 }
 extern "C" int mx_unet_context_stats(const mx_unet* u, long* hits, long* misses) {
@@ -1792,7 +1855,7 @@ extern "C" size_t mx_unet_block_cache_bytes(const mx_unet* u, int batch, int H, 
 extern "C" int mx_unet_forward_cached(mx_unet* u, void* stream, const void* latents, int io_dtype, const float* timesteps, const void* ehs,
                                       const void* text_embeds, const float* time_ids, void* out, int batch, int H, int W, int ctx_len,
                                       int gn_patch, void* workspace, size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache") || refuse_regions(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached";
   MX_CHECK(!cache || cache->dev_down == nullptr, who + ": the device decision (dev_down) serves the patch unit only (mx_unet_forward_cached_mixed)");
   MX_CHECK(cache && cache->predict && cache->state, who + ": cache, cache->predict and cache->state are required");
@@ -1825,7 +1888,7 @@ extern "C" size_t mx_unet_workspace_bytes_cached_mixed(const mx_unet* u, const m
 extern "C" int mx_unet_forward_cached_mixed(mx_unet* u, void* stream, const mx_unet_group* groups, int n_groups, int io_dtype, const float* timesteps,
                                             const void* ehs, const void* text_embeds, const float* time_ids, int ctx_len, int gn_patch, void* workspace,
                                             size_t workspace_bytes, mx_block_cache* cache) {
-  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache")) return 1;
+  if (refuse_image_prompt(u, "through the block-skip cache") || refuse_freeu(u, "through the block-skip cache") || refuse_tome(u, "through the block-skip cache") || refuse_hypertile(u, "through the block-skip cache") || refuse_attn_mass(u, "through the block-skip cache") || refuse_regions(u, "through the block-skip cache")) return 1;
   const std::string who = "unet_forward_cached_mixed";
   MX_CHECK(cache && (cache->predict || cache->dev_down) && cache->state && cache->slots && cache->slot_valid,
            who + ": cache with predict (or dev_down), state, slots and slot_valid is required");
@@ -1860,7 +1923,7 @@ extern "C" size_t mx_unet_workspace_bytes_pp(const mx_unet* u, int batch, int H_
 extern "C" int mx_unet_forward_pp(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                   const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W, int ctx_len,
                                   const mx_pp_comm* comm, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel") || refuse_regions(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr, "unet_forward_pp: null communicator");
   mx::ForwardCall c = forward_call(stream, io_dtype, timesteps, ehs, text_embeds, time_ids, ctx_len, workspace, workspace_bytes);
   c.latents = latents_local; c.out = out_local; c.batch = batch; c.H = H_local; c.W = W; c.comm = comm;
@@ -1882,7 +1945,7 @@ extern "C" size_t mx_unet_pp_state_bytes(const mx_unet* u, int batch, int H_loca
 extern "C" int mx_unet_forward_pp_stale(mx_unet* u, void* stream, const void* latents_local, int io_dtype, const float* timesteps, const void* ehs,
                                         const void* text_embeds, const float* time_ids, void* out_local, int batch, int H_local, int W,
                                         int ctx_len, const mx_pp_comm* comm, const mx_pp_stale* stale, void* workspace, size_t workspace_bytes) {
-  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel")) return 1;
+  if (refuse_image_prompt(u, "patch-parallel") || refuse_freeu(u, "patch-parallel") || refuse_tome(u, "patch-parallel") || refuse_hypertile(u, "patch-parallel") || refuse_attn_mass(u, "patch-parallel") || refuse_regions(u, "patch-parallel")) return 1;
   MX_CHECK(comm != nullptr && stale != nullptr, "unet_forward_pp_stale: null communicator / state");
   MX_CHECK(stale->mode == MX_PP_WARMUP || stale->mode == MX_PP_STALE, "unet_forward_pp_stale: mode must be MX_PP_WARMUP or MX_PP_STALE");
   MX_CHECK(stale->state != nullptr && ((uintptr_t)stale->state & 255) == 0, "unet_forward_pp_stale: state must be 256-byte aligned device memory");

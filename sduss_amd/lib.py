@@ -277,6 +277,7 @@ SYMBOLS = {
     "mx_sag_fold": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_i), _i, _i, _i64, _i]),
     "mx_attention_cross_ip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i]),
     "mx_attention_cross_ip_grouped": (_i, [_vp, C.POINTER(AttnIpProblem), _i, _i, _i, _i, _i, _i]),
+    "mx_attention_cross_regions": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "mx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "mx_groupnorm_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mx_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
@@ -295,6 +296,7 @@ SYMBOLS = {
     "mx_unet_context_stats": (_i, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "mx_unet_set_ip_adapter": (_i, [_vp, _vp, C.c_uint64, C.POINTER(WeightEntry), _i, _i]),
     "mx_unet_set_image_tokens": (_i, [_vp, _vp, _vp]),
+    "mx_unet_set_regions": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp), _i]),
     "mx_unet_set_freeu": (_i, [_vp, _f, _f, _f, _f]),
     "mx_freeu": (_i, [_vp, C.POINTER(FreeUProblem), _i, _i, _i, _f, _f]),
     "mx_freeu_route": (_i, [C.POINTER(FreeUProblem), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

@@ -439,6 +439,28 @@ def attention_cross_ip_grouped(problems, heads: int, n_img: int) -> list:
     return outs
 
 
+REGION_SETS = 4        # MX_REGION_SETS: prompts a sample in one regional launch
+
+
+def attention_cross_regions(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, weights: torch.Tensor, counts: torch.Tensor, heads: int, lq: int,
+                            n_sets: int, seg_len: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Regional prompts, one launch (mx_attention_cross_regions): o[b, i] = sum over r < counts[b] of weights[b, r, i] softmax(q_i k_{b,r}^T) v_{b,r}.
+    q prescaled [B*Lq, H*64]; k [B*n_sets*seg_ld, H*64] with set r of sample b from row (b*n_sets + r)*seg_ld, seg_ld = vt_ld(seg_len); vt [B, H*64, ldvt]
+    as pack_vt over the n_sets*seg_ld rows of a sample; weights fp32 [B, n_sets, Lq] and counts int32 [B] on the device.  ``out``: a bf16
+    [B*Lq, >= H*64] buffer to write into."""
+    l = _lib.load()
+    for t_ in (q, k, vt):
+        _bf16(t_)
+    b = vt.shape[0]
+    assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and weights.shape == (b, n_sets, lq)
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == b
+    o = torch.empty_like(q) if out is None else out
+    _lib.check(l.mx_attention_cross_regions(_lib.current_stream(), q.data_ptr(), q.shape[1], k.data_ptr(), k.shape[1], vt.data_ptr(), vt.shape[2],
+                                            vt.shape[1] * vt.shape[2], weights.data_ptr(), counts.data_ptr(), o.data_ptr(), o.stride(0), b, heads, lq,
+                                            n_sets, seg_len), "mx_attention_cross_regions")
+    return o
+
+
 def freeu_route(shapes, c_skip: int) -> tuple:
     """(slab, [staged], [chain]) of one FreeU launch over problems of ``shapes`` = [(B, H, W), ...] (mx_freeu_route, host only): the channels per
     workgroup, per problem whether the slab is staged in LDS, and the longest sequential addition chain of its sums."""

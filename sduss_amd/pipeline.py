@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from .lib import MxError
+from .regions import Regions, batch_operands, token_grids
 from .step_state import StepCache, _upload, new_uid
 from .unet import MxUNet
 
@@ -102,6 +103,7 @@ class Request:
     ip_scale: float = 0.0                 # the image prompt's scale; 0 without one
     sag_scale: float = 0.0                # self-attention guidance (SDXLDenoiser.set_sag); 0 without it
     sag_blur_sigma: float = 1.0           # the sigma of its 9 x 9 Gaussian blur
+    regions: Optional[object] = None      # regional prompts (SDXLDenoiser.set_regions): a regions.Regions; None without them
 
     def done(self) -> bool:
         return self.step_index >= self.num_inference_steps
@@ -426,7 +428,8 @@ class Denoiser:
                                tuple(getattr(r, "sampler", "euler") for r in reqs),
                                tuple((getattr(r, "seed", None), getattr(r, "eta", 0.0)) for r in reqs),
                                tuple((id(getattr(r, "image_tokens", None)), getattr(r, "ip_scale", 0.0)) for r in reqs),
-                               tuple((getattr(r, "sag_scale", 0.0), getattr(r, "sag_blur_sigma", 1.0)) for r in reqs)), reqs,
+                               tuple((getattr(r, "sag_scale", 0.0), getattr(r, "sag_blur_sigma", 1.0)) for r in reqs),
+                               tuple(id(getattr(r, "regions", None)) for r in reqs)), reqs,
                               lambda: self._cond(reqs, do_classifier_free_guidance), lambda: self._inpaint_rows(reqs), lambda: self._multistep_rows(reqs),
                               lambda: self._image_rows(reqs, do_classifier_free_guidance))
         lat = self._cache.latents(e, reqs)
@@ -461,9 +464,13 @@ class Denoiser:
             (cond, uid, image), ts = (parts[0].entry.cond, parts[0].entry.uid, parts[0].entry.image), parts[0].timesteps
         else:
             (cond, uid, image), ts = self._mixed_composition(parts), torch.cat([p.timesteps for p in parts])
+        regions = self._regions_begin(parts, image, do_classifier_free_guidance)      # a request here has regional prompts: refused here, or the wide context
         sag = self._sag_begin(parts, do_classifier_free_guidance)      # a request here asks for self-attention guidance: refused here, ahead of every
         if self.announces_composition:       # announcement, or its capture announced.  The composition's text embeddings are fixed: K / V^T of all layers once
             self._model.set_context_key(uid)
+        if regions is not None:              # the composition's wide context, counts and weight tables, built once per composition
+            cond = (regions[0], *cond[1:])
+            self._model.set_regions(*regions[1:])
         if image is not None:                # a request here has an image prompt: the rows' tokens and scales, built once per composition
             self._model.set_image_tokens(*image)
         if through_dict:
@@ -495,6 +502,12 @@ class Denoiser:
             raise MxError(f"{type(self).__name__}: self-attention guidance is served by the SDXL model only")
         return None
 
+    def _regions_begin(self, parts: List[_Part], image, do_classifier_free_guidance: bool):
+        """None unless a request of this step has regional prompts (only SDXLDenoiser.set_regions makes one)"""
+        if any(getattr(r, "regions", None) is not None for p in parts for r in p.reqs):
+            raise MxError(f"{type(self).__name__}: regional prompts are served by the SDXL model only")
+        return None
+
     def _step_resolution(self, res: str, reqs: list, do_classifier_free_guidance: bool, is_sliced: bool, patch_size: int) -> None:
         self._step([res], {res: reqs}, do_classifier_free_guidance, is_sliced, patch_size, through_dict=True)
 
@@ -507,6 +520,7 @@ class SDXLDenoiser(Denoiser):
     def __init__(self, unet: MxUNet, guidance_scale: float = 5.0):
         super().__init__(unet, guidance_scale)     # reference default (pipeline_..._esymred.py:265)
         self.unet = unet
+        self._region_comp: Dict[int, tuple] = {}   # per composition with a regional request: (wide context, counts, weight tables, seg_len)
 
     def set_timesteps(self, req: Request, sampler: str = "euler", schedule: str = "default", eta: float = 1.0) -> None:
         """the request's schedule and sampler.  ``sampler``: "euler" (EulerDiscreteScheduler, the default), "dpmpp_2m" (DPM-Solver++ 2M), "ab2"
@@ -571,6 +585,43 @@ class SDXLDenoiser(Denoiser):
         if not (blur_sigma > 0.0 and blur_sigma < float("inf")):
             raise MxError(f"SDXLDenoiser.set_sag: blur_sigma must be positive, got {blur_sigma!r}")
         req.sag_scale, req.sag_blur_sigma = float(scale), float(blur_sigma)
+
+    # ---- regional prompts ("attention couple"; sduss_amd/regions.py, csrc/attention_regions.hip) ----------
+    def set_regions(self, req: Request, prompt_embeds: Optional[torch.Tensor], masks: Optional[torch.Tensor] = None) -> None:
+        """Regional prompts for ``req`` from its next step on: ``prompt_embeds`` [R, 77, 2048] (R <= 4; set 0 is the request's own prompt: the cross-attention
+        reads ``req.prompt_embeds`` there, row 0 is its place in the list; the pooled ``text_embeds`` stay as they are) and ``masks`` [R, H_lat, W_lat], non-negative, float
+        or bool.  Every cross-attention layer then blends the prompts' attention outputs per token with the weights regions.mask_weights makes of the
+        masks (area mean over the token's cell, normalised over the prompts; a token no mask covers listens to set 0).  The unconditional CFG row is
+        untouched.  ``prompt_embeds`` None takes the regions away.  One resolution a step; not through the block-skip cache, and not in a step that
+        carries an image prompt or self-attention guidance.  Other requests of the batch are untouched."""
+        if prompt_embeds is None:
+            req.regions = None
+            return
+        if masks is None:
+            raise MxError("SDXLDenoiser.set_regions: prompt_embeds need their masks")
+        req.regions = Regions(prompt_embeds, masks, tuple(req.latents.shape[2:]))
+
+    def _regions_begin(self, parts: List[_Part], image, do_classifier_free_guidance: bool):
+        """None when no request of the step has regions; else the composition's (wide context, counts, weight tables, seg_len)"""
+        if not any(getattr(r, "regions", None) is not None for p in parts for r in p.reqs):
+            return None
+        who, m = "SDXLDenoiser: regional prompts", self.unet
+        if len(parts) != 1:
+            raise MxError(f"{who} do not run on a step of several resolutions in one sequence")
+        if getattr(m, "_block_caches", None) is not None:
+            raise MxError(f"{who} do not run through the block-skip cache")
+        p = parts[0]
+        if image is not None:
+            raise MxError(f"{who} do not run in a step that carries an image prompt")
+        if any(getattr(r, "sag_scale", 0.0) > 0.0 for r in p.reqs):
+            raise MxError(f"{who} do not run in a step with self-attention guidance: its third forward would drop them")
+        comp = self._region_comp.get(p.entry.uid)
+        if comp is None:
+            if len(self._region_comp) > 32:
+                self._region_comp.clear()
+            grids = token_grids(m.cfg, *p.latents.shape[2:])
+            comp = self._region_comp[p.entry.uid] = batch_operands([r.regions for r in p.reqs], p.entry.cond[0], 2 if do_classifier_free_guidance else 1, grids)
+        return comp
 
     def _sag_begin(self, parts: List[_Part], do_classifier_free_guidance: bool):
         """None when no request of the step has SAG; else the composition's (rows, uid, conditioning) after capture has been announced"""

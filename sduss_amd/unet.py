@@ -91,6 +91,8 @@ class MxUNet(ModelSlot):
         self._ip_live = None
         self._mass_next = None             # set_attention_mass: (mass, mask, rows) of the NEXT forward only
         self._mass_live = None
+        self._regions_next = None          # set_regions: (counts, weights per grid, seg_len, n_sets) of the NEXT forward only
+        self._regions_live = None
         self._freeu_on = False             # enable_freeu
         self._tome = None                  # enable_tome: (ratio, sx, sy, max_downsample) while on
         self._hypertile = None             # enable_hypertile: (tile_tokens, max_depth) while on
@@ -107,12 +109,22 @@ class MxUNet(ModelSlot):
         self._next_ctx_key = int(key)
 
     def _take_announcement(self) -> tuple:
-        """(context key, image tokens, attention-mass buffers) announced for the next forward, all one-shot"""
-        announced, self._next_ctx_key, self._ip_next, self._mass_next = (self._next_ctx_key, self._ip_next, self._mass_next), 0, None, None
+        """(context key, image tokens, attention-mass buffers, regions) announced for the next forward, all one-shot"""
+        announced = (self._next_ctx_key, self._ip_next, self._mass_next, self._regions_next)
+        self._next_ctx_key, self._ip_next, self._mass_next, self._regions_next = 0, None, None, None
         return announced
 
     def _announce(self, announced) -> None:      # forward() took them; where the call is ONE uncached sequence, that sequence gets them back
-        self._next_ctx_key, self._ip_next, self._mass_next = announced
+        self._next_ctx_key, self._ip_next, self._mass_next, self._regions_next = announced
+
+    def _hand_regions(self, rg, rows: int) -> None:
+        if rg is not None:
+            counts, tables, seg_len, n_sets = rg
+            if counts.numel() != rows:
+                raise _lib.MxError(f"regions of {counts.numel()} rows announced for a forward of {rows} rows")
+            ptrs = (C.c_void_p * len(tables))(*[t.data_ptr() for t in tables])
+            _lib.check(self._lib.mx_unet_set_regions(self._handle, n_sets, seg_len, counts.data_ptr(), ptrs, len(tables)), "mx_unet_set_regions")
+            self._regions_live = rg        # alive until the next announcement, like the image tokens
 
     def _hand_attention_mass(self, am, rows: int) -> None:
         if am is not None:
@@ -129,23 +141,29 @@ class MxUNet(ModelSlot):
             self._ip_live = ip             # alive until the next announcement: the forward that reads them has been issued by then
 
     def _before_forward(self, rows: int) -> None:
-        key, ip, am = self._take_announcement()
+        key, ip, am, rg = self._take_announcement()
         _lib.check(self._lib.mx_unet_set_context_key(self._handle, key), "mx_unet_set_context_key")
         self._hand_image_tokens(ip, rows)
         self._hand_attention_mass(am, rows)
+        self._hand_regions(rg, rows)
 
     def _before_trace(self, rows: int) -> None:
         ip, self._ip_next = self._ip_next, None
         am, self._mass_next = self._mass_next, None
+        rg, self._regions_next = self._regions_next, None
         self._hand_image_tokens(ip, rows)
         self._hand_attention_mass(am, rows)
+        self._hand_regions(rg, rows)
 
     def _drop_announcement(self, announced, what: str) -> None:
         if announced is None:
             ip, self._ip_next = self._ip_next, None
             am, self._mass_next = self._mass_next, None
+            rg, self._regions_next = self._regions_next, None
         else:
-            ip, am = announced[1], announced[2]
+            ip, am, rg = announced[1], announced[2], announced[3]
+        if rg is not None:
+            raise _lib.MxError(f"regional prompts do not run through {what}: they are served by ONE uncached launch sequence")
         if ip is not None:
             raise _lib.MxError(f"an image prompt does not run through {what}: it is served by ONE uncached launch sequence")
         if am is not None:
@@ -204,6 +222,8 @@ class MxUNet(ModelSlot):
             scale = added_cond_kwargs.get("ip_scale", 1.0)
             scale = scale if torch.is_tensor(scale) else torch.full((tokens.shape[0],), float(scale))
             self.set_image_tokens(tokens, scale)
+        if added_cond_kwargs.get("region_counts") is not None:    # the wide context is encoder_hidden_states itself: [rows, n_sets * seg_ld, dim]
+            self.set_regions(added_cond_kwargs["region_counts"], added_cond_kwargs["region_weights"], added_cond_kwargs.get("region_seg_len", 77))
         return self._route(sample, timestep, (encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]),
                            is_sliced, patch_size, input_indices)
 
@@ -231,6 +251,17 @@ class MxUNet(ModelSlot):
         ip_scale = ip_scale.to(device=self.device, dtype=torch.float32).contiguous()
         assert tokens.ndim == 3 and tokens.shape[1:] == (16, self.cfg.cross_attention_dim) and ip_scale.shape == (tokens.shape[0],)
         self._ip_next = (tokens, ip_scale)
+
+    # ---- regional prompts (sduss_amd/regions.py; mx_attention_cross_regions) ---------------------------------
+    def set_regions(self, counts: torch.Tensor, weights_by_grid: Sequence[torch.Tensor], seg_len: int = 77) -> None:
+        """Announce regional prompts for the NEXT forward of this model (mx_unet_set_regions; one-shot like set_image_tokens): ``counts`` int [rows], the
+        prompts of each row (1..4); ``weights_by_grid`` one fp32 [rows, n_sets, L] per token grid with transformers, finest first (regions.token_grids).
+        That forward takes encoder_hidden_states [rows, n_sets * vt_ld(seg_len), dim] (regions.batch_operands).  Rows with count 1 compute the plain
+        forward's bits.  The block-cache and patch-parallel forwards, a batch of several resolutions and a forward with image tokens refuse."""
+        counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
+        tables = [t.to(device=self.device, dtype=torch.float32).contiguous() for t in weights_by_grid]
+        assert counts.ndim == 1 and tables and all(t.ndim == 3 and t.shape[:2] == (counts.numel(), tables[0].shape[1]) for t in tables)
+        self._regions_next = (counts, tables, int(seg_len), int(tables[0].shape[1]))
 
     # ---- self-attention guidance's capture (mx_unet_set_attn_mass; sag.hip) --------------------------------
     def mid_grid(self, H_lat: int, W_lat: int) -> Tuple[int, int]:
